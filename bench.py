@@ -2,7 +2,8 @@
 """
 bench.py -- Mcells/s for N^3 delta(x) realisations on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--edge 1024] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--edge 1024] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-other-configs]]
 
 One "step" = one realisation seed -> delta(x) resident in HBM + rms
 (generate_delta_field(save_potential=False) semantics: rows K,T,R,S fused into
@@ -12,13 +13,18 @@ the c2r FFT, then the moments).  Native counter-based RNG, float32, the shipped
 JSON line.  For N > 1 the driver launches this under torch.distributed.run, one
 rank per GPU.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps, writes the outputs of the last
+one if --dump-outputs is given (dump_outputs()) and prints the line.
+
+With --full the line also carries what takes runs of its own:
   roofline     -- dominant kernel: algorithmic bytes per launch / its mean duration
                   (HIP events on the plan's stream, eager launches inside this run)
   cpu_baseline -- the oracle (numpy restatement of the reference path) timed on
                   this host, 1 thread, on the SAME grid (512^3 only if 1024^3 does
                   not fit the host), rank 0, N = 1 only
   other_configs -- the other BASELINE configurations / API paths, timed in this run
+  N > 1: the per-phase times of an eager step, the cross-check through the other
+  kz-slab exchange and the single-GPU / ensemble comparators
 """
 import argparse
 import json
@@ -33,6 +39,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 21          # cells of the field in the --dump-outputs sample
+DUMP_SEED = 20261016           # ... drawn by a generator of this fixed seed
+DUMP_CHUNK_BYTES = 256 << 20   # the field is downloaded in slabs of x planes of at most this size
 
 
 def grid_for(ngpus, n):
@@ -328,6 +337,45 @@ def other_configs(power, spacing, device, only=None):
     return out
 
 
+def dump_outputs(dirname, plan, mean, std, rank=0, world=1):
+    """--dump-outputs: what the timed path leaves its caller after the last timed step -- the delta(x) field, resident on the
+    device, and its moments -- as DIR/<name>.npy.  The whole field is too large to write (4 GiB at 1024^3), so it is sampled:
+      delta_sample.npy        float32  the field at up to DUMP_SAMPLE cells drawn from the whole grid (generator seed DUMP_SEED)
+      delta_sample_index.npy  float64  their flat C-order indices into the (nx, ny, nz) grid, ascending
+      delta_x0.npy            float32  the whole plane x = 0
+      delta_moments.npy       float64  [mean, rms] of the field (rf_moments, what the line's rms_last rounds)
+    The cells depend on the grid alone, so two builds run with the same arguments write the same cells of the same realisation.
+    N > 1: every rank writes the sampled cells of its own x slab (delta_sample_rank<r>.npy, delta_sample_index_rank<r>.npy);
+    rank 0 also writes the plane and the moments.  About 28 MB in all."""
+    nx, ny, nz = plan.nx, plan.ny, plan.nz
+    plane = ny * nz
+    total = nx * plane
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+    x_lo = rank * plan.nx_local                       # this rank's x slab in the whole grid
+    idx = idx[(idx >= x_lo * plane) & (idx < (x_lo + plan.nx_local) * plane)]
+    vals = np.empty(len(idx), plan.real_dtype)
+    cx = max(1, DUMP_CHUNK_BYTES // (plane * plan.real_dtype.itemsize))
+    buf = np.empty((min(cx, plan.nx_local), ny, nz), plan.real_dtype)
+    x0_plane = None
+    for x0 in range(0, plan.nx_local, cx):
+        x1 = min(x0 + cx, plan.nx_local)
+        part = plan.download_real(out=buf[:x1 - x0], x0=x0, x1=x1)
+        if rank == 0 and x0 == 0:
+            x0_plane = part[0].copy()
+        lo, hi = np.searchsorted(idx, [(x_lo + x0) * plane, (x_lo + x1) * plane])
+        vals[lo:hi] = part.reshape(-1)[idx[lo:hi] - (x_lo + x0) * plane]
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(dirname, "delta_sample%s.npy" % suffix), vals)
+    np.save(os.path.join(dirname, "delta_sample_index%s.npy" % suffix), idx.astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(dirname, "delta_x0.npy"), x0_plane)
+        np.save(os.path.join(dirname, "delta_moments.npy"), np.array([mean, std], np.float64))
+
+
 def main_multi(args, rank, world, local_rank, shape, power, spacing):
     """N > 1: one process per GPU, kz-slab / x-slab decomposition with one RCCL all-to-all per realisation.
     No torch in these processes: the unique id travels through a file, barriers and the max over ranks
@@ -402,9 +450,11 @@ def main_multi(args, rank, world, local_rank, shape, power, spacing):
         mode = "rccl"
     if not set_mode(mode):
         raise RuntimeError("RANDOMFIELD_MULTI_MODE=%s is not available for this job" % mode)
-    plan.realise(seed=999)                             # eager single step: per-phase event times
-    plan.sync()
-    kern = np.array(plan.kernel_ms())                  # x, y, exchange+z, all-reduce
+    kern = None
+    if args.full:
+        plan.realise(seed=999)                         # eager single step: per-phase event times
+        plan.sync()
+        kern = np.array(plan.kernel_ms())              # x, y, exchange+z, all-reduce
     # kz-slab modes: the rank's kz slab as ONE block per peer, or as 4 sub-slabs (RF_FLAG_EXCHANGE_CHUNKS; the gathering z pass then reads
     # 4 x shorter segments, which one GPU's virtual ranks found 5 - 9 % faster).  RANDOMFIELD_EXCHANGE_CHUNKS = an
     # integer is honoured as given; 'auto' (default) times both layouts and keeps 4 only if it is faster AND reproduces the rms of 1.
@@ -438,11 +488,13 @@ def main_multi(args, rank, world, local_rank, shape, power, spacing):
     wall = time.perf_counter() - t0
     wall = float(dplan.allreduce([wall], op="max")[0])
     mean, std = plan.moments()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan, mean, std, rank=rank, world=world)
     # After the timed region: the last timed realisation once more through the OTHER kz-slab exchange (direct <-> rccl).  The two must give
     # the same field (the same cells in the same places), so the same rms to the last bits the all-reduce order leaves: evidence on the
     # line itself that the mode that was timed moved every tile to where it belongs on this host.
     cross = None
-    if mode in ("direct", "rccl"):
+    if args.full and mode in ("direct", "rccl"):
         other = "rccl" if mode == "direct" else "direct"
         try:
             if other not in calib:          # (only a mode that came through its calibration a moment ago: nothing here may cost the line)
@@ -460,44 +512,45 @@ def main_multi(args, rank, world, local_rank, shape, power, spacing):
             set_mode(mode)
             plan.set_exchange_chunks(chunks)
     rccl_ranks = plan.comm_size()                      # what RCCL itself says the communicator spans (ncclCommCount)
-    # the N = 1 equivalent in the SAME job: every rank times the per-GPU cube (edge^3, what `--gpus 1` runs: `steps` realisations
-    # replayed from one hipGraph) alone on its own GPU, no communicator involved; slowest and fastest rank reported
-    from randomfield_amd import _hip
-    e = args.edge
-    single = _hip.DevicePlan(e, e, e, np.complex64, device=local_rank)
-    single.set_kgrid(*powertools.ksq_axes(e, e, e, spacing))
-    single.set_power(*powertools.sigma_table(power, (e, e, e), spacing))
-    single.realise_batch_prepare(args.steps)
-    single.realise_batch(np.arange(1000, 1000 + max(args.warmup, 1), dtype=np.uint64), want_rms=False)
-    single.sync()
-    dplan.barrier()
-    t0 = time.perf_counter()
-    single.realise_batch(np.arange(123, 123 + args.steps, dtype=np.uint64), want_rms=False)
-    single.sync()
-    t_single = (time.perf_counter() - t0) / args.steps * 1e3
-    single.close()
-    t_single_max = float(dplan.allreduce([t_single], op="max")[0])
-    t_single_min = -float(dplan.allreduce([-t_single], op="max")[0])
-    # a labelled comparator, NOT this job: every GPU its own realisation of the WHOLE grid, no exchange (what a user with an ensemble
-    # of independent realisations gets from the node; it needs the whole grid to fit one GPU)
-    t_full = float("inf")
-    if world > 1:
-        try:
-            full = _hip.DevicePlan(nx, ny, nz, np.complex64, device=local_rank)
-            full.set_kgrid(*powertools.ksq_axes(nx, ny, nz, spacing))
-            full.set_power(*powertools.sigma_table(power, (nx, ny, nz), spacing))
-            full.realise_batch_prepare(1)
-            full.realise_batch(np.array([1], dtype=np.uint64), want_rms=False)
-            full.sync()
-            t0 = time.perf_counter()
-            for i in range(3):
-                full.realise_batch(np.array([2 + i], dtype=np.uint64), want_rms=False)
-            full.sync()
-            t_full = (time.perf_counter() - t0) / 3
-            full.close()
-        except RuntimeError:
-            pass                                      # (the whole grid does not fit one GPU: no such comparator)
-        t_full = float(dplan.allreduce([min(t_full, 1e9)], op="max")[0])
+    if args.full:
+        # the N = 1 equivalent in the SAME job: every rank times the per-GPU cube (edge^3, what `--gpus 1` runs: `steps` realisations
+        # replayed from one hipGraph) alone on its own GPU, no communicator involved; slowest and fastest rank reported
+        from randomfield_amd import _hip
+        e = args.edge
+        single = _hip.DevicePlan(e, e, e, np.complex64, device=local_rank)
+        single.set_kgrid(*powertools.ksq_axes(e, e, e, spacing))
+        single.set_power(*powertools.sigma_table(power, (e, e, e), spacing))
+        single.realise_batch_prepare(args.steps)
+        single.realise_batch(np.arange(1000, 1000 + max(args.warmup, 1), dtype=np.uint64), want_rms=False)
+        single.sync()
+        dplan.barrier()
+        t0 = time.perf_counter()
+        single.realise_batch(np.arange(123, 123 + args.steps, dtype=np.uint64), want_rms=False)
+        single.sync()
+        t_single = (time.perf_counter() - t0) / args.steps * 1e3
+        single.close()
+        t_single_max = float(dplan.allreduce([t_single], op="max")[0])
+        t_single_min = -float(dplan.allreduce([-t_single], op="max")[0])
+        # a labelled comparator, NOT this job: every GPU its own realisation of the WHOLE grid, no exchange (what a user with an ensemble
+        # of independent realisations gets from the node; it needs the whole grid to fit one GPU)
+        t_full = float("inf")
+        if world > 1:
+            try:
+                full = _hip.DevicePlan(nx, ny, nz, np.complex64, device=local_rank)
+                full.set_kgrid(*powertools.ksq_axes(nx, ny, nz, spacing))
+                full.set_power(*powertools.sigma_table(power, (nx, ny, nz), spacing))
+                full.realise_batch_prepare(1)
+                full.realise_batch(np.array([1], dtype=np.uint64), want_rms=False)
+                full.sync()
+                t0 = time.perf_counter()
+                for i in range(3):
+                    full.realise_batch(np.array([2 + i], dtype=np.uint64), want_rms=False)
+                full.sync()
+                t_full = (time.perf_counter() - t0) / 3
+                full.close()
+            except RuntimeError:
+                pass                                      # (the whole grid does not fit one GPU: no such comparator)
+            t_full = float(dplan.allreduce([min(t_full, 1e9)], op="max")[0])
     cells = float(nx) * ny * nz
     sweep = 8.0 * nx * ny * (nz // 2 + 1)
     xgmi_bytes = (world - 1) / world * sweep / world if mode in ("direct", "rccl") else 0.0     # egress per GPU of the exchange
@@ -517,21 +570,9 @@ def main_multi(args, rank, world, local_rank, shape, power, spacing):
                    "grid": [nx, ny, nz], "rms_last": round(std, 6), "multi_gpu_mode": mode, "exchange_sub_slabs": chunks, "rccl_ranks": rccl_ranks,
                    "launcher": "bench.py's own child ranks" if os.environ.get("RANDOMFIELD_LAUNCH_NONCE", "").startswith("bench-") else "external (torch.distributed.run)",
                    "mode_calibration_ms_per_step": {k: round(v, 3) for k, v in calib.items()},
-                   "modes_rejected": rejected, "exchange_cross_check": cross},
-        "single_gpu_equivalent": {"ms_per_step": round(t_single_max, 4), "ms_per_step_fastest_rank": round(t_single_min, 4),
-                                  "grid": [e, e, e], "Mcells_s": round(float(e) ** 3 / t_single_max / 1e3, 1),
-                                  "speedup_of_this_job": round(cells * args.steps / wall / (float(e) ** 3 / (t_single_max * 1e-3)), 3),
-                                  "note": "every rank alone on its own GPU in this same job (%d^3, %d realisations from one hipGraph, "
-                                          "as `--gpus 1`); slowest rank quoted" % (e, args.steps),
-                                  # NOT config 4 and not `value`: N independent realisations of the whole grid, one per GPU, no exchange
-                                  "ensemble_Mcells_s": (round(world * cells / t_full / 1e6, 1) if world > 1 and t_full < 1e8 else None),
-                                  "ensemble_note": "comparator only: every GPU generates its OWN %dx%dx%d realisation (no slab decomposition, no "
-                                                   "exchange; slowest rank): what an ensemble of independent realisations gets from the node" % (nx, ny, nz)},
+                   "modes_rejected": rejected},
         "pipeline": {"algorithmic_GBs": round(5 * sweep * args.steps / wall / 1e9, 1),
                      "frac_of_hbm_peak": round(5 * sweep * args.steps / wall / 1e9 / (HBM_PEAK_GBS * world), 4),
-                     "kernel_ms_rank0_unpipelined_step": {"x": round(float(kern[0]), 4), "y": round(float(kern[1]), 4),
-                                                   "exchange+z": round(float(kern[2]), 4),
-                                                   "allreduce": round(float(kern[3]), 4)},
                      "xgmi_egress_bytes_per_gpu": xgmi_bytes,
                      # the exchange's own roofline: xGMI is point to point, one link per peer.  AMD's 153.6 GB/s per link is the sum of
                      # both directions (7 links = 1075 GB/s aggregate), i.e. 76.8 GB/s per link and direction; the other reading is kept
@@ -546,20 +587,57 @@ def main_multi(args, rank, world, local_rank, shape, power, spacing):
                      "unit": "GB/s", "frac": round(5 * sweep * args.steps / wall / 1e9 / (HBM_PEAK_GBS * world), 4),
                      "traffic": None},
     }
+    if args.full:
+        out["config"]["exchange_cross_check"] = cross
+        out["pipeline"]["kernel_ms_rank0_unpipelined_step"] = {"x": round(float(kern[0]), 4), "y": round(float(kern[1]), 4),
+                                                               "exchange+z": round(float(kern[2]), 4),
+                                                               "allreduce": round(float(kern[3]), 4)}
+        out["single_gpu_equivalent"] = {"ms_per_step": round(t_single_max, 4), "ms_per_step_fastest_rank": round(t_single_min, 4),
+                                        "grid": [e, e, e], "Mcells_s": round(float(e) ** 3 / t_single_max / 1e3, 1),
+                                        "speedup_of_this_job": round(cells * args.steps / wall / (float(e) ** 3 / (t_single_max * 1e-3)), 3),
+                                        "note": "every rank alone on its own GPU in this same job (%d^3, %d realisations from one hipGraph, "
+                                                "as `--gpus 1`); slowest rank quoted" % (e, args.steps),
+                                        # NOT config 4 and not `value`: N independent realisations of the whole grid, one per GPU, no exchange
+                                        "ensemble_Mcells_s": (round(world * cells / t_full / 1e6, 1) if world > 1 and t_full < 1e8 else None),
+                                        "ensemble_note": "comparator only: every GPU generates its OWN %dx%dx%d realisation (no slab decomposition, "
+                                                         "no exchange; slowest rank): what an ensemble of independent realisations gets from the node"
+                                                         % (nx, ny, nz)}
     dplan.barrier()
     plan.close()
     if rank == 0:
         print(json.dumps(out))
 
 
-def build_line(shape, steps, warmup, gpus, wall, gpu_ms, std, kern, merged_ms, merged_n, nslab, slab_planes, traffic_path=None):
-    """The N = 1 JSON line from the measured numbers -- no GPU call in here, so that tests/test_bench_contract.py can run it with stubbed
-    timings: wall = seconds of the `steps` timed realisations, gpu_ms = the same by HIP events, std = rms of the last field,
-    kern = [x main kernel, y, z, reduce, x launch over the kz = 0 tiles] in ms (eager realisations), merged_ms / merged_n = mean
-    duration and launches per realisation of the merged z + y launch (None / 0 where the shape has none), nslab / slab_planes = how
-    the y / z passes are launched."""
+def headline(shape, steps, warmup, gpus, wall, gpu_ms, std):
+    """The N = 1 JSON line of a plain run: the figures of the timed region alone (wall = seconds of the `steps` timed realisations,
+    gpu_ms = the same by HIP events, std = rms of the last field).  No GPU call in here (tests/test_bench_contract.py)."""
     nx, ny, nz = shape
     cells = float(nx) * ny * nz
+    return {
+        "metric": "Mcells/s for N^3 delta(x) realisation",
+        "value": round(cells * steps / wall / 1e6, 1),
+        "unit": "Mcells/s",
+        "n_gpus": gpus, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(wall / steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%dx%dx%d float32 delta(x) realisations back to back (hipGraph replay), "
+                               "native Philox4x32-7 RNG, shipped 500-row P(k), spacing 2.5 Mpc/h" % (nx, ny, nz),
+                   "grid": [nx, ny, nz], "rms_last": round(std, 6),
+                   "parity": ("native stream = this repo's own definition (no reference counterpart): the kernel instantiations "
+                              "of this run are value-checked against the oracle's float64 restatement at 1e-5 * rms in "
+                              "tests/test_gpu_parity.py::test_native_generation_bench_instantiations_against_oracle; the "
+                              "same-seed path (rng='reference') is in other_configs (--full)")},
+        "gpu_ms_per_step_events": round(gpu_ms / steps, 4),
+    }
+
+
+def build_line(shape, steps, warmup, gpus, wall, gpu_ms, std, kern, merged_ms, merged_n, nslab, slab_planes, traffic_path=None):
+    """The N = 1 JSON line of a --full run from the measured numbers -- no GPU call in here, so that tests/test_bench_contract.py can
+    run it with stubbed timings: headline()'s arguments, and kern = [x main kernel, y, z, reduce, x launch over the kz = 0 tiles] in ms
+    (eager realisations), merged_ms / merged_n = mean duration and launches per realisation of the merged z + y launch (None / 0 where
+    the shape has none), nslab / slab_planes = how the y / z passes are launched."""
+    nx, ny, nz = shape
     sweep = 8.0 * nx * ny * (nz // 2 + 1)           # bytes of one sweep of the packed complex64 array
     # kern = [x main kernel, y, z, reduce, x launch over the kz = 0 tiles]; the x pass writes one sweep, of which the
     # main kernel writes all tiles but one per ky row
@@ -594,18 +672,8 @@ def build_line(shape, steps, warmup, gpus, wall, gpu_ms, std, kern, merged_ms, m
                 traffic_source += " (taken with %s y / z launches per realisation, this run has %d)" % (tj.get("yz_slabs"), nslab)
         else:
             traffic_source = "the committed PMC passes are for a %s grid on one GPU, not this run's" % (tj.get("grid", [1024, 1024, 1024]),)
-    out = {
-        "metric": "Mcells/s for N^3 delta(x) realisation",
-        "value": round(cells * steps / wall / 1e6, 1),
-        "unit": "Mcells/s",
-        "n_gpus": gpus, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(wall / steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%dx%dx%d float32 delta(x) realisations back to back (hipGraph replay), "
-                               "native Philox4x32-7 RNG, shipped 500-row P(k), spacing 2.5 Mpc/h" % (nx, ny, nz),
-                   "grid": [nx, ny, nz], "rms_last": round(std, 6)},
-        "gpu_ms_per_step_events": round(gpu_ms / steps, 4),
+    out = headline(shape, steps, warmup, gpus, wall, gpu_ms, std)
+    out.update({
         "pipeline": {"algorithmic_GBs": round(5 * sweep * steps / wall / 1e9, 1),
                      "frac_of_hbm_peak": round(5 * sweep * steps / wall / 1e9 / HBM_PEAK_GBS, 4),
                      "kernel_ms": {"x": round(float(kern[0]), 4), "y": round(float(kern[1]), 4),
@@ -625,7 +693,7 @@ def build_line(shape, steps, warmup, gpus, wall, gpu_ms, std, kern, merged_ms, m
                      "algorithmic_bytes_per_launch": alg[dom] / launches[dom], "avg_ms": round(float(pass_ms[dom]) / launches[dom], 5),
                      "launches_per_realisation": launches[dom],
                      "whole_pipeline_frac": round(5 * sweep * steps / wall / 1e9 / HBM_PEAK_GBS, 4)},
-    }
+    })
     # An estimate of the bytes that really cross the HBM pins: `achieved` / `frac` price ALGORITHMIC bytes, but when
     # the y and z passes run slab by slab the slab goes from the y pass to the z pass through the 256 MiB Infinity Cache and the z pass
     # overwrites it in place, so per realisation only the x pass's write (S), the y pass's read (S) and the z pass's result (S) reach
@@ -667,10 +735,6 @@ def build_line(shape, steps, warmup, gpus, wall, gpu_ms, std, kern, merged_ms, m
                            "frac_hbm_est": round(2 * sweep / nslab / (merged_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                            "hbm_bytes_est_note": hbm_note}
         out["pipeline"]["launches_per_realisation"] = {"x": 3, "y": 1, "z + y merged": merged_n, "z": 1, "reduce": 1}
-    out["config"]["parity"] = ("native stream = this repo's own definition (no reference counterpart): the kernel instantiations "
-                               "of this run are value-checked against the oracle's float64 restatement at 1e-5 * rms in "
-                               "tests/test_gpu_parity.py::test_native_generation_bench_instantiations_against_oracle; the "
-                               "same-seed path (rng='reference') is in other_configs")
     return out
 
 
@@ -729,13 +793,21 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--edge", type=int, default=1024, help="per-GPU cube edge")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="cube edge of the CPU baseline sample (0 = the workload's own edge)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel times and roofline objects, the "
+                         "other BASELINE configurations, the CPU baseline; N > 1: the exchange cross-check and the comparators")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed sample of the field, its moments) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: cube edge of the CPU baseline sample (0 = the workload's own edge)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the other BASELINE configurations")
     ap.add_argument("--force-multi", action="store_true", help="debug: run the N>1 code path with one rank")
     ap.add_argument("--child-config", default=None, help=argparse.SUPPRESS)      # (other_configs' float64 part in a process of its own)
     ap.add_argument("--child-device", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a plain `python bench.py --gpus N`: no launcher has prepared RANK / WORLD_SIZE, so this process becomes the launcher.
@@ -769,33 +841,34 @@ def main():
     plan.set_kgrid(*powertools.ksq_axes(nx, ny, nz, spacing))
     plan.set_power(*powertools.sigma_table(power, (nx, ny, nz), spacing))
 
-    # --- per-kernel timing (HIP events on the plan's stream, eager launches) ---
-    kern = np.zeros(5)
-    reps = max(3, min(args.steps, 10))
-    plan.realise(seed=1)
+    plan.realise(seed=1)                            # (untimed: the plan's buffers are touched before anything is timed, whatever W is)
     plan.sync()
-    for i in range(reps):
-        plan.realise(seed=100 + i)
-        plan.sync()
-        kern += np.array(plan.kernel_ms())
-    kern /= reps
-
-    # the graph-replayed realisations of the timed region put the z pass of slab s and the y pass of slab s + 1 into ONE launch
-    # (rf_k_yz.hip) where the shape allows: that launch, timed with an event behind every launch of eager realisations
-    merged_ms, merged_n = None, 0
-    try:
-        plan.set_merged_yz(2)
-        tot = cnt = 0
+    if args.full:
+        # --- per-kernel timing (HIP events on the plan's stream, eager launches) ---
+        kern = np.zeros(5)
+        reps = max(3, min(args.steps, 10))
         for i in range(reps):
-            plan.realise(seed=200 + i)
+            plan.realise(seed=100 + i)
             plan.sync()
-            ms, n_l = plan.merged_yz_ms()
-            tot += ms
-            cnt += n_l
-        merged_ms, merged_n = tot / cnt, cnt // reps
-    except RuntimeError:
-        pass                                        # (a shape rf_k_yz.hip does not serve: one launch per pass and slab, as timed above)
-    plan.set_merged_yz(1)
+            kern += np.array(plan.kernel_ms())
+        kern /= reps
+
+        # the graph-replayed realisations of the timed region put the z pass of slab s and the y pass of slab s + 1 into ONE launch
+        # (rf_k_yz.hip) where the shape allows: that launch, timed with an event behind every launch of eager realisations
+        merged_ms, merged_n = None, 0
+        try:
+            plan.set_merged_yz(2)
+            tot = cnt = 0
+            for i in range(reps):
+                plan.realise(seed=200 + i)
+                plan.sync()
+                ms, n_l = plan.merged_yz_ms()
+                tot += ms
+                cnt += n_l
+            merged_ms, merged_n = tot / cnt, cnt // reps
+        except RuntimeError:
+            pass                                    # (a shape rf_k_yz.hip does not serve: one launch per pass and slab, as timed above)
+        plan.set_merged_yz(1)
 
     # --- the timed region: W warm-up + K steps replayed from one hipGraph -----
     plan.realise_batch_prepare(args.steps)           # capture + instantiate outside the timed region
@@ -809,13 +882,18 @@ def main():
     wall = time.perf_counter() - t0
     gpu_ms = plan.elapsed_ms()
     mean, std = plan.moments()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan, mean, std)
 
-    nslab, slab_planes = plan.yz_slabs()
-    out = build_line((nx, ny, nz), args.steps, args.warmup, args.gpus, wall, gpu_ms, std, kern, merged_ms, merged_n, nslab, slab_planes)
+    if args.full:
+        nslab, slab_planes = plan.yz_slabs()
+        out = build_line((nx, ny, nz), args.steps, args.warmup, args.gpus, wall, gpu_ms, std, kern, merged_ms, merged_n, nslab, slab_planes)
+    else:
+        out = headline((nx, ny, nz), args.steps, args.warmup, args.gpus, wall, gpu_ms, std)
     plan.close()
-    if rank == 0 and args.gpus == 1 and not args.no_other_configs:
+    if rank == 0 and args.gpus == 1 and args.full and not args.no_other_configs:
         out["other_configs"] = other_configs(power, spacing, local_rank)
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.gpus == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(power, spacing, args.cpu_sample or args.edge)
         out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
     if rank == 0:

@@ -5,6 +5,8 @@ the GPU and the oracle).  The keys the driver and the review read, their units a
 import importlib.util
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -114,3 +116,71 @@ def test_other_configs_carry_every_baseline_configuration():
         # the direct exchange's stand-in (no copy kernel at all): far below the copy stand-in's
         for k in ("direct exchange stand-in, one stream", "direct exchange stand-in, storing y pass on the exchange stream"):
             assert 0 < e[k]["pipelined_ms_per_realisation"] < e["128 workgroups"]["pipelined_ms_per_realisation"]
+
+
+def test_plain_line_carries_the_headline_alone():
+    """headline() -- the line of a plain run, no --full -- holds the figures of the timed region and nothing that needs runs of its own;
+    build_line() (--full) is the same line with the extras added."""
+    b = _bench_module()
+    plain = b.headline((1024, 1024, 1024), 20, 5, 1, 0.0772, 77.0, 2.3137)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "gpu_ms_per_step_events"):
+        assert key in plain, key
+    assert not {"roofline", "pipeline", "cpu_baseline", "other_configs"} & set(plain)
+    assert plain["ms_per_step"] == pytest.approx(3.86, rel=1e-6) and plain["value"] == pytest.approx(1024 ** 3 / 3.86e-3 / 1e6, rel=1e-4)
+    assert plain["unit"] == "Mcells/s" and plain["higher_is_better"] is True and plain["dtype"] == "f32" and plain["steps"] == 20
+    full = _stub_line()
+    assert {k: v for k, v in full.items() if k in plain} == plain
+
+
+def test_bench_options():
+    """--full and --dump-outputs exist (argparse answers --help before anything loads HIP)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60, cwd=ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+class _HostPlan:
+    """What dump_outputs() reads of a DevicePlan, over a host array: rank `rank` of `world` x slabs"""
+
+    def __init__(self, field, rank=0, world=1):
+        self.field, self.rank = field, rank
+        self.nx, self.ny, self.nz = field.shape
+        self.nx_local = self.nx // world
+        self.real_dtype = field.dtype
+
+    def download_real(self, out=None, x0=0, x1=None):
+        lo = self.rank * self.nx_local
+        assert 0 <= x0 < x1 <= self.nx_local and out.shape == (x1 - x0, self.ny, self.nz) and out.flags.c_contiguous
+        out[...] = self.field[lo + x0:lo + x1]
+        return out
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_field(tmp_path, monkeypatch):
+    """The sample is the field at ascending, seeded positions (slab by slab download, a chunk smaller than the slab); the same call
+    writes the same files; N ranks write the cells of their own x slabs, which together are the one-rank sample."""
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 600)
+    field = np.random.default_rng(7).standard_normal((16, 12, 10)).astype(np.float32)
+    monkeypatch.setattr(b, "DUMP_CHUNK_BYTES", 3 * 12 * 10 * 4)
+    b.dump_outputs(str(tmp_path / "one"), _HostPlan(field), float(field.mean()), float(field.std()))
+    got = {n[:-4]: np.load(str(tmp_path / "one" / n)) for n in os.listdir(tmp_path / "one")}
+    assert sorted(got) == ["delta_moments", "delta_sample", "delta_sample_index", "delta_x0"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    idx = got["delta_sample_index"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < field.size and 400 < len(idx) <= 600
+    assert np.array_equal(got["delta_sample"], field.reshape(-1)[idx]) and np.array_equal(got["delta_x0"], field[0])
+    assert np.allclose(got["delta_moments"], [field.mean(), field.std()])
+    b.dump_outputs(str(tmp_path / "again"), _HostPlan(field), float(field.mean()), float(field.std()))
+    for n, v in got.items():
+        assert np.array_equal(np.load(str(tmp_path / "again" / (n + ".npy"))), v), n
+    for r in range(4):
+        b.dump_outputs(str(tmp_path / "four"), _HostPlan(field, rank=r, world=4), float(field.mean()), float(field.std()), rank=r, world=4)
+    parts = [np.load(str(tmp_path / "four" / ("delta_sample_index_rank%d.npy" % r))) for r in range(4)]
+    assert np.array_equal(np.concatenate(parts), got["delta_sample_index"])
+    assert np.array_equal(np.concatenate([np.load(str(tmp_path / "four" / ("delta_sample_rank%d.npy" % r))) for r in range(4)]),
+                          got["delta_sample"])
+    assert np.array_equal(np.load(str(tmp_path / "four" / "delta_x0.npy")), field[0])
+    # a grid no larger than the sample is written whole
+    small = field[:2, :3, :4].copy()
+    b.dump_outputs(str(tmp_path / "small"), _HostPlan(small), 0.0, 1.0)
+    assert np.array_equal(np.load(str(tmp_path / "small" / "delta_sample.npy")), small.reshape(-1))

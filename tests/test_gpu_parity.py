@@ -1888,7 +1888,7 @@ def test_slabs_and_blocked_intermediate_only_move_data(hip, dpower, shape, dtype
 
 
 def test_bench_multi_gpu_code_path_with_one_rank(hip):
-    """`bench.py --force-multi` runs main_multi -- DistributedPlan, the deadline-guarded first exchange, the pipelined slab
+    """`bench.py --force-multi --full` runs main_multi -- DistributedPlan, the deadline-guarded first exchange, the pipelined slab
     batch, the RCCL all-reduces (a one-rank communicator) -- as a child process on one GPU and prints a well-formed line."""
     import json
     import os
@@ -1897,7 +1897,7 @@ def test_bench_multi_gpu_code_path_with_one_rank(hip):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-multi", "--steps", "3", "--warmup", "1",
-                        "--edge", "256", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--edge", "256", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["steps"] == 3 and line["unit"] == "Mcells/s" and line["value"] > 0
@@ -1914,6 +1914,77 @@ def test_bench_multi_gpu_code_path_with_one_rank(hip):
     cross = line["config"]["exchange_cross_check"]
     assert cross["agree"] is True and cross["other_mode"] != line["config"]["multi_gpu_mode"]
     assert abs(cross["rms_timed_mode"] - line["config"]["rms_last"]) < 1e-5
+
+
+def test_bench_plain_run_dumps_its_last_timed_field(hip, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line alone, and --dump-outputs writes what its last timed step computed:
+    the sampled cells, the plane x = 0 and the moments of that seed's field realised once more here.  Two runs with the same
+    arguments write the same field values."""
+    import json
+    import subprocess
+    import sys
+    from randomfield_amd import powertools
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, edge = 3, 256
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--edge", str(edge), "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["unit"] == "Mcells/s" and line["config"]["grid"] == [edge] * 3
+    assert not {"roofline", "pipeline", "other_configs", "cpu_baseline"} & set(line), "a plain run measures the headline alone"
+    names = ["delta_moments.npy", "delta_sample.npy", "delta_sample_index.npy", "delta_x0.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(os.listdir(tmp_path / "b")) == names
+    out = {n[:-4]: np.load(str(tmp_path / "a" / n)) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values()) and sum(v.nbytes for v in out.values()) <= 64 << 20
+    for n in ("delta_sample.npy", "delta_sample_index.npy", "delta_x0.npy"):
+        assert np.array_equal(np.load(str(tmp_path / "b" / n)), out[n[:-4]]), n
+    plan = hip.DevicePlan(edge, edge, edge, np.complex64)
+    plan.set_kgrid(*powertools.ksq_axes(edge, edge, edge, 2.5))
+    plan.set_power(*powertools.sigma_table(powertools.load_default_power(), (edge, edge, edge), 2.5))
+    plan.realise(seed=123 + steps - 1)                                    # the seed of the last timed step
+    field = plan.download_real()
+    mean, rms = plan.moments()
+    plan.close()
+    idx = out["delta_sample_index"].astype(np.int64)
+    assert len(idx) > 1000 and np.all(np.diff(idx) > 0) and idx[-1] < edge ** 3
+    assert np.max(np.abs(out["delta_sample"] - field.reshape(-1)[idx])) <= 1e-6 * rms
+    assert np.max(np.abs(out["delta_x0"] - field[0])) <= 1e-6 * rms
+    assert abs(out["delta_moments"][1] - rms) <= 1e-6 * rms and abs(out["delta_moments"][0] - mean) <= 1e-6 * rms
+    assert abs(line["config"]["rms_last"] - rms) <= 1e-5
+
+
+def test_bench_multi_gpu_code_path_plain_run_dumps_its_last_timed_field(hip, tmp_path):
+    """`bench.py --force-multi` without --full: the slab pipeline's line without the comparators, and --dump-outputs writes the field of
+    the last timed realisation (the single-GPU field of that seed)."""
+    import json
+    import subprocess
+    import sys
+    from randomfield_amd import powertools
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, edge = 3, 256
+    env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-multi", "--steps", str(steps), "--warmup", "1",
+                        "--edge", str(edge), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["config"]["multi_gpu_mode"] in ("rccl", "direct")
+    assert "single_gpu_equivalent" not in line and "exchange_cross_check" not in line["config"]
+    assert "kernel_ms_rank0_unpipelined_step" not in line["pipeline"]
+    plan = hip.DevicePlan(edge, edge, edge, np.complex64)
+    plan.set_kgrid(*powertools.ksq_axes(edge, edge, edge, 2.5))
+    plan.set_power(*powertools.sigma_table(powertools.load_default_power(), (edge, edge, edge), 2.5))
+    plan.realise(seed=123 + steps - 1)
+    field = plan.download_real()
+    mean, rms = plan.moments()
+    plan.close()
+    idx = np.load(str(tmp_path / "delta_sample_index.npy")).astype(np.int64)
+    assert len(idx) > 1000
+    assert np.max(np.abs(np.load(str(tmp_path / "delta_sample.npy")) - field.reshape(-1)[idx])) <= 1e-6 * rms
+    assert np.max(np.abs(np.load(str(tmp_path / "delta_x0.npy")) - field[0])) <= 1e-6 * rms
+    assert abs(np.load(str(tmp_path / "delta_moments.npy"))[1] - rms) <= 1e-6 * rms
 
 
 def test_two_distributed_plans_in_a_row(hip, dpower, monkeypatch, tmp_path):
