@@ -9,6 +9,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
+#include <pthread.h>
+#include <thread>
 #include <vector>
 #include "../rf_configs.h"
 #include "../rf_host.h"
@@ -496,48 +499,102 @@ int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, d
 }
 
 
-// ---- non-power-of-two path (rf_generic.h): the same block functions the kernels run, one "thread" per block ----
+// ---- non-power-of-two path (rf_generic.h): the same block functions the kernels run ----
+// One "thread" per block by default (tid, nth) = (0, 1) with a no-op barrier; with emu_set_generic_threads(nth > 1) every block is run by
+// nth host threads that share the block's LDS image and meet at a real barrier wherever the kernels call __syncthreads() -- the
+// kernels' own thread walk (GenericWalk::fixed when nth % tile == 0), four loads in flight, per-thread stores and barrier placement.
 struct NoSync { void operator()() const {} };
+struct BarrierSync {
+  pthread_barrier_t* bar;
+  void operator()() const { pthread_barrier_wait(bar); }
+};
 
-// The library's sequences (rf_generic.h generic_*_seq) with every launch replaced by a loop over its blocks, one "thread" each.
+// The library's sequences (rf_generic.h generic_*_seq) with every launch replaced by a loop over its blocks.
 // g_generic_cap: the longest line kept "in LDS" -- the library's cap is 8192 / 4096; tests lower it so that small grids take the
 // four-step form of the long axes.
 int g_generic_cap = 0;                  // 0: generic_max_axis(dtype)
 int g_generic_tile = 3;                 // lines per block of the strided passes: 3 = deliberately not dividing the line counts (the walk by
                                         // index); 1 = the kernels' walk, a thread staying on one line (GenericWalk::fixed)
+int g_generic_threads = 1;              // host threads per block (1: the single-thread emulation)
+
+// body(tid, sync) on g_generic_threads host threads (thread 0 is the caller); body loops over the blocks of one launch itself and
+// calls sync() after each block, which stands for the workgroup boundary: the LDS image is reused by the next block
+template <class Body> void run_generic_threads(Body body) {
+  const int nth = g_generic_threads;
+  if (nth <= 1) { body(0, NoSync()); return; }
+  pthread_barrier_t bar;
+  pthread_barrier_init(&bar, nullptr, (unsigned)nth);
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nth; ++t) pool.emplace_back([&body, &bar, t] { body(t, BarrierSync{&bar}); });
+  body(0, BarrierSync{&bar});
+  for (auto& th : pool) th.join();
+  pthread_barrier_destroy(&bar);
+}
+
 template <typename T> struct EmuGenericOps {
   const cplx<T>*rx, *ry, *rz;
   int nx, ny, nz, M;                    // M = row length of the contiguous complex transform's root table / 2 (packed) -- see callers
   long long rows;
-  std::vector<cplx<T>> lds;
+  // the block's LDS: exactly the bytes the launchers ask for with the stage and position tables switched on (rf_k_generic.hip
+  // strided_shape / row_shape), on the heap -- an index past them is a heap overrun for AddressSanitizer
+  std::unique_ptr<unsigned char[]> lds_raw;
   double s1 = 0, s2 = 0;
   const cplx<T>* root(int which) const { return which == 0 ? rx : (which == 1 ? ry : rz); }
+  cplx<T>* lds_image(const GenericAxis& ax, int pitch) {
+    const size_t bytes = (size_t)generic_bufs(ax) * ax.n * pitch * sizeof(cplx<T>) + generic_extra_bytes(ax, (int)sizeof(cplx<T>));
+    lds_raw.reset(new unsigned char[bytes]);
+    return reinterpret_cast<cplx<T>*>(lds_raw.get());
+  }
+  int nthreads() const { return g_generic_threads > 1 ? g_generic_threads : 1; }
+  // rows per block of the contiguous passes: 2 for the single thread; the kernels' 8 / 4 (rows_per_block) with threads
+  int row_tile() const { return g_generic_threads > 1 ? (g_generic_tile < 8 ? g_generic_tile : 8) : 2; }
   int axis(const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    const int TC = g_generic_tile;
-    lds.resize(2 * (size_t)ax.n * TC + 2 * ax.n + 4);
-    for (long long b = 0; b * TC < nlines; ++b)
-      generic_axis_block<T>((const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds.data(), b, 0, 1, NoSync(), 1);
+    const int TC = g_generic_tile, nth = nthreads();
+    cplx<T>* lds = lds_image(ax, TC);
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TC < nlines; ++b) {
+        generic_axis_block<T>((const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
     return 0;
   }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
-    const int TC = g_generic_tile;
-    lds.resize(2 * (size_t)L.ax.n * TC + 2 * L.ax.n + 4);
-    for (long long b = 0; b * TC < L.nlines(); ++b)
-      generic_lines_block<T>((const cplx<T>*)src, (cplx<T>*)dst, L, TC, root(which), lds.data(), b, 0, 1, NoSync(), 1);
+    const int TC = g_generic_tile, nth = nthreads();
+    cplx<T>* lds = lds_image(L.ax, TC);
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TC < L.nlines(); ++b) {
+        generic_lines_block<T>((const cplx<T>*)src, (cplx<T>*)dst, L, TC, root(which), lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
     return 0;
   }
   GenericAxis az;
   int row_c2r(const void* G, void* W, double scale) {
-    const int TR = 2;
-    lds.resize(2 * (size_t)az.n * generic_row_pitch(TR) + 2 * az.n + 4);
-    for (long long b = 0; b * TR < rows; ++b)
-      generic_row_c2r_block<T>((const cplx<T>*)G, (T*)W, az, rows, TR, rz, (T)scale, lds.data(), b, 0, 1, NoSync(), s1, s2, 1);
+    const int TR = row_tile(), nth = nthreads();
+    cplx<T>* lds = lds_image(az, generic_row_pitch(TR));
+    std::vector<double> p1(nth, 0.0), p2(nth, 0.0);          // every thread's share of (sum, sum of squares)
+    run_generic_threads([&](int tid, auto sync) {
+      double a1 = 0, a2 = 0;
+      for (long long b = 0; b * TR < rows; ++b) {
+        generic_row_c2r_block<T>((const cplx<T>*)G, (T*)W, az, rows, TR, rz, (T)scale, lds, b, tid, nth, sync, a1, a2, 1);
+        sync();
+      }
+      p1[tid] = a1; p2[tid] = a2;
+    });
+    for (int t = 0; t < nth; ++t) { s1 += p1[t]; s2 += p2[t]; }      // in thread order: deterministic
     return 0;
   }
   int row_r2c(const void* W, void* G) {
-    const int TR = 2;
-    lds.resize(2 * (size_t)az.n * generic_row_pitch(TR) + 2 * az.n + 4);
-    for (long long b = 0; b * TR < rows; ++b) generic_row_r2c_block<T>((const T*)W, (cplx<T>*)G, az, rows, TR, rz, lds.data(), b, 0, 1, NoSync(), 1);
+    const int TR = row_tile(), nth = nthreads();
+    cplx<T>* lds = lds_image(az, generic_row_pitch(TR));
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TR < rows; ++b) {
+        generic_row_r2c_block<T>((const T*)W, (cplx<T>*)G, az, rows, TR, rz, lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
     return 0;
   }
   int untangle(const void* G, void* Z) { for (long long i = 0; i < rows * M; ++i) generic_untangle_at<T>((const cplx<T>*)G, (cplx<T>*)Z, M, rz, i); return 0; }
@@ -569,7 +626,7 @@ int generic_c2r_impl(int nx, int ny, int nz, const cplx<T>* K, T* W, double* s1,
   const long long nzh = nz / 2 + 1;
   auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
   std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
-  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny};
+  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
   ops.az = d.az;
   const int rc = generic_c2r_seq(ops, d, K, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
   if (s1) *s1 = ops.s1;
@@ -584,7 +641,7 @@ int generic_r2c_impl(int nx, int ny, int nz, const T* W, cplx<T>* K) {
   const long long nzh = nz / 2 + 1;
   auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
   std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
-  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny};
+  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
   ops.az = d.az;
   return generic_r2c_seq(ops, d, W, K, G.data(), G2.data());
 }
@@ -595,7 +652,7 @@ int generic_c2c_impl(int nx, int ny, int nz, int dir, cplx<T>* D) {
   if (!emu_dims<T>(nx, ny, nz, false, d)) return -1;
   auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
   std::vector<cplx<T>> G((size_t)nx * ny * nz);
-  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz, (long long)nx * ny};
+  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz, (long long)nx * ny, nullptr};
   ops.az = d.az;
   return generic_c2c_seq(ops, d, D, G.data(), dir, dir > 0 ? 1.0 / ((double)nx * ny * nz) : 1.0);
 }
@@ -781,6 +838,9 @@ int emu_set_rowblock(int rb) { const int old = g_rowblock; g_rowblock = rb; retu
 // form -- lowered by tests so that small grids exercise it
 int emu_set_generic_cap(int cap) { const int old = g_generic_cap; g_generic_cap = cap; return old; }
 int emu_set_generic_tile(int tc) { const int old = g_generic_tile; g_generic_tile = tc > 0 ? tc : 3; return old; }
+// host threads per block of the generic path (1, the default: one "thread" with a no-op barrier).  With nth > 1 the block functions
+// run on nth threads with a real barrier; nth a multiple of the tile takes the kernels' own walk (GenericWalk::fixed)
+int emu_set_generic_threads(int nth) { const int old = g_generic_threads; g_generic_threads = nth > 1 ? (nth < 1024 ? nth : 1024) : 1; return old; }
 // 1 (default): the float32 generation pass of length 1024 on tile pairs (ColPair), as the product; 0: one tile per workgroup (ColFFT)
 int emu_set_pairs(int on) { const int old = g_pairs; g_pairs = on; return old; }
 // FastGenColIOT::share_row (rf_fft_gen.h): the butterfly row of slot jl when L butterflies are dealt to slots of S per wave so that

@@ -17,9 +17,9 @@ def _dp(a):
 
 
 def build(force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("emu/rf_emu.cpp", "rf_core.h", "rf_fft.h", "rf_configs.h", "rf_host.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("emu/rf_emu.cpp", "rf_core.h", "rf_fft.h", "rf_configs.h", "rf_host.h", "rf_generic.h")]
     if force or not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SO, srcs[0]])
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-o", SO, srcs[0]])
     return SO
 
 
@@ -173,3 +173,20 @@ def generic_c2c(data, inverse):
                                out.ctypes.data_as(ctypes.c_void_p))
     assert rc == 0, rc
     return out
+
+
+class generic_threads:
+    """Context manager: the generic block functions on `nth` host threads with a real barrier (emu_set_generic_threads) and `tile`
+    lines per block (emu_set_generic_tile); nth a multiple of the tile is the kernels' own thread walk."""
+
+    def __init__(self, nth, tile):
+        self.nth, self.tile = nth, tile
+
+    def __enter__(self):
+        self.old = (lib().emu_set_generic_threads(self.nth), lib().emu_set_generic_tile(self.tile))
+        return self
+
+    def __exit__(self, *exc):
+        lib().emu_set_generic_threads(self.old[0])
+        lib().emu_set_generic_tile(self.old[1])
+        return False

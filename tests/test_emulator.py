@@ -520,3 +520,98 @@ def test_axes_too_long_for_one_line_take_the_four_step_form(shape, cap):
     finally:
         emu_util.lib().emu_set_generic_cap(old)
         emu_util.lib().emu_set_generic_tile(3)
+
+
+# ---- the generic block functions on real host threads: the kernels' own thread walk, LDS tables and barriers ----------------------
+# (nth, tile): nth % tile == 0, so GenericWalk::fixed holds as in every kernel launch (rf_k_generic.hip strided_shape: tile 16 / 8 / 4
+# with 256 ... 1024 threads); the contiguous passes take min(tile, 8) rows per block (rows_per_block: 8 / 4)
+THREADED = [(16, 4), (16, 8), (16, 16), (32, 4), (32, 8), (32, 16)]
+# packed line counts ny * nzh, nx * nzh with nzh odd: no multiple of the tiles (70 / 98 / 140 rows; 182 / 130 / 140;
+# 630 / 420 / 600); (6, 50, 20): a radix-5 axis, 550 / 66 lines; (14, 22, 52): the primes 7, 11, 13 -- the two-buffer form.
+# (A barrier among 32 host threads costs tens of microseconds, and a grid of (40, 60, 80) has 10^5 of them per transform: the grids
+# stay small, the tolerances do not move.)
+THREADED_SHAPES = [(4, 6, 8), (14, 10, 12), (10, 14, 24), (6, 50, 20), (14, 22, 52), (20, 30, 40)]
+
+
+def _generic_all(shape, ct, rt, seed):
+    """c2r (+ moments), r2c, c2c forward and inverse of fixed random inputs through the emulator's generic path"""
+    rng = np.random.RandomState(seed)
+    nx, ny, nz = shape
+    ks = (rng.normal(size=(nx, ny, nz // 2 + 1)) + 1j * rng.normal(size=(nx, ny, nz // 2 + 1))).astype(ct)
+    f = rng.normal(size=shape).astype(rt)
+    a = (rng.normal(size=shape) + 1j * rng.normal(size=shape)).astype(ct)
+    out, s1, s2 = emu_util.generic_c2r(ks)
+    return dict(ks=ks, f=f, a=a, c2r=out, s1=s1, s2=s2, r2c=emu_util.generic_r2c(f), fwd=emu_util.generic_c2c(a, False),
+                inv=emu_util.generic_c2c(a, True))
+
+
+def _check_generic_against_numpy(shape, got, tol):
+    ref = np.fft.irfftn(got["ks"].astype(np.complex128), s=shape, axes=(0, 1, 2))
+    assert np.max(np.abs(got["c2r"] - ref)) <= tol * ref.std()
+    assert abs(got["s1"] - ref.sum()) <= 10 * tol * ref.std() * ref.size and abs(got["s2"] - (ref ** 2).sum()) <= 10 * tol * (ref ** 2).sum()
+    ref = np.fft.rfftn(got["f"].astype(np.float64))
+    assert np.max(np.abs(got["r2c"] - ref)) <= tol * np.abs(ref).std() * 4
+    for key, fn in (("fwd", np.fft.fftn), ("inv", np.fft.ifftn)):
+        ref = fn(got["a"].astype(np.complex128))
+        assert np.max(np.abs(got[key] - ref)) <= tol * np.abs(ref).std() * 4
+
+
+@pytest.mark.parametrize("shape", THREADED_SHAPES)
+def test_generic_blocks_on_host_threads_against_numpy(shape):
+    """The statements of generic_axis_block / generic_row_*_block that only a multi-thread block reaches -- the fixed walk's four
+    loads in flight, its per-thread store walk, the tile-wide LDS images with the stage and position tables staged behind them, and
+    every barrier -- on 16 and 32 host threads per block with 4, 8 and 16 lines per block, the LDS sized to the byte as the launchers
+    size it.  Same tolerances as the single-thread cases; and since every element sees the same butterflies in the same order, the
+    arrays are bit-identical to the single-thread run (the moments are sums in another order: compared at 1e-12)."""
+    for ct, rt, tol in ((np.complex64, np.float32, 3e-6), (np.complex128, np.float64, 3e-14)):
+        one = _generic_all(shape, ct, rt, 5)
+        _check_generic_against_numpy(shape, one, tol)
+        for nth, tile in THREADED:
+            with emu_util.generic_threads(nth, tile):
+                got = _generic_all(shape, ct, rt, 5)
+            _check_generic_against_numpy(shape, got, tol)
+            for key in ("c2r", "r2c", "fwd", "inv"):
+                assert np.array_equal(got[key], one[key]), (nth, tile, key)
+            assert abs(got["s1"] - one["s1"]) <= 1e-12 * np.abs(one["c2r"]).sum() and abs(got["s2"] - one["s2"]) <= 1e-12 * one["s2"]
+
+
+@pytest.mark.parametrize("name", ["stages_4x6x8_c64.npz", "stages_6x4x12_c64.npz", "stages_4x6x8_c128.npz"])
+def test_generic_c2r_on_host_threads_reproduces_reference_fields(name):
+    """The reference's own k-space -> delta(x) pairs (tests/test_transform.py:11) through the threaded blocks."""
+    g = golden(name)
+    tol = 1e-6 if g["kspace"].dtype == np.complex64 else 1e-14
+    one = emu_util.generic_c2r(g["kspace"])[0]
+    for nth, tile in THREADED:
+        with emu_util.generic_threads(nth, tile):
+            out, s1, s2 = emu_util.generic_c2r(g["kspace"])
+        assert np.max(np.abs(out - g["delta"])) <= tol * float(g["rms"])
+        assert np.array_equal(out, one)
+        n = out.size
+        assert abs(np.sqrt(s2 / n - (s1 / n) ** 2) - float(g["rms"])) <= 10 * tol * float(g["rms"])
+
+
+@pytest.mark.parametrize("shape,cap", [((12, 10, 24), 8), ((6, 100, 16), 12), ((4, 6, 192), 16), ((22, 26, 12), 14)])
+def test_four_step_form_on_host_threads(shape, cap):
+    """generic_lines_block with threads: the fixed walk's twiddle index advanced per element ((e q) mod n as a running sum), its four
+    loads in flight and the sub-line bases formed once per thread, every axis long in turn (cap lowered as in the single-thread test);
+    (22, 26, 12): 2 x 11 and 2 x 13 -- prime factors in both steps, line counts (182, 154) that divide no tile."""
+    nx, ny, nz = shape
+    old = emu_util.lib().emu_set_generic_cap(cap)
+    try:
+        for ct, rt, tol in ((np.complex64, np.float32, 4e-6), (np.complex128, np.float64, 4e-14)):
+            one = _generic_all(shape, ct, rt, 7)
+            for nth, tile in THREADED:
+                with emu_util.generic_threads(nth, tile):
+                    got = _generic_all(shape, ct, rt, 7)
+                ref = np.fft.irfftn(got["ks"].astype(np.complex128), s=shape, axes=(0, 1, 2))
+                assert np.max(np.abs(got["c2r"] - ref)) <= tol * ref.std()
+                assert abs(got["s1"] - ref.sum()) <= 10 * tol * ref.std() * ref.size and abs(got["s2"] - (ref ** 2).sum()) <= 10 * tol * (ref ** 2).sum()
+                ref = np.fft.rfftn(got["f"].astype(np.float64))
+                assert np.max(np.abs(got["r2c"] - ref)) <= tol * np.abs(ref).std() * 4
+                for key, fn in (("fwd", np.fft.fftn), ("inv", np.fft.ifftn)):
+                    ref = fn(got["a"].astype(np.complex128))
+                    assert np.max(np.abs(got[key] - ref)) <= tol * np.abs(ref).std() * 4
+                for key in ("c2r", "r2c", "fwd", "inv"):
+                    assert np.array_equal(got[key], one[key]), (nth, tile, key)
+    finally:
+        emu_util.lib().emu_set_generic_cap(old)

@@ -1354,8 +1354,9 @@ GENERIC_SHAPES = [(40, 60, 80), (10, 14, 24), (12, 18, 8), (26, 34, 44), (24, 8,
 @pytest.mark.parametrize("shape", GENERIC_SHAPES)
 def test_generic_shapes_against_oracle(hip, dpower, shape):
     """Any even shape runs on the GPU (transform.py:172-177 asks for nothing more; (40, 60, 80) is the shape of the
-    reference's tests/test_random.py:12-22): same-noise field, rms, k-space, forward transform and potential
-    against the oracle / numpy, float32 and float64."""
+    reference's tests/test_random.py:12-22): same-noise field, rms, k-space, forward transform and the native
+    generator's field against the oracle / numpy, float32 and float64 (tests/test_gpu_generic.py does the same on grids where
+    every pass has many workgroups)."""
     nx, ny, nz = shape
     k, Pk = dpower
     spacing = 2.5 if max(shape) <= 100 else 0.5                  # keep the grid's k range inside the table
@@ -1376,13 +1377,19 @@ def test_generic_shapes_against_oracle(hip, dpower, shape):
         plan.execute_r2c()
         back = plan.download_k()
         assert np.max(np.abs(back - kref)) <= 20 * tol * np.max(np.abs(kref))
-        # native generator: deterministic, right amplitude (statistics need cells: skip the tiny grids)
+        # native generator: value by value against the oracle's restatement of the same stream (the default fast flavour at
+        # 1e-5 * rms, the exact chain at the dtype's tolerance), and deterministic
+        nnoise = cpu_ref.native_noise(3, nx, ny, nz, dtype)
+        nref, nrms = cpu_ref.generate_delta_field(nx, ny, nz, spacing, k, Pk, noise=nnoise, dtype=dtype, double_fft=True)
         plan.realise(seed=3)
         a = plan.download_real()
+        assert np.max(np.abs(a - nref)) <= 1e-5 * nrms and abs(plan.moments()[1] - nrms) <= 1e-5 * nrms
         plan.realise(seed=3)
         assert np.array_equal(a, plan.download_real())
-        if nx * ny * nz >= 4000:
-            assert abs(plan.moments()[1] / rms - 1) < 0.5
+        plan.set_exact_generation(True)
+        plan.realise(seed=3)
+        assert np.max(np.abs(plan.download_real() - nref)) <= tol * nrms
+        plan.set_exact_generation(False)
         rms_b = plan.realise_batch([3, 4, 5])
         assert abs(rms_b[0] - float(np.std(a.astype(np.float64)))) <= 10 * tol * rms and len(set(rms_b)) == 3
         plan.close()

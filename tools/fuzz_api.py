@@ -60,7 +60,7 @@ def main():
                 field = p.download_real()
                 noise = cpu_ref.native_noise(seed, nx, ny, nz, ct)
                 ref, rms = cpu_ref.generate_delta_field(nx, ny, nz, SPACING, k, Pk, noise=noise, dtype=ct, double_fft=True)
-                assert np.max(np.abs(field - ref)) <= 2e-5 * rms, ("native", shape, ct)
+                assert np.max(np.abs(field - ref)) <= 1e-5 * rms, ("native", shape, ct)
             elif op == "gen":
                 seed = int(rng.randint(1, 2 ** 31))
                 p.generate(seed=seed)
