@@ -43,7 +43,7 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * this repository returned the constant 1 while the surface grew from ~20 to 70 entry points; 5.0 is the first version that means
  * something: the consumer surface below + the diagnostics of randomfield_hip_diag.h.) */
 #define RF_ABI_MAJOR 5
-#define RF_ABI_MINOR 3
+#define RF_ABI_MINOR 4
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
 int rf_version(void);                            /* (major << 16) | minor */
 /* bit mask of the groups of entry points this build exports (each bit: every function of the group is present and works as this
@@ -63,7 +63,8 @@ enum {
   RF_FEATURE_GENERIC_SHAPES = 1 << 9,      /* every even shape (axes of up to 8192 complex64 / 4096 complex128 points, or two factors that fit): rf_shape_supported(_dtype) == 2 */
   RF_FEATURE_EXCHANGE_CHUNKS = 1 << 10,    /* RF_FLAG_EXCHANGE_CHUNKS */
   RF_FEATURE_DIRECT_EXCHANGE = 1 << 12,    /* rf_comm_enable_direct: the y pass stores into the peers' receive buffers (IPC-mapped), no all-to-all kernels */
-  RF_FEATURE_DIAGNOSTICS = 1 << 11         /* the entry points of randomfield_hip_diag.h (timing per kernel, launch structure, virtual ranks) */
+  RF_FEATURE_DIAGNOSTICS = 1 << 11,        /* the entry points of randomfield_hip_diag.h (timing per kernel, launch structure, virtual ranks) */
+  RF_FEATURE_GENERIC_FUSED = 1 << 13       /* RF_FLAG_FUSED_GENERIC_GENERATION; rf_kernel_ms on generic plans */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -100,9 +101,16 @@ int rf_plan_nbytes(rf_plan* plan, size_t* nbytes);          /* transform.py:221,
  * RF_FLAG_EXCHANGE_CHUNKS = 32 (multi-rank plans in exchange mode; the value is a count, a power of two): the rank's kz slab is
  * generated, x- and y-transformed and SENT as `value` sub-slabs, so that inside ONE realisation (one generate_delta_field call,
  * generate.py:144-230) the all-to-all of sub-slab c runs on a second stream under the forward passes of sub-slab c + 1 instead of
- * behind all of them; the gathering z pass reads ranks x value segments per row.  1 (default) = one exchange of the whole slab. */
+ * behind all of them; the gathering z pass reads ranks x value segments per row.  1 (default) = one exchange of the whole slab.
+ * RF_FLAG_FUSED_GENERIC_GENERATION = 64 (default OFF; packed single-rank plans on the generic kernels, rf_shape_supported == 2; refused
+ * elsewhere): rf_realise and rf_realise_batch generate the half spectrum inside the first FFT pass instead of storing it and reading
+ * it back -- 5 sweeps of the half spectrum instead of 7 and no k-space array; the field and its moments are bit-identical.  As on
+ * the tiled kernels, such a realisation leaves NO k space behind: rf_download_k reports "no k-space data" on a fresh plan, and an
+ * array left by rf_generate / rf_upload_k stays as it was.  rf_generate, rf_execute_c2r, rf_realise_potential, rf_execute_r2c are
+ * unaffected.  (A plan whose x axis is too long for one LDS line -- the four-step form -- accepts the flag and generates into a
+ * scratch array instead: same contract, no saving.) */
 enum { RF_FLAG_EXACT_GENERATION = 1, RF_FLAG_FORCE_SLAB_PATH = 2, RF_FLAG_REPLICATED_GENERATION = 4, RF_FLAG_TRANSPOSED_INTERMEDIATE = 8,
-       RF_FLAG_YZ_SLAB_PLANES = 16, RF_FLAG_EXCHANGE_CHUNKS = 32 };
+       RF_FLAG_YZ_SLAB_PLANES = 16, RF_FLAG_EXCHANGE_CHUNKS = 32, RF_FLAG_FUSED_GENERIC_GENERATION = 64 };
 int rf_plan_set_flag(rf_plan* plan, int flag, int value);
 /* run on a caller-owned HIP stream (hipStream_t passed as void*); NULL restores the plan's own stream */
 int rf_plan_set_stream(rf_plan* plan, void* hip_stream);

@@ -27,10 +27,10 @@ _c_dp = ctypes.POINTER(ctypes.c_double)
 
 # the ABI this binding was written against (include/randomfield_hip.h RF_ABI_MAJOR / RF_ABI_MINOR): load() refuses a library of
 # another major version or an older minor one
-ABI_MAJOR, ABI_MINOR = 5, 3
+ABI_MAJOR, ABI_MINOR = 5, 4
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
-            "diagnostics": 1 << 11, "direct_exchange": 1 << 12}
+            "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -239,6 +239,7 @@ class DevicePlan(object):
         # deviates / the power and k tables of this device plan change, whoever changes them
         self.noise_epoch = 0
         self.power_epoch = 0
+        self._fused_generation = False
         if self.unpacked:
             if nranks != 1:
                 raise ValueError("unpacked c2c plans are single-GPU")
@@ -305,6 +306,18 @@ class DevicePlan(object):
         size, the y pass runs in place there and the z pass gathers from it into the field buffer (RF_FLAG_TRANSPOSED_INTERMEDIATE:
         5 % faster at 2048^3 float32, slower at 1024^3, twice the device memory)."""
         check(self._lib.rf_plan_set_flag(self._h, 8, int(bool(on))), "rf_plan_set_flag")
+
+    def set_fused_generation(self, on=True):
+        """Plans on the generic kernels (``tiled`` is False; packed, one rank): ``realise`` / ``realise_batch`` generate the half
+        spectrum inside the first FFT pass instead of writing it out and reading it back (RF_FLAG_FUSED_GENERIC_GENERATION).  Same
+        field bit for bit; like a tiled plan, the realisation then leaves no k space for ``download_k``.  Refused on other plans."""
+        check(self._lib.rf_plan_set_flag(self._h, 64, int(bool(on))), "rf_plan_set_flag")
+        self._fused_generation = bool(on)
+
+    @property
+    def fused_generation(self):
+        """Whether :meth:`set_fused_generation` is on (read-only)."""
+        return self._fused_generation
 
     def set_yz_slab_planes(self, planes=-1):
         """x planes per slab of the y / z passes (single-GPU plans): -1 automatic (about the Infinity Cache's size), 0 = whole grid."""
@@ -798,6 +811,6 @@ class DevicePlan(object):
         return n.value, b.value
 
     def kernel_ms(self):
-        ms = (ctypes.c_float * 5)()      # x (main kernel), y, z, reduce, x kz=0 repair launch
+        ms = (ctypes.c_float * 5)()      # x (main kernel), y, z, reduce, x kz=0 repair launch (generic plans: [4] = the separate generation launch)
         check(self._lib.rf_kernel_ms(self._h, ms), "rf_kernel_ms")
         return list(ms)

@@ -559,6 +559,25 @@ template <typename T> struct EmuGenericOps {
     });
     return 0;
   }
+  // generic_realise_seq: the x pass with the generator as its source, and the generation alone (rows K,T,R,S, API layout)
+  int axis_gen(const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    const int TC = g_generic_tile, nth = nthreads();
+    cplx<T>* lds = lds_image(ax, TC);
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TC < nlines; ++b) {
+        generic_axis_gen_block<T>(gp, gp.seed, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
+    return 0;
+  }
+  int gen_kspace(const GenParams& gp, void* K) {
+    const int nzh = gp.nz / 2 + 1;
+    for (int ix = 0; ix < gp.nx; ++ix)
+      for (int iy = 0; iy < gp.ny; ++iy)
+        for (int iz = 0; iz < nzh; ++iz) ((cplx<T>*)K)[((size_t)ix * gp.ny + iy) * nzh + iz] = gen_cell<T>(gp, gp.seed, ix, iy, iz);
+    return 0;
+  }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     const int TC = g_generic_tile, nth = nthreads();
     cplx<T>* lds = lds_image(L.ax, TC);
@@ -629,6 +648,22 @@ int generic_c2r_impl(int nx, int ny, int nz, const cplx<T>* K, T* W, double* s1,
   EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
   ops.az = d.az;
   const int rc = generic_c2r_seq(ops, d, K, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
+  if (s1) *s1 = ops.s1;
+  if (s2) *s2 = ops.s2;
+  return rc;
+}
+
+// a realisation with the generation inside the x pass (rf_generic.h generic_realise_seq; an x axis beyond the cap: its unfused fallback)
+template <typename T>
+int generic_realise_impl(int nx, int ny, int nz, const GenParams& gp, T* W, double* s1, double* s2) {
+  GenericDims d;
+  if (!emu_dims<T>(nx, ny, nz, true, d)) return -1;
+  const long long nzh = nz / 2 + 1;
+  auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
+  std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
+  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
+  ops.az = d.az;
+  const int rc = generic_realise_seq(ops, d, gp, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
   if (s1) *s1 = ops.s1;
   if (s2) *s2 = ops.s2;
   return rc;
@@ -743,6 +778,14 @@ int emu_row_lookup(const unsigned long long* first, int nseg, unsigned long long
 int emu_generic_c2r(int f64, int nx, int ny, int nz, const void* K, void* W, double* s1, double* s2) {
   return f64 ? generic_c2r_impl<double>(nx, ny, nz, (const cplx<double>*)K, (double*)W, s1, s2)
              : generic_c2r_impl<float>(nx, ny, nz, (const cplx<float>*)K, (float*)W, s1, s2);
+}
+// emu_generate_kspace + emu_generic_c2r in one: the generation inside the x pass (honours emu_set_generic_threads / _tile / _cap)
+int emu_generic_realise(int f64, int nx, int ny, int nz, const double* kx2, const double* ky2, const double* kz2,
+                        const double* log10k, const double* sigma, int nt, int noise_mode, uint64_t seed,
+                        const double* noise, void* W, double* s1, double* s2) {
+  GenHost h;
+  fill_gen(h, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, noise_mode, seed, noise);
+  return f64 ? generic_realise_impl<double>(nx, ny, nz, h.gp, (double*)W, s1, s2) : generic_realise_impl<float>(nx, ny, nz, h.gp, (float*)W, s1, s2);
 }
 int emu_generic_r2c(int f64, int nx, int ny, int nz, const void* W, void* K) {
   return f64 ? generic_r2c_impl<double>(nx, ny, nz, (const double*)W, (cplx<double>*)K)

@@ -745,16 +745,38 @@ int queue_xyz(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipS
 struct HipGenericOps {
   rf_plan* p;
   hipStream_t s;
+  // per-kernel times of a realisation (rf_kernel_ms): the inverse sequence launches on the x, y and z root tables in that order, so
+  // ev[1] goes in front of the first launch of the y pass and ev[2] in front of the first of the contiguous pass
+  bool timed = false;
+  int phase = 0;
+  int enter(int ph) {
+    if (timed) while (phase < ph) RF_HIP(hipEventRecord(p->ev[++phase], s));
+    return 0;
+  }
   const void* root(int which) const { return which == 0 ? p->tw_x : (which == 1 ? p->tw_y : p->tw_z); }
   int axis(const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    if (int rc = enter(which)) return rc;
     RF_HIP(launch_generic_axis(p->f64, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
     return 0;
   }
+  // the x pass with the generator as its source (rf_generic.h generic_realise_seq)
+  int axis_gen(const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    RF_HIP(launch_generic_axis_gen(p->f64, gp, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
+    return 0;
+  }
+  // ... and, for a plan whose x axis is split, the generation as a launch of its own into a scratch array (rf_kernel_ms: entry 4)
+  int gen_kspace(const GenParams& gp, void* K) {
+    RF_HIP(launch_gen_kspace(p->f64, K, gp, s));
+    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
+    return 0;
+  }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
+    if (int rc = enter(which)) return rc;
     RF_HIP(launch_generic_lines(p->f64, src, dst, L, root(which), s));
     return 0;
   }
   int row_c2r(const void* G, void* W, double scale) {
+    if (int rc = enter(2)) return rc;
     RF_HIP(launch_generic_row_c2r(p->f64, G, W, p->gdims.az, (long long)p->nx * p->ny, p->tw_z, scale, p->partials, s));
     return 0;
   }
@@ -762,7 +784,7 @@ struct HipGenericOps {
     RF_HIP(launch_generic_row_r2c(p->f64, W, G, p->gdims.az, (long long)p->nx * p->ny, p->tw_z, s));
     return 0;
   }
-  int untangle(const void* G, void* Z) { RF_HIP(launch_generic_untangle(p->f64, G, Z, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z, s)); return 0; }
+  int untangle(const void* G, void* Z) { if (int rc = enter(2)) return rc; RF_HIP(launch_generic_untangle(p->f64, G, Z, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z, s)); return 0; }
   int tangle(const void* Z, void* G) { RF_HIP(launch_generic_tangle(p->f64, Z, G, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z, s)); return 0; }
   int moments(const void* W) { RF_HIP(launch_generic_moments(p->f64, W, (long long)p->nx * p->ny * p->nz, p->partials, p->npartials, s)); return 0; }
   int copy(void* dst, const void* src, size_t bytes) { RF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); return 0; }
@@ -775,13 +797,17 @@ int ensure_g2(rf_plan* p) {
 }
 
 // non-power-of-two grid: API-layout half spectrum K -> x pass into G -> y pass -> contiguous c2r pass into W (rf_generic.h
-// generic_c2r_seq: axes too long for one line of the LDS take the four-step form through the scratch arrays), (sum, sumsq) into stats_out
-int generic_c2r(rf_plan* p, const void* K, double* stats_out) {
+// generic_c2r_seq: axes too long for one line of the LDS take the four-step form through the scratch arrays), (sum, sumsq) into stats_out.
+// gen != null (K is ignored): the x pass generates the half spectrum instead of loading it (RF_FLAG_FUSED_GENERIC_GENERATION,
+// generic_realise_seq).  timed: events ev[1] .. ev[3] behind the x pass, the y pass and the contiguous pass.
+int generic_c2r(rf_plan* p, const void* K, double* stats_out, bool timed = false, const GenParams* gen = nullptr) {
   if (int rc = ensure_g(p)) return rc;
   if (int rc = ensure_g2(p)) return rc;
-  HipGenericOps ops{p, p->stream};
+  HipGenericOps ops{p, p->stream, timed};
   const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-  if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G, p->G2, p->W, scale)) return rc;
+  if (gen) { if (int rc = generic_realise_seq(ops, p->gdims, *gen, p->G, p->G2, p->W, scale)) return rc; }
+  else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G, p->G2, p->W, scale)) return rc;
+  if (int rc = ops.enter(3)) return rc;
   RF_HIP(launch_reduce_partials(p->partials, p->npartials, stats_out, p->partials + 2 * p->npartials, p->stream));
   return 0;
 }
@@ -789,18 +815,23 @@ int generic_c2r(rf_plan* p, const void* K, double* stats_out) {
 // one realisation / transform on the plan's stream into the primary buffer
 int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
   if (p->generic) {
+    // per-kernel times (rf_kernel_ms): ev[0] | generation launch | ev[5] | x | ev[1] | y | ev[2] | contiguous | ev[3] | reduce | ev[4]
+    p->slab_timed = 0;
+    p->slab_merged = 0;
+    p->repair_timed = false;                        // (here: "the generation was a launch of its own", entry 4)
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
-    if (!kspace) {                                  // rows K,T,R,S into the API-layout buffer first
-      RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->noise_resident, "no float64 deviates resident on the device");
+    if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->noise_resident, "no float64 deviates resident on the device");
+    const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and k_valid stay as they are
+    if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
       if (int rc = ensure_k(p)) return rc;
       RF_HIP(launch_gen_kspace(p->f64, p->K, gp, p->stream));
+      if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], p->stream)); p->repair_timed = true; }
       p->k_valid = true;
       p->aux_valid = false;
       kspace = p->K;
     }
-    if (int rc = generic_c2r(p, kspace, p->stats)) return rc;
+    if (int rc = generic_c2r(p, kspace, p->stats, p->timed, fused ? &gp : nullptr)) return rc;
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->timed = false;                               // no per-kernel events on this path
     p->cur = p->W;
     p->stats_slot = 0;
     p->real_valid = true;
@@ -945,7 +976,7 @@ int rf_version(void) { return RF_ABI_VERSION; }
 unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
-         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS;
+         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1188,6 +1219,14 @@ int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
 
 int rf_plan_set_flag(rf_plan* p, int flag, int value) {
   RF_REQUIRE(p, "null plan");
+  if (flag == RF_FLAG_FUSED_GENERIC_GENERATION) {  // the x pass generates the half spectrum it transforms (rf_generic.h generic_realise_seq)
+    RF_REQUIRE(p->generic && !p->unpacked && p->nranks == 1,
+               "RF_FLAG_FUSED_GENERIC_GENERATION is for packed single-rank plans on the generic kernels (shapes that are not powers of two): "
+               "the tiled kernels always generate inside their x pass");
+    RF_HIP(hipStreamSynchronize(p->stream));
+    p->fused_generic = value != 0;
+    return 0;
+  }
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(flag == RF_FLAG_EXACT_GENERATION || flag == RF_FLAG_FORCE_SLAB_PATH || flag == RF_FLAG_REPLICATED_GENERATION ||
              flag == RF_FLAG_TRANSPOSED_INTERMEDIATE || flag == RF_FLAG_YZ_SLAB_PLANES || flag == RF_FLAG_EXCHANGE_CHUNKS, "unknown flag");
@@ -1563,7 +1602,7 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     }
     return 0;
   }
-  if (p->generic) {             // no fused generation, no graph: realisations one after the other
+  if (p->generic) {             // no graph: realisations one after the other
     RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
     RF_HIP(hipSetDevice(p->device));
     if (p->stats_cap < n) {
@@ -1573,14 +1612,17 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
       RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
       p->stats_cap = n + 64;
     }
-    if (int rc = ensure_k(p)) return rc;
+    const bool fused = p->fused_generic;        // generation inside the x pass: no K, k_valid as it was (queue_c2r)
+    if (!fused) { if (int rc = ensure_k(p)) return rc; }
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
     for (int i = 0; i < n; ++i) {
-      RF_HIP(launch_gen_kspace(p->f64, p->K, make_gen(p, seeds[i], RF_NOISE_NATIVE, false), p->stream));
-      if (int rc = generic_c2r(p, p->K, p->stats + 2 * i)) return rc;
+      const GenParams gp = make_gen(p, seeds[i], RF_NOISE_NATIVE, false);
+      if (!fused) RF_HIP(launch_gen_kspace(p->f64, p->K, gp, p->stream));
+      if (int rc = generic_c2r(p, p->K, p->stats + 2 * i, false, fused ? &gp : nullptr)) return rc;
     }
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->cur = p->W; p->timed = false; p->real_valid = true; p->stats_valid = true; p->k_valid = true; p->aux_valid = false;
+    p->cur = p->W; p->timed = false; p->real_valid = true; p->stats_valid = true;
+    if (!fused) { p->k_valid = true; p->aux_valid = false; }
     p->stats_slot = n - 1;
     if (rms_out) {
       std::vector<double> st(2 * (size_t)n);

@@ -341,13 +341,45 @@ inline size_t generic_extra_bytes(const GenericAxis& ax, int elem_bytes) {
   return (size_t)ax.n * elem_bytes + (ax.smooth ? (((size_t)ax.n * 2 + 15) & ~(size_t)15) : 0);
 }
 
+// Where a strided pass takes element e of line l from (the load half of generic_axis_block_from; the stages and the stores do not
+// depend on it).  line(l, base): a thread that stays on ONE line (GenericWalk::fixed) says so once, `base` being that line's start as
+// the pass addresses it; at(e) is then that line's element e.  at(l, e): any element (the walk by index).  INFLIGHT: elements a
+// thread fetches before it uses the first.
+//   GenericMemSource: an array -- src[(l / inner) * outer + l % inner + e * stride].
+template <typename T> struct GenericMemSource {
+  enum { INFLIGHT = 4 };
+  const cplx<T>* src;
+  long long stride, inner, outer, base;
+  RF_HD GenericMemSource(const cplx<T>* s, long long st, long long in, long long ou) : src(s), stride(st), inner(in), outer(ou), base(0) {}
+  RF_HD void line(long long, long long b) { base = b; }
+  RF_HD cplx<T> at(int e) const { return src[base + e * stride]; }
+  RF_HD cplx<T> at(long long l, int e) const { return src[(l / inner) * outer + l % inner + e * stride]; }
+};
+//   GenericGenSource: no array -- the x pass of a realisation, whose line l = iy * (nz/2 + 1) + iz of the half spectrum [nx][ny][nz/2+1]
+//   has element e = cell (ix = e, iy, iz): rows K,T,R,S of that cell (rf_core.h gen_cell: Hermitian roles of the kz = 0 and nz/2 planes
+//   by regenerating the mirrored draw, the DC cell, native and external noise), the very value launch_gen_kspace would have stored and
+//   the pass loaded.  iy and iz by a plain 64-bit division, once per thread where it stays on a line (ny * nzh is beyond what FastDiv
+//   divides exactly).  One cell at a time: a cell is some hundred instructions with a table search, not a load to keep in flight.
+template <typename T> struct GenericGenSource {
+  enum { INFLIGHT = 1 };
+  GenParams gp;
+  uint64_t seed;
+  long long nzh;
+  int iy, iz;
+  RF_HD GenericGenSource(const GenParams& g, uint64_t sd) : gp(g), seed(sd), nzh(g.nz / 2 + 1), iy(0), iz(0) {}
+  RF_HD void line(long long l, long long) { iy = (int)(l / nzh); iz = (int)(l % nzh); }
+  RF_HD cplx<T> at(int e) const { return gen_cell<T>(gp, seed, e, iy, iz); }
+  RF_HD cplx<T> at(long long l, int e) const { return gen_cell<T>(gp, seed, e, (int)(l / nzh), (int)(l % nzh)); }
+};
+
 // Strided (or contiguous) complex pass: block `blk` transforms lines [blk TC, blk TC + TC) of length ax.n;
 // line l starts at (l / inner) * outer + l % inner and its elements are `stride` apart.  src == dst is allowed
 // (a block reads all of its lines before it writes any).  lds: generic_bufs(ax) * ax.n * TC elements.
-template <typename T, class Sync>
-RF_HD void generic_axis_block(const cplx<T>* src, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
-                              long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
-                              cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
+// `from`: where the elements come from (above); (stride, inner, outer) address dst, and src too when it is an array.
+template <typename T, class Source, class Sync>
+RF_HD void generic_axis_block_from(Source from, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
+                                   long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
+                                   cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
   const int n = ax.n, total = n * TC;
   const long long l0 = blk * TC;
   cplx<T>*a = lds, *b = lds + total;
@@ -364,16 +396,18 @@ RF_HD void generic_axis_block(const cplx<T>* src, cplx<T>* dst, const GenericAxi
     // four loads in flight per thread before the first is used (the loop below, left to the compiler, waits for each load in turn:
     // the position of the LDS write is a run-time loop over the radices)
     const bool live = lf < nlines;
-    for (int e = walk.e0; e < n; e += 4 * walk.estep) {
-      cplx<T> v[4];
+    constexpr int U = Source::INFLIGHT;
+    from.line(lf, basef);
+    for (int e = walk.e0; e < n; e += U * walk.estep) {
+      cplx<T> v[U];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < U; ++u) {
         const int ee = e + u * walk.estep;
         v[u] = mk<T>((T)0, (T)0);
-        if (live && ee < n) v[u] = src[basef + ee * stride];
+        if (live && ee < n) v[u] = from.at(ee);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < U; ++u) {
         const int ee = e + u * walk.estep;
         if (ee < n) a[(ptab ? (int)ptab[ee] : generic_pos(ax, ee)) * TC + walk.c0] = v[u];
       }
@@ -384,7 +418,7 @@ RF_HD void generic_axis_block(const cplx<T>* src, cplx<T>* dst, const GenericAxi
       walk.at(idx, i, c, e);
       const long long l = l0 + c;
       cplx<T> v = mk<T>((T)0, (T)0);
-      if (l < nlines) v = src[(l / inner) * outer + l % inner + e * stride];
+      if (l < nlines) v = from.at(l, e);
       a[(ptab ? (int)ptab[e] : generic_pos(ax, e)) * TC + c] = v;
     }
   }
@@ -413,6 +447,22 @@ RF_HD void generic_axis_block(const cplx<T>* src, cplx<T>* dst, const GenericAxi
       }
     }
   }
+}
+
+template <typename T, class Sync>
+RF_HD void generic_axis_block(const cplx<T>* src, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
+                              long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
+                              cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
+  generic_axis_block_from<T>(GenericMemSource<T>(src, stride, inner, outer), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk,
+                             tid, nth, sync, tw_lds);
+}
+// the x pass of a realisation with its k space generated on the way in (GenericGenSource): same LDS positions, stages and stores
+template <typename T, class Sync>
+RF_HD void generic_axis_gen_block(const GenParams& gp, uint64_t seed, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
+                                  long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
+                                  cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
+  generic_axis_block_from<T>(GenericGenSource<T>(gp, seed), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
+                             tw_lds);
 }
 
 // Pitch of the LDS image of the contiguous passes (element e of row c at [e * pitch + c]).  Their threads walk ALONG a row on load and
@@ -727,6 +777,9 @@ RF_HD void generic_tangle_at(const cplx<T>* Z, cplx<T>* G, int M, const cplx<T>*
 //   row_c2r(G, W, scale) / row_r2c(W, G)                                   the fused contiguous passes of rows that fit the LDS
 //   untangle(G, Z) / tangle(Z, G) / moments(W)                             the pieces of the contiguous passes for long rows
 //   copy(dst, src, bytes)
+//   axis_gen(gen, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() whose source is the generator (generic_axis_gen_block)
+//   gen_kspace(gen, K)                                                     rows K,T,R,S into an API-layout array (generic_realise_seq only;
+//                                                                          `gen` is whatever the Ops' generator takes: the sequence hands it on)
 // ---------------------------------------------------------------------------
 // Lines of a strided pass that go into one workgroup together (neighbours in memory: tc lines = segments of tc elements): the widest
 // tile up to 16 whose image(s) and stage table fit a CU's LDS (rf_k_generic.hip strided_shape launches exactly this).  Below 4 lines
@@ -757,12 +810,11 @@ int generic_long_pass(Ops& ops, const void* src, void* tmp, void* dst, const Gen
 }
 // half spectrum K [nx][ny][nz/2+1] -> dense reals W [nx][ny][nz] (np.fft.irfftn with `scale`); G, G2: scratch arrays of K's size (G2 is
 // touched only when an axis is long); the (sum, sumsq) partials are left by row_c2r / moments
+// (generic_c2r_after_x: everything behind the x pass, whose output is in G -- shared with generic_realise_seq)
 template <class Ops>
-int generic_c2r_seq(Ops& ops, const GenericDims& d, const void* K, void* G, void* G2, void* W, double scale) {
+int generic_c2r_after_x(Ops& ops, const GenericDims& d, void* G, void* G2, void* W, double scale) {
   const long long nzh = d.nz / 2 + 1, M = d.nz / 2;
-  const long long Lx = (long long)d.ny * nzh, Ly = (long long)d.nx * nzh, rows = (long long)d.nx * d.ny;
-  if (d.lx.split()) { if (int rc = generic_long_pass(ops, K, G2, G, d.lx, Lx, Lx, 0, Lx, Lx, 0, Lx, 0, 1, +1, 1.0)) return rc; }
-  else if (int rc = ops.axis(K, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
+  const long long Ly = (long long)d.nx * nzh, rows = (long long)d.nx * d.ny;
   void* cur = G;
   if (d.ly.split()) { if (int rc = generic_long_pass(ops, G, G, G2, d.ly, nzh, nzh, (long long)d.ny * nzh, nzh, nzh, (long long)d.ny * nzh, Ly, 1, 1, +1, 1.0)) return rc; cur = G2; }
   else if (int rc = ops.axis(G, G, d.ay, nzh, nzh, (long long)d.ny * nzh, Ly, 1, +1, 1.0)) return rc;
@@ -771,6 +823,29 @@ int generic_c2r_seq(Ops& ops, const GenericDims& d, const void* K, void* G, void
   if (int rc = ops.untangle(cur, other)) return rc;
   if (int rc = generic_long_pass(ops, other, other, W, d.lz, 1, 1, M, 1, 1, M, rows, 2, 2, +1, scale)) return rc;     // W as rows of M complex = nz reals
   return ops.moments(W);
+}
+template <class Ops>
+int generic_c2r_seq(Ops& ops, const GenericDims& d, const void* K, void* G, void* G2, void* W, double scale) {
+  const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
+  if (d.lx.split()) { if (int rc = generic_long_pass(ops, K, G2, G, d.lx, Lx, Lx, 0, Lx, Lx, 0, Lx, 0, 1, +1, 1.0)) return rc; }
+  else if (int rc = ops.axis(K, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
+  return generic_c2r_after_x(ops, d, G, G2, W, scale);
+}
+// A realisation without its half spectrum in memory: generic_c2r_seq whose first pass GENERATES the cells it transforms
+// (GenericGenSource) instead of loading what a generation launch stored -- 5 sweeps of the half spectrum instead of 7, and no array K.
+// Same values in the same LDS positions through the same stages: the field and its moments are those of gen_kspace + generic_c2r_seq,
+// bit for bit.  Only an x axis that is ONE line of the LDS is fused (!d.lx.split()): the four-step form reads its input twice over
+// (sub-lines, then their transposes), so for such a plan the spectrum is generated into the scratch array G2 and the unfused
+// sequence runs from there.  G, G2: as generic_c2r_seq (G2 is touched only when an axis is long).
+template <class Ops, class Gen>
+int generic_realise_seq(Ops& ops, const GenericDims& d, const Gen& gen, void* G, void* G2, void* W, double scale) {
+  const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
+  if (d.lx.split()) {
+    if (int rc = ops.gen_kspace(gen, G2)) return rc;
+    return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
+  }
+  if (int rc = ops.axis_gen(gen, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
+  return generic_c2r_after_x(ops, d, G, G2, W, scale);
 }
 // dense reals W -> half spectrum K (np.fft.rfftn); W is left untouched
 template <class Ops>

@@ -16,6 +16,17 @@ __global__ __launch_bounds__(1024) void generic_axis_kernel(const cplx<T>* src, 
                         (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
 }
 
+// the x pass of a realisation whose source is the generator (rf_generic.h GenericGenSource): GenParams by value, as gen_kspace_kernel
+template <typename T>
+__global__ __launch_bounds__(1024) void generic_axis_gen_kernel(GenParams gp, cplx<T>* dst, GenericAxis ax, long long stride, long long inner,
+                                                              long long outer, long long nlines, int TC, const cplx<T>* __restrict__ root,
+                                                              int sign, T scale, int tw_lds) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const uint64_t seed = gp.seed_dev ? *gp.seed_dev : gp.seed;
+  generic_axis_gen_block<T>(gp, seed, dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, reinterpret_cast<cplx<T>*>(lds_raw),
+                            (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void generic_row_c2r_kernel(const cplx<T>* __restrict__ G, T* __restrict__ W, GenericAxis ax,
                                                              long long nrows, int TR, const cplx<T>* __restrict__ root, T scale,
@@ -137,6 +148,27 @@ hipError_t axis_t(const void* src, void* dst, const GenericAxis& ax, long long s
   return hipGetLastError();
 }
 
+// the same shape and LDS attribute latch as axis_t (the attribute is set by the first call, which is never inside a capture: generic
+// plans are not graph-captured)
+template <typename T>
+hipError_t axis_gen_t(const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
+                      long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  if (ax.n != gp.nx || nlines != (long long)gp.ny * (gp.nz / 2 + 1)) return hipErrorInvalidValue;      // lines of the half spectrum along x, nothing else
+  const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
+  const int tc = sh.tc;
+  const long long nblk = (nlines + tc - 1) / tc;
+  if (nblk <= 0) return hipSuccess;
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  const size_t lds = sh.lds;
+  if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
+  static LdsAttrLatch latch;
+  if (lds > 65536)
+    if (hipError_t e = latch.ensure((const void*)generic_axis_gen_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
+  hipLaunchKernelGGL(generic_axis_gen_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, gp, (cplx<T>*)dst, ax, stride, inner, outer, nlines, tc,
+                     (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
+  return hipGetLastError();
+}
+
 template <typename T> int rows_per_block(const GenericAxis& ax) { return generic_lines_per_block(ax.n, (int)sizeof(cplx<T>), 8, 49152, generic_bufs(ax), true); }   // + the reduction's static LDS
 
 }  // namespace
@@ -145,6 +177,12 @@ hipError_t launch_generic_axis(int f64, const void* src, void* dst, const Generi
                                long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
   return f64 ? axis_t<double>(src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
              : axis_t<float>(src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
+}
+
+hipError_t launch_generic_axis_gen(int f64, const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                   long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return f64 ? axis_gen_t<double>(gp, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
+             : axis_gen_t<float>(gp, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
 }
 
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s) {

@@ -169,6 +169,10 @@ hipError_t launch_mt_share_widen(const void* recv, double* noise, long long npai
 // complex pass along one axis: line l starts at (l / inner) * outer + l % inner, elements `stride` apart; src == dst allowed
 hipError_t launch_generic_axis(int f64, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
                                long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
+// the x pass of a realisation with its source generated, not loaded: element e of line l = cell (e, l / (nz/2+1), l % (nz/2+1)) of gp's
+// half spectrum (rf_generic.h GenericGenSource); ax.n == gp.nx and nlines == gp.ny * (gp.nz/2 + 1), else hipErrorInvalidValue
+hipError_t launch_generic_axis_gen(int f64, const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                   long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
 // axes too long for the LDS (rf_generic.h GenericLong): one step of the four-step transform (lines with sub-lines); the Hermitian
 // (un)tangle of long rows as passes of their own; (sum, sum of squares) of a real array into nblocks partial pairs
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s);

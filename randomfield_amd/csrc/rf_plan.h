@@ -198,13 +198,14 @@ struct rf_plan {
   bool repair_timed = false;
   bool aux_valid = false;              // the k buffer's memory currently holds an auxiliary REAL field (lensing potential)
   bool unpacked = false;               // c2c plan: W is the full [nx][ny][nz] complex array, only rf_*_c / rf_execute_c2c apply
-  // non-power-of-two grid (rf_generic.h): the transforms run on API-layout arrays, K -> G -> W; no fused generation,
-  // no graphs, one rank.  gax / gay factor nx / ny, gaz factors nz/2 (packed plans) or nz (c2c plans)
+  // non-power-of-two grid (rf_generic.h): the transforms run on API-layout arrays, K -> G -> W (generation fused into the x pass only
+  // with fused_generic), no graphs, one rank.  gax / gay factor nx / ny, gaz factors nz/2 (packed plans) or nz (c2c plans)
   bool generic = false;
   void* G = nullptr;                   // lazy scratch [nx][ny][nz/2+1] complex (c2c plans: [nx][ny][nz], for a long axis)
   void* G2 = nullptr;                  // lazy second scratch: only when an axis is too long for one line (four-step form, rf_generic.h)
   rf::GenericAxis gax, gay, gaz;
   rf::GenericDims gdims;               // the same + the split of the long axes, as the sequences of rf_generic.h take them
+  bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; k_valid untouched)
   bool timed = false;
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations
