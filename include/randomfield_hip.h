@@ -43,7 +43,7 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * this repository returned the constant 1 while the surface grew from ~20 to 70 entry points; 5.0 is the first version that means
  * something: the consumer surface below + the diagnostics of randomfield_hip_diag.h.) */
 #define RF_ABI_MAJOR 5
-#define RF_ABI_MINOR 4
+#define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
 int rf_version(void);                            /* (major << 16) | minor */
 /* bit mask of the groups of entry points this build exports (each bit: every function of the group is present and works as this
@@ -64,7 +64,8 @@ enum {
   RF_FEATURE_EXCHANGE_CHUNKS = 1 << 10,    /* RF_FLAG_EXCHANGE_CHUNKS */
   RF_FEATURE_DIRECT_EXCHANGE = 1 << 12,    /* rf_comm_enable_direct: the y pass stores into the peers' receive buffers (IPC-mapped), no all-to-all kernels */
   RF_FEATURE_DIAGNOSTICS = 1 << 11,        /* the entry points of randomfield_hip_diag.h (timing per kernel, launch structure, virtual ranks) */
-  RF_FEATURE_GENERIC_FUSED = 1 << 13       /* RF_FLAG_FUSED_GENERIC_GENERATION; rf_kernel_ms on generic plans */
+  RF_FEATURE_GENERIC_FUSED = 1 << 13,      /* RF_FLAG_FUSED_GENERIC_GENERATION; rf_kernel_ms on generic plans */
+  RF_FEATURE_GRADIENT = 1 << 14            /* rf_load_gradient, rf_execute_gradient_c2r: the vector field of the saved potential */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -251,6 +252,24 @@ int rf_affine_z(rf_plan* plan, const double* mul_z, int nz, double add);
 int rf_save_potential(rf_plan* plan);
 /* k buffer <- scale * potential(k)  (then rf_execute_c2r gives the Newtonian potential) */
 int rf_load_potential(rf_plan* plan, double scale);
+
+/* ---- gradient of the saved potential: displacement / velocity components -- */
+/* psi_a(k) = i k_a delta(k) / k^2, a = axis in {0, 1, 2} (x, y, z), so that div psi = -delta: the vector field the saved potential
+ * is kept for.  k_a = dk * m, m the signed mode number of the cell along the axis and dk = 2 pi / (n_axis * spacing) (the caller's);
+ * m = 0 at the axis' own Nyquist index, where i k is not Hermitian: that plane and the DC cell are exactly 0.  The factor
+ * scale * dk * m is formed in float64 and rounded once to the plan's real type.
+ * source = RF_GRAD_FROM_POTENTIAL: from the stored potential (rf_save_potential / rf_realise_potential), which is left as it is;
+ * source = RF_GRAD_FROM_KSPACE: from the k buffer holding delta(k) -- the factor takes the 1 / k^2, summed in float64 from the
+ * tables of rf_set_kgrid -- for plans that regenerate their potential instead of storing it.
+ * Packed single-rank plans, tiled and generic; c2c plans, nranks > 1, another axis and a missing source are refused, nothing queued. */
+enum { RF_GRAD_FROM_POTENTIAL = 0, RF_GRAD_FROM_KSPACE = 1 };
+/* k buffer <- psi_a(k) (RF_GRAD_FROM_KSPACE: in place); rf_download_k and rf_execute_c2r then work as usual */
+int rf_load_gradient(rf_plan* plan, int axis, double scale, double dk, int source);
+/* the real field psi_a(x) in place of the current one, moments as after rf_execute_c2r.  Generic plans apply the factor inside their
+ * x pass (no sweep of its own; the field is that of rf_load_gradient + rf_execute_c2r bit for bit), tiled plans run those two steps.
+ * The k buffer afterwards: RF_GRAD_FROM_KSPACE consumes it (no k-space data until the next generate / upload / load);
+ * RF_GRAD_FROM_POTENTIAL leaves what it held (generic plans) or psi_a(k) (tiled plans). */
+int rf_execute_gradient_c2r(rf_plan* plan, int axis, double scale, double dk, int source);
 
 /* ---- host <-> device (layout conversion to/from the reference's arrays) -- */
 int rf_upload_k(rf_plan* plan, const void* host);            /* (nx, ny, nz/2+1) complex */

@@ -20,12 +20,15 @@ extern "C" {
 /* ---- timing and launch structure ----------------------------------------- */
 /* GPU time of each kernel of the last rf_realise, 5 floats: x pass (main kernel), y pass, z pass, reduce,
  * and the small x-pass launch that repairs the kz = 0 tiles (0 when the x pass is a single launch).
- * Plans on the generic kernels (shapes that are not powers of two), after rf_realise or rf_execute_c2r, from events around the launches:
- *   [0] the x pass -- with the generation inside it under RF_FLAG_FUSED_GENERIC_GENERATION; both steps of a four-step x axis
+ * Plans on the generic kernels (shapes that are not powers of two), after rf_realise, rf_execute_c2r or rf_execute_gradient_c2r, from
+ * events around the launches:
+ *   [0] the x pass -- with the generation inside it under RF_FLAG_FUSED_GENERIC_GENERATION, with the factor i k_a inside it after
+ *       rf_execute_gradient_c2r; both steps of a four-step x axis
  *   [1] the y pass (both steps of a four-step axis)
  *   [2] the contiguous pass (for long rows: untangle, the two steps, moments)
  *   [3] reduce
- *   [4] the generation as a launch of its own (0 when it is fused into the x pass, and after rf_execute_c2r)
+ *   [4] the generation as a launch of its own (0 when it is fused into the x pass, and after rf_execute_c2r); after
+ *       rf_execute_gradient_c2r: the elementwise gradient kernel of a plan whose x axis is in the four-step form, else 0
  * so that [4] + [0] is everything in front of the y pass. */
 int rf_kernel_ms(rf_plan* plan, float* ms5);
 /* The z pass of slab s and the y pass of slab s + 1 in ONE launch (the next slab's tiles fill the compute units the draining pass leaves

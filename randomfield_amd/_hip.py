@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librandomfield_hip.so")
 
 RF_F32, RF_F64 = 0, 1
+RF_GRAD_FROM_POTENTIAL, RF_GRAD_FROM_KSPACE = 0, 1        # `source` of load_gradient / execute_gradient
 DIRECT_RECORD_BYTES = 192                 # RF_DIRECT_RECORD_BYTES (randomfield_hip_diag.h)
 NOISE_NATIVE, NOISE_EXTERNAL, NOISE_RESIDENT = 0, 1, 2
 LAYOUT_DENSE, LAYOUT_PADDED = 0, 1
@@ -27,10 +28,10 @@ _c_dp = ctypes.POINTER(ctypes.c_double)
 
 # the ABI this binding was written against (include/randomfield_hip.h RF_ABI_MAJOR / RF_ABI_MINOR): load() refuses a library of
 # another major version or an older minor one
-ABI_MAJOR, ABI_MINOR = 5, 4
+ABI_MAJOR, ABI_MINOR = 5, 5
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
-            "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13}
+            "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -78,6 +79,8 @@ SIGNATURES = {
     "rf_affine_z": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double]),
     "rf_save_potential": (ctypes.c_int, [ctypes.c_void_p]),
     "rf_load_potential": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
+    "rf_load_gradient": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "rf_execute_gradient_c2r": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
     "rf_lensing_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "rf_download_aux": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "rf_upload_k": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -623,6 +626,17 @@ class DevicePlan(object):
 
     def load_potential(self, scale=1.0):
         check(self._lib.rf_load_potential(self._h, float(scale)), "rf_load_potential")
+
+    def load_gradient(self, axis, scale, dk, source):
+        """k buffer <- i k_axis * scale * delta(k) / k^2 (rf_load_gradient): one component of the gradient of the potential, from
+        the stored potential (``source=RF_GRAD_FROM_POTENTIAL``) or from the k buffer holding delta(k), in place
+        (``RF_GRAD_FROM_KSPACE``).  ``dk`` = 2 pi / (n_axis * spacing)."""
+        check(self._lib.rf_load_gradient(self._h, int(axis), float(scale), float(dk), int(source)), "rf_load_gradient")
+
+    def execute_gradient(self, axis, scale, dk, source):
+        """The real field of that component (rf_execute_gradient_c2r).  Generic plans apply the factor inside their x pass, tiled
+        plans run load_gradient + execute_c2r.  ``RF_GRAD_FROM_KSPACE`` consumes the k buffer."""
+        check(self._lib.rf_execute_gradient_c2r(self._h, int(axis), float(scale), float(dk), int(source)), "rf_execute_gradient_c2r")
 
     # -- host <-> device --------------------------------------------------
     @property

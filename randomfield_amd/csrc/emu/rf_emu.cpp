@@ -578,6 +578,28 @@ template <typename T> struct EmuGenericOps {
         for (int iz = 0; iz < nzh; ++iz) ((cplx<T>*)K)[((size_t)ix * gp.ny + iy) * nzh + iz] = gen_cell<T>(gp, gp.seed, ix, iy, iz);
     return 0;
   }
+  // generic_gradient_c2r_seq: the x pass through GenericGradSource, and the component alone (the elementwise kernel's loop)
+  int axis_grad(const GradParams& gr, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    const int TC = g_generic_tile, nth = nthreads();
+    cplx<T>* lds = lds_image(ax, TC);
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TC < nlines; ++b) {
+        generic_axis_grad_block<T>(gr, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
+    return 0;
+  }
+  int grad_kspace(const GradParams& gr, const void* S, void* K) {
+    const int nzh = gr.nz / 2 + 1;
+    for (int ix = 0; ix < gr.nx; ++ix)
+      for (int iy = 0; iy < gr.ny; ++iy)
+        for (int iz = 0; iz < nzh; ++iz) {
+          const size_t row = (size_t)ix * gr.ny + iy;
+          ((cplx<T>*)K)[row * nzh + iz] = grad_cell<T>(gr, ((const cplx<T>*)S)[row * gr.pitch + iz], ix, iy, iz);
+        }
+    return 0;
+  }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     const int TC = g_generic_tile, nth = nthreads();
     cplx<T>* lds = lds_image(L.ax, TC);
@@ -667,6 +689,31 @@ int generic_realise_impl(int nx, int ny, int nz, const GenParams& gp, T* W, doub
   if (s1) *s1 = ops.s1;
   if (s2) *s2 = ops.s2;
   return rc;
+}
+
+// one component of the gradient of the potential as a field, the factor inside the x pass (rf_generic.h generic_gradient_c2r_seq; an x
+// axis beyond the cap: its unfused fallback)
+template <typename T>
+int generic_gradient_c2r_impl(int nx, int ny, int nz, const GradParams& gr, const cplx<T>* S, T* W, double* s1, double* s2) {
+  GenericDims d;
+  if (!emu_dims<T>(nx, ny, nz, true, d)) return -1;
+  const long long nzh = nz / 2 + 1;
+  auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
+  std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
+  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
+  ops.az = d.az;
+  const int rc = generic_gradient_c2r_seq(ops, d, gr, S, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
+  if (s1) *s1 = ops.s1;
+  if (s2) *s2 = ops.s2;
+  return rc;
+}
+inline bool emu_grad_params(int nx, int ny, int nz, int axis, double scale, double dk, int divide, const double* kx2, const double* ky2, const double* kz2,
+                            long long spitch, GradParams& g) {
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || axis < 0 || axis > 2 || spitch < nz / 2 + 1 || (divide && !(kx2 && ky2 && kz2))) return false;
+  memset(&g, 0, sizeof(g));
+  g.nx = nx; g.ny = ny; g.nz = nz; g.axis = axis; g.divide = divide != 0; g.sdk = scale * dk;
+  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2; g.pitch = spitch;
+  return true;
 }
 
 template <typename T>
@@ -786,6 +833,24 @@ int emu_generic_realise(int f64, int nx, int ny, int nz, const double* kx2, cons
   GenHost h;
   fill_gen(h, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, noise_mode, seed, noise);
   return f64 ? generic_realise_impl<double>(nx, ny, nz, h.gp, (double*)W, s1, s2) : generic_realise_impl<float>(nx, ny, nz, h.gp, (float*)W, s1, s2);
+}
+// K [nx][ny][nz/2+1] = i k_axis S (rf_core.h grad_cell over an array, as the elementwise gradient kernel): S has rows of spitch cells and
+// holds delta(k) / k^2, or delta(k) with divide != 0 (kx2, ky2, kz2: the k^2 tables; S == K is allowed)
+int emu_gradient_k(int f64, int nx, int ny, int nz, int axis, double scale, double dk, int divide, const double* kx2, const double* ky2,
+                   const double* kz2, const void* S, long long spitch, void* K) {
+  GradParams g;
+  if (!emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g)) return -1;
+  if (f64) { EmuGenericOps<double> ops{}; return ops.grad_kspace(g, S, K); }
+  EmuGenericOps<float> ops{};
+  return ops.grad_kspace(g, S, K);
+}
+// the field of that component with the factor applied inside the x pass (honours emu_set_generic_threads / _tile / _cap)
+int emu_generic_gradient_c2r(int f64, int nx, int ny, int nz, int axis, double scale, double dk, int divide, const double* kx2, const double* ky2,
+                             const double* kz2, const void* S, long long spitch, void* W, double* s1, double* s2) {
+  GradParams g;
+  if (!emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g)) return -1;
+  return f64 ? generic_gradient_c2r_impl<double>(nx, ny, nz, g, (const cplx<double>*)S, (double*)W, s1, s2)
+             : generic_gradient_c2r_impl<float>(nx, ny, nz, g, (const cplx<float>*)S, (float*)W, s1, s2);
 }
 int emu_generic_r2c(int f64, int nx, int ny, int nz, const void* W, void* K) {
   return f64 ? generic_r2c_impl<double>(nx, ny, nz, (const double*)W, (cplx<double>*)K)

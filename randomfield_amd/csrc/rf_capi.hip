@@ -770,6 +770,17 @@ struct HipGenericOps {
     if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
     return 0;
   }
+  // the x pass of a gradient component with i k_a applied to the cells it loads (rf_generic.h generic_gradient_c2r_seq), and the
+  // component as a sweep of its own for a plan whose x axis is split
+  int axis_grad(const GradParams& gr, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    RF_HIP(launch_generic_axis_grad(p->f64, gr, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
+    return 0;
+  }
+  int grad_kspace(const GradParams& gr, const void* S, void* K) {
+    RF_HIP(launch_gradient(p->f64, S, K, gr, s));
+    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }       // (rf_kernel_ms: entry 4, as the generation launch)
+    return 0;
+  }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     if (int rc = enter(which)) return rc;
     RF_HIP(launch_generic_lines(p->f64, src, dst, L, root(which), s));
@@ -976,7 +987,7 @@ int rf_version(void) { return RF_ABI_VERSION; }
 unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
-         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED;
+         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1844,6 +1855,79 @@ int rf_load_potential(rf_plan* p, double scale) {
   RF_HIP(launch_scale_copy(p->f64, p->P, p->K, (long long)p->nx * p->ny * (p->nzl + 1), (int)p->nzl + 1, p->ppitch, scale, p->stream));
   p->k_valid = true;
   p->aux_valid = false;
+  return 0;
+}
+
+}  // extern "C"
+namespace rfc {
+// what both gradient calls refuse, and the parameters of the component (rf_core.h GradParams): the source is the stored potential
+// (rows of ppitch cells) or the plan's k-space array in divide mode
+int gradient_params(rf_plan* p, int axis, double scale, double dk, int source, GradParams& g, const void*& S) {
+  RF_REQUIRE(p, "null plan");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the gradient of the potential runs on single-rank plans");
+  RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
+  RF_REQUIRE(source == RF_GRAD_FROM_POTENTIAL || source == RF_GRAD_FROM_KSPACE, "source must be RF_GRAD_FROM_POTENTIAL or RF_GRAD_FROM_KSPACE");
+  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
+  else {
+    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+    RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  }
+  memset(&g, 0, sizeof(g));
+  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
+  g.axis = axis;
+  g.divide = source == RF_GRAD_FROM_KSPACE;
+  g.sdk = scale * dk;
+  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
+  g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
+  S = g.divide ? p->K : p->P;
+  return 0;
+}
+}  // namespace rfc
+extern "C" {
+
+int rf_load_gradient(rf_plan* p, int axis, double scale, double dk, int source) {
+  GradParams g;
+  const void* S = nullptr;
+  if (int rc = gradient_params(p, axis, scale, dk, source, g, S)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_k(p)) return rc;
+  RF_HIP(launch_gradient(p->f64, S, p->K, g, p->stream));
+  p->k_valid = true;
+  p->aux_valid = false;
+  return 0;
+}
+
+int rf_execute_gradient_c2r(rf_plan* p, int axis, double scale, double dk, int source) {
+  GradParams g;
+  const void* S = nullptr;
+  if (int rc = gradient_params(p, axis, scale, dk, source, g, S)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  if (!p->generic) {    // the component as a sweep of its own, then the plan's inverse transform
+    if (int rc = rf_load_gradient(p, axis, scale, dk, source)) return rc;
+    const int rc = rf_execute_c2r(p);
+    if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;     // (K held delta(k) and was consumed; the fused form leaves it: one contract)
+    return rc;
+  }
+  // generic plans: i k_a is applied by the x pass to the cells it loads (rf_generic.h generic_gradient_c2r_seq); K, P are only read
+  if (int rc = ensure_g(p)) return rc;
+  if (int rc = ensure_g2(p)) return rc;
+  p->slab_timed = 0;
+  p->slab_merged = 0;
+  p->repair_timed = false;
+  p->timed = true;                                  // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
+  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  HipGenericOps ops{p, p->stream, true};
+  const double norm = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
+  if (int rc = generic_gradient_c2r_seq(ops, p->gdims, g, S, p->G, p->G2, p->W, norm)) return rc;
+  if (int rc = ops.enter(3)) return rc;
+  RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, p->stream));
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  p->cur = p->W;
+  p->stats_slot = 0;
+  p->real_valid = true;
+  p->stats_valid = true;
+  if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
   return 0;
 }
 

@@ -395,6 +395,37 @@ RF_HD cplx<T> gen_packed(const GenParams& g, uint64_t seed, int ix, int iy, int 
   return a;
 }
 
+// ----------------------------------------------- gradient of the potential --
+// One component of the vector field of the saved potential: psi_a(k) = i k_a phi(k), phi = delta(k) / k^2, so that div psi = -delta
+// (displacements, and with a per-plane factor velocities).  k_a = dk * m with m the signed mode number of the cell along the axis;
+// m = 0 at the axis' own Nyquist index (i k is not Hermitian there) and at index 0, so those planes -- the DC cell among them -- are
+// exactly zero.  `divide`: the source holds delta(k), not delta(k) / k^2, and the factor takes the 1 / k^2 (sum of the plan's tables
+// in float64).  The factor is formed in float64 and rounded ONCE to the array's real type; the products are the second rounding.
+struct GradParams {
+  int nx, ny, nz;             // real-space grid; cells of the half spectrum [nx][ny][nz/2+1]
+  int axis;                   // 0, 1, 2: x, y, z
+  int divide;                 // the source holds delta(k): divide by k^2
+  double sdk;                 // scale * dk, dk = 2 pi / (n_axis spacing)
+  const double* kx2;          // the k^2 tables of GenParams (read in divide mode only)
+  const double* ky2;
+  const double* kz2;
+  long long pitch;            // cells per row (ix, iy) of the SOURCE array (nz/2 + 1, or the potential's padded pitch)
+};
+// signed mode number of index i of an axis of n points (half: the z axis of the half spectrum, i in [0, n/2])
+RF_HD int grad_mode(int i, int n, bool half) {
+  if (2 * i == n) return 0;
+  return (half || 2 * i < n) ? i : i - n;
+}
+template <typename T>
+RF_HD cplx<T> grad_cell(const GradParams& g, cplx<T> v, int ix, int iy, int iz) {
+  const int m = g.axis == 0 ? grad_mode(ix, g.nx, false) : (g.axis == 1 ? grad_mode(iy, g.ny, false) : grad_mode(iz, g.nz, true));
+  if (m == 0) return mk<T>((T)0, (T)0);            // (also keeps the 0 / 0 of the DC cell out of divide mode)
+  double fd = g.sdk * (double)m;
+  if (g.divide) fd = fd / ((g.kx2[ix] + g.ky2[iy]) + g.kz2[iz]);
+  const T f = (T)fd;
+  return mk<T>(-(f * v.y), f * v.x);
+}
+
 // ------------------------------------------------- fast native generation --
 // float32 plans with the native RNG do rows K,T,R,S entirely in float32: the
 // values are this repo's own definition (checked against the oracle's

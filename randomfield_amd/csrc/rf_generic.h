@@ -372,6 +372,25 @@ template <typename T> struct GenericGenSource {
   RF_HD cplx<T> at(long long l, int e) const { return gen_cell<T>(gp, seed, e, (int)(l / nzh), (int)(l % nzh)); }
 };
 
+//   GenericGradSource: an array seen through grad_cell (rf_core.h) -- the x pass of one component of the potential's gradient.  Line
+//   l = iy * (nz/2 + 1) + iz of the half spectrum [nx][ny][nz/2+1], element e = cell (ix = e, iy, iz) of the source (the stored
+//   potential, whose rows may be padded, or the k-space array in divide mode: g.pitch cells per row either way), times i k_a: the very
+//   value the elementwise gradient kernel would have stored and the pass loaded.
+template <typename T> struct GenericGradSource {
+  enum { INFLIGHT = 4 };
+  const cplx<T>* src;
+  GradParams g;
+  long long nzh, stride, base;
+  int iy, iz;
+  RF_HD GenericGradSource(const GradParams& gp, const cplx<T>* s) : src(s), g(gp), nzh(gp.nz / 2 + 1), stride((long long)gp.ny * gp.pitch), base(0), iy(0), iz(0) {}
+  RF_HD void line(long long l, long long) { iy = (int)(l / nzh); iz = (int)(l % nzh); base = (long long)iy * g.pitch + iz; }
+  RF_HD cplx<T> at(int e) const { return grad_cell<T>(g, src[base + e * stride], e, iy, iz); }
+  RF_HD cplx<T> at(long long l, int e) const {
+    const int y = (int)(l / nzh), z = (int)(l % nzh);
+    return grad_cell<T>(g, src[(long long)y * g.pitch + z + e * stride], e, y, z);
+  }
+};
+
 // Strided (or contiguous) complex pass: block `blk` transforms lines [blk TC, blk TC + TC) of length ax.n;
 // line l starts at (l / inner) * outer + l % inner and its elements are `stride` apart.  src == dst is allowed
 // (a block reads all of its lines before it writes any).  lds: generic_bufs(ax) * ax.n * TC elements.
@@ -462,6 +481,15 @@ RF_HD void generic_axis_gen_block(const GenParams& gp, uint64_t seed, cplx<T>* d
                                   long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
                                   cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
   generic_axis_block_from<T>(GenericGenSource<T>(gp, seed), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
+                             tw_lds);
+}
+
+// the x pass of a gradient component with i k_a applied on the way in (GenericGradSource): same LDS positions, stages and stores
+template <typename T, class Sync>
+RF_HD void generic_axis_grad_block(const GradParams& gp, const cplx<T>* src, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
+                                   long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
+                                   cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
+  generic_axis_block_from<T>(GenericGradSource<T>(gp, src), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
                              tw_lds);
 }
 
@@ -845,6 +873,24 @@ int generic_realise_seq(Ops& ops, const GenericDims& d, const Gen& gen, void* G,
     return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
   }
   if (int rc = ops.axis_gen(gen, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
+  return generic_c2r_after_x(ops, d, G, G2, W, scale);
+}
+// One component of the gradient of the potential as a real field: generic_c2r_seq of i k_a S (S: the stored potential, or k space in
+// divide mode -- `grad` says which, rf_core.h GradParams) whose x pass applies the factor to the cells it loads (GenericGradSource)
+// instead of loading what the elementwise gradient kernel stored: no sweep of its own, S is left untouched.  Same values in the same
+// LDS positions through the same stages: the field and its moments are those of grad_kspace + generic_c2r_seq, bit for bit.  An x axis
+// in the four-step form reads its input twice over, so for such a plan the component goes into the scratch array G2 and the unfused
+// sequence runs from there (as generic_realise_seq).  Ops provides, besides the above:
+//   axis_grad(grad, S, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() through GenericGradSource (generic_axis_grad_block)
+//   grad_kspace(grad, S, K)                                                          i k_a S into an API-layout array
+template <class Ops>
+int generic_gradient_c2r_seq(Ops& ops, const GenericDims& d, const GradParams& grad, const void* S, void* G, void* G2, void* W, double scale) {
+  const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
+  if (d.lx.split()) {
+    if (int rc = ops.grad_kspace(grad, S, G2)) return rc;
+    return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
+  }
+  if (int rc = ops.axis_grad(grad, S, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
   return generic_c2r_after_x(ops, d, G, G2, W, scale);
 }
 // dense reals W -> half spectrum K (np.fft.rfftn); W is left untouched

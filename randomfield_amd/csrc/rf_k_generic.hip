@@ -27,6 +27,16 @@ __global__ __launch_bounds__(1024) void generic_axis_gen_kernel(GenParams gp, cp
                             (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
 }
 
+// the x pass of one gradient component: the cells of `src` times i k_a on the way in (rf_generic.h GenericGradSource); src != dst
+template <typename T>
+__global__ __launch_bounds__(1024) void generic_axis_grad_kernel(GradParams gp, const cplx<T>* __restrict__ src, cplx<T>* __restrict__ dst, GenericAxis ax,
+                                                               long long stride, long long inner, long long outer, long long nlines, int TC,
+                                                               const cplx<T>* __restrict__ root, int sign, T scale, int tw_lds) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  generic_axis_grad_block<T>(gp, src, dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, reinterpret_cast<cplx<T>*>(lds_raw),
+                             (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void generic_row_c2r_kernel(const cplx<T>* __restrict__ G, T* __restrict__ W, GenericAxis ax,
                                                              long long nrows, int TR, const cplx<T>* __restrict__ root, T scale,
@@ -169,6 +179,27 @@ hipError_t axis_gen_t(const GenParams& gp, void* dst, const GenericAxis& ax, lon
   return hipGetLastError();
 }
 
+// the same shape and LDS attribute latch again
+template <typename T>
+hipError_t axis_grad_t(const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
+                       long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  // lines of the half spectrum along x, out of place, nothing else
+  if (ax.n != gp.nx || nlines != (long long)gp.ny * (gp.nz / 2 + 1) || gp.pitch < gp.nz / 2 + 1 || gp.axis < 0 || gp.axis > 2 || src == dst) return hipErrorInvalidValue;
+  const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
+  const int tc = sh.tc;
+  const long long nblk = (nlines + tc - 1) / tc;
+  if (nblk <= 0) return hipSuccess;
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  const size_t lds = sh.lds;
+  if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
+  static LdsAttrLatch latch;
+  if (lds > 65536)
+    if (hipError_t e = latch.ensure((const void*)generic_axis_grad_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
+  hipLaunchKernelGGL(generic_axis_grad_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, gp, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner,
+                     outer, nlines, tc, (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
+  return hipGetLastError();
+}
+
 template <typename T> int rows_per_block(const GenericAxis& ax) { return generic_lines_per_block(ax.n, (int)sizeof(cplx<T>), 8, 49152, generic_bufs(ax), true); }   // + the reduction's static LDS
 
 }  // namespace
@@ -183,6 +214,12 @@ hipError_t launch_generic_axis_gen(int f64, const GenParams& gp, void* dst, cons
                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
   return f64 ? axis_gen_t<double>(gp, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
              : axis_gen_t<float>(gp, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
+}
+
+hipError_t launch_generic_axis_grad(int f64, const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return f64 ? axis_grad_t<double>(gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
+             : axis_grad_t<float>(gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
 }
 
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s) {

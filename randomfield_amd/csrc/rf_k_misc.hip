@@ -227,6 +227,23 @@ __global__ __launch_bounds__(256) void scale_copy_kernel(const cplx<T>* __restri
   }
 }
 
+// K (rows of nzh = nz/2 + 1 cells) = i k_a S (rows of gp.pitch cells): one component of the gradient of the potential (rf_core.h
+// grad_cell).  Rows (ix, iy) as gen_kspace_kernel walks them: blockDim.x threads along kz -- whole lines loaded and stored --
+// blockDim.y rows per workgroup, a row's indices formed once with 32-bit divisions.  S == K is allowed (no __restrict__): a cell is
+// read and written by the same thread.
+template <typename T>
+__global__ __launch_bounds__(256) void gradient_kernel(const cplx<T>* S, cplx<T>* K, GradParams gp, unsigned nrows) {
+  const int nzh = gp.nz / 2 + 1;
+  for (unsigned long long r0 = (unsigned long long)blockIdx.x * blockDim.y; r0 < nrows; r0 += (unsigned long long)gridDim.x * blockDim.y) {
+    const unsigned long long rr = r0 + threadIdx.y;
+    if (rr >= nrows) continue;
+    const unsigned row = (unsigned)rr, ix = row / (unsigned)gp.ny, iy = row - ix * (unsigned)gp.ny;
+    const cplx<T>* Sr = S + (long long)row * gp.pitch;
+    cplx<T>* Kr = K + (long long)row * nzh;
+    for (int iz = threadIdx.x; iz < nzh; iz += blockDim.x) Kr[iz] = grad_cell<T>(gp, Sr[iz], (int)ix, (int)iy, iz);
+  }
+}
+
 // after the forward x and y passes slot kz = 0 holds C = A0 + i A_nyq with A0, A_nyq Hermitian in (kx, ky):
 // A0(k) = (C(k) + conj C(-k)) / 2,  A_nyq(k) = (C(k) - conj C(-k)) / (2i)
 // W: [nx][ny][nzl] (this rank's kz planes kz0 .. kz0 + nzl; one rank: nzl = nz/2, kz0 = 0);  K: the side array [nx][ny][nzl + 1]
@@ -533,6 +550,21 @@ hipError_t launch_save_potential(int f64, const void* K, void* P, int nx, int ny
   const long long total = (long long)nx * ny * zpitch;
   if (f64) hipLaunchKernelGGL(save_potential_kernel<double>, dim3(grid_for(total, 256)), dim3(256), 0, s, (const cplx<double>*)K, (cplx<double>*)P, nx, ny, nz, kx2, ky2, kz2, zpitch, zoff, ppitch);
   else hipLaunchKernelGGL(save_potential_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, s, (const cplx<float>*)K, (cplx<float>*)P, nx, ny, nz, kx2, ky2, kz2, zpitch, zoff, ppitch);
+  return hipGetLastError();
+}
+
+hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s) {
+  const long long nrows = (long long)gp.nx * gp.ny;
+  const int nzh = gp.nz / 2 + 1;
+  if (nrows <= 0 || nrows > 0x7fffffffLL || gp.pitch < nzh || gp.axis < 0 || gp.axis > 2) return hipErrorInvalidValue;
+  // the block shape of launch_gen_kspace; 16 workgroups per CU, grid-stride over the rest of the rows
+  int tx = 1;
+  while (tx < 256 && tx < nzh) tx <<= 1;
+  const int ty = 256 / tx;
+  const long long nblk = (nrows + ty - 1) / ty;
+  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);
+  if (f64) hipLaunchKernelGGL(gradient_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, gp, (unsigned)nrows);
+  else hipLaunchKernelGGL(gradient_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, gp, (unsigned)nrows);
   return hipGetLastError();
 }
 

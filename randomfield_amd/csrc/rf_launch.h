@@ -138,6 +138,9 @@ hipError_t launch_save_potential(int f64, const void* K, void* P, int nx, int ny
                                  const double* ky2, const double* kz2, int zpitch, int zoff, int ppitch, hipStream_t s);
 // (n = cells of K; P's rows hold ppitch >= zpitch cells)
 hipError_t launch_scale_copy(int f64, const void* P, void* K, long long n, int zpitch, int ppitch, double scale, hipStream_t s);
+// K (rows of nz/2 + 1 cells) = i k_a S, S with rows of gp.pitch cells (rf_core.h grad_cell): the stored potential, or K itself in divide
+// mode (S == K is allowed: every cell is read and written by the same thread).  Single-rank layouts.
+hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s);
 
 // on-GPU replay of RandomState(seed).normal (rf_k_mt.hip)
 // one stage of the jump tree: states[i + m * dist] = states[i] advanced by m * dist segments, i < nsrc, m = 1 .. nmult
@@ -173,6 +176,10 @@ hipError_t launch_generic_axis(int f64, const void* src, void* dst, const Generi
 // half spectrum (rf_generic.h GenericGenSource); ax.n == gp.nx and nlines == gp.ny * (gp.nz/2 + 1), else hipErrorInvalidValue
 hipError_t launch_generic_axis_gen(int f64, const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner,
                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
+// the x pass of one gradient component: element e of line l = cell (e, l / (nz/2+1), l % (nz/2+1)) of `src` (rows of gp.pitch cells) times
+// i k_a (rf_generic.h GenericGradSource); ax.n == gp.nx, nlines == gp.ny * (gp.nz/2 + 1) and src != dst, else hipErrorInvalidValue
+hipError_t launch_generic_axis_grad(int f64, const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
 // axes too long for the LDS (rf_generic.h GenericLong): one step of the four-step transform (lines with sub-lines); the Hermitian
 // (un)tangle of long rows as passes of their own; (sum, sum of squares) of a real array into nblocks partial pairs
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s);

@@ -488,6 +488,81 @@ class Generator(object):
         self._field_on_host = False
         return self.download_field() if download else None
 
+    def calculate_displacement_field(self, axis, light_cone=False, *, scale=1.0, factor_z=None, download=True):
+        """
+        One component of the vector field of the saved potential (an extension: the reference keeps delta(k)/k**2 "for later
+        calculations of the lensing potential or the bulk velocity vector field", generate.py:200-217, and has no method for the
+        latter):
+
+            psi_a(r) = irfftn( i k_a * scale * delta(k) / k**2 ),    a = ``axis`` in (0, 1, 2) or ('x', 'y', 'z'),
+
+        so that div psi = -scale * delta: with ``scale=1`` the Zel'dovich displacement in Mpc/h.  The mode of the axis' own
+        Nyquist frequency is dropped (i k is not Hermitian there).  ``light_cone=True`` multiplies plane z by
+        ``growth_function[z]``; ``factor_z`` is any (nz,) table used instead -- a H f G along z (expansion factor, Hubble rate,
+        growth rate, growth function) turns the displacement into a peculiar velocity.
+
+        Returns a *view* of the plan's buffer that later calls overwrite; ``delta_field_rms`` and the saved potential are left
+        alone, so the three components can be asked for one after another.  hip backend: a stored potential
+        (``Generator(store_potential=True)``) is differentiated on the device as it is.  A regenerated one (the default where the
+        plan can form delta(k)/k**2 again) costs one generation sweep of k space per call with ``rng='native'``; with
+        ``rng='reference'`` the first call runs the storing form of the realisation once (one realisation, and from then on the
+        device memory of ``store_potential=True``: ``self.potential`` becomes the stored potential of the same field) and every
+        later call reads what it stored.
+        """
+        if self.distributed:
+            raise NotImplementedError("calculate_displacement_field runs on single-GPU plans (distributed=False).")
+        if self.potential is None:
+            raise RuntimeError("No saved potential field.")
+        if isinstance(axis, str):
+            if axis not in ("x", "y", "z"):
+                raise ValueError("Invalid axis: {0!r} (expected 0, 1, 2, 'x', 'y' or 'z').".format(axis))
+            axis = "xyz".index(axis)
+        if axis not in (0, 1, 2):
+            raise ValueError("Invalid axis: {0!r} (expected 0, 1, 2, 'x', 'y' or 'z').".format(axis))
+        axis = int(axis)
+        shape = self.plan_c2r.shape
+        nz = shape[2]
+        if factor_z is not None:
+            factor = np.asarray(factor_z, float).reshape(nz)
+        elif light_cone:
+            factor = self._need_table("growth_function")
+        else:
+            factor = None
+        dk = 2 * np.pi / (shape[axis] * self.grid_spacing_Mpc_h)
+        if self.backend == "numpy":
+            n = shape[axis]
+            m = np.arange(nz // 2 + 1) if axis == 2 else np.fft.fftfreq(n, 1.0 / n)
+            m = np.where(np.abs(m) == n // 2, 0.0, m)          # the axis' Nyquist mode (n is even: transform.Plan accepts nothing else)
+            # (the factor is rounded to the array's COMPLEX type here, where the device rounds the real factor once and multiplies the
+            # two parts -- rf_core.h grad_cell; both are two roundings per component, the fields agree to a few float32 ulp)
+            ik = (1j * scale * dk * m).reshape([-1 if a == axis else 1 for a in range(3)])
+            self.plan_c2r.data_in[:] = self.potential
+            self.plan_c2r.data_in *= ik.astype(self.plan_c2r.data_in.dtype)
+            field = self.plan_c2r.execute()
+            if factor is not None:
+                field *= factor
+            return field
+        from . import _hip
+        dev = self.plan_c2r.device
+        if isinstance(self.potential, _RegeneratedPotential):
+            self.potential.check_current()
+            if self.potential.noise is None:
+                dev.generate(self.potential.seed, None)                      # delta(k) again: one generation sweep
+                dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_KSPACE)
+            else:
+                # the replayed reference stream is resident as float32 pairs, which only the fused generation pass reads (rf_generate
+                # wants float64 deviates): run the storing form of the call once, as _RegeneratedPotential.download() does -- the field
+                # buffer is about to be overwritten anyway -- and keep what it stored for the other components
+                dev.realise_potential(self.potential.seed, self.potential.noise)
+                self.potential = _DevicePotential(self)
+                dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_POTENTIAL)
+        else:
+            dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_POTENTIAL)
+        if factor is not None:
+            dev.scale_z(factor)
+        self._field_on_host = False
+        return self.download_field() if download else None
+
     def calculate_lensing_potential(self, i_min=None, show_plot=False, save_plot_name=None):
         """
         Calculate the lensing potential psi(r) (generate.py:352-416):

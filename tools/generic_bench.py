@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Timing of the generic (non-power-of-two) path: realisations on grids such as 1000^3 against the tiled 1024^3.
-usage: generic_bench.py [--lib variant.so] [--fused] [--f64] [--reps N] [edge | NXxNYxNZ ...]
+usage: generic_bench.py [--lib variant.so] [--fused | --gradient] [--f64] [--reps N] [edge | NXxNYxNZ ...]
 --fused: every generic shape twice in ONE process and on one plan -- generation as a launch of its own (the default of the C ABI), then
-inside the x pass (RF_FLAG_FUSED_GENERIC_GENERATION) -- interleaved rounds, median wall time per realisation, rf_kernel_ms of each."""
+inside the x pass (RF_FLAG_FUSED_GENERIC_GENERATION) -- interleaved rounds, median wall time per realisation, rf_kernel_ms of each.
+--gradient: one component of the gradient of the potential (rf_execute_gradient_c2r) on every generic shape, in ONE process and on one
+plan: the factor inside the x pass against the elementwise kernel + rf_execute_c2r, with the plain rf_execute_c2r as the yardstick."""
 import os
 import sys
 import time
@@ -83,9 +85,66 @@ def run_fused(shape, ct=np.complex64, reps=3, rounds=5):
         shape, np.dtype(ct).name, med[True] / med[False], reps, 5 * es * (1 + 2.0 / nz), 5 * es, 7 * es), flush=True)
 
 
+def run_gradient(shape, ct=np.complex64, reps=3, rounds=5, axis=0):
+    """Three forms on one plan with the stored potential of one realisation as the source, interleaved rounds, medians: the plain c2r
+    of the k buffer (yardstick), load_gradient + execute_c2r (a read-and-write sweep of k space more), execute_gradient (no sweep)."""
+    nx, ny, nz = shape
+    p = make(shape, ct)
+    if p.tiled:
+        p.close()
+        print("%-20s tiled plan: rf_execute_gradient_c2r runs the elementwise kernel + rf_execute_c2r there" % (shape,), flush=True)
+        return
+    P = _hip.RF_GRAD_FROM_POTENTIAL
+    dk = 2 * np.pi / (shape[axis] * 2.5)
+    p.realise_potential(seed=1)
+
+    def plain():
+        p.execute_c2r()
+
+    def unfused():
+        p.load_gradient(axis, 1.0, dk, P)
+        p.execute_c2r()
+
+    def fused():
+        p.execute_gradient(axis, 1.0, dk, P)
+
+    forms = (("c2r", plain), ("sweep+c2r", unfused), ("fused", fused))
+
+    def window(f, n):
+        t0 = time.perf_counter()
+        for _ in range(n):
+            f()
+        p.sync()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    std = {}
+    p.load_gradient(axis, 1.0, dk, P)          # (the yardstick transforms the component too: same data in every form)
+    for name, f in forms:
+        f()
+        p.sync()
+        std[name] = p.moments()[1]
+    assert std["fused"] == std["sweep+c2r"], "the fused form changed the field's rms: %r" % (std,)
+    reps = max(reps, min(400, int(300.0 / max(window(fused, 3), 1e-3)) + 1))      # windows of at least 0.3 s
+    wall = {name: [] for name, _ in forms}
+    kern = {name: [] for name, _ in forms}
+    for r in range(rounds):
+        for name, f in forms:
+            wall[name].append(window(f, reps))
+            kern[name].append(p.kernel_ms())
+    p.close()
+    med = {name: float(np.median(wall[name])) for name in wall}
+    for name, _ in forms:
+        k = np.median(np.array(kern[name]), axis=0)
+        print("%-20s %-10s axis %d %-10s %9.3f ms (min %.3f max %.3f)  rms %.4g  kernels of the c2r %s" % (
+            shape, np.dtype(ct).name, axis, name, med[name], min(wall[name]), max(wall[name]), std[name],
+            " ".join("%s %.3f" % (n, v) for n, v in zip(KERNELS, k))), flush=True)
+    print("%-20s %-10s fused / (sweep + c2r) = %.3f, fused / c2r = %.3f, (sweep + c2r) / c2r = %.3f (%d calls per window)" % (
+        shape, np.dtype(ct).name, med["fused"] / med["sweep+c2r"], med["fused"] / med["c2r"], med["sweep+c2r"] / med["c2r"], reps), flush=True)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
-    fused, ct, reps = False, np.complex64, 3
+    fused, gradient, ct, reps = False, False, np.complex64, 3
     while args and args[0].startswith("--"):
         if args[0] == "--lib":
             _hip.LIB_PATH = os.path.abspath(args[1])
@@ -96,6 +155,9 @@ if __name__ == "__main__":
         elif args[0] == "--fused":
             fused = True
             args = args[1:]
+        elif args[0] == "--gradient":
+            gradient = True
+            args = args[1:]
         elif args[0] == "--f64":
             ct = np.complex128
             args = args[1:]
@@ -103,4 +165,4 @@ if __name__ == "__main__":
             sys.exit(__doc__)
     for a in args or ["500", "512", "1000", "1024"]:
         shape = tuple(int(v) for v in a.split("x")) if "x" in a else (int(a),) * 3
-        (run_fused if fused else run)(shape, ct, reps)
+        (run_gradient if gradient else run_fused if fused else run)(shape, ct, reps)
