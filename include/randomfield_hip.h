@@ -41,7 +41,8 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * every addition.  rf_version() returns the RF_ABI_VERSION the loaded library was built from: a consumer compares its major with the
  * header it was compiled against and asks rf_abi_features() which groups of entry points the build carries.  (History: rounds 1-4 of
  * this repository returned the constant 1 while the surface grew from ~20 to 70 entry points; 5.0 is the first version that means
- * something: the consumer surface below + the diagnostics of randomfield_hip_diag.h.) */
+ * something: the consumer surface below + the diagnostics of randomfield_hip_diag.h.)  rf_measure_power was added WITHOUT a new
+ * minor number -- the version stays 5.5 -- and is announced by its feature bit alone: ask rf_abi_features() & RF_FEATURE_POWER_MEASURE. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -65,7 +66,8 @@ enum {
   RF_FEATURE_DIRECT_EXCHANGE = 1 << 12,    /* rf_comm_enable_direct: the y pass stores into the peers' receive buffers (IPC-mapped), no all-to-all kernels */
   RF_FEATURE_DIAGNOSTICS = 1 << 11,        /* the entry points of randomfield_hip_diag.h (timing per kernel, launch structure, virtual ranks) */
   RF_FEATURE_GENERIC_FUSED = 1 << 13,      /* RF_FLAG_FUSED_GENERIC_GENERATION; rf_kernel_ms on generic plans */
-  RF_FEATURE_GRADIENT = 1 << 14            /* rf_load_gradient, rf_execute_gradient_c2r: the vector field of the saved potential */
+  RF_FEATURE_GRADIENT = 1 << 14,           /* rf_load_gradient, rf_execute_gradient_c2r: the vector field of the saved potential */
+  RF_FEATURE_POWER_MEASURE = 1 << 15       /* rf_measure_power: the binned power spectrum of the k buffer or of the field */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -270,6 +272,23 @@ int rf_load_gradient(rf_plan* plan, int axis, double scale, double dk, int sourc
  * The k buffer afterwards: RF_GRAD_FROM_KSPACE consumes it (no k-space data until the next generate / upload / load);
  * RF_GRAD_FROM_POTENTIAL leaves what it held (generic plans) or psi_a(k) (tiled plans). */
 int rf_execute_gradient_c2r(rf_plan* plan, int axis, double scale, double dk, int source);
+
+/* ---- binned power spectrum (rf_abi_features() & RF_FEATURE_POWER_MEASURE) -- */
+/* The estimator that closes P(k) -> delta(x) -> P^(k): one sweep of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform
+ * values, as rf_generate / rf_upload_k / rf_execute_r2c leave them.  Cell (ix, iy, iz) has k^2 = (kx2[ix] + ky2[iy]) + kz2[iz] (float64,
+ * the tables of rf_set_kgrid) and the weight w = 1 on the planes iz = 0 and iz = nz/2, 2 elsewhere.  k_edges: nbins + 1 strictly
+ * increasing edges in k, k_edges[0] >= 0, 1 <= nbins <= 1024; they are squared once in float64 and a cell belongs to bin b iff
+ * e2[b] <= k^2 < e2[b+1].  The DC cell and cells outside all bins are dropped.  Per bin: count = sum of w (exact), sum_k = sum of
+ * w sqrt(k^2), sum_p = sum of w |delta(k)|^2, values widened to float64 and summed in float64 in a fixed order: the same plan, data and
+ * edges give the same bits on every call.  With N = nx ny nz and V = N spacing^3: k = sum_k / count, P = (V / N^2) sum_p / count.
+ * source = RF_POWER_FROM_KSPACE reads the k buffer and changes nothing.  source = RF_POWER_FROM_FIELD transforms the current field first:
+ * generic plans as rf_execute_r2c does (the field stays, the k buffer then holds delta(k)); tiled plans run the forward passes in place
+ * and sweep the packed array directly -- no k-space array is allocated or written, the field is consumed as by rf_execute_r2c, the k
+ * buffer and its validity stay as they were, and the sums differ from rf_execute_r2c + RF_POWER_FROM_KSPACE by summation order only.
+ * Packed single-rank plans, tiled and generic, both dtypes; c2c plans, nranks > 1, a missing kgrid, bad edges and a missing source are
+ * refused with nothing queued.  Blocks until the three arrays (nbins entries each) are on the host; rf_elapsed_ms covers the call. */
+enum { RF_POWER_FROM_KSPACE = 0, RF_POWER_FROM_FIELD = 1 };
+int rf_measure_power(rf_plan* plan, int source, const double* k_edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p);
 
 /* ---- host <-> device (layout conversion to/from the reference's arrays) -- */
 int rf_upload_k(rf_plan* plan, const void* host);            /* (nx, ny, nz/2+1) complex */

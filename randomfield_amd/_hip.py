@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "librandomfield_hip.so")
 
 RF_F32, RF_F64 = 0, 1
 RF_GRAD_FROM_POTENTIAL, RF_GRAD_FROM_KSPACE = 0, 1        # `source` of load_gradient / execute_gradient
+RF_POWER_FROM_KSPACE, RF_POWER_FROM_FIELD = 0, 1          # `source` of measure_power
 DIRECT_RECORD_BYTES = 192                 # RF_DIRECT_RECORD_BYTES (randomfield_hip_diag.h)
 NOISE_NATIVE, NOISE_EXTERNAL, NOISE_RESIDENT = 0, 1, 2
 LAYOUT_DENSE, LAYOUT_PADDED = 0, 1
@@ -31,7 +32,8 @@ _c_dp = ctypes.POINTER(ctypes.c_double)
 ABI_MAJOR, ABI_MINOR = 5, 5
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
-            "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14}
+            "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
+            "power_measure": 1 << 15}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -81,6 +83,7 @@ SIGNATURES = {
     "rf_load_potential": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     "rf_load_gradient": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
     "rf_execute_gradient_c2r": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
     "rf_lensing_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "rf_download_aux": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "rf_upload_k": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -637,6 +640,20 @@ class DevicePlan(object):
         """The real field of that component (rf_execute_gradient_c2r).  Generic plans apply the factor inside their x pass, tiled
         plans run load_gradient + execute_c2r.  ``RF_GRAD_FROM_KSPACE`` consumes the k buffer."""
         check(self._lib.rf_execute_gradient_c2r(self._h, int(axis), float(scale), float(dk), int(source)), "rf_execute_gradient_c2r")
+
+    def measure_power(self, edges, source=RF_POWER_FROM_KSPACE):
+        """Per-bin sums of the binned power spectrum (rf_measure_power): ``edges`` are ``nbins + 1`` increasing edges in k; returns
+        ``(count, sum_k, sum_p)`` -- uint64 sum of the weights, float64 sums of w |k| and w |delta(k)|^2 -- of the k buffer
+        (``RF_POWER_FROM_KSPACE``, nothing changes) or of the current field (``RF_POWER_FROM_FIELD``: forward transform first; tiled
+        plans consume the field and touch no k-space array, generic plans keep the field and leave delta(k) in the k buffer)."""
+        e = _f64(np.asarray(edges, np.float64).ravel())
+        nbins = len(e) - 1
+        count = np.zeros(max(nbins, 1), np.uint64)
+        sum_k = np.zeros(max(nbins, 1), np.float64)
+        sum_p = np.zeros(max(nbins, 1), np.float64)
+        check(self._lib.rf_measure_power(self._h, int(source), _dp(e), nbins, count.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                                         _dp(sum_k), _dp(sum_p)), "rf_measure_power")
+        return count, sum_k, sum_p
 
     # -- host <-> device --------------------------------------------------
     @property

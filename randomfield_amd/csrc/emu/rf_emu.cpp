@@ -852,6 +852,32 @@ int emu_generic_gradient_c2r(int f64, int nx, int ny, int nz, int axis, double s
   return f64 ? generic_gradient_c2r_impl<double>(nx, ny, nz, g, (const cplx<double>*)S, (double*)W, s1, s2)
              : generic_gradient_c2r_impl<float>(nx, ny, nz, g, (const cplx<float>*)S, (float*)W, s1, s2);
 }
+// the binned power spectrum (rf_core.h power_load / power_cell over an array, as rf_measure_power's sweep; cells in array order): S is
+// the API-layout half spectrum [nx][ny][nz/2+1], or with packed != 0 the array [nx][ny][nz/2] the tiled forward passes leave (slot
+// kz = 0 = A0 + i A_nyq).  edges: nbins + 1 edges in k, squared here as the host side of the call squares them.
+int emu_measure_power(int f64, int nx, int ny, int nz, int packed, const double* kx2, const double* ky2, const double* kz2, const void* S,
+                      const double* edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p) {
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || nbins < 1 || nbins > 1024 || !(kx2 && ky2 && kz2 && S && edges) || !(edges[0] >= 0.0)) return -1;
+  for (int b = 0; b < nbins; ++b) if (!(edges[b] < edges[b + 1])) return -1;
+  PowerParams g;
+  memset(&g, 0, sizeof(g));
+  g.nx = nx; g.ny = ny; g.nz = nz; g.nbins = nbins; g.packed = packed != 0;
+  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2;
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = edges[b] * edges[b];
+  for (int b = 0; b < nbins; ++b) { count[b] = 0; sum_k[b] = 0.0; sum_p[b] = 0.0; }
+  for (int ix = 0; ix < nx; ++ix)
+    for (int iy = 0; iy < ny; ++iy)
+      for (int iz = 0; iz <= nz / 2; ++iz) {
+        int w = 0;
+        double wk = 0.0, wp = 0.0;
+        const int b = f64 ? power_cell<double>(g, e2.data(), power_load<double>(g, (const cplx<double>*)S, ix, iy, iz), ix, iy, iz, w, wk, wp)
+                          : power_cell<float>(g, e2.data(), power_load<float>(g, (const cplx<float>*)S, ix, iy, iz), ix, iy, iz, w, wk, wp);
+        if (b < 0) continue;
+        count[b] += (unsigned long long)w; sum_k[b] += wk; sum_p[b] += wp;
+      }
+  return 0;
+}
 int emu_generic_r2c(int f64, int nx, int ny, int nz, const void* W, void* K) {
   return f64 ? generic_r2c_impl<double>(nx, ny, nz, (const double*)W, (cplx<double>*)K)
              : generic_r2c_impl<float>(nx, ny, nz, (const float*)W, (cplx<float>*)K);

@@ -987,7 +987,7 @@ int rf_version(void) { return RF_ABI_VERSION; }
 unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
-         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT;
+         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1202,7 +1202,7 @@ int rf_plan_destroy(rf_plan* p) {
   if (p->dl_stream) { (void)hipStreamSynchronize(p->dl_stream); (void)hipStreamDestroy(p->dl_stream); }
   for (auto& e : p->sink_ev) (void)hipEventDestroy(e);
   void* bufs[] = {p->peer_tab, p->W, p->R, p->W2, p->R2, p->K, p->P_base, p->G, p->G2, p->tw_x, p->tw_y, p->tw_z, p->kx2, p->ky2, p->kz2, p->xt, p->st, p->sl, p->bin,
-                  p->X, p->lntab, p->ypart, p->noise, p->mt_scratch, p->mt_send, p->mt_recv, p->mt_sbase, p->mt_first, p->mt_pos, p->mt_npos_dev, p->mt_states, p->mt_counts, p->mt_offsets, p->mt_rowtab, p->mt_flags, p->br_tmp, p->fixbuf, p->partials, p->stats, p->seeds_dev, p->ztab, p->frec, p->coll_scratch};
+                  p->X, p->lntab, p->ypart, p->noise, p->mt_scratch, p->mt_send, p->mt_recv, p->mt_sbase, p->mt_first, p->mt_pos, p->mt_npos_dev, p->mt_states, p->mt_counts, p->mt_offsets, p->mt_rowtab, p->mt_flags, p->br_tmp, p->fixbuf, p->partials, p->stats, p->seeds_dev, p->ztab, p->frec, p->coll_scratch, p->pw_buf};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < 2; ++i) {
@@ -1389,6 +1389,34 @@ int queue_r2c_slab_cols(rf_plan* p, hipStream_t s) {
   p->aux_valid = false;
   return 0;
 }
+// single-rank forward transform of the field in W.  Generic plans: rows -> half spectrum in K, then the y and x forward passes
+// (rf_generic.h generic_r2c_seq); W is untouched.  Tiled plans: the three passes in place in W, then (unpack) the API-layout array K;
+// without it W is left packed (slot kz = 0 = A0 + i A_nyq), K and k_valid as they were (rf_measure_power reads W directly).
+int queue_r2c_single(rf_plan* p, bool unpack) {
+  const long long nzc = p->nzc;
+  const ColGeom gx{(long long)p->ny * nzc, 0, (long long)p->ny * nzc}, gy{nzc, (long long)p->ny * nzc, nzc};
+  if (p->generic) {
+    if (int rc = ensure_k(p)) return rc;
+    if (generic_any_long(p)) { if (int rc = ensure_g(p)) return rc; if (int rc = ensure_g2(p)) return rc; }
+    HipGenericOps ops{p, p->stream};
+    if (int rc = generic_r2c_seq(ops, p->gdims, p->W, p->K, p->G, p->G2)) return rc;
+    p->k_valid = true;          // the real field in W is untouched on this path
+    p->aux_valid = false;
+    return 0;
+  }
+  if (unpack) { if (int rc = ensure_k(p)) return rc; }
+  RF_HIP(launch_row_r2c(p->f64, (int)nzc, p->W, (long long)p->nx * p->ny, p->tw_z, p->stream));     // z, in place
+  RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W, gy, (long long)p->nx * nzc, p->tw_y, p->stream));   // y forward
+  RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W, gx, (long long)p->ny * nzc, p->tw_x, p->stream));   // x forward
+  p->real_valid = false;      // the field buffer now holds packed k space
+  p->stats_valid = false;
+  if (unpack) {
+    RF_HIP(launch_unpack_kspace(p->f64, p->W, p->K, p->nx, p->ny, (int)nzc, 0, p->stream));
+    p->k_valid = true;
+    p->aux_valid = false;
+  }
+  return 0;
+}
 }  // namespace rfc
 extern "C" {
 
@@ -1410,29 +1438,10 @@ int rf_execute_r2c(rf_plan* p) {
     p->timed = false;
     return 0;
   }
-  const long long nzc = p->nzc;
-  const ColGeom gx{(long long)p->ny * nzc, 0, (long long)p->ny * nzc}, gy{nzc, (long long)p->ny * nzc, nzc};
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  if (p->generic) {            // rows -> half spectrum in K, then the y and x forward passes (rf_generic.h generic_r2c_seq)
-    if (generic_any_long(p)) { if (int rc = ensure_g(p)) return rc; if (int rc = ensure_g2(p)) return rc; }
-    HipGenericOps ops{p, p->stream};
-    if (int rc = generic_r2c_seq(ops, p->gdims, p->W, p->K, p->G, p->G2)) return rc;
-    RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->timed = false;
-    p->k_valid = true;          // the real field in W is untouched on this path
-    p->aux_valid = false;
-    return 0;
-  }
-  RF_HIP(launch_row_r2c(p->f64, (int)nzc, p->W, (long long)p->nx * p->ny, p->tw_z, p->stream));     // z, in place
-  RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W, gy, (long long)p->nx * nzc, p->tw_y, p->stream));   // y forward
-  RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W, gx, (long long)p->ny * nzc, p->tw_x, p->stream));   // x forward
-  RF_HIP(launch_unpack_kspace(p->f64, p->W, p->K, p->nx, p->ny, (int)nzc, 0, p->stream));
+  if (int rc = queue_r2c_single(p, true)) return rc;
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   p->timed = false;
-  p->real_valid = false;      // the field buffer now holds packed k space
-  p->stats_valid = false;
-  p->k_valid = true;
-  p->aux_valid = false;
   return 0;
 }
 
@@ -1928,6 +1937,57 @@ int rf_execute_gradient_c2r(rf_plan* p, int axis, double scale, double dk, int s
   p->real_valid = true;
   p->stats_valid = true;
   if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
+  return 0;
+}
+
+int rf_measure_power(rf_plan* p, int source, const double* k_edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p) {
+  RF_REQUIRE(p, "null plan");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the power spectrum measurement runs on single-rank plans");
+  RF_REQUIRE(source == RF_POWER_FROM_KSPACE || source == RF_POWER_FROM_FIELD, "source must be RF_POWER_FROM_KSPACE or RF_POWER_FROM_FIELD");
+  RF_REQUIRE(k_edges && count && sum_k && sum_p, "null argument");
+  RF_REQUIRE(nbins >= 1 && nbins <= 1024, "nbins must be between 1 and 1024");
+  RF_REQUIRE(k_edges[0] >= 0.0, "bad k_edges: the first edge must not be negative");
+  for (int b = 0; b < nbins; ++b) RF_REQUIRE(k_edges[b] < k_edges[b + 1], "bad k_edges: the edges must be strictly increasing");
+  RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+  else RF_REQUIRE(p->real_valid && p->cur == p->W, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  RF_HIP(hipSetDevice(p->device));
+  // one lazy buffer: [squared edges, 1025 slots][result 3 x 1024][three planes of per-workgroup partials]
+  const PowerLaunch L = power_launch_shape(p->nx, p->ny, p->nz, nbins);
+  const long long plane_words = (long long)L.grid * nbins;
+  const size_t head_words = 1025 + 3 * 1024, need = (head_words + 3 * (size_t)plane_words) * 8;
+  if (p->pw_bytes < need) {
+    RF_HIP(hipStreamSynchronize(p->stream));
+    if (p->pw_buf) { RF_HIP(hipFree(p->pw_buf)); p->pw_buf = nullptr; p->pw_bytes = 0; }
+    RF_HIP(hipMalloc(&p->pw_buf, need));
+    p->pw_bytes = need;
+  }
+  double* e2_dev = (double*)p->pw_buf;
+  unsigned long long* out_dev = (unsigned long long*)p->pw_buf + 1025;
+  unsigned long long* part_dev = (unsigned long long*)p->pw_buf + head_words;
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = k_edges[b] * k_edges[b];
+  RF_HIP(hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false)) return rc; }     // tiled plans: W packed, no K
+  PowerParams g;
+  memset(&g, 0, sizeof(g));
+  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
+  g.nbins = nbins;
+  g.packed = source == RF_POWER_FROM_FIELD && !p->generic;
+  g.kz_sorted = 1;
+  for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) g.kz_sorted = 0;
+  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
+  RF_HIP(launch_power(p->f64, g.packed ? p->W : p->K, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  p->timed = false;
+  std::vector<unsigned long long> out(3 * (size_t)nbins);
+  RF_HIP(hipMemcpyAsync(out.data(), out_dev, out.size() * 8, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  memcpy(count, out.data(), (size_t)nbins * 8);
+  memcpy(sum_k, out.data() + nbins, (size_t)nbins * 8);
+  memcpy(sum_p, out.data() + 2 * (size_t)nbins, (size_t)nbins * 8);
   return 0;
 }
 

@@ -426,6 +426,60 @@ RF_HD cplx<T> grad_cell(const GradParams& g, cplx<T> v, int ix, int iy, int iz) 
   return mk<T>(-(f * v.y), f * v.x);
 }
 
+// --------------------------------------------------- binned power spectrum --
+// The estimator of rf_measure_power: cell (ix, iy, iz) of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform values
+// carries k^2 = (kx2[ix] + ky2[iy]) + kz2[iz] (float64, the sum order of grad_cell) and the weight w = 1 on the planes iz = 0 and
+// iz = nz/2, 2 elsewhere (the half spectrum stands for the full one).  It belongs to bin b iff e2[b] <= k^2 < e2[b+1], e2 the caller's
+// edges squared once in float64 by the host: no sqrt in the decision, so np.searchsorted(edges * edges, k2, 'right') - 1 agrees
+// exactly.  The DC cell and cells outside all bins are dropped.  A bin sums w (integer), w sqrt(k^2) and w (re^2 + im^2), the values
+// widened to float64 first.
+struct PowerParams {
+  int nx, ny, nz;
+  int nbins;
+  int kz_sorted;              // kz2 does not decrease with iz (checked by the host): consecutive cells of a row have non-decreasing bins
+  int packed;                 // the source is the packed array [nx][ny][nz/2] the tiled forward passes leave (power_load), not the API layout
+  const double* kx2;
+  const double* ky2;
+  const double* kz2;
+};
+// the bin of k2 among the nbins + 1 squared edges e2, or -1
+RF_HD int power_bin(const double* e2, int nbins, double k2) {
+  int lo = 0, hi = nbins + 1;                   // first index with e2[index] > k2
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (e2[mid] <= k2) lo = mid + 1; else hi = mid;
+  }
+  return (lo >= 1 && lo <= nbins) ? lo - 1 : -1;
+}
+// returns the bin of the cell (-1: dropped) and its three contributions
+template <typename T>
+RF_HD int power_cell(const PowerParams& g, const double* e2, cplx<T> v, int ix, int iy, int iz, int& w, double& wk, double& wp) {
+  w = 0; wk = 0.0; wp = 0.0;
+  if (ix == 0 && iy == 0 && iz == 0) return -1;
+  const double k2 = (g.kx2[ix] + g.ky2[iy]) + g.kz2[iz];
+  const int b = power_bin(e2, g.nbins, k2);
+  if (b < 0) return -1;
+  w = (iz == 0 || 2 * iz == g.nz) ? 1 : 2;
+  const double re = (double)v.x, im = (double)v.y;
+  wk = (double)w * sqrt(k2);
+  wp = (double)w * (re * re + im * im);
+  return b;
+}
+// cell (ix, iy, iz) of the half spectrum: from the API layout (rows of nz/2 + 1 cells), or from the packed array [nx][ny][nz/2] whose
+// slot kz = 0 holds C = A0 + i A_nyq -- untangled with unpack_kspace_kernel's formula and rounded to T as that kernel rounds
+template <typename T>
+RF_HD cplx<T> power_load(const PowerParams& g, const cplx<T>* S, int ix, int iy, int iz) {
+  const int nzc = g.nz / 2;
+  const long long col = (long long)ix * g.ny + iy;
+  if (!g.packed) return S[col * (nzc + 1) + iz];
+  if (iz > 0 && iz < nzc) return S[col * nzc + iz];
+  const cplx<T> a = S[col * nzc];
+  const long long mcol = (long long)((g.nx - ix) % g.nx) * g.ny + (g.ny - iy) % g.ny;
+  const cplx<T> b = S[mcol * nzc];
+  if (iz == 0) return mk<T>((T)0.5 * (a.x + b.x), (T)0.5 * (a.y - b.y));
+  return mk<T>((T)0.5 * (a.y + b.y), (T)0.5 * (b.x - a.x));
+}
+
 // ------------------------------------------------- fast native generation --
 // float32 plans with the native RNG do rows K,T,R,S entirely in float32: the
 // values are this repo's own definition (checked against the oracle's

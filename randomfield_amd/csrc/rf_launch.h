@@ -141,6 +141,14 @@ hipError_t launch_scale_copy(int f64, const void* P, void* K, long long n, int z
 // K (rows of nz/2 + 1 cells) = i k_a S, S with rows of gp.pitch cells (rf_core.h grad_cell): the stored potential, or K itself in divide
 // mode (S == K is allowed: every cell is read and written by the same thread).  Single-rank layouts.
 hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s);
+// the binned power spectrum of a half spectrum (rf_core.h power_cell; rf_k_power.hip).  S: API layout, or the packed array of the tiled
+// forward passes (gp.packed); e2_dev: the gp.nbins + 1 squared edges.  partials: three planes of plane_words 8-byte words each
+// (count, sum_k, sum_p per workgroup and bin: plane_words >= grid * nbins of power_launch_shape, else hipErrorInvalidValue);
+// out: [count nbins][sum_k nbins][sum_p nbins], 8-byte words
+struct PowerLaunch { int tx = 1, ty = 1; unsigned grid = 1; size_t lds = 0; };
+PowerLaunch power_launch_shape(int nx, int ny, int nz, int nbins);
+hipError_t launch_power(int f64, const void* S, const PowerParams& gp, const double* e2_dev, unsigned long long* partials, long long plane_words,
+                        unsigned long long* out, hipStream_t s);
 
 // on-GPU replay of RandomState(seed).normal (rf_k_mt.hip)
 // one stage of the jump tree: states[i + m * dist] = states[i] advanced by m * dist segments, i < nsrc, m = 1 .. nmult

@@ -206,6 +206,8 @@ struct rf_plan {
   rf::GenericAxis gax, gay, gaz;
   rf::GenericDims gdims;               // the same + the split of the long axes, as the sequences of rf_generic.h take them
   bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; k_valid untouched)
+  void* pw_buf = nullptr;               // lazy, rf_measure_power: squared edges, result, per-workgroup partials
+  size_t pw_bytes = 0;
   bool timed = false;
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations
@@ -233,5 +235,6 @@ int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed);
 int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStream_t s);
 int queue_r2c_slab_rows(rf_plan* p, hipStream_t s);
 int queue_r2c_slab_cols(rf_plan* p, hipStream_t s);
+int queue_r2c_single(rf_plan* p, bool unpack);
 int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_host, bool whole);
 }  // namespace rfc

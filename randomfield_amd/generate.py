@@ -403,6 +403,52 @@ class Generator(object):
             self._field_on_host = True
         return self.plan_c2r.data_out
 
+    def measure_power_spectrum(self, field=None, *, k_edges=None, nbins=None):
+        """
+        Binned power spectrum of a field on this grid (an extension; the reference has no such method): the estimator that
+        closes P(k) -> delta(x) -> P^(k).
+
+        ``field=None`` measures the current field -- the one on the device (hip backend) or ``plan_c2r.data_out`` (numpy backend);
+        an ``(nx, ny, nz)`` array is uploaded (hip) or copied into the plan's host buffer (numpy) first and becomes the current
+        field.  ``k_edges`` are ``nbins + 1`` strictly increasing, non-negative bin edges in h/Mpc, at most 1024 bins; by default
+        ``powertools.default_k_edges(shape, spacing, nbins)``: linear from ``k_min`` to ``k_max``, ``min(shape) // 2`` bins.
+
+        Every mode of the forward transform with ``edges[b] <= |k| < edges[b+1]`` (decided on squared values) enters bin b, the
+        stored half spectrum standing for the full one (weight 2 away from the planes kz = 0 and nz/2); the DC mode is dropped.
+        Returns a structured array with the fields ``'k'`` (mean |k| of the bin's modes), ``'Pk'`` (V / N**2 times the mean of
+        |delta(k)|**2, V the box volume and N the number of cells -- the convention of ``self.power``, so the two can be compared
+        directly) and ``'nmodes'`` (number of modes); empty bins hold NaN.
+
+        hip backend: one sweep on the device (``rf_measure_power``), reproducible bit for bit from call to call.  On
+        power-of-two grids (the tiled kernels) the forward transform runs in place and the DEVICE COPY OF THE FIELD IS CONSUMED:
+        a later :meth:`download_field` needs the field to be on the host already (it is after ``generate_delta_field()`` with
+        the default ``download=True`` and after passing ``field``); other shapes keep the field on the device.
+        ``distributed=True`` raises ``NotImplementedError``.
+        """
+        if self.distributed:
+            raise NotImplementedError("measure_power_spectrum runs on single-GPU plans.")
+        shape = tuple(self.plan_c2r.shape)
+        if k_edges is None:
+            k_edges = powertools.default_k_edges(shape, self.grid_spacing_Mpc_h, nbins)
+        k_edges = np.asarray(k_edges, np.float64).ravel()
+        if nbins is not None and len(k_edges) != int(nbins) + 1:
+            raise ValueError("k_edges must have nbins + 1 entries.")
+        if field is not None:
+            field = np.asarray(field)
+            if field.shape != shape:
+                raise ValueError("field must have the shape {0}.".format(shape))
+            self.plan_c2r.data_out[...] = field
+            self._field_on_host = True
+            if self.backend == "hip":
+                self.plan_c2r.device.upload_real(self.plan_c2r.data_out_padded, padded=True)
+        if self.backend == "numpy":
+            kdata = np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
+            sums = powertools.bin_power(kdata, self.grid_spacing_Mpc_h, k_edges)
+        else:
+            from . import _hip
+            sums = self.plan_c2r.device.measure_power(k_edges, _hip.RF_POWER_FROM_FIELD)
+        return powertools.power_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
+
     def _need_table(self, name):
         value = getattr(self, name)
         if value is None:

@@ -17,7 +17,8 @@ import numpy as np
 from . import transform
 
 __all__ = ["get_k_bounds", "create_ksq_grids", "ksq_axes", "fill_with_log10k", "validate_power", "filter_power",
-           "sigma_table", "tabulate_sigmas", "load_default_power", "make_power"]
+           "sigma_table", "tabulate_sigmas", "load_default_power", "make_power", "bin_power", "default_k_edges",
+           "power_estimate"]
 
 
 def grid_k_range(shape, spacing):
@@ -43,6 +44,77 @@ def ksq_axes(nx, ny, nz, spacing, packed=True):
     if packed:
         kz = kz[:nz // 2 + 1]
     return kx ** 2, ky ** 2, kz ** 2
+
+
+def default_k_edges(shape, spacing, nbins=None):
+    """``nbins + 1`` linear bin edges in k from ``k_min`` to ``k_max`` of :func:`grid_k_range` (the fundamental mode of the longest
+    axis ... the corner of the Nyquist cube); the last edge is nudged up by an ulp so that the corner mode is counted
+    (and the first one down where rounding would otherwise lose the fundamental mode).
+    ``nbins`` defaults to ``min(shape) // 2``."""
+    if nbins is None:
+        nbins = min(shape) // 2
+    nbins = int(nbins)
+    if not 1 <= nbins <= 1024:
+        raise ValueError("nbins must be between 1 and 1024.")
+    k_min, k_max = grid_k_range(shape, spacing)
+    edges = np.linspace(k_min, k_max, nbins + 1)
+    # the bin rule compares SQUARES (e * e against the sum of the three k**2 tables): the nudge goes to the first float whose square
+    # lies above the corner cell's k**2 as those tables give it -- one ulp above k_max, or a few where the roundings differ
+    corner = sum(float(t[n // 2]) for t, n in zip(ksq_axes(*shape, spacing), shape))
+    last = np.nextafter(max(edges[-1], k_max, np.sqrt(corner)), np.inf)
+    while last * last <= corner:
+        last = np.nextafter(last, np.inf)
+    edges[-1] = last
+    # ... and likewise the first edge may not lie above the fundamental mode of the longest axis as its table gives it
+    lowest = min(float(t[1]) for t in ksq_axes(*shape, spacing))
+    while edges[0] * edges[0] > lowest:
+        edges[0] = np.nextafter(edges[0], 0.0)
+    return edges
+
+
+def bin_power(kdata, spacing, edges):
+    """Per-bin sums of the binned power spectrum of a half spectrum -- the numpy statement of the definition the device call
+    ``rf_measure_power`` implements (csrc/rf_core.h power_cell).
+
+    ``kdata`` is ``(nx, ny, nz/2 + 1)`` complex, unnormalised forward-transform values delta(k).  Cell (ix, iy, iz) has
+    ``k2 = (kx2[ix] + ky2[iy]) + kz2[iz]`` in float64 and the weight w = 1 on the planes iz = 0 and iz = nz/2, 2 elsewhere; it belongs
+    to bin b iff ``edges[b]**2 <= k2 < edges[b+1]**2`` (the edges are squared once, no sqrt in the decision).  The DC cell and cells
+    outside all bins are dropped.  Returns ``(count, sum_k, sum_p)``: the uint64 sum of w, and the float64 sums of ``w * sqrt(k2)``
+    and ``w * |delta(k)|**2`` per bin."""
+    edges = np.asarray(edges, np.float64).ravel()
+    nbins = len(edges) - 1
+    if not 1 <= nbins <= 1024 or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+        raise ValueError("edges must be 2 ... 1025 strictly increasing non-negative values.")
+    nx, ny, nz = transform.expanded_shape(kdata, packed=True)
+    kx2, ky2, kz2 = ksq_axes(nx, ny, nz, spacing)
+    k2 = (kx2[:, None, None] + ky2[None, :, None]) + kz2[None, None, :]
+    b = np.searchsorted(edges * edges, k2.ravel(), side="right") - 1
+    w = np.full(k2.shape, 2, np.int64)
+    w[:, :, 0] = 1
+    w[:, :, nz // 2] = 1
+    w = w.ravel()
+    keep = (b >= 0) & (b < nbins)
+    keep[0] = False                          # the DC cell
+    b, w = b[keep], w[keep]
+    re = kdata.real.astype(np.float64).ravel()[keep]
+    im = kdata.imag.astype(np.float64).ravel()[keep]
+    count = np.bincount(b, weights=w, minlength=nbins).astype(np.uint64)      # (exact: integers far below 2**53)
+    sum_k = np.bincount(b, weights=w * np.sqrt(k2.ravel()[keep]), minlength=nbins)
+    sum_p = np.bincount(b, weights=w * (re * re + im * im), minlength=nbins)
+    return count, sum_k, sum_p
+
+
+def power_estimate(count, sum_k, sum_p, shape, spacing):
+    """The structured array ('k', 'Pk', 'nmodes') of the sums of :func:`bin_power` / ``DevicePlan.measure_power``: with
+    N = nx ny nz and V = N spacing**3, ``k = sum_k / count`` and ``Pk = (V / N**2) sum_p / count``; NaN in empty bins."""
+    n = float(shape[0]) * float(shape[1]) * float(shape[2])
+    out = np.empty(len(count), [("k", float), ("Pk", float), ("nmodes", np.uint64)])
+    c = np.asarray(count, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["k"] = np.where(c > 0, np.asarray(sum_k) / c, np.nan)
+        out["Pk"] = np.where(c > 0, (spacing ** 3 / n) * np.asarray(sum_p) / c, np.nan)
+    out["nmodes"] = count
+    return out
 
 
 def create_ksq_grids(data, spacing, packed):
