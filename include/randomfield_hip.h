@@ -42,7 +42,8 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * header it was compiled against and asks rf_abi_features() which groups of entry points the build carries.  (History: rounds 1-4 of
  * this repository returned the constant 1 while the surface grew from ~20 to 70 entry points; 5.0 is the first version that means
  * something: the consumer surface below + the diagnostics of randomfield_hip_diag.h.)  rf_measure_power was added WITHOUT a new
- * minor number -- the version stays 5.5 -- and is announced by its feature bit alone: ask rf_abi_features() & RF_FEATURE_POWER_MEASURE. */
+ * minor number -- the version stays 5.5 -- and is announced by its feature bit alone: ask rf_abi_features() & RF_FEATURE_POWER_MEASURE.
+ * The same holds for the second-order (2LPT) calls: rf_abi_features() & RF_FEATURE_LPT2. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -67,7 +68,9 @@ enum {
   RF_FEATURE_DIAGNOSTICS = 1 << 11,        /* the entry points of randomfield_hip_diag.h (timing per kernel, launch structure, virtual ranks) */
   RF_FEATURE_GENERIC_FUSED = 1 << 13,      /* RF_FLAG_FUSED_GENERIC_GENERATION; rf_kernel_ms on generic plans */
   RF_FEATURE_GRADIENT = 1 << 14,           /* rf_load_gradient, rf_execute_gradient_c2r: the vector field of the saved potential */
-  RF_FEATURE_POWER_MEASURE = 1 << 15       /* rf_measure_power: the binned power spectrum of the k buffer or of the field */
+  RF_FEATURE_POWER_MEASURE = 1 << 15,      /* rf_measure_power: the binned power spectrum of the k buffer or of the field */
+  RF_FEATURE_LPT2 = 1 << 16                /* rf_load_hessian, rf_execute_hessian_c2r, rf_lpt2_source, rf_lpt2_potential, RF_GRAD_FROM_POTENTIAL2:
+                                              the second-order Lagrangian displacement */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -262,9 +265,12 @@ int rf_load_potential(rf_plan* plan, double scale);
  * scale * dk * m is formed in float64 and rounded once to the plan's real type.
  * source = RF_GRAD_FROM_POTENTIAL: from the stored potential (rf_save_potential / rf_realise_potential), which is left as it is;
  * source = RF_GRAD_FROM_KSPACE: from the k buffer holding delta(k) -- the factor takes the 1 / k^2, summed in float64 from the
- * tables of rf_set_kgrid -- for plans that regenerate their potential instead of storing it.
+ * tables of rf_set_kgrid -- for plans that regenerate their potential instead of storing it;
+ * source = RF_GRAD_FROM_POTENTIAL2 (RF_FEATURE_LPT2): from the second-order potential of rf_lpt2_potential, read exactly as
+ * RF_GRAD_FROM_POTENTIAL reads the stored one; refused ("no second-order potential") unless that call has run since the stored
+ * potential was last written.
  * Packed single-rank plans, tiled and generic; c2c plans, nranks > 1, another axis and a missing source are refused, nothing queued. */
-enum { RF_GRAD_FROM_POTENTIAL = 0, RF_GRAD_FROM_KSPACE = 1 };
+enum { RF_GRAD_FROM_POTENTIAL = 0, RF_GRAD_FROM_KSPACE = 1, RF_GRAD_FROM_POTENTIAL2 = 2 };
 /* k buffer <- psi_a(k) (RF_GRAD_FROM_KSPACE: in place); rf_download_k and rf_execute_c2r then work as usual */
 int rf_load_gradient(rf_plan* plan, int axis, double scale, double dk, int source);
 /* the real field psi_a(x) in place of the current one, moments as after rf_execute_c2r.  Generic plans apply the factor inside their
@@ -272,6 +278,35 @@ int rf_load_gradient(rf_plan* plan, int axis, double scale, double dk, int sourc
  * The k buffer afterwards: RF_GRAD_FROM_KSPACE consumes it (no k-space data until the next generate / upload / load);
  * RF_GRAD_FROM_POTENTIAL leaves what it held (generic plans) or psi_a(k) (tiled plans). */
 int rf_execute_gradient_c2r(rf_plan* plan, int axis, double scale, double dk, int source);
+
+/* ---- second-order (2LPT) displacement (rf_abi_features() & RF_FEATURE_LPT2) -- */
+/* H_ab(k) = D_a D_b phi(k) = -scale (dk_a m_a)(dk_b m_b) phi(k), 0 <= a <= b <= 2: one component of the Hessian of the potential, D the
+ * spectral derivative of rf_load_gradient (m = 0 at index 0 and at the axis' own Nyquist index, on the diagonal a = b too, so that H_ab
+ * is the gradient applied twice).  Cells with m_a m_b = 0 -- the DC cell among them -- are exactly 0.  The real factor is formed in
+ * float64 (and divided by k^2 from the tables of rf_set_kgrid when the source is delta(k)) and rounded once to the plan's real type.
+ * source: RF_GRAD_FROM_POTENTIAL or RF_GRAD_FROM_KSPACE, state handling as rf_load_gradient.
+ * Packed single-rank plans, tiled and generic; c2c plans, nranks > 1, axes outside 0..2, a > b and a missing source are refused, nothing
+ * queued. */
+/* k buffer <- H_ab(k) (RF_GRAD_FROM_KSPACE: in place) */
+int rf_load_hessian(rf_plan* plan, int a, int b, double scale, double dk_a, double dk_b, int source);
+/* the real field H_ab(x) in place of the current one; generic plans apply the factor inside their x pass (the field is that of
+ * rf_load_hessian + rf_execute_c2r bit for bit), tiled plans run those two steps.  Moments and the k buffer afterwards: as
+ * rf_execute_gradient_c2r. */
+int rf_execute_hessian_c2r(rf_plan* plan, int a, int b, double scale, double dk_a, double dk_b, int source);
+/* The source of the second-order potential, S(x) = sum over a < b of H_aa H_bb - H_ab^2 with scale = 1, from the STORED potential
+ * (rf_save_potential / rf_realise_potential; only read, bit-identical afterwards): six Hessian transforms in the order xx, yy, zz, xy,
+ * xz, yz, each followed by one elementwise sweep in the plan's real type (fused multiply-adds, no atomics: the same bits on every
+ * call).  dk[3] = 2 pi / (n_a * spacing) per axis.  S(x) becomes the current real field (rf_download_real); its moments are not
+ * computed (rf_moments refuses until the next transform); the k buffer holds no k-space data afterwards.  The first call allocates
+ * two arrays of the field's size for the accumulators (counted by rf_plan_nbytes, freed with the plan). */
+int rf_lpt2_source(rf_plan* plan, const double* dk);
+/* phi2(k) = rfftn(S)(k) / k^2, 0 at DC, k^2 as rf_save_potential forms it: rf_lpt2_source, the forward transform as rf_execute_r2c,
+ * the division -- into the accumulators' memory, in the stored potential's layout.  Afterwards the k buffer holds S(k), the field buffer
+ * is as rf_execute_r2c leaves it, and rf_load_gradient / rf_execute_gradient_c2r take RF_GRAD_FROM_POTENTIAL2:
+ * psi2_a(x) = rf_execute_gradient_c2r(a, 3/7, dk_a, RF_GRAD_FROM_POTENTIAL2), so that x = q + D1 psi1 + D1^2 psi2 (D2 = -3/7 D1^2).
+ * The second-order potential is dropped by everything that writes the stored one (rf_save_potential, rf_realise_potential) and by the
+ * next rf_lpt2_source.  Needs rf_set_kgrid. */
+int rf_lpt2_potential(rf_plan* plan, const double* dk);
 
 /* ---- binned power spectrum (rf_abi_features() & RF_FEATURE_POWER_MEASURE) -- */
 /* The estimator that closes P(k) -> delta(x) -> P^(k): one sweep of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform

@@ -18,7 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librandomfield_hip.so")
 
 RF_F32, RF_F64 = 0, 1
-RF_GRAD_FROM_POTENTIAL, RF_GRAD_FROM_KSPACE = 0, 1        # `source` of load_gradient / execute_gradient
+RF_GRAD_FROM_POTENTIAL, RF_GRAD_FROM_KSPACE = 0, 1        # `source` of load_gradient / execute_gradient / load_hessian / execute_hessian
+RF_GRAD_FROM_POTENTIAL2 = 2                               # ... of the gradient calls alone: the second-order potential (lpt2_potential)
 RF_POWER_FROM_KSPACE, RF_POWER_FROM_FIELD = 0, 1          # `source` of measure_power
 DIRECT_RECORD_BYTES = 192                 # RF_DIRECT_RECORD_BYTES (randomfield_hip_diag.h)
 NOISE_NATIVE, NOISE_EXTERNAL, NOISE_RESIDENT = 0, 1, 2
@@ -33,7 +34,7 @@ ABI_MAJOR, ABI_MINOR = 5, 5
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
-            "power_measure": 1 << 15}
+            "power_measure": 1 << 15, "lpt2": 1 << 16}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -83,6 +84,10 @@ SIGNATURES = {
     "rf_load_potential": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     "rf_load_gradient": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
     "rf_execute_gradient_c2r": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "rf_load_hessian": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "rf_execute_hessian_c2r": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "rf_lpt2_source": (ctypes.c_int, [ctypes.c_void_p, _c_dp]),
+    "rf_lpt2_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp]),
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
     "rf_lensing_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "rf_download_aux": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
@@ -246,6 +251,7 @@ class DevicePlan(object):
         self.noise_epoch = 0
         self.power_epoch = 0
         self._fused_generation = False
+        self.lpt2_valid = False                         # lpt2_potential has run since the stored potential was last written through this object
         if self.unpacked:
             if nranks != 1:
                 raise ValueError("unpacked c2c plans are single-GPU")
@@ -554,6 +560,7 @@ class DevicePlan(object):
     def realise_potential(self, seed=0, noise=None):
         """generate_delta_field(save_potential=True): the field, and delta(k)/k**2 in the potential buffer."""
         mode, ptr, keep = self._noise_arg(noise)
+        self.lpt2_valid = False
         check(self._lib.rf_realise_potential(self._h, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), mode, ptr),
               "rf_realise_potential")
 
@@ -625,6 +632,7 @@ class DevicePlan(object):
         check(self._lib.rf_affine_z(self._h, _dp(f), len(f), float(add)), "rf_affine_z")
 
     def save_potential(self):
+        self.lpt2_valid = False
         check(self._lib.rf_save_potential(self._h), "rf_save_potential")
 
     def load_potential(self, scale=1.0):
@@ -640,6 +648,32 @@ class DevicePlan(object):
         """The real field of that component (rf_execute_gradient_c2r).  Generic plans apply the factor inside their x pass, tiled
         plans run load_gradient + execute_c2r.  ``RF_GRAD_FROM_KSPACE`` consumes the k buffer."""
         check(self._lib.rf_execute_gradient_c2r(self._h, int(axis), float(scale), float(dk), int(source)), "rf_execute_gradient_c2r")
+
+    def load_hessian(self, a, b, scale, dk_a, dk_b, source):
+        """k buffer <- -scale * k_a k_b * delta(k) / k^2 (rf_load_hessian), ``0 <= a <= b <= 2``: one component of the Hessian of the
+        potential, the gradient's spectral derivative applied twice; sources as :meth:`load_gradient`."""
+        check(self._lib.rf_load_hessian(self._h, int(a), int(b), float(scale), float(dk_a), float(dk_b), int(source)), "rf_load_hessian")
+
+    def execute_hessian(self, a, b, scale, dk_a, dk_b, source):
+        """The real field of that component (rf_execute_hessian_c2r): inside the x pass on generic plans, load_hessian +
+        execute_c2r on tiled ones."""
+        check(self._lib.rf_execute_hessian_c2r(self._h, int(a), int(b), float(scale), float(dk_a), float(dk_b), int(source)),
+              "rf_execute_hessian_c2r")
+
+    def lpt2_source(self, dk):
+        """The current field <- S(x) = sum_{a<b} (H_aa H_bb - H_ab^2) of the stored potential (rf_lpt2_source); ``dk``: the three
+        2 pi / (n_a * spacing).  The stored potential is only read; the k buffer holds no k-space data afterwards."""
+        d = _f64(np.asarray(dk, np.float64).reshape(3))
+        self.lpt2_valid = False
+        check(self._lib.rf_lpt2_source(self._h, _dp(d)), "rf_lpt2_source")
+
+    def lpt2_potential(self, dk):
+        """The second-order potential rfftn(S) / k^2 (rf_lpt2_potential), read afterwards by ``load_gradient`` / ``execute_gradient``
+        with ``RF_GRAD_FROM_POTENTIAL2``; the k buffer holds S(k), the field buffer is as after :meth:`execute_r2c`."""
+        d = _f64(np.asarray(dk, np.float64).reshape(3))
+        self.lpt2_valid = False
+        check(self._lib.rf_lpt2_potential(self._h, _dp(d)), "rf_lpt2_potential")
+        self.lpt2_valid = True          # (what the calls of THIS object did to the plan's second-order potential; the library keeps its own flag)
 
     def measure_power(self, edges, source=RF_POWER_FROM_KSPACE):
         """Per-bin sums of the binned power spectrum (rf_measure_power): ``edges`` are ``nbins + 1`` increasing edges in k; returns

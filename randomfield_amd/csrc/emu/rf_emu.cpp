@@ -600,6 +600,28 @@ template <typename T> struct EmuGenericOps {
         }
     return 0;
   }
+  // generic_hessian_c2r_seq: the x pass through GenericHessSource, and the component alone (the elementwise kernel's loop)
+  int axis_hess(const HessParams& hs, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    const int TC = g_generic_tile, nth = nthreads();
+    cplx<T>* lds = lds_image(ax, TC);
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TC < nlines; ++b) {
+        generic_axis_hess_block<T>(hs, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
+    return 0;
+  }
+  int hess_kspace(const HessParams& hs, const void* S, void* K) {
+    const int nzh = hs.nz / 2 + 1;
+    for (int ix = 0; ix < hs.nx; ++ix)
+      for (int iy = 0; iy < hs.ny; ++iy)
+        for (int iz = 0; iz < nzh; ++iz) {
+          const size_t row = (size_t)ix * hs.ny + iy;
+          ((cplx<T>*)K)[row * nzh + iz] = hess_cell<T>(hs, ((const cplx<T>*)S)[row * hs.pitch + iz], ix, iy, iz);
+        }
+    return 0;
+  }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     const int TC = g_generic_tile, nth = nthreads();
     cplx<T>* lds = lds_image(L.ax, TC);
@@ -714,6 +736,44 @@ inline bool emu_grad_params(int nx, int ny, int nz, int axis, double scale, doub
   g.nx = nx; g.ny = ny; g.nz = nz; g.axis = axis; g.divide = divide != 0; g.sdk = scale * dk;
   g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2; g.pitch = spitch;
   return true;
+}
+
+// one component of the Hessian of the potential as a field (rf_generic.h generic_hessian_c2r_seq), as generic_gradient_c2r_impl
+template <typename T>
+int generic_hessian_c2r_impl(int nx, int ny, int nz, const HessParams& hs, const cplx<T>* S, T* W, double* s1, double* s2) {
+  GenericDims d;
+  if (!emu_dims<T>(nx, ny, nz, true, d)) return -1;
+  const long long nzh = nz / 2 + 1;
+  auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
+  std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
+  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
+  ops.az = d.az;
+  const int rc = generic_hessian_c2r_seq(ops, d, hs, S, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
+  if (s1) *s1 = ops.s1;
+  if (s2) *s2 = ops.s2;
+  return rc;
+}
+inline bool emu_hess_params(int nx, int ny, int nz, int a, int b, double scale, double dk_a, double dk_b, int divide, const double* kx2, const double* ky2,
+                            const double* kz2, long long spitch, HessParams& g) {
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || a < 0 || a > b || b > 2 || spitch < nz / 2 + 1 || (divide && !(kx2 && ky2 && kz2))) return false;
+  memset(&g, 0, sizeof(g));
+  g.nx = nx; g.ny = ny; g.nz = nz; g.a = a; g.b = b; g.divide = divide != 0; g.sdk2 = -scale * dk_a * dk_b;
+  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2; g.pitch = spitch;
+  return true;
+}
+template <typename T>
+int lpt2_accumulate_impl(int step, T* H, T* Tacc, T* Sacc, long long n) {
+  for (long long i = 0; i < n; ++i) {
+    switch (step) {
+      case LPT2_FIRST: lpt2_step<T, LPT2_FIRST>(H[i], Tacc[i], Sacc[i]); break;
+      case LPT2_DIAG2: lpt2_step<T, LPT2_DIAG2>(H[i], Tacc[i], Sacc[i]); break;
+      case LPT2_DIAG3: lpt2_step<T, LPT2_DIAG3>(H[i], Tacc[i], Sacc[i]); break;
+      case LPT2_OFF: lpt2_step<T, LPT2_OFF>(H[i], Tacc[i], Sacc[i]); break;
+      case LPT2_LAST: lpt2_step<T, LPT2_LAST>(H[i], Tacc[i], Sacc[i]); break;
+      default: return -1;
+    }
+  }
+  return 0;
 }
 
 template <typename T>
@@ -851,6 +911,31 @@ int emu_generic_gradient_c2r(int f64, int nx, int ny, int nz, int axis, double s
   if (!emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g)) return -1;
   return f64 ? generic_gradient_c2r_impl<double>(nx, ny, nz, g, (const cplx<double>*)S, (double*)W, s1, s2)
              : generic_gradient_c2r_impl<float>(nx, ny, nz, g, (const cplx<float>*)S, (float*)W, s1, s2);
+}
+// K [nx][ny][nz/2+1] = D_a D_b S = -scale k_a k_b S (rf_core.h hess_cell over an array, as the elementwise Hessian kernel), 0 <= a <= b <= 2;
+// S, spitch, divide and S == K as emu_gradient_k
+int emu_hessian_k(int f64, int nx, int ny, int nz, int a, int b, double scale, double dk_a, double dk_b, int divide, const double* kx2,
+                  const double* ky2, const double* kz2, const void* S, long long spitch, void* K) {
+  HessParams g;
+  if (!emu_hess_params(nx, ny, nz, a, b, scale, dk_a, dk_b, divide, kx2, ky2, kz2, spitch, g)) return -1;
+  if (f64) { EmuGenericOps<double> ops{}; return ops.hess_kspace(g, S, K); }
+  EmuGenericOps<float> ops{};
+  return ops.hess_kspace(g, S, K);
+}
+// the field of that component with the factor applied inside the x pass (honours emu_set_generic_threads / _tile / _cap)
+int emu_generic_hessian_c2r(int f64, int nx, int ny, int nz, int a, int b, double scale, double dk_a, double dk_b, int divide, const double* kx2,
+                            const double* ky2, const double* kz2, const void* S, long long spitch, void* W, double* s1, double* s2) {
+  HessParams g;
+  if (!emu_hess_params(nx, ny, nz, a, b, scale, dk_a, dk_b, divide, kx2, ky2, kz2, spitch, g)) return -1;
+  return f64 ? generic_hessian_c2r_impl<double>(nx, ny, nz, g, (const cplx<double>*)S, (double*)W, s1, s2)
+             : generic_hessian_c2r_impl<float>(nx, ny, nz, g, (const cplx<float>*)S, (float*)W, s1, s2);
+}
+// one step (0 .. 4: FIRST, DIAG2, DIAG3, OFF, LAST) of the 2LPT source's sweep over n elements (rf_core.h lpt2_step, the function the
+// kernel calls per element): H the component, T and S the accumulators; LAST leaves the source in H
+int emu_lpt2_accumulate(int f64, int step, void* H, void* T, void* S, long long n) {
+  if (n < 0 || !(H && T && S)) return -1;
+  return f64 ? lpt2_accumulate_impl<double>(step, (double*)H, (double*)T, (double*)S, n)
+             : lpt2_accumulate_impl<float>(step, (float*)H, (float*)T, (float*)S, n);
 }
 // the binned power spectrum (rf_core.h power_load / power_cell over an array, as rf_measure_power's sweep; cells in array order): S is
 // the API-layout half spectrum [nx][ny][nz/2+1], or with packed != 0 the array [nx][ny][nz/2] the tiled forward passes leave (slot

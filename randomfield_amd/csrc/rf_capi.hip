@@ -781,6 +781,16 @@ struct HipGenericOps {
     if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }       // (rf_kernel_ms: entry 4, as the generation launch)
     return 0;
   }
+  // ... and of a Hessian component (generic_hessian_c2r_seq)
+  int axis_hess(const HessParams& hs, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    RF_HIP(launch_generic_axis_hess(p->f64, hs, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
+    return 0;
+  }
+  int hess_kspace(const HessParams& hs, const void* S, void* K) {
+    RF_HIP(launch_hessian(p->f64, S, K, hs, s));
+    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
+    return 0;
+  }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     if (int rc = enter(which)) return rc;
     RF_HIP(launch_generic_lines(p->f64, src, dst, L, root(which), s));
@@ -987,7 +997,7 @@ int rf_version(void) { return RF_ABI_VERSION; }
 unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
-         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE;
+         RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE | RF_FEATURE_LPT2;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1202,7 +1212,7 @@ int rf_plan_destroy(rf_plan* p) {
   if (p->dl_stream) { (void)hipStreamSynchronize(p->dl_stream); (void)hipStreamDestroy(p->dl_stream); }
   for (auto& e : p->sink_ev) (void)hipEventDestroy(e);
   void* bufs[] = {p->peer_tab, p->W, p->R, p->W2, p->R2, p->K, p->P_base, p->G, p->G2, p->tw_x, p->tw_y, p->tw_z, p->kx2, p->ky2, p->kz2, p->xt, p->st, p->sl, p->bin,
-                  p->X, p->lntab, p->ypart, p->noise, p->mt_scratch, p->mt_send, p->mt_recv, p->mt_sbase, p->mt_first, p->mt_pos, p->mt_npos_dev, p->mt_states, p->mt_counts, p->mt_offsets, p->mt_rowtab, p->mt_flags, p->br_tmp, p->fixbuf, p->partials, p->stats, p->seeds_dev, p->ztab, p->frec, p->coll_scratch, p->pw_buf};
+                  p->X, p->lntab, p->ypart, p->noise, p->mt_scratch, p->mt_send, p->mt_recv, p->mt_sbase, p->mt_first, p->mt_pos, p->mt_npos_dev, p->mt_states, p->mt_counts, p->mt_offsets, p->mt_rowtab, p->mt_flags, p->br_tmp, p->fixbuf, p->partials, p->stats, p->seeds_dev, p->ztab, p->frec, p->coll_scratch, p->pw_buf, p->L};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < 2; ++i) {
@@ -1223,7 +1233,7 @@ int rf_plan_destroy(rf_plan* p) {
 
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
-  *nbytes = p->w_bytes * (1 + (p->R ? 1 : 0) + (p->W2 ? 2 : 0) + (p->X ? 1 : 0)) + (p->K ? p->k_bytes : 0) + (p->P ? p->p_bytes : 0) + ((p->G ? 1 : 0) + (p->G2 ? 1 : 0)) * (p->unpacked ? p->w_bytes : p->k_bytes) +
+  *nbytes = p->w_bytes * (1 + (p->R ? 1 : 0) + (p->W2 ? 2 : 0) + (p->X ? 1 : 0)) + (p->K ? p->k_bytes : 0) + (p->P ? p->p_bytes : 0) + (p->L ? p->l_bytes : 0) + ((p->G ? 1 : 0) + (p->G2 ? 1 : 0)) * (p->unpacked ? p->w_bytes : p->k_bytes) +
             p->noise_cap * sizeof(double) + p->mt_scratch_bytes;      // + resident deviates and the replay's scratch runs
   return 0;
 }
@@ -1528,6 +1538,7 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
     return queue_xy(p, make_gen(p, 0, RF_NOISE_NATIVE, false), p->K, p->W, p->stream, false);
   }
   if (int rc = ensure_p(p)) return rc;
+  p->p2_valid = false;                               // (P is rewritten: a second-order potential made from the old one is stale)
   p->timed = whole;
   p->pot_target = p->P;
   p->resident_fast = (mode == RF_NOISE_RESIDENT);
@@ -1851,6 +1862,7 @@ int rf_save_potential(rf_plan* p) {
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_p(p)) return rc;
+  p->p2_valid = false;
   RF_HIP(launch_save_potential(p->f64, p->K, p->P, p->nx, p->ny, p->nz, p->kx2, p->ky2, p->kz2, p->nzl + 1, p->kz0, p->ppitch, p->stream));
   return 0;
 }
@@ -1876,8 +1888,10 @@ int gradient_params(rf_plan* p, int axis, double scale, double dk, int source, G
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->nranks == 1, "the gradient of the potential runs on single-rank plans");
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
-  RF_REQUIRE(source == RF_GRAD_FROM_POTENTIAL || source == RF_GRAD_FROM_KSPACE, "source must be RF_GRAD_FROM_POTENTIAL or RF_GRAD_FROM_KSPACE");
+  RF_REQUIRE(source == RF_GRAD_FROM_POTENTIAL || source == RF_GRAD_FROM_KSPACE || source == RF_GRAD_FROM_POTENTIAL2,
+             "source must be RF_GRAD_FROM_POTENTIAL, RF_GRAD_FROM_KSPACE or RF_GRAD_FROM_POTENTIAL2");
   if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
+  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L && p->p2_valid, "no second-order potential: call rf_lpt2_potential first");
   else {
     RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
     RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
@@ -1889,7 +1903,37 @@ int gradient_params(rf_plan* p, int axis, double scale, double dk, int source, G
   g.sdk = scale * dk;
   g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
   g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
+  S = g.divide ? p->K : (source == RF_GRAD_FROM_POTENTIAL2 ? p->L : p->P);
+  return 0;
+}
+// the same for the Hessian calls (rf_core.h HessParams)
+int hessian_params(rf_plan* p, int a, int b, double scale, double dk_a, double dk_b, int source, HessParams& g, const void*& S) {
+  RF_REQUIRE(p, "null plan");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the Hessian of the potential runs on single-rank plans");
+  RF_REQUIRE(a >= 0 && a <= 2 && b >= 0 && b <= 2, "axes must be 0, 1 or 2");
+  RF_REQUIRE(a <= b, "axes must be given as a <= b");
+  RF_REQUIRE(source == RF_GRAD_FROM_POTENTIAL || source == RF_GRAD_FROM_KSPACE, "source must be RF_GRAD_FROM_POTENTIAL or RF_GRAD_FROM_KSPACE");
+  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
+  else {
+    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+    RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  }
+  memset(&g, 0, sizeof(g));
+  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
+  g.a = a; g.b = b;
+  g.divide = source == RF_GRAD_FROM_KSPACE;
+  g.sdk2 = -scale * dk_a * dk_b;
+  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
+  g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
   S = g.divide ? p->K : p->P;
+  return 0;
+}
+// the accumulators of rf_lpt2_source, later the second-order potential
+int ensure_l(rf_plan* p) {
+  if (p->L) return 0;
+  p->l_bytes = 2 * p->w_bytes > p->p_bytes ? 2 * p->w_bytes : p->p_bytes;
+  RF_HIP(hipMalloc(&p->L, p->l_bytes));
   return 0;
 }
 }  // namespace rfc
@@ -1937,6 +1981,94 @@ int rf_execute_gradient_c2r(rf_plan* p, int axis, double scale, double dk, int s
   p->real_valid = true;
   p->stats_valid = true;
   if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
+  return 0;
+}
+
+int rf_load_hessian(rf_plan* p, int a, int b, double scale, double dk_a, double dk_b, int source) {
+  HessParams g;
+  const void* S = nullptr;
+  if (int rc = hessian_params(p, a, b, scale, dk_a, dk_b, source, g, S)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_k(p)) return rc;
+  RF_HIP(launch_hessian(p->f64, S, p->K, g, p->stream));
+  p->k_valid = true;
+  p->aux_valid = false;
+  return 0;
+}
+
+int rf_execute_hessian_c2r(rf_plan* p, int a, int b, double scale, double dk_a, double dk_b, int source) {
+  HessParams g;
+  const void* S = nullptr;
+  if (int rc = hessian_params(p, a, b, scale, dk_a, dk_b, source, g, S)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  if (!p->generic) {    // the component as a sweep of its own, then the plan's inverse transform
+    if (int rc = rf_load_hessian(p, a, b, scale, dk_a, dk_b, source)) return rc;
+    const int rc = rf_execute_c2r(p);
+    if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;     // (as rf_execute_gradient_c2r: one contract for both kinds of plan)
+    return rc;
+  }
+  // generic plans: the factor is applied by the x pass to the cells it loads (rf_generic.h generic_hessian_c2r_seq); K, P are only read
+  if (int rc = ensure_g(p)) return rc;
+  if (int rc = ensure_g2(p)) return rc;
+  p->slab_timed = 0;
+  p->slab_merged = 0;
+  p->repair_timed = false;
+  p->timed = true;
+  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  HipGenericOps ops{p, p->stream, true};
+  const double norm = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
+  if (int rc = generic_hessian_c2r_seq(ops, p->gdims, g, S, p->G, p->G2, p->W, norm)) return rc;
+  if (int rc = ops.enter(3)) return rc;
+  RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, p->stream));
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  p->cur = p->W;
+  p->stats_slot = 0;
+  p->real_valid = true;
+  p->stats_valid = true;
+  if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
+  return 0;
+}
+
+// S(x) = sum_{a<b} (H_aa H_bb - H_ab^2) of the stored potential (rf_core.h lpt2_step): six Hessian transforms with scale 1 in the order
+// xx, yy, zz, xy, xz, yz, each followed by its step of the sweep over the field buffer and the accumulators in L
+int rf_lpt2_source(rf_plan* p, const double* dk) {
+  RF_REQUIRE(p && dk, "null argument");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the second-order source runs on single-rank plans");
+  RF_REQUIRE(p->P, "no saved potential");
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_l(p)) return rc;
+  p->p2_valid = false;                               // (the accumulators take the memory of the second-order potential)
+  static const int comp[6][3] = {{0, 0, LPT2_FIRST}, {1, 1, LPT2_DIAG2}, {2, 2, LPT2_DIAG3}, {0, 1, LPT2_OFF}, {0, 2, LPT2_OFF}, {1, 2, LPT2_LAST}};
+  void* T = p->L;
+  void* S = (char*)p->L + p->w_bytes;
+  const long long n = (long long)p->nx * p->ny * p->nz;
+  for (const auto& c : comp) {
+    if (int rc = rf_execute_hessian_c2r(p, c[0], c[1], 1.0, dk[c[0]], dk[c[1]], RF_GRAD_FROM_POTENTIAL)) return rc;
+    RF_HIP(launch_lpt2_accumulate(p->f64, c[2], p->W, T, S, n, p->stream));
+  }
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));       // (rf_elapsed_ms: the last component's transform and the last step)
+  p->timed = false;
+  p->cur = p->W;
+  p->real_valid = true;
+  p->stats_valid = false;
+  p->k_valid = false;                                // (tiled plans left a Hessian component there: one contract)
+  p->aux_valid = false;
+  return 0;
+}
+
+// phi2(k) = rfftn(S)(k) / k^2 into L, in the stored potential's layout: the source, the forward transform, the division
+int rf_lpt2_potential(rf_plan* p, const double* dk) {
+  RF_REQUIRE(p && dk, "null argument");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the second-order potential runs on single-rank plans");
+  RF_REQUIRE(p->P, "no saved potential");
+  RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  if (int rc = rf_lpt2_source(p, dk)) return rc;
+  if (int rc = rf_execute_r2c(p)) return rc;
+  RF_HIP(launch_save_potential(p->f64, p->K, p->L, p->nx, p->ny, p->nz, p->kx2, p->ky2, p->kz2, p->nzl + 1, p->kz0, p->ppitch, p->stream));
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  p->p2_valid = true;
   return 0;
 }
 

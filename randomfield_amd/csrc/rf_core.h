@@ -426,6 +426,51 @@ RF_HD cplx<T> grad_cell(const GradParams& g, cplx<T> v, int ix, int iy, int iz) 
   return mk<T>(-(f * v.y), f * v.x);
 }
 
+// ------------------------------------------- second-order (2LPT) source ------
+// One component of the Hessian of the potential: H_ab(k) = D_a D_b phi(k) = -scale (dk_a m_a)(dk_b m_b) phi(k), D_a the spectral
+// derivative of grad_cell (m = 0 at index 0 and at the axis' own Nyquist index -- on the diagonal a = b too, so that H_ab is exactly
+// "the gradient applied twice").  Cells with m_a m_b = 0 are exact zeros, the DC cell among them.  The real factor is formed in
+// float64, takes the 1 / k^2 in divide mode, and is rounded ONCE to the array's real type; the two products are the second rounding
+// (the budget of grad_cell).  pitch, divide and the tables: as GradParams.
+struct HessParams {
+  int nx, ny, nz;
+  int a, b;                   // 0 <= a <= b <= 2
+  int divide;
+  double sdk2;                // -scale * dk_a * dk_b
+  const double* kx2;
+  const double* ky2;
+  const double* kz2;
+  long long pitch;
+};
+RF_HD int hess_axis_mode(const HessParams& g, int axis, int ix, int iy, int iz) {
+  return axis == 0 ? grad_mode(ix, g.nx, false) : (axis == 1 ? grad_mode(iy, g.ny, false) : grad_mode(iz, g.nz, true));
+}
+template <typename T>
+RF_HD cplx<T> hess_cell(const HessParams& g, cplx<T> v, int ix, int iy, int iz) {
+  const int ma = hess_axis_mode(g, g.a, ix, iy, iz), mb = g.b == g.a ? ma : hess_axis_mode(g, g.b, ix, iy, iz);
+  if (ma == 0 || mb == 0) return mk<T>((T)0, (T)0);
+  double fd = g.sdk2 * ((double)ma * (double)mb);
+  if (g.divide) fd = fd / ((g.kx2[ix] + g.ky2[iy]) + g.kz2[iz]);
+  const T f = (T)fd;
+  return mk<T>(f * v.x, f * v.y);
+}
+
+// The real-space sweep that turns the six components into S = sum_{a<b} (H_aa H_bb - H_ab^2), one step per component h in the fixed
+// order xx, yy, zz, xy, xz, yz; t, s: the accumulators.  Explicit fma: host and device round the same number of times.
+//   FIRST  t = h                       DIAG2  s = t h; t = t + h            DIAG3  s = fma(t, h, s)
+//   OFF    s = fma(-h, h, s)           LAST   h = fma(-h, h, s)  (the source lands where the component was)
+enum { LPT2_FIRST = 0, LPT2_DIAG2 = 1, LPT2_DIAG3 = 2, LPT2_OFF = 3, LPT2_LAST = 4 };
+RF_HD float lpt2_fma(float a, float b, float c) { return fmaf(a, b, c); }
+RF_HD double lpt2_fma(double a, double b, double c) { return fma(a, b, c); }
+template <typename T, int STEP>
+RF_HD void lpt2_step(T& h, T& t, T& s) {
+  if (STEP == LPT2_FIRST) t = h;
+  else if (STEP == LPT2_DIAG2) { s = t * h; t = t + h; }
+  else if (STEP == LPT2_DIAG3) s = lpt2_fma(t, h, s);
+  else if (STEP == LPT2_OFF) s = lpt2_fma(-h, h, s);
+  else h = lpt2_fma(-h, h, s);
+}
+
 // --------------------------------------------------- binned power spectrum --
 // The estimator of rf_measure_power: cell (ix, iy, iz) of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform values
 // carries k^2 = (kx2[ix] + ky2[iy]) + kz2[iz] (float64, the sum order of grad_cell) and the weight w = 1 on the planes iz = 0 and

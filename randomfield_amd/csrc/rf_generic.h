@@ -391,6 +391,22 @@ template <typename T> struct GenericGradSource {
   }
 };
 
+//   GenericHessSource: the same array seen through hess_cell (rf_core.h) -- the x pass of one component of the potential's Hessian.
+template <typename T> struct GenericHessSource {
+  enum { INFLIGHT = 4 };
+  const cplx<T>* src;
+  HessParams g;
+  long long nzh, stride, base;
+  int iy, iz;
+  RF_HD GenericHessSource(const HessParams& hp, const cplx<T>* s) : src(s), g(hp), nzh(hp.nz / 2 + 1), stride((long long)hp.ny * hp.pitch), base(0), iy(0), iz(0) {}
+  RF_HD void line(long long l, long long) { iy = (int)(l / nzh); iz = (int)(l % nzh); base = (long long)iy * g.pitch + iz; }
+  RF_HD cplx<T> at(int e) const { return hess_cell<T>(g, src[base + e * stride], e, iy, iz); }
+  RF_HD cplx<T> at(long long l, int e) const {
+    const int y = (int)(l / nzh), z = (int)(l % nzh);
+    return hess_cell<T>(g, src[(long long)y * g.pitch + z + e * stride], e, y, z);
+  }
+};
+
 // Strided (or contiguous) complex pass: block `blk` transforms lines [blk TC, blk TC + TC) of length ax.n;
 // line l starts at (l / inner) * outer + l % inner and its elements are `stride` apart.  src == dst is allowed
 // (a block reads all of its lines before it writes any).  lds: generic_bufs(ax) * ax.n * TC elements.
@@ -490,6 +506,15 @@ RF_HD void generic_axis_grad_block(const GradParams& gp, const cplx<T>* src, cpl
                                    long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
                                    cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
   generic_axis_block_from<T>(GenericGradSource<T>(gp, src), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
+                             tw_lds);
+}
+
+// ... and of a Hessian component, D_a D_b applied on the way in (GenericHessSource)
+template <typename T, class Sync>
+RF_HD void generic_axis_hess_block(const HessParams& hp, const cplx<T>* src, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
+                                   long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
+                                   cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
+  generic_axis_block_from<T>(GenericHessSource<T>(hp, src), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
                              tw_lds);
 }
 
@@ -891,6 +916,21 @@ int generic_gradient_c2r_seq(Ops& ops, const GenericDims& d, const GradParams& g
     return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
   }
   if (int rc = ops.axis_grad(grad, S, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
+  return generic_c2r_after_x(ops, d, G, G2, W, scale);
+}
+// One component of the Hessian of the potential as a real field: generic_gradient_c2r_seq with hess_cell for grad_cell (rf_core.h
+// HessParams, GenericHessSource) -- the field and its moments are those of hess_kspace + generic_c2r_seq, bit for bit; an x axis in the
+// four-step form takes the same fallback through G2.  Ops provides:
+//   axis_hess(hess, S, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() through GenericHessSource (generic_axis_hess_block)
+//   hess_kspace(hess, S, K)                                                          D_a D_b S into an API-layout array
+template <class Ops>
+int generic_hessian_c2r_seq(Ops& ops, const GenericDims& d, const HessParams& hess, const void* S, void* G, void* G2, void* W, double scale) {
+  const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
+  if (d.lx.split()) {
+    if (int rc = ops.hess_kspace(hess, S, G2)) return rc;
+    return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
+  }
+  if (int rc = ops.axis_hess(hess, S, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
   return generic_c2r_after_x(ops, d, G, G2, W, scale);
 }
 // dense reals W -> half spectrum K (np.fft.rfftn); W is left untouched

@@ -37,6 +37,16 @@ __global__ __launch_bounds__(1024) void generic_axis_grad_kernel(GradParams gp, 
                              (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
 }
 
+// the x pass of one Hessian component: the cells of `src` times -k_a k_b on the way in (rf_generic.h GenericHessSource); src != dst
+template <typename T>
+__global__ __launch_bounds__(1024) void generic_axis_hess_kernel(HessParams hp, const cplx<T>* __restrict__ src, cplx<T>* __restrict__ dst, GenericAxis ax,
+                                                               long long stride, long long inner, long long outer, long long nlines, int TC,
+                                                               const cplx<T>* __restrict__ root, int sign, T scale, int tw_lds) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  generic_axis_hess_block<T>(hp, src, dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, reinterpret_cast<cplx<T>*>(lds_raw),
+                             (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void generic_row_c2r_kernel(const cplx<T>* __restrict__ G, T* __restrict__ W, GenericAxis ax,
                                                              long long nrows, int TR, const cplx<T>* __restrict__ root, T scale,
@@ -200,6 +210,27 @@ hipError_t axis_grad_t(const GradParams& gp, const void* src, void* dst, const G
   return hipGetLastError();
 }
 
+// ... and once more for the Hessian's x pass
+template <typename T>
+hipError_t axis_hess_t(const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
+                       long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  if (ax.n != hp.nx || nlines != (long long)hp.ny * (hp.nz / 2 + 1) || hp.pitch < hp.nz / 2 + 1 || hp.a < 0 || hp.a > hp.b || hp.b > 2 || src == dst)
+    return hipErrorInvalidValue;
+  const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
+  const int tc = sh.tc;
+  const long long nblk = (nlines + tc - 1) / tc;
+  if (nblk <= 0) return hipSuccess;
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  const size_t lds = sh.lds;
+  if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
+  static LdsAttrLatch latch;
+  if (lds > 65536)
+    if (hipError_t e = latch.ensure((const void*)generic_axis_hess_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
+  hipLaunchKernelGGL(generic_axis_hess_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, hp, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner,
+                     outer, nlines, tc, (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
+  return hipGetLastError();
+}
+
 template <typename T> int rows_per_block(const GenericAxis& ax) { return generic_lines_per_block(ax.n, (int)sizeof(cplx<T>), 8, 49152, generic_bufs(ax), true); }   // + the reduction's static LDS
 
 }  // namespace
@@ -220,6 +251,12 @@ hipError_t launch_generic_axis_grad(int f64, const GradParams& gp, const void* s
                                     long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
   return f64 ? axis_grad_t<double>(gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
              : axis_grad_t<float>(gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
+}
+
+hipError_t launch_generic_axis_hess(int f64, const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return f64 ? axis_hess_t<double>(hp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
+             : axis_hess_t<float>(hp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
 }
 
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s) {

@@ -244,6 +244,36 @@ __global__ __launch_bounds__(256) void gradient_kernel(const cplx<T>* S, cplx<T>
   }
 }
 
+// K = D_a D_b S: one component of the Hessian of the potential (rf_core.h hess_cell); rows, block shape and S == K as gradient_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void hessian_kernel(const cplx<T>* S, cplx<T>* K, HessParams hp, unsigned nrows) {
+  const int nzh = hp.nz / 2 + 1;
+  for (unsigned long long r0 = (unsigned long long)blockIdx.x * blockDim.y; r0 < nrows; r0 += (unsigned long long)gridDim.x * blockDim.y) {
+    const unsigned long long rr = r0 + threadIdx.y;
+    if (rr >= nrows) continue;
+    const unsigned row = (unsigned)rr, ix = row / (unsigned)hp.ny, iy = row - ix * (unsigned)hp.ny;
+    const cplx<T>* Sr = S + (long long)row * hp.pitch;
+    cplx<T>* Kr = K + (long long)row * nzh;
+    for (int iz = threadIdx.x; iz < nzh; iz += blockDim.x) Kr[iz] = hess_cell<T>(hp, Sr[iz], (int)ix, (int)iy, iz);
+  }
+}
+
+// One step of the 2LPT source (rf_core.h lpt2_step) over dense real arrays: 16 bytes per lane and array, grid-strided, every cell on
+// its own.  A step touches only the arrays it needs: FIRST H -> T; DIAG2 H, T -> S, T; DIAG3 H, T, S -> S; OFF H, S -> S; LAST H, S -> H.
+template <typename T, int VEC, int STEP>
+__global__ __launch_bounds__(256) void lpt2_accumulate_kernel(T* __restrict__ H, T* __restrict__ Tacc, T* __restrict__ Sacc, long long nvec) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
+    MapVec<T, VEC> h = MapVec<T, VEC>::load(H, i), t, s;
+    if (STEP == LPT2_DIAG2 || STEP == LPT2_DIAG3) t = MapVec<T, VEC>::load(Tacc, i);
+    if (STEP == LPT2_DIAG3 || STEP == LPT2_OFF || STEP == LPT2_LAST) s = MapVec<T, VEC>::load(Sacc, i);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) lpt2_step<T, STEP>(h.v[e], t.v[e], s.v[e]);
+    if (STEP == LPT2_FIRST || STEP == LPT2_DIAG2) t.store(Tacc, i);
+    if (STEP == LPT2_DIAG2 || STEP == LPT2_DIAG3 || STEP == LPT2_OFF) s.store(Sacc, i);
+    if (STEP == LPT2_LAST) h.store(H, i);
+  }
+}
+
 // after the forward x and y passes slot kz = 0 holds C = A0 + i A_nyq with A0, A_nyq Hermitian in (kx, ky):
 // A0(k) = (C(k) + conj C(-k)) / 2,  A_nyq(k) = (C(k) - conj C(-k)) / (2i)
 // W: [nx][ny][nzl] (this rank's kz planes kz0 .. kz0 + nzl; one rank: nzl = nz/2, kz0 = 0);  K: the side array [nx][ny][nzl + 1]
@@ -566,6 +596,43 @@ hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp
   if (f64) hipLaunchKernelGGL(gradient_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, gp, (unsigned)nrows);
   else hipLaunchKernelGGL(gradient_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, gp, (unsigned)nrows);
   return hipGetLastError();
+}
+
+hipError_t launch_hessian(int f64, const void* S, void* K, const HessParams& hp, hipStream_t s) {
+  const long long nrows = (long long)hp.nx * hp.ny;
+  const int nzh = hp.nz / 2 + 1;
+  if (nrows <= 0 || nrows > 0x7fffffffLL || hp.pitch < nzh || hp.a < 0 || hp.a > hp.b || hp.b > 2) return hipErrorInvalidValue;
+  int tx = 1;                                        // (the block shape of launch_gradient)
+  while (tx < 256 && tx < nzh) tx <<= 1;
+  const int ty = 256 / tx;
+  const long long nblk = (nrows + ty - 1) / ty;
+  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);
+  if (f64) hipLaunchKernelGGL(hessian_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, hp, (unsigned)nrows);
+  else hipLaunchKernelGGL(hessian_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, hp, (unsigned)nrows);
+  return hipGetLastError();
+}
+
+template <typename T, int VEC>
+static hipError_t lpt2_accumulate_t(int step, T* H, T* Tacc, T* Sacc, long long n, hipStream_t s) {
+  if (n <= 0 || n % VEC || (uintptr_t)H % 16 || (uintptr_t)Tacc % 16 || (uintptr_t)Sacc % 16) return hipErrorInvalidValue;
+  const long long nvec = n / VEC;
+  const dim3 grid(grid_for(nvec, 256)), block(256);
+#define RF_LPT2(ST) hipLaunchKernelGGL((lpt2_accumulate_kernel<T, VEC, ST>), grid, block, 0, s, H, Tacc, Sacc, nvec)
+  switch (step) {
+    case LPT2_FIRST: RF_LPT2(LPT2_FIRST); break;
+    case LPT2_DIAG2: RF_LPT2(LPT2_DIAG2); break;
+    case LPT2_DIAG3: RF_LPT2(LPT2_DIAG3); break;
+    case LPT2_OFF: RF_LPT2(LPT2_OFF); break;
+    case LPT2_LAST: RF_LPT2(LPT2_LAST); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RF_LPT2
+  return hipGetLastError();
+}
+
+hipError_t launch_lpt2_accumulate(int f64, int step, void* H, void* T, void* S, long long n, hipStream_t s) {
+  return f64 ? lpt2_accumulate_t<double, 2>(step, (double*)H, (double*)T, (double*)S, n, s)
+             : lpt2_accumulate_t<float, 4>(step, (float*)H, (float*)T, (float*)S, n, s);
 }
 
 hipError_t launch_scale_copy(int f64, const void* P, void* K, long long n, int zpitch, int ppitch, double scale, hipStream_t s) {

@@ -123,6 +123,12 @@ struct rf_plan {
   void* P_base = nullptr;                 // the allocation P lives in
   size_t w_bytes = 0, k_bytes = 0, p_bytes = 0;      // field buffer, k-space side array, potential array (padded rows)
   int ppitch = 0;                         // cells per row of the potential array: nzl + 1, rounded up to even on float32 plans
+  // lazy, rf_lpt2_source: the accumulators T and S of the real-space sweep (2 x w_bytes); once the source exists they are dead and the
+  // same memory holds the second-order potential in P's padded layout (rf_lpt2_potential; p_bytes <= l_bytes).  p2_valid is cleared by
+  // everything that writes P or starts a new source.
+  void* L = nullptr;
+  size_t l_bytes = 0;
+  bool p2_valid = false;
   void *tw_x = nullptr, *tw_y = nullptr, *tw_z = nullptr;
   double *kx2 = nullptr, *ky2 = nullptr, *kz2 = nullptr;
   double *xt = nullptr, *st = nullptr, *sl = nullptr;

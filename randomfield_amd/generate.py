@@ -180,6 +180,7 @@ class Generator(object):
         self.grid_spacing_Mpc_h = grid_spacing_Mpc_h
         self.k_min, self.k_max = powertools.get_k_bounds(self.plan_c2r.data_in, grid_spacing_Mpc_h, packed=True)
         self.potential = None
+        self._lpt2 = None                   # second-order potential of the current field: the array (numpy) / its potential object (hip)
 
         if nz % num_plot_sections != 0:
             raise ValueError("Z-axis does not evenly divided into {0} plot sections.".format(num_plot_sections))
@@ -258,6 +259,7 @@ class Generator(object):
             raise NotImplementedError("plot_slice is outside the accelerated path (see DESIGN.md).")
         nx, ny, nz = self.plan_c2r.shape
         self.smoothed_power = powertools.filter_power(self.power, smoothing_length_Mpc_h)
+        self._lpt2 = None
 
         if self.backend == "numpy":
             data = self.plan_c2r.data_in
@@ -390,6 +392,7 @@ class Generator(object):
         else:
             rms = dev.realise_lognormal(self._native_seed(seed), None)
         self.potential = None
+        self._lpt2 = None
         self.delta_field_rms = self.plan_c2r.data_out.dtype.type(rms)
         self._field_on_host = False
         if self.verbose:
@@ -534,7 +537,7 @@ class Generator(object):
         self._field_on_host = False
         return self.download_field() if download else None
 
-    def calculate_displacement_field(self, axis, light_cone=False, *, scale=1.0, factor_z=None, download=True):
+    def calculate_displacement_field(self, axis, light_cone=False, *, order=1, scale=1.0, factor_z=None, download=True):
         """
         One component of the vector field of the saved potential (an extension: the reference keeps delta(k)/k**2 "for later
         calculations of the lensing potential or the bulk velocity vector field", generate.py:200-217, and has no method for the
@@ -554,7 +557,22 @@ class Generator(object):
         ``rng='reference'`` the first call runs the storing form of the realisation once (one realisation, and from then on the
         device memory of ``store_potential=True``: ``self.potential`` becomes the stored potential of the same field) and every
         later call reads what it stored.
+
+        ``order=2`` returns the second-order Lagrangian (2LPT) term instead,
+
+            (3/7) * scale**2 * psi2_a(r),    psi2_a = irfftn( i k_a * rfftn(S) / k**2 ),
+            S = sum over a < b of  H_aa H_bb - H_ab**2,    H_ab = D_a D_b irfftn(delta(k) / k**2),
+
+        D_a the same spectral derivative (so the Nyquist planes are dropped on the diagonal of H too), with the convention
+        x = q + D1 psi1 + D1**2 psi2, i.e. D2 = -(3/7) D1**2 and div psi2 = -(3/7) S.  ``light_cone=True`` multiplies plane z by
+        ``growth_function[z]**2``; ``factor_z`` overrides it.  The second-order potential is formed once per field (six Hessian
+        transforms, one forward transform) and kept until the next field; each component is then one gradient transform.  hip
+        backend: it needs the potential in device memory, so a regenerated one is first turned into a stored one by running the
+        storing form of the realisation once (``self.potential`` becomes the stored potential of the same field, the field
+        buffer is overwritten).  Any other ``order`` raises ``ValueError``.
         """
+        if order not in (1, 2):
+            raise ValueError("Invalid order: {0!r} (expected 1 or 2).".format(order))
         if self.distributed:
             raise NotImplementedError("calculate_displacement_field runs on single-GPU plans (distributed=False).")
         if self.potential is None:
@@ -575,6 +593,10 @@ class Generator(object):
         else:
             factor = None
         dk = 2 * np.pi / (shape[axis] * self.grid_spacing_Mpc_h)
+        if order == 2:
+            if factor_z is None and light_cone:
+                factor = factor * factor
+            return self._second_order_displacement(axis, dk, scale, factor, download)
         if self.backend == "numpy":
             n = shape[axis]
             m = np.arange(nz // 2 + 1) if axis == 2 else np.fft.fftfreq(n, 1.0 / n)
@@ -604,6 +626,95 @@ class Generator(object):
                 dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_POTENTIAL)
         else:
             dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_POTENTIAL)
+        if factor is not None:
+            dev.scale_z(factor)
+        self._field_on_host = False
+        return self.download_field() if download else None
+
+    # ---- second order (2LPT) ------------------------------------------------
+    def _dk3(self):
+        return [2 * np.pi / (n * self.grid_spacing_Mpc_h) for n in self.plan_c2r.shape]
+
+    def _modes(self, axis):
+        """signed mode numbers along ``axis`` of the half spectrum (broadcastable), 0 at the axis' Nyquist index"""
+        shape = self.plan_c2r.shape
+        n = shape[axis]
+        m = np.arange(shape[2] // 2 + 1, dtype=float) if axis == 2 else np.fft.fftfreq(n, 1.0 / n)
+        m = np.where(np.abs(m) == n // 2, 0.0, m)
+        return m.reshape([-1 if a == axis else 1 for a in range(3)])
+
+    def _lpt2_source_numpy(self):
+        """S(x) in the plan's real type (a new array): the six Hessian components through the plan's own inverse transform, the
+        factor rounded to the array's complex type as the first-order branch rounds its own"""
+        dk3 = self._dk3()
+        ctype = self.plan_c2r.data_in.dtype
+        H = {}
+        for a in range(3):
+            for b in range(a, 3):
+                f = -(dk3[a] * self._modes(a)) * (dk3[b] * self._modes(b))
+                self.plan_c2r.data_in[:] = self.potential
+                self.plan_c2r.data_in *= (f + 0j).astype(ctype)
+                H[a, b] = self.plan_c2r.execute().copy()
+        S = H[0, 0] * H[1, 1]
+        S += (H[0, 0] + H[1, 1]) * H[2, 2]
+        for ab in ((0, 1), (0, 2), (1, 2)):
+            S -= H[ab] * H[ab]
+        return S
+
+    def _stored_device_potential(self):
+        """hip backend: the potential in device memory -- a regenerated one is stored by running the storing form of the realisation
+        once (as the rng='reference' branch of the first-order method)"""
+        dev = self.plan_c2r.device
+        if isinstance(self.potential, _RegeneratedPotential):
+            self.potential.check_current()
+            dev.realise_potential(self.potential.seed, self.potential.noise)
+            self.potential = _DevicePotential(self)
+        return dev
+
+    def lpt2_source(self, download=True):
+        """
+        The source of the second-order potential, S(r) = sum over a < b of H_aa H_bb - H_ab**2 (see
+        :meth:`calculate_displacement_field`, ``order=2``), of the saved potential.  Returns a view of the plan's buffer; on the
+        hip backend S becomes the current device field (``download=False`` leaves it there).
+        """
+        if self.distributed:
+            raise NotImplementedError("lpt2_source runs on single-GPU plans (distributed=False).")
+        if self.potential is None:
+            raise RuntimeError("No saved potential field.")
+        if self.backend == "numpy":
+            self.plan_c2r.data_out[...] = self._lpt2_source_numpy()
+            self._field_on_host = True
+            return self.plan_c2r.data_out
+        dev = self._stored_device_potential()
+        self._lpt2 = None                          # (the accumulators take the second-order potential's memory)
+        dev.lpt2_source(self._dk3())
+        self._field_on_host = False
+        return self.download_field() if download else None
+
+    def _second_order_displacement(self, axis, dk, scale, factor, download):
+        shape = self.plan_c2r.shape
+        scale2 = 3.0 / 7.0 * float(scale) ** 2
+        if self.backend == "numpy":
+            if self._lpt2 is None:
+                kx2, ky2, kz2 = (np.asarray(a, np.float64) for a in powertools.ksq_axes(*shape, self.grid_spacing_Mpc_h))
+                k2 = (kx2[:, None, None] + ky2[None, :, None]) + kz2[None, None, :]
+                k2[0, 0, 0] = 1.0
+                phi2 = np.fft.rfftn(np.asarray(self._lpt2_source_numpy(), np.float64), axes=(0, 1, 2)) / k2
+                phi2[0, 0, 0] = 0.0
+                self._lpt2 = phi2.astype(self.plan_c2r.data_in.dtype)
+            ik = 1j * scale2 * dk * self._modes(axis)
+            self.plan_c2r.data_in[:] = self._lpt2
+            self.plan_c2r.data_in *= ik.astype(self.plan_c2r.data_in.dtype)
+            field = self.plan_c2r.execute()
+            if factor is not None:
+                field *= factor
+            return field
+        from . import _hip
+        dev = self._stored_device_potential()
+        if self._lpt2 is not self.potential or not dev.lpt2_valid:
+            dev.lpt2_potential(self._dk3())
+            self._lpt2 = self.potential
+        dev.execute_gradient(axis, scale2, dk, _hip.RF_GRAD_FROM_POTENTIAL2)
         if factor is not None:
             dev.scale_z(factor)
         self._field_on_host = False
