@@ -43,7 +43,9 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * this repository returned the constant 1 while the surface grew from ~20 to 70 entry points; 5.0 is the first version that means
  * something: the consumer surface below + the diagnostics of randomfield_hip_diag.h.)  rf_measure_power was added WITHOUT a new
  * minor number -- the version stays 5.5 -- and is announced by its feature bit alone: ask rf_abi_features() & RF_FEATURE_POWER_MEASURE.
- * The same holds for the second-order (2LPT) calls: rf_abi_features() & RF_FEATURE_LPT2. */
+ * The same holds for the second-order (2LPT) calls: rf_abi_features() & RF_FEATURE_LPT2.
+ * And for the particle calls -- the resident displacement buffer and the cloud-in-cell paint, rf_particles_accumulate, rf_particles_upload,
+ * rf_particles_download, rf_particles_paint: rf_abi_features() & RF_FEATURE_PARTICLES, the version stays 5.5. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -69,8 +71,10 @@ enum {
   RF_FEATURE_GENERIC_FUSED = 1 << 13,      /* RF_FLAG_FUSED_GENERIC_GENERATION; rf_kernel_ms on generic plans */
   RF_FEATURE_GRADIENT = 1 << 14,           /* rf_load_gradient, rf_execute_gradient_c2r: the vector field of the saved potential */
   RF_FEATURE_POWER_MEASURE = 1 << 15,      /* rf_measure_power: the binned power spectrum of the k buffer or of the field */
-  RF_FEATURE_LPT2 = 1 << 16                /* rf_load_hessian, rf_execute_hessian_c2r, rf_lpt2_source, rf_lpt2_potential, RF_GRAD_FROM_POTENTIAL2:
+  RF_FEATURE_LPT2 = 1 << 16,               /* rf_load_hessian, rf_execute_hessian_c2r, rf_lpt2_source, rf_lpt2_potential, RF_GRAD_FROM_POTENTIAL2:
                                               the second-order Lagrangian displacement */
+  RF_FEATURE_PARTICLES = 1 << 17           /* rf_particles_accumulate, rf_particles_upload, rf_particles_download, rf_particles_paint: the three
+                                              displacement components resident on the device, painted back onto the grid (cloud in cell) */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -307,6 +311,32 @@ int rf_lpt2_source(rf_plan* plan, const double* dk);
  * The second-order potential is dropped by everything that writes the stored one (rf_save_potential, rf_realise_potential) and by the
  * next rf_lpt2_source.  Needs rf_set_kgrid. */
 int rf_lpt2_potential(rf_plan* plan, const double* dk);
+
+/* ---- particles: resident displacements and the cloud-in-cell paint (rf_abi_features() & RF_FEATURE_PARTICLES) -- */
+/* One particle of unit mass per lattice cell q = (ix, iy, iz).  Its displacement s_a(q), a = 0, 1, 2, in length units lives in a buffer
+ * Q[3][nx][ny][nz] of the plan's real type, allocated (and zeroed) by the first of these calls together with nothing else; the paint adds
+ * an accumulator grid of 8 bytes per cell.  Both are counted by rf_plan_nbytes and freed with the plan.  Packed single-rank plans, tiled
+ * and generic; c2c plans and nranks > 1 are refused, nothing queued.  No call here touches the k buffer, the stored potential or the
+ * second-order potential. */
+/* Q_axis = (first ? 0 : Q_axis) + coeff * W, W the current real field, which is left as it is: one elementwise sweep, coeff rounded once
+ * to the plan's real type, then one product (first) or one fused multiply-add per cell -- no atomics, the same bits on every call.
+ * x = q + D1 psi1 + D1^2 psi2: rf_execute_gradient_c2r(a, 1, dk_a, RF_GRAD_FROM_POTENTIAL), rf_particles_accumulate(a, D1, 1), then
+ * rf_execute_gradient_c2r(a, 3/7, dk_a, RF_GRAD_FROM_POTENTIAL2), rf_particles_accumulate(a, D1 * D1, 0). */
+int rf_particles_accumulate(rf_plan* plan, int axis, double coeff, int first);
+/* one component, a dense [nx][ny][nz] array of the plan's real type, from / to the host (blocking) */
+int rf_particles_upload(rf_plan* plan, int axis, const void* host);
+int rf_particles_download(rf_plan* plan, int axis, void* host);
+/* Cloud-in-cell mass assignment of the displaced particles; delta_cic becomes the current real field (rf_download_real,
+ * rf_measure_power(RF_POWER_FROM_FIELD)), its moments are not computed (rf_moments refuses until the next transform).  inv_h[a] =
+ * 1 / (grid spacing along a), positive and finite.  Per axis, in float64: u = (double)s_a * inv_h[a] (one rounded product), c = floor(u),
+ * t = floor((u - c) * 65536) in [0, 65535] (for -2^-54 <= u < 0 alone u - c rounds to 1 and t = 65536); the weights 65536 - t and t go to the cells j0 = (i_a + c) mod n_a -- the mod formed in
+ * float64 before any conversion to integer, so every finite u lands inside the grid -- and j1 = (j0 + 1) mod n_a.  The eight products of
+ * three weights (exact, summing to 2^48 per particle) are added to an unsigned 64-bit grid A with integer atomics: A, and with it the
+ * field, is the same bit for bit on every call, whichever kernel form runs.  delta_cic = (double)A * 2^-48 - 1, rounded once to the plan's
+ * real type.  A particle whose u is not finite on some axis (a NaN or infinite displacement) adds nothing; *dropped is their number.
+ * LIMIT: fewer than 65536 (2^64 / 2^48) particles' worth of mass may land in one cell; beyond it A wraps around, undetected.  Gaussian
+ * initial conditions stay orders of magnitude below.  Blocks until *dropped is on the host. */
+int rf_particles_paint(rf_plan* plan, const double* inv_h, unsigned long long* dropped);
 
 /* ---- binned power spectrum (rf_abi_features() & RF_FEATURE_POWER_MEASURE) -- */
 /* The estimator that closes P(k) -> delta(x) -> P^(k): one sweep of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform

@@ -29,7 +29,9 @@ extern "C" {
  *   [3] reduce
  *   [4] the generation as a launch of its own (0 when it is fused into the x pass, and after rf_execute_c2r); after
  *       rf_execute_gradient_c2r: the elementwise gradient kernel of a plan whose x axis is in the four-step form, else 0
- * so that [4] + [0] is everything in front of the y pass. */
+ * so that [4] + [0] is everything in front of the y pass.
+ * After rf_particles_paint (any plan): [0] clearing the accumulator grid, [1] the scatter kernel, [2] the conversion into the field,
+ * [3] = [4] = 0. */
 int rf_kernel_ms(rf_plan* plan, float* ms5);
 /* The z pass of slab s and the y pass of slab s + 1 in ONE launch (the next slab's tiles fill the compute units the draining pass leaves
  * idle; float32 plans whose y pass is the 1024-point one and whose rows hold 512 complex: the 1024^3 pipeline).  mode 0: never;
@@ -46,6 +48,14 @@ int rf_yz_slabs(rf_plan* plan, int* nslab, int* planes);
 /* ---- internal buffers ------------------------------------------------------ */
 /* copy deviates [first, first+count) of the device noise buffer to the host (tests) */
 int rf_download_noise(rf_plan* plan, double* host, unsigned long long first, unsigned long long count);
+
+/* the raw 64-bit accumulator grid [nx][ny][nz] of the last rf_particles_paint (2^48 per unit of mass); refused before the first paint */
+int rf_particles_download_counts(rf_plan* plan, unsigned long long* host);
+/* which kernel the paint's scatter runs: 0 = the library's choice, 1 = global (one lane per particle, eight 64-bit integer atomics into
+ * the grid), 2 = tiled (LDS tiles of brick + halo, flushed with one global atomic per non-zero tile cell).  Same grid bit for bit. */
+int rf_particles_set_paint_form(rf_plan* plan, int form);
+/* the tiled kernel's brick (lattice cells per axis, brick3[3]) and halo (cells on every side): the tile is brick + 2 halo per axis */
+int rf_particles_paint_geometry(rf_plan* plan, int* brick3, int* halo);
 
 /* ---- virtual ranks: the multi-GPU pipeline step by step on one device ------ */
 /* The slab pipeline in separate steps, for tests and custom exchanges: forward = generation + x and y

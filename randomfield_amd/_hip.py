@@ -34,7 +34,7 @@ ABI_MAJOR, ABI_MINOR = 5, 5
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
-            "power_measure": 1 << 15, "lpt2": 1 << 16}
+            "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -88,6 +88,10 @@ SIGNATURES = {
     "rf_execute_hessian_c2r": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
     "rf_lpt2_source": (ctypes.c_int, [ctypes.c_void_p, _c_dp]),
     "rf_lpt2_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp]),
+    "rf_particles_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
+    "rf_particles_upload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rf_particles_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rf_particles_paint": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
     "rf_lensing_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "rf_download_aux": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
@@ -117,6 +121,9 @@ DIAG_SIGNATURES = {
     "rf_mt_share_exchange_local": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
     "rf_download_noise": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_ulonglong, ctypes.c_ulonglong]),
     "rf_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "rf_particles_download_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_particles_set_paint_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rf_particles_paint_geometry": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "rf_set_merged_yz": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rf_merged_yz_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]),
     "rf_yz_slabs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -674,6 +681,51 @@ class DevicePlan(object):
         self.lpt2_valid = False
         check(self._lib.rf_lpt2_potential(self._h, _dp(d)), "rf_lpt2_potential")
         self.lpt2_valid = True          # (what the calls of THIS object did to the plan's second-order potential; the library keeps its own flag)
+
+    # -- particles: the resident displacements and their cloud-in-cell paint ----
+    def particles_accumulate(self, axis, coeff, first):
+        """Q_axis = (0 if first else Q_axis) + coeff * W (rf_particles_accumulate): the current real field, left as it is, into
+        component ``axis`` of the resident particle-displacement buffer; one fma sweep in the plan's real type."""
+        check(self._lib.rf_particles_accumulate(self._h, int(axis), float(coeff), 1 if first else 0), "rf_particles_accumulate")
+
+    def particles_upload(self, axis, data):
+        """component ``axis`` of the displacement buffer <- a dense (nx, ny, nz) array of the plan's real type (rf_particles_upload)"""
+        if data.shape != (self.nx, self.ny, self.nz) or data.dtype != self.real_dtype:
+            raise ValueError("particles_upload: wrong shape or dtype")
+        data = np.ascontiguousarray(data)
+        check(self._lib.rf_particles_upload(self._h, int(axis), data.ctypes.data_as(ctypes.c_void_p)), "rf_particles_upload")
+
+    def particles_download(self, axis, out=None):
+        if out is None:
+            out = np.empty((self.nx, self.ny, self.nz), self.real_dtype)
+        if out.shape != (self.nx, self.ny, self.nz) or out.dtype != self.real_dtype or not out.flags.c_contiguous:
+            raise ValueError("particles_download: out has the wrong shape, dtype or layout")
+        check(self._lib.rf_particles_download(self._h, int(axis), out.ctypes.data_as(ctypes.c_void_p)), "rf_particles_download")
+        return out
+
+    def particles_paint(self, inv_h):
+        """Cloud-in-cell mass assignment of the displaced lattice particles (rf_particles_paint): delta_cic becomes the current real
+        field; ``inv_h``: the three 1 / (grid spacing).  Returns the number of particles dropped for a non-finite displacement."""
+        h = _f64(np.asarray(inv_h, np.float64).reshape(3))
+        dropped = ctypes.c_ulonglong(0)
+        check(self._lib.rf_particles_paint(self._h, _dp(h), ctypes.byref(dropped)), "rf_particles_paint")
+        return int(dropped.value)
+
+    def particles_download_counts(self):
+        """diagnostic: the raw uint64 accumulator grid of the last paint, 2**48 per unit of mass (rf_particles_download_counts)"""
+        out = np.empty((self.nx, self.ny, self.nz), np.uint64)
+        check(self._lib.rf_particles_download_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))), "rf_particles_download_counts")
+        return out
+
+    def set_paint_form(self, form=0):
+        """diagnostic: the scatter kernel of :meth:`particles_paint` -- 0 the library's choice, 1 global atomics, 2 LDS tiles"""
+        check(self._lib.rf_particles_set_paint_form(self._h, int(form)), "rf_particles_set_paint_form")
+
+    def paint_geometry(self):
+        """diagnostic: ``((bx, by, bz), halo)`` of the tiled scatter kernel (rf_particles_paint_geometry)"""
+        brick, halo = (ctypes.c_int * 3)(), ctypes.c_int()
+        check(self._lib.rf_particles_paint_geometry(self._h, brick, ctypes.byref(halo)), "rf_particles_paint_geometry")
+        return tuple(brick), halo.value
 
     def measure_power(self, edges, source=RF_POWER_FROM_KSPACE):
         """Per-bin sums of the binned power spectrum (rf_measure_power): ``edges`` are ``nbins + 1`` increasing edges in k; returns

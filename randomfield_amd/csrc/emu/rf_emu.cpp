@@ -6,6 +6,7 @@
 // checks index math, twiddles, Hermitian packing and the generation rules
 // against the oracle without a GPU.  It is not a product path: nothing in
 // randomfield_amd/ loads it.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -776,6 +777,113 @@ int lpt2_accumulate_impl(int step, T* H, T* Tacc, T* Sacc, long long n) {
   return 0;
 }
 
+// ---- particles (rf_core.h cic_*): the cloud-in-cell paint as rf_k_particles.hip runs it, on nth real host threads that add with
+// __atomic operations to the shared accumulator grid and -- in the tiled form -- to the brick's shared tile image
+template <class Body> void run_threads(int nth, Body body) {
+  if (nth <= 1) { body(0, NoSync()); return; }
+  pthread_barrier_t bar;
+  pthread_barrier_init(&bar, nullptr, (unsigned)nth);
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nth; ++t) pool.emplace_back([&body, &bar, t] { body(t, BarrierSync{&bar}); });
+  body(0, BarrierSync{&bar});
+  for (auto& th : pool) th.join();
+  pthread_barrier_destroy(&bar);
+}
+inline void atomic_add_u64(unsigned long long* p, uint64_t w) { __atomic_fetch_add(p, (unsigned long long)w, __ATOMIC_RELAXED); }
+
+template <typename T>
+int particles_paint_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, int form, int bx, int by, int bz, int halo,
+                         int nth, unsigned long long* A, unsigned long long* dropped) {
+  const long long n = (long long)nx * ny * nz;
+  memset(A, 0, (size_t)n * 8);
+  *dropped = 0;
+  if (form == 1) {                                   // cic_paint_global_kernel: one "lane" per particle
+    run_threads(nth, [&](int tid, auto sync) {
+      unsigned long long nd = 0;
+      for (long long i = tid; i < n; i += nth) {
+        const long long row = i / nz;
+        const int iz = (int)(i - row * nz), ix = (int)(row / ny), iy = (int)(row - (long long)ix * ny);
+        CicAxis x, y, z;
+        if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) { ++nd; continue; }
+        cic_scatter_global(x, y, z, ny, nz, [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+      }
+      if (nd) atomic_add_u64(dropped, nd);
+    });
+    return 0;
+  }
+  // cic_paint_tiled_kernel: bricks one after the other, the threads of a brick share its tile image and meet at the kernel's barriers
+  CicTile t;
+  t.bx = bx; t.by = by; t.bz = bz; t.h = halo; t.x0 = t.y0 = t.z0 = 0;
+  std::vector<unsigned long long> tile((size_t)t.cells());
+  const int nbx = (nx + bx - 1) / bx, nby = (ny + by - 1) / by, nbz = (nz + bz - 1) / bz;
+  run_threads(nth, [&](int tid, auto sync) {
+    unsigned long long nd = 0;
+    for (int b = 0; b < nbx * nby * nbz; ++b) {
+      CicTile tb = t;
+      tb.z0 = (b % nbz) * bz; tb.y0 = ((b / nbz) % nby) * by; tb.x0 = (b / nbz / nby) * bx;
+      for (int s = tid; s < tb.cells(); s += nth) tile[s] = 0ull;
+      sync();
+      for (int row = tid; row < bx * by; row += nth) {
+        const int lx = row / by, ly = row - lx * by, ix = tb.x0 + lx, iy = tb.y0 + ly;
+        for (int lz = 0; lz < bz; ++lz) {
+          const int iz = tb.z0 + lz;
+          if (ix >= nx || iy >= ny || iz >= nz) continue;
+          const long long i = ((long long)ix * ny + iy) * nz + iz;
+          CicAxis x, y, z;
+          if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) { ++nd; continue; }
+          cic_scatter_tiled(x, y, z, lx, ly, lz, tb, ny, nz,
+                            [&](int slot, uint64_t w) { atomic_add_u64(&tile[slot], w); },
+                            [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+        }
+      }
+      sync();
+      for (int s = tid; s < tb.cells(); s += nth)
+        if (tile[s]) atomic_add_u64(A + cic_tile_cell(tb, s, nx, ny, nz), tile[s]);
+      sync();
+    }
+    if (nd) atomic_add_u64(dropped, nd);
+  });
+  return 0;
+}
+
+// what the tiled form does with these particles, counted with the kernel's own rule (cic_scatter_tiled): particles that leave their
+// brick's tile, their adds straight into A, and the non-zero tile cells the bricks flush
+template <typename T>
+int particles_tile_stats_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, int bx, int by, int bz, int halo,
+                              unsigned long long* out4) {
+  CicTile t;
+  t.bx = bx; t.by = by; t.bz = bz; t.h = halo; t.x0 = t.y0 = t.z0 = 0;
+  std::vector<unsigned long long> tile((size_t)t.cells());
+  unsigned long long fallback = 0, fallback_adds = 0, flushed = 0, dropped = 0;
+  for (int x0 = 0; x0 < nx; x0 += bx)
+    for (int y0 = 0; y0 < ny; y0 += by)
+      for (int z0 = 0; z0 < nz; z0 += bz) {
+        t.x0 = x0; t.y0 = y0; t.z0 = z0;
+        std::fill(tile.begin(), tile.end(), 0ull);
+        for (int lx = 0; lx < bx && x0 + lx < nx; ++lx)
+          for (int ly = 0; ly < by && y0 + ly < ny; ++ly)
+            for (int lz = 0; lz < bz && z0 + lz < nz; ++lz) {
+              const long long i = ((long long)(x0 + lx) * ny + (y0 + ly)) * nz + (z0 + lz);
+              CicAxis x, y, z;
+              if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, x0 + lx, y0 + ly, z0 + lz, nx, ny, nz, x, y, z)) { ++dropped; continue; }
+              const unsigned long long before = fallback_adds;
+              cic_scatter_tiled(x, y, z, lx, ly, lz, t, ny, nz, [&](int slot, uint64_t w) { tile[slot] += w; },
+                                [&](long long, uint64_t) { ++fallback_adds; });
+              if (fallback_adds != before) ++fallback;
+            }
+        for (unsigned long long v : tile) flushed += v != 0;
+      }
+  out4[0] = fallback; out4[1] = fallback_adds; out4[2] = flushed; out4[3] = dropped;
+  return 0;
+}
+
+template <typename T>
+int particles_accumulate_impl(int first, double coeff, const T* W, T* Q, long long n) {
+  const T c = (T)coeff;
+  for (long long i = 0; i < n; ++i) Q[i] = particles_axpy<T>(first != 0, c, W[i], first ? (T)0 : Q[i]);
+  return 0;
+}
+
 template <typename T>
 int generic_r2c_impl(int nx, int ny, int nz, const T* W, cplx<T>* K) {
   GenericDims d;
@@ -936,6 +1044,39 @@ int emu_lpt2_accumulate(int f64, int step, void* H, void* T, void* S, long long 
   if (n < 0 || !(H && T && S)) return -1;
   return f64 ? lpt2_accumulate_impl<double>(step, (double*)H, (double*)T, (double*)S, n)
              : lpt2_accumulate_impl<float>(step, (float*)H, (float*)T, (float*)S, n);
+}
+// The cloud-in-cell paint of the lattice particles displaced by (sx, sy, sz) -- dense [nx][ny][nz] arrays of float32 / float64 -- into the
+// 64-bit grid A[nx][ny][nz] (cleared here; rf_core.h cic_particle, the functions rf_k_particles.hip calls).  form 1: every particle adds
+// straight into A; form 2: bricks of bx x by x bz cells with a tile of brick + halo each, flushed with wrapped indices.  nth > 1: that many
+// real host threads share A and the tile through atomic adds.  *dropped: particles with a non-finite displacement.
+int emu_particles_paint(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int form, int bx, int by,
+                        int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped) {
+  if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && A && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
+  if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
+  return f64 ? particles_paint_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth, A, dropped)
+             : particles_paint_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
+}
+// the tiled form's traffic for these particles, by the kernel's own rule: out4 = {particles that leave their brick's tile, their adds
+// straight into A, non-zero tile cells flushed, dropped particles}
+int emu_particles_tile_stats(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int bx, int by, int bz,
+                             int halo, unsigned long long* out4) {
+  if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && out4) || bx < 1 || by < 1 || bz < 1 || halo < 1) return -1;
+  return f64 ? particles_tile_stats_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, bx, by, bz, halo, out4)
+             : particles_tile_stats_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, bx, by, bz, halo, out4);
+}
+// Q = coeff W (first) or Q + coeff W over n elements (rf_core.h particles_axpy, the function the kernel calls per element)
+int emu_particles_accumulate(int f64, int first, double coeff, const void* W, void* Q, long long n) {
+  if (n < 0 || !(W && Q)) return -1;
+  return f64 ? particles_accumulate_impl<double>(first, coeff, (const double*)W, (double*)Q, n)
+             : particles_accumulate_impl<float>(first, coeff, (const float*)W, (float*)Q, n);
+}
+// W = (double)A 2^-48 - 1 rounded once (rf_core.h cic_delta)
+int emu_particles_delta(int f64, const unsigned long long* A, void* W, long long n) {
+  if (n < 0 || !(A && W)) return -1;
+  for (long long i = 0; i < n; ++i) {
+    if (f64) ((double*)W)[i] = cic_delta<double>(A[i]); else ((float*)W)[i] = cic_delta<float>(A[i]);
+  }
+  return 0;
 }
 // the binned power spectrum (rf_core.h power_load / power_cell over an array, as rf_measure_power's sweep; cells in array order): S is
 // the API-layout half spectrum [nx][ny][nz/2+1], or with packed != 0 the array [nx][ny][nz/2] the tiled forward passes leave (slot

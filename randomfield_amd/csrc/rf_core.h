@@ -525,6 +525,109 @@ RF_HD cplx<T> power_load(const PowerParams& g, const cplx<T>* S, int ix, int iy,
   return mk<T>((T)0.5 * (a.y + b.y), (T)0.5 * (b.x - a.x));
 }
 
+// ------------------------------------------- particles: cloud-in-cell paint --
+// One particle of unit mass per lattice cell q = (ix, iy, iz), displaced by s_a(q) (length units); inv_h[a] = 1 / (grid spacing).
+// Per axis, all in float64:
+//   u  = (double)s * inv_h       ONE correctly rounded product, never contracted with what follows (pragma / volatile as mul_then_add)
+//   c  = floor(u),  t = (uint32) floor((u - c) * 65536) in [0, 65535]   (u - c and the scaling are exact IEEE operations that numpy
+//        repeats bit for bit; for -2^-54 <= u < 0 alone u - c rounds to 1 and t = 65536: all the weight on j1, the particle's own cell)
+//   j0 = (i + c) mod n, formed in float64 BEFORE any conversion to integer: m = fmod(c, n) (exact, |m| < n), r = i + m (exact),
+//        r += n if r < 0, r -= n if r >= n -- any finite u gives an index in [0, n);   j1 = (j0 + 1) mod n
+//   w0 = 65536 - t on j0,  w1 = t on j1
+// A particle adds the eight products w_x w_y w_z (exact in 64 bits; they sum to exactly 2^48) to an unsigned 64-bit accumulator grid
+// A[nx][ny][nz].  Integer addition is associative: A is the same for every launch shape, kernel form, thread count and run.  A particle
+// with a non-finite u on any axis (a non-finite displacement, or a product beyond the float64 range) adds nothing and is counted.
+// LIMIT: fewer than 2^64 / 2^48 = 65536 particles' worth of mass may land in one cell (no detection; Gaussian initial conditions are
+// orders of magnitude below it).  The field is delta = (double)A * 2^-48 - 1, rounded once to the array's real type.
+struct CicAxis {
+  double c;                   // floor(u): the whole-cell part of the displacement
+  int j0, j1;                 // wrapped target indices
+  uint32_t w0, w1;            // their integer weights, w0 + w1 = 65536
+};
+RF_HD bool cic_axis(double s, double inv_h, int i, int n, CicAxis& o) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const double u = s * inv_h;
+#else
+  volatile double uv = s * inv_h;
+  const double u = uv;
+#endif
+  if (!(fabs(u) <= 1.7976931348623157e308)) return false;      // NaN, +-inf
+  const double c = floor(u);
+  const double f = u - c;                                      // in [0, 1]
+  const uint32_t t = (uint32_t)floor(f * 65536.0);
+  const double dn = (double)n;
+  const double m = fabs(c) < dn ? c : fmod(c, dn);             // (fmod(c, n) == c for |c| < n)
+  double r = (double)i + m;
+  if (r < 0.0) r += dn;
+  if (r >= dn) r -= dn;
+  o.c = c;
+  o.j0 = (int)r;
+  o.j1 = o.j0 + 1 == n ? 0 : o.j0 + 1;
+  o.w0 = 65536u - t;
+  o.w1 = t;
+  return true;
+}
+// the three axes of one particle; false: dropped
+template <typename T>
+RF_HD bool cic_particle(T sx, T sy, T sz, const double* inv_h, int ix, int iy, int iz, int nx, int ny, int nz, CicAxis& x, CicAxis& y, CicAxis& z) {
+  const bool okx = cic_axis((double)sx, inv_h[0], ix, nx, x), oky = cic_axis((double)sy, inv_h[1], iy, ny, y), okz = cic_axis((double)sz, inv_h[2], iz, nz, z);
+  return okx && oky && okz;
+}
+RF_HD uint64_t cic_weight(const CicAxis& x, const CicAxis& y, const CicAxis& z, int k) {
+  return (uint64_t)((k & 4) ? x.w1 : x.w0) * (uint64_t)((k & 2) ? y.w1 : y.w0) * (uint64_t)((k & 1) ? z.w1 : z.w0);
+}
+// the eight adds of one particle straight into A: add(cell index, weight); zero weights add nothing and are skipped
+template <class Add>
+RF_HD void cic_scatter_global(const CicAxis& x, const CicAxis& y, const CicAxis& z, int ny, int nz, Add&& add) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint64_t w = cic_weight(x, y, z, k);
+    if (w) add(((long long)((k & 4) ? x.j1 : x.j0) * ny + ((k & 2) ? y.j1 : y.j0)) * nz + ((k & 1) ? z.j1 : z.j0), w);
+  }
+}
+// The tiled form: a workgroup owns the brick of lattice cells [x0, x0 + bx) x [y0, y0 + by) x [z0, z0 + bz) and a tile image of
+// brick + halo h on every side, tile[tx][ty][tz] with t = b + 2 h, tile slot 0 standing for cell x0 - h (UNWRAPPED: periodic wrapping
+// happens when the tile is flushed, cic_tile_cell).  A particle whose eight cells all fall inside the tile adds there; any other adds
+// straight into A as cic_scatter_global does.  The test is against the WHOLE tile (cic_tile_slot: -h <= l + c <= b + h - 2 for the local
+// index l), not a window around the particle: every particle with -h <= u < h stays, and one inside the brick may move much further.
+struct CicTile {
+  int bx, by, bz, h;
+  int x0, y0, z0;
+  RF_HD int tx() const { return bx + 2 * h; }
+  RF_HD int ty() const { return by + 2 * h; }
+  RF_HD int tz() const { return bz + 2 * h; }
+  RF_HD int cells() const { return tx() * ty() * tz(); }
+};
+// tile slot of j0 along one axis for the particle at local index li (slot + 1 is then inside too), or -1
+RF_HD int cic_tile_slot(const CicAxis& a, int li, int b, int h) {
+  const double lo = (double)li + a.c;                          // (compared in float64: c may be far outside the int range)
+  return (lo >= (double)-h && lo <= (double)(b + h - 2)) ? (int)lo + h : -1;
+}
+template <class AddTile, class AddGlobal>
+RF_HD void cic_scatter_tiled(const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const CicTile& t, int ny, int nz,
+                             AddTile&& add_tile, AddGlobal&& add_global) {
+  const int sx = cic_tile_slot(x, lx, t.bx, t.h), sy = cic_tile_slot(y, ly, t.by, t.h), sz = cic_tile_slot(z, lz, t.bz, t.h);
+  if (sx < 0 || sy < 0 || sz < 0) { cic_scatter_global(x, y, z, ny, nz, add_global); return; }
+  const int py = t.tz(), px = t.ty() * py, base = sx * px + sy * py + sz;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint64_t w = cic_weight(x, y, z, k);
+    if (w) add_tile(base + ((k & 4) ? px : 0) + ((k & 2) ? py : 0) + (k & 1), w);
+  }
+}
+RF_HD int cic_wrap(int v, int n) { v %= n; return v < 0 ? v + n : v; }
+// the cell of A that tile slot s stands for (several slots alias one cell when the grid is smaller than the tile)
+RF_HD long long cic_tile_cell(const CicTile& t, int s, int nx, int ny, int nz) {
+  const int py = t.tz(), px = t.ty() * py;
+  const int ax = s / px, ay = (s - ax * px) / py, az = s - ax * px - ay * py;
+  return ((long long)cic_wrap(t.x0 - t.h + ax, nx) * ny + cic_wrap(t.y0 - t.h + ay, ny)) * nz + cic_wrap(t.z0 - t.h + az, nz);
+}
+// delta = (double)A 2^-48 - 1, rounded once to T (the scaling is exact, so a fused multiply-add gives the same bits)
+template <typename T> RF_HD T cic_delta(uint64_t a) { return (T)((double)a * (1.0 / 281474976710656.0) - 1.0); }
+// Q = coeff W (first) or Q + coeff W: coeff already rounded to T, one explicit fma in T (lpt2_fma), so host and device round alike
+template <typename T> RF_HD T particles_axpy(bool first, T coeff, T w, T q) { return first ? coeff * w : lpt2_fma(coeff, w, q); }
+
 // ------------------------------------------------- fast native generation --
 // float32 plans with the native RNG do rows K,T,R,S entirely in float32: the
 // values are this repo's own definition (checked against the oracle's

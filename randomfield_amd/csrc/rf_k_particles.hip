@@ -1,0 +1,169 @@
+// particles (rf_core.h cic_axis ... cic_delta): the resident displacement buffer's fma sweep and the cloud-in-cell paint of the displaced
+// lattice particles into an unsigned 64-bit accumulator grid.  Integer atomics only -- vector (global) and LDS ones: integer addition is
+// associative, so the accumulator holds the same bits for every launch shape, either form and every run.  No floating-point atomics.
+#include "rf_kernels.h"
+#include "rf_launch.h"
+
+namespace rf {
+namespace {
+
+typedef unsigned long long u64;
+
+struct CicGrid {
+  int nx, ny, nz;
+  double inv_h[3];
+};
+
+// the wave's dropped particles -> one integer atomic (nothing when the wave dropped none)
+__device__ __forceinline__ void cic_count_dropped(int mine, u64* dropped) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(dropped, (u64)mine);
+}
+
+// Form 1, global: one lane per particle, lanes along z (a wave's adds to one of the eight corners are 512 contiguous bytes wherever the
+// displacement varies slowly), eight no-return 64-bit integer atomics straight into A.  blockDim.x is a multiple of 64.
+template <typename T>
+__global__ __launch_bounds__(256) void cic_paint_global_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
+                                                               u64* __restrict__ A, u64* __restrict__ dropped, CicGrid g, long long n) {
+  int ndrop = 0;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  // (every lane of a wave runs the same number of steps: the shuffles below see whole waves)
+  for (long long i0 = (long long)blockIdx.x * blockDim.x; i0 < n; i0 += step) {
+    const long long i = i0 + threadIdx.x;
+    if (i >= n) continue;
+    const long long row = i / g.nz;
+    const int iz = (int)(i - row * g.nz), ix = (int)(row / g.ny), iy = (int)(row - (long long)ix * g.ny);
+    CicAxis x, y, z;
+    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; continue; }
+    cic_scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+  }
+  cic_count_dropped(ndrop, dropped);
+}
+
+// Form 2, tiled: a workgroup owns a brick of BX x BY x BZ lattice cells (BZ = 64: a wave takes one z row of the brick, so its lanes hit
+// consecutive LDS and memory addresses) and accumulates with LDS 64-bit integer atomics into a tile of brick + halo H.  Particles whose
+// eight cells do not all fall inside the tile add straight into A as form 1 does.  The tile is flushed with one global atomic per
+// non-zero tile cell, indices wrapped periodically there: neighbouring bricks' halos overlap, bricks at the grid's edge are partial, and
+// on a grid smaller than the tile several tile cells alias one cell of A -- the atomic flush covers all three.
+constexpr int CIC_BX = 8, CIC_BY = 8, CIC_BZ = 64, CIC_H = 2, CIC_NT = 512;
+constexpr int CIC_TILE_CELLS = (CIC_BX + 2 * CIC_H) * (CIC_BY + 2 * CIC_H) * (CIC_BZ + 2 * CIC_H);      // 12 x 12 x 68 = 9792 cells, 78336 bytes
+static_assert(2 * CIC_TILE_CELLS * 8 <= 163840, "two workgroups per compute unit");
+
+template <typename T>
+__global__ __launch_bounds__(CIC_NT) void cic_paint_tiled_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
+                                                                 u64* __restrict__ A, u64* __restrict__ dropped, CicGrid g, int nby, int nbz) {
+  extern __shared__ __attribute__((aligned(16))) u64 cic_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned b = blockIdx.x, bz = b % (unsigned)nbz, bxy = b / (unsigned)nbz, by = bxy % (unsigned)nby, bx = bxy / (unsigned)nby;
+  CicTile t;
+  t.bx = CIC_BX; t.by = CIC_BY; t.bz = CIC_BZ; t.h = CIC_H;
+  t.x0 = (int)bx * CIC_BX; t.y0 = (int)by * CIC_BY; t.z0 = (int)bz * CIC_BZ;
+  for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) cic_lds[s] = 0ull;
+  __syncthreads();
+  int ndrop = 0;
+  const int iz = t.z0 + lane;
+  for (int row = wave; row < CIC_BX * CIC_BY; row += CIC_NT / 64) {
+    const int lx = row / CIC_BY, ly = row - lx * CIC_BY, ix = t.x0 + lx, iy = t.y0 + ly;
+    if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
+    const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
+    CicAxis x, y, z;
+    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; continue; }
+    cic_scatter_tiled(x, y, z, lx, ly, lane, t, g.ny, g.nz,
+                      [&](int slot, uint64_t w) { atomicAdd(&cic_lds[slot], (u64)w); },
+                      [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+  }
+  __syncthreads();
+  for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) {
+    const u64 v = cic_lds[s];
+    if (v) atomicAdd(A + cic_tile_cell(t, s, g.nx, g.ny, g.nz), v);
+  }
+  cic_count_dropped(ndrop, dropped);
+}
+
+// W = (double)A 2^-48 - 1 rounded once to T (rf_core.h cic_delta)
+template <typename T>
+__global__ __launch_bounds__(256) void cic_convert_kernel(const u64* __restrict__ A, T* __restrict__ W, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) W[i] = cic_delta<T>(A[i]);
+}
+
+// Q = coeff W (first) or fma(coeff, W, Q), shaped like lpt2_accumulate_kernel: VEC elements (16 bytes) per lane and array, grid-strided
+// (every axis of a plan is even, so the arrays are whole numbers of 16 bytes)
+template <typename T, int VEC, bool FIRST>
+__global__ __launch_bounds__(256) void particles_accumulate_kernel(const T* __restrict__ W, T* __restrict__ Q, T coeff, long long nvec) {
+  typedef T vt __attribute__((ext_vector_type(VEC)));
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
+    const vt w = __builtin_nontemporal_load(reinterpret_cast<const vt*>(W) + i);
+    vt q;
+    if (!FIRST) q = __builtin_nontemporal_load(reinterpret_cast<const vt*>(Q) + i);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) q[e] = particles_axpy<T>(FIRST, coeff, w[e], FIRST ? (T)0 : q[e]);
+    __builtin_nontemporal_store(q, reinterpret_cast<vt*>(Q) + i);
+  }
+}
+
+inline unsigned sweep_grid(long long n, int block) {
+  long long g = (n + block - 1) / block;
+  if (g > 256 * 16) g = 256 * 16;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+
+template <typename T, int VEC>
+hipError_t particles_accumulate_t(const T* W, T* Q, double coeff, int first, long long n, hipStream_t s) {
+  if (n <= 0 || n % VEC || (uintptr_t)W % 16 || (uintptr_t)Q % 16) return hipErrorInvalidValue;
+  const long long nvec = n / VEC;
+  const dim3 grid(sweep_grid(nvec, 256)), block(256);
+  const T c = (T)coeff;
+  if (first) hipLaunchKernelGGL((particles_accumulate_kernel<T, VEC, true>), grid, block, 0, s, W, Q, c, nvec);
+  else hipLaunchKernelGGL((particles_accumulate_kernel<T, VEC, false>), grid, block, 0, s, W, Q, c, nvec);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t cic_paint_t(int form, const T* Q, u64* A, u64* dropped, int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
+  const long long n = (long long)nx * ny * nz;
+  CicGrid g;
+  g.nx = nx; g.ny = ny; g.nz = nz;
+  for (int a = 0; a < 3; ++a) g.inv_h[a] = inv_h[a];
+  const T *Qx = Q, *Qy = Q + n, *Qz = Q + 2 * n;
+  if (form == 1) {
+    hipLaunchKernelGGL(cic_paint_global_kernel<T>, dim3(sweep_grid(n, 256)), dim3(256), 0, s, Qx, Qy, Qz, A, dropped, g, n);
+    return hipGetLastError();
+  }
+  const long long nbx = (nx + CIC_BX - 1) / CIC_BX, nby = (ny + CIC_BY - 1) / CIC_BY, nbz = (nz + CIC_BZ - 1) / CIC_BZ;
+  const long long nb = nbx * nby * nbz;
+  if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
+  static LdsAttrLatch latch;
+  const int lds = CIC_TILE_CELLS * 8;
+  if (hipError_t e = latch.ensure(reinterpret_cast<const void*>(&cic_paint_tiled_kernel<T>), lds)) return e;
+  hipLaunchKernelGGL(cic_paint_tiled_kernel<T>, dim3((unsigned)nb), dim3(CIC_NT), lds, s, Qx, Qy, Qz, A, dropped, g, (int)nby, (int)nbz);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double coeff, int first, long long n, hipStream_t s) {
+  return f64 ? particles_accumulate_t<double, 2>((const double*)W, (double*)Q, coeff, first, n, s)
+             : particles_accumulate_t<float, 4>((const float*)W, (float*)Q, coeff, first, n, s);
+}
+
+hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
+                            const double* inv_h, hipStream_t s) {
+  if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
+  return f64 ? cic_paint_t<double>(form, (const double*)Q, A, dropped, nx, ny, nz, inv_h, s)
+             : cic_paint_t<float>(form, (const float*)Q, A, dropped, nx, ny, nz, inv_h, s);
+}
+
+void cic_paint_geometry(int* brick3, int* halo) {
+  brick3[0] = CIC_BX; brick3[1] = CIC_BY; brick3[2] = CIC_BZ;
+  *halo = CIC_H;
+}
+
+hipError_t launch_cic_convert(int f64, const unsigned long long* A, void* W, long long n, hipStream_t s) {
+  if (n <= 0) return hipErrorInvalidValue;
+  if (f64) hipLaunchKernelGGL(cic_convert_kernel<double>, dim3(sweep_grid(n, 256)), dim3(256), 0, s, A, (double*)W, n);
+  else hipLaunchKernelGGL(cic_convert_kernel<float>, dim3(sweep_grid(n, 256)), dim3(256), 0, s, A, (float*)W, n);
+  return hipGetLastError();
+}
+
+}  // namespace rf

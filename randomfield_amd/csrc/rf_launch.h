@@ -148,6 +148,19 @@ hipError_t launch_hessian(int f64, const void* S, void* K, const HessParams& hp,
 // real arrays H (the component just transformed), T and S (the accumulators); n a multiple of 16 bytes' worth of elements and the
 // arrays 16-byte aligned, else hipErrorInvalidValue.  LPT2_LAST writes the source into H.
 hipError_t launch_lpt2_accumulate(int f64, int step, void* H, void* T, void* S, long long n, hipStream_t s);
+// particles (rf_k_particles.hip).  Q = coeff W (first != 0) or Q + coeff W over n elements of dense real arrays (rf_core.h
+// particles_axpy; coeff is rounded to the real type once): 16 bytes per lane; n a multiple of 16 bytes' worth of elements and the arrays
+// 16-byte aligned, else hipErrorInvalidValue
+hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double coeff, int first, long long n, hipStream_t s);
+// the cloud-in-cell scatter of the lattice particles displaced by Q[3][nx][ny][nz] into the CLEARED 64-bit accumulator grid A
+// (rf_core.h cic_particle): form 1 = global atomics, form 2 = LDS tiles flushed with global atomics; *dropped (cleared by the caller)
+// counts the particles with a non-finite displacement.  Same A from both forms.
+hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
+                            const double* inv_h, hipStream_t s);
+// the brick (cells per axis) and the halo of form 2's tile
+void cic_paint_geometry(int* brick3, int* halo);
+// W = (double)A 2^-48 - 1, rounded once to the real type (rf_core.h cic_delta)
+hipError_t launch_cic_convert(int f64, const unsigned long long* A, void* W, long long n, hipStream_t s);
 // the binned power spectrum of a half spectrum (rf_core.h power_cell; rf_k_power.hip).  S: API layout, or the packed array of the tiled
 // forward passes (gp.packed); e2_dev: the gp.nbins + 1 squared edges.  partials: three planes of plane_words 8-byte words each
 // (count, sum_k, sum_p per workgroup and bin: plane_words >= grid * nbins of power_launch_shape, else hipErrorInvalidValue);

@@ -129,6 +129,14 @@ struct rf_plan {
   void* L = nullptr;
   size_t l_bytes = 0;
   bool p2_valid = false;
+  // lazy, rf_particles_*: the particle displacements Q[3][nx][ny][nz] of the plan's real type (3 x w_bytes) and the 64-bit accumulator
+  // grid A[nx][ny][nz] of the cloud-in-cell paint (8 bytes per cell), both counted by rf_plan_nbytes; pa_drop: the paint's counter of
+  // dropped particles (8 bytes).  pa_valid: A holds the counts of a paint; paint_form: 0 auto, 1 global, 2 tiled.
+  void* Q = nullptr;
+  void* A = nullptr;
+  void* pa_drop = nullptr;
+  bool pa_valid = false;
+  int paint_form = 0;
   void *tw_x = nullptr, *tw_y = nullptr, *tw_z = nullptr;
   double *kx2 = nullptr, *ky2 = nullptr, *kz2 = nullptr;
   double *xt = nullptr, *st = nullptr, *sl = nullptr;

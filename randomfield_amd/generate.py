@@ -181,6 +181,8 @@ class Generator(object):
         self.k_min, self.k_max = powertools.get_k_bounds(self.plan_c2r.data_in, grid_spacing_Mpc_h, packed=True)
         self.potential = None
         self._lpt2 = None                   # second-order potential of the current field: the array (numpy) / its potential object (hip)
+        self._particles = None              # particle displacements: the (3, nx, ny, nz) array (numpy) / True once the device buffer is filled (hip)
+        self.particles_dropped = 0
 
         if nz % num_plot_sections != 0:
             raise ValueError("Z-axis does not evenly divided into {0} plot sections.".format(num_plot_sections))
@@ -260,6 +262,7 @@ class Generator(object):
         nx, ny, nz = self.plan_c2r.shape
         self.smoothed_power = powertools.filter_power(self.power, smoothing_length_Mpc_h)
         self._lpt2 = None
+        self._particles = None               # (displacements belong to the field they were made for or set beside)
 
         if self.backend == "numpy":
             data = self.plan_c2r.data_in
@@ -393,6 +396,7 @@ class Generator(object):
             rms = dev.realise_lognormal(self._native_seed(seed), None)
         self.potential = None
         self._lpt2 = None
+        self._particles = None               # (displacements belong to the field they were made for or set beside)
         self.delta_field_rms = self.plan_c2r.data_out.dtype.type(rms)
         self._field_on_host = False
         if self.verbose:
@@ -717,6 +721,93 @@ class Generator(object):
         dev.execute_gradient(axis, scale2, dk, _hip.RF_GRAD_FROM_POTENTIAL2)
         if factor is not None:
             dev.scale_z(factor)
+        self._field_on_host = False
+        return self.download_field() if download else None
+
+    # ---- particles: the displaced lattice and its cloud-in-cell paint ---------
+    def particle_displacements(self, order=2, D1=1.0, download=True):
+        """
+        The Lagrangian displacements s = D1 psi1 (``order=1``) or D1 psi1 + D1**2 psi2 (``order=2``) of the lattice particles, one
+        per cell, in Mpc/h -- from :meth:`calculate_displacement_field`, whose ``order=2`` term already carries the 3/7.  The three
+        components are kept together (hip backend: in a device buffer, ``rf_particles_accumulate``) for :meth:`paint_particles`
+        and :meth:`particle_positions`, until the next field is generated (``generate_delta_field`` / ``generate_density_field``
+        drop them).  Returns a new ``(3, nx, ny, nz)`` array of the plan's real type, or None with ``download=False``.  The field
+        buffer is left holding the last component transformed.
+        """
+        if order not in (1, 2):
+            raise ValueError("Invalid order: {0!r} (expected 1 or 2).".format(order))
+        rtype = self.plan_c2r.data_out.dtype.type
+        d1, d2 = float(D1), float(D1) * float(D1)
+        if self.backend == "numpy":
+            Q = np.empty((3,) + tuple(self.plan_c2r.shape), rtype)
+            for axis in range(3):
+                Q[axis] = rtype(d1) * self.calculate_displacement_field(axis, order=1)
+                if order == 2:
+                    Q[axis] += rtype(d2) * self.calculate_displacement_field(axis, order=2)
+            self._particles = Q
+            return self._download_particles() if download else None
+        for axis in range(3):
+            self.calculate_displacement_field(axis, order=1, download=False)
+            dev = self.plan_c2r.device
+            dev.particles_accumulate(axis, d1, first=True)
+            if order == 2:
+                self.calculate_displacement_field(axis, order=2, download=False)
+                dev.particles_accumulate(axis, d2, first=False)
+        self._particles = True
+        return self._download_particles() if download else None
+
+    def set_particle_displacements(self, s):
+        """Bring your own displacements: a ``(3, nx, ny, nz)`` array in Mpc/h, converted to the plan's real type (copied; kept until
+        the next field is generated, as those of :meth:`particle_displacements`)."""
+        if self.distributed:
+            raise NotImplementedError("particles live on single-GPU plans (distributed=False).")
+        s = np.asarray(s)
+        if s.shape != (3,) + tuple(self.plan_c2r.shape):
+            raise ValueError("displacements must have the shape {0}.".format((3,) + tuple(self.plan_c2r.shape)))
+        s = np.ascontiguousarray(s, self.plan_c2r.data_out.dtype)
+        if self.backend == "numpy":
+            self._particles = s.copy()
+            return
+        for axis in range(3):
+            self.plan_c2r.device.particles_upload(axis, s[axis])
+        self._particles = True
+
+    def _download_particles(self):
+        if self._particles is None:
+            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+        if self.backend == "numpy":
+            return self._particles.copy()              # (a new array on both backends)
+        return np.stack([self.plan_c2r.device.particles_download(axis) for axis in range(3)])
+
+    def particle_positions(self):
+        """float64 ``(3, nx, ny, nz)``: (q h + s) mod L per axis, q the lattice index, h the grid spacing, L = n h the box length."""
+        Q = self._download_particles()
+        h = float(self.grid_spacing_Mpc_h)
+        out = np.empty(Q.shape, np.float64)
+        for axis, n in enumerate(self.plan_c2r.shape):
+            q = np.arange(n, dtype=np.float64).reshape([-1 if a == axis else 1 for a in range(3)])
+            out[axis] = np.mod(q * h + Q[axis].astype(np.float64), n * h)
+        return out
+
+    def paint_particles(self, download=True):
+        """
+        Cloud-in-cell mass assignment of the displaced particles onto the grid: delta_cic = (mass per cell) - 1 becomes the current
+        field, so ``measure_power_spectrum()`` with no argument measures the particles.  The weights are integers in units of
+        2**-16 per axis, summed in a ``uint64`` grid: the result is the same bit for bit on every call (hip backend:
+        ``rf_particles_paint``, integer atomics).  Particles with a non-finite displacement are dropped and counted in
+        ``self.particles_dropped``.  Fewer than 65536 particles' worth of mass may land in one cell.  Returns the field, or None
+        with ``download=False``.
+        """
+        if self._particles is None:
+            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+        inv_h = [1.0 / float(self.grid_spacing_Mpc_h)] * 3
+        if self.backend == "numpy":
+            from . import particles
+            A, self.particles_dropped = particles.paint_counts(self._particles, inv_h)
+            self.plan_c2r.data_out[...] = particles.counts_to_delta(A, self.plan_c2r.data_out.dtype)
+            self._field_on_host = True
+            return self.plan_c2r.data_out if download else None
+        self.particles_dropped = self.plan_c2r.device.particles_paint(inv_h)
         self._field_on_host = False
         return self.download_field() if download else None
 
