@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void unpack_kspace_kernel(const cplx<T>* __res
 
 inline unsigned grid_for(long long n, int block) {
   long long g = (n + block - 1) / block;
-  if (g > 256 * 16) g = 256 * 16;   // 16 blocks per CU, grid-stride the rest
+  if (g > 256 * 16) g = 256 * 16;   // 16 blocks per CU, grid-stride the rest (the strides: tests/test_gpu_at_scale.py)
   if (g < 1) g = 1;
   return (unsigned)g;
 }
@@ -592,7 +592,7 @@ hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp
   while (tx < 256 && tx < nzh) tx <<= 1;
   const int ty = 256 / tx;
   const long long nblk = (nrows + ty - 1) / ty;
-  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);
+  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);     // (more rows, and rows longer than tx: tests/test_gpu_at_scale.py)
   if (f64) hipLaunchKernelGGL(gradient_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, gp, (unsigned)nrows);
   else hipLaunchKernelGGL(gradient_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, gp, (unsigned)nrows);
   return hipGetLastError();
@@ -606,7 +606,7 @@ hipError_t launch_hessian(int f64, const void* S, void* K, const HessParams& hp,
   while (tx < 256 && tx < nzh) tx <<= 1;
   const int ty = 256 / tx;
   const long long nblk = (nrows + ty - 1) / ty;
-  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);
+  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);     // (more rows, and rows longer than tx: tests/test_gpu_at_scale.py)
   if (f64) hipLaunchKernelGGL(hessian_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, hp, (unsigned)nrows);
   else hipLaunchKernelGGL(hessian_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, hp, (unsigned)nrows);
   return hipGetLastError();

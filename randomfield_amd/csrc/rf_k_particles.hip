@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void particles_accumulate_kernel(const T* __re
 
 inline unsigned sweep_grid(long long n, int block) {
   long long g = (n + block - 1) / block;
-  if (g > 256 * 16) g = 256 * 16;
+  if (g > 256 * 16) g = 256 * 16;          // (the grid-stride loops beyond it: tests/test_gpu_at_scale.py)
   return (unsigned)(g < 1 ? 1 : g);
 }
 

@@ -123,7 +123,7 @@ PowerLaunch power_launch_shape(int nx, int ny, int nz, int nbins) {
   L.tx = tx;
   L.ty = nthreads / tx;
   const long long nrows = (long long)nx * ny, nblk = (nrows + L.ty - 1) / L.ty;
-  const long long cap = nbins <= 128 ? 2048 : 1024;        // workgroups: rows of the partial planes (<= 2^20 words per plane)
+  const long long cap = nbins <= 128 ? 2048 : 1024;        // workgroups: rows of the partial planes (<= 2^20 words per plane); more rows than cap * ty: tests/test_gpu_at_scale.py
   L.grid = (unsigned)(nblk < cap ? (nblk < 1 ? 1 : nblk) : cap);
   L.lds = (size_t)((nbins + 1) + 3 * (nthreads / 64) * nbins) * 8;
   return L;

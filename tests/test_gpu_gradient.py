@@ -9,7 +9,10 @@ Generic plans apply the factor inside their x pass: that field must be load_grad
 
 Shapes: tiled plans (16, 16, 16) both dtypes and (16, 32, 64); generic plans one workgroup (4, 6, 8), tile 16 in place (40, 60, 80), a
 ragged last workgroup (30, 14, 22), two LDS buffers (154, 28, 44), tile 4 (2400, 6, 8), and an x axis in the four-step form
-(16384, 4, 6), which takes the elementwise kernel into scratch."""
+(16384, 4, 6), which takes the elementwise kernel into scratch.  nz >= 512 -- rows of nz/2 + 1 > 256 cells, so the kernels' kz loop
+takes a second step, and on float32 plans potential rows padded to nz/2 + 64 cells: tiled (16, 16, 512) complex64 (pitch 320; also
+under test_stored_potential, where the generation pass itself writes the potential) and (8, 8, 512) complex128 (no padding), generic
+(6, 10, 520) complex64 (pitch 324 read by the x pass).  More rows or cells than one launch holds: tests/test_gpu_at_scale.py."""
 import numpy as np
 import pytest
 
@@ -21,8 +24,10 @@ pytestmark = pytest.mark.gpu
 SPACING = 0.5
 C64, C128 = np.complex64, np.complex128
 TOL = {C64: 1e-5, C128: 1e-11}
-TILED = [((16, 16, 16), C64), ((16, 16, 16), C128), ((16, 32, 64), C64)]
-GENERIC = [((4, 6, 8), C64), ((4, 6, 8), C128), ((40, 60, 80), C64), ((30, 14, 22), C64), ((154, 28, 44), C128), ((2400, 6, 8), C64)]
+TILED = [((16, 16, 16), C64), ((16, 16, 16), C128), ((16, 32, 64), C64),
+         ((16, 16, 512), C64), ((8, 8, 512), C128)]     # nz/2 + 1 > 256: two kz steps; float32: potential rows of nz/2 + 64 cells
+GENERIC = [((4, 6, 8), C64), ((4, 6, 8), C128), ((40, 60, 80), C64), ((30, 14, 22), C64), ((154, 28, 44), C128), ((2400, 6, 8), C64),
+           ((6, 10, 520), C64)]       # the x pass reads padded potential rows (pitch 324)
 
 
 def _ids(v):
@@ -155,7 +160,7 @@ def test_four_step_x_axis_takes_the_fallback(hip):
     plan.close()
 
 
-@pytest.mark.parametrize("shape", [(16, 16, 16), (40, 60, 80)], ids=_ids)
+@pytest.mark.parametrize("shape", [(16, 16, 16), (40, 60, 80), (16, 16, 512)], ids=_ids)
 def test_stored_potential(hip, dpower, shape):
     dtype = C64
     plan = make_plan(hip, shape, dtype, dpower)

@@ -8,7 +8,10 @@ within 4 eps of the float64 formula with exact zeros where m_a m_b = 0; the sour
 TOL * sum_{a<b} (|H_aa| rms_bb + |H_bb| rms_aa + 2 |H_ab| rms_ab) + 8 eps A(x), A = sum |the six products| (two transformed factors
 per product, at most 11 roundings of eps/2 A in the sweep); psi2 against the oracle applied to the device's own S within 2 TOL rms
 (two transforms).  Generic plans apply the Hessian factor inside their x pass: that field must be load_hessian + execute_c2r bit for
-bit, the four-step fallback of (16384, 4, 6) included.  Shapes: those of tests/test_gpu_gradient.py, one per launch class."""
+bit, the four-step fallback of (16384, 4, 6) included.  Shapes: those of tests/test_gpu_gradient.py, one per launch class, its three
+nz >= 512 shapes among them ((16, 16, 512) complex64, (8, 8, 512) complex128, (6, 10, 520) complex64: the second kz step of
+hessian_kernel, and Hessian, source and second-order potential on the padded potential pitch).  The grid-stride loops of
+hessian_kernel and lpt2_accumulate_kernel: tests/test_gpu_at_scale.py."""
 import numpy as np
 import pytest
 
@@ -21,9 +24,10 @@ pytestmark = pytest.mark.gpu
 SPACING = 0.5
 C64, C128 = np.complex64, np.complex128
 TOL = {C64: 1e-5, C128: 1e-11}
-TILED = [((16, 16, 16), C64), ((16, 16, 16), C128), ((16, 32, 64), C64)]
+TILED = [((16, 16, 16), C64), ((16, 16, 16), C128), ((16, 32, 64), C64),
+         ((16, 16, 512), C64), ((8, 8, 512), C128)]     # nz/2 + 1 > 256: two kz steps; float32: potential rows of nz/2 + 64 cells
 GENERIC = [((4, 6, 8), C64), ((4, 6, 8), C128), ((40, 60, 80), C64), ((30, 14, 22), C64), ((154, 28, 44), C128), ((2400, 6, 8), C64),
-           ((16384, 4, 6), C64)]
+           ((16384, 4, 6), C64), ((6, 10, 520), C64)]       # ... and padded potential rows under the x pass (pitch 324)
 
 
 def _ids(v):

@@ -1114,7 +1114,8 @@ def test_lensing_kernel_closed_form(hip, K):
 
 
 @pytest.mark.parametrize("dtype", [np.complex64, np.complex128])
-@pytest.mark.parametrize("shape", [(64, 32, 128), (1024, 8, 32), (512, 16, 64), (16, 16, 16), (2048, 8, 32)])
+@pytest.mark.parametrize("shape", [(64, 32, 128), (1024, 8, 32), (512, 16, 64), (16, 16, 16), (2048, 8, 32),
+                                   (16, 16, 512), (1024, 8, 512)])     # nz >= 512: float32 potential rows of nz/2 + 64 cells
 def test_fused_potential_store_native(hip, dpower, shape, dtype):
     """rf_realise_potential = the reference's default generate_delta_field(save_potential=True) (generate.py:191-219) with
     the native generator: delta(k)/k**2 written by the generation pass itself.  The field must be the one rf_realise
@@ -1152,7 +1153,8 @@ def test_fused_potential_store_native(hip, dpower, shape, dtype):
 
 
 @pytest.mark.parametrize("shape,dtype", [((64, 32, 128), np.complex64), ((1024, 8, 32), np.complex64), ((2048, 8, 32), np.complex64),
-                                         ((512, 16, 64), np.complex128), ((1024, 8, 32), np.complex128), ((16, 16, 16), np.complex64)])
+                                         ((512, 16, 64), np.complex128), ((1024, 8, 32), np.complex128), ((16, 16, 16), np.complex64),
+                                         ((16, 16, 512), np.complex64), ((1024, 8, 512), np.complex64)])     # the padded potential pitch
 def test_regenerated_potential_equals_stored_one(hip, dpower, shape, dtype):
     """rf_realise_scaled_potential: calculate_newtonian_potential (generate.py:333-343) with delta(k)/k**2 formed again inside the
     generation pass instead of read from a stored array -- against the stored route (rf_realise_potential, rf_load_potential,

@@ -4,7 +4,13 @@ rf_particles_set_paint_form; rf_k_particles.hip) and Generator.particle_displace
 Oracle: tests/cic_oracle.py.  The accumulator grid is integer: every form (global atomics, LDS tiles, the library's choice) must give
 the oracle's grid with np.array_equal, and the field is that grid scaled and rounded once, so it is compared exactly too.  The
 accumulate step: the coefficients are exactly representable, `first` is one rounding (eps/2 |coeff W|), a further add one fma rounding,
-held to the two-rounding bound 2 eps (|Q| + |coeff W|) that also covers the numpy backend."""
+held to the two-rounding bound 2 eps (|Q| + |coeff W|) that also covers the numpy backend.
+
+Shapes: tiled plans (16, 16, 16) both dtypes and (16, 32, 64); generic plans (4, 6, 8) both dtypes, (30, 14, 22) and (40, 60, 80):
+at most 192 000 particles, one stride of every sweep.  test_generator_end_to_end also runs (64, 64, 512), 2 097 152 particles: two
+strides of the global paint and of the conversion, the padded potential under calculate_displacement_field(order=1|2) and
+measure_power_spectrum of the painted field on a tiled plan with nz = 512.  The forms and the accumulate step beyond one stride:
+tests/test_gpu_at_scale.py."""
 import numpy as np
 import pytest
 
@@ -206,7 +212,7 @@ def test_refusals(hip):
     plan.close()
 
 
-@pytest.mark.parametrize("shape", [(16, 16, 16), (40, 60, 80)], ids=_ids)
+@pytest.mark.parametrize("shape", [(16, 16, 16), (40, 60, 80), (64, 64, 512)], ids=_ids)
 def test_generator_end_to_end(hip, shape):
     from randomfield_amd import Generator
     rt, D1 = np.float32, 0.5

@@ -9,6 +9,8 @@ the kernel with the unpack kernel's formula and rounding, so only the summation 
 Shapes: tiled plans (16, 16, 16) both dtypes and (16, 32, 64); generic plans one workgroup with rows shorter than a wave (4, 6, 8),
 (40, 60, 80), a ragged last workgroup (30, 14, 22), (154, 28, 44) complex128, and rows longer than a workgroup (4, 6, 1200).  Rows of
 at least 33 cells -- (16, 32, 64), (40, 60, 80), (4, 6, 1200) -- take the run-based reduction of the sweep, shorter ones the loop over bins.
+Tiled (16, 16, 512): rows of 257 cells, a second kz step that holds the Nyquist plane alone, which the packed FROM_FIELD sweep untangles
+from slot kz = 0 of two rows.  More rows than the sweep's workgroups take in one stride: tests/test_gpu_at_scale.py.
 
 Generator, complex64, measure_power_spectrum(field) against the oracle on np.fft.rfftn(field): the float32 FFT's rounding is relative to
 the largest amplitude, not to each bin's, so no bound follows from the formats.  Measured once on an MI355X: largest relative bin
@@ -22,7 +24,8 @@ from power_oracle import C64, C128
 pytestmark = pytest.mark.gpu
 
 SPACING = 2.5
-TILED = [((16, 16, 16), C64), ((16, 16, 16), C128), ((16, 32, 64), C64)]
+TILED = [((16, 16, 16), C64), ((16, 16, 16), C128), ((16, 32, 64), C64),
+         ((16, 16, 512), C64)]        # nz/2 + 1 = 257: a second kz step of one cell, the Nyquist plane the packed sweep untangles
 GENERIC = [((4, 6, 8), C64), ((4, 6, 8), C128), ((40, 60, 80), C64), ((30, 14, 22), C64), ((154, 28, 44), C128),
            ((4, 6, 1200), C64)]        # rows of several waves and several steps: the run-based reduction, a ragged last step
 # largest relative bin difference of Pk measured for complex64 (see the module docstring), per shape
