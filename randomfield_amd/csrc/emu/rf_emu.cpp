@@ -549,78 +549,42 @@ template <typename T> struct EmuGenericOps {
   int nthreads() const { return g_generic_threads > 1 ? g_generic_threads : 1; }
   // rows per block of the contiguous passes: 2 for the single thread; the kernels' 8 / 4 (rows_per_block) with threads
   int row_tile() const { return g_generic_threads > 1 ? (g_generic_tile < 8 ? g_generic_tile : 8) : 2; }
+  // one strided pass whose elements come from `from` (rf_generic.h generic_axis_block_from), block after block
+  template <class Source>
+  int axis_source(Source from, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    const int TC = g_generic_tile, nth = nthreads();
+    cplx<T>* lds = lds_image(ax, TC);
+    run_generic_threads([&](int tid, auto sync) {
+      for (long long b = 0; b * TC < nlines; ++b) {
+        generic_axis_block_from<T>(from, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
+        sync();
+      }
+    });
+    return 0;
+  }
   int axis(const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    const int TC = g_generic_tile, nth = nthreads();
-    cplx<T>* lds = lds_image(ax, TC);
-    run_generic_threads([&](int tid, auto sync) {
-      for (long long b = 0; b * TC < nlines; ++b) {
-        generic_axis_block<T>((const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
-        sync();
+    return axis_source(GenericMemSource<T>((const cplx<T>*)src, stride, inner, outer), dst, ax, stride, inner, outer, nlines, which, sign, scale);
+  }
+  // generic_c2r_from_seq: the Source and the cell of a descriptor -- the generator, or a component of the gradient / Hessian of S
+  static GenericGenSource<T> source(const GenParams& gp, const void*) { return GenericGenSource<T>(gp, gp.seed); }
+  template <class P> static GenericDerivSource<T, P> source(const P& dp, const void* S) { return GenericDerivSource<T, P>(dp, (const cplx<T>*)S); }
+  static cplx<T> cell(const GenParams& gp, const void*, long long, int ix, int iy, int iz) { return gen_cell<T>(gp, gp.seed, ix, iy, iz); }
+  template <class P> static cplx<T> cell(const P& dp, const void* S, long long row, int ix, int iy, int iz) {
+    return deriv_cell<T>(dp, ((const cplx<T>*)S)[row * dp.pitch + iz], ix, iy, iz);
+  }
+  template <class From>
+  int axis_from(const From& from, const void* S, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    return axis_source(source(from, S), dst, ax, stride, inner, outer, nlines, which, sign, scale);
+  }
+  // ... and the cells alone, API layout (the loop of gen_kspace_kernel / the elementwise derivative kernel; S == K is allowed)
+  template <class From>
+  int materialise(const From& from, const void* S, void* K) {
+    const int nzh = from.nz / 2 + 1;
+    for (int ix = 0; ix < from.nx; ++ix)
+      for (int iy = 0; iy < from.ny; ++iy) {
+        const long long row = (long long)ix * from.ny + iy;
+        for (int iz = 0; iz < nzh; ++iz) ((cplx<T>*)K)[row * nzh + iz] = cell(from, S, row, ix, iy, iz);
       }
-    });
-    return 0;
-  }
-  // generic_realise_seq: the x pass with the generator as its source, and the generation alone (rows K,T,R,S, API layout)
-  int axis_gen(const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    const int TC = g_generic_tile, nth = nthreads();
-    cplx<T>* lds = lds_image(ax, TC);
-    run_generic_threads([&](int tid, auto sync) {
-      for (long long b = 0; b * TC < nlines; ++b) {
-        generic_axis_gen_block<T>(gp, gp.seed, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
-        sync();
-      }
-    });
-    return 0;
-  }
-  int gen_kspace(const GenParams& gp, void* K) {
-    const int nzh = gp.nz / 2 + 1;
-    for (int ix = 0; ix < gp.nx; ++ix)
-      for (int iy = 0; iy < gp.ny; ++iy)
-        for (int iz = 0; iz < nzh; ++iz) ((cplx<T>*)K)[((size_t)ix * gp.ny + iy) * nzh + iz] = gen_cell<T>(gp, gp.seed, ix, iy, iz);
-    return 0;
-  }
-  // generic_gradient_c2r_seq: the x pass through GenericGradSource, and the component alone (the elementwise kernel's loop)
-  int axis_grad(const GradParams& gr, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    const int TC = g_generic_tile, nth = nthreads();
-    cplx<T>* lds = lds_image(ax, TC);
-    run_generic_threads([&](int tid, auto sync) {
-      for (long long b = 0; b * TC < nlines; ++b) {
-        generic_axis_grad_block<T>(gr, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
-        sync();
-      }
-    });
-    return 0;
-  }
-  int grad_kspace(const GradParams& gr, const void* S, void* K) {
-    const int nzh = gr.nz / 2 + 1;
-    for (int ix = 0; ix < gr.nx; ++ix)
-      for (int iy = 0; iy < gr.ny; ++iy)
-        for (int iz = 0; iz < nzh; ++iz) {
-          const size_t row = (size_t)ix * gr.ny + iy;
-          ((cplx<T>*)K)[row * nzh + iz] = grad_cell<T>(gr, ((const cplx<T>*)S)[row * gr.pitch + iz], ix, iy, iz);
-        }
-    return 0;
-  }
-  // generic_hessian_c2r_seq: the x pass through GenericHessSource, and the component alone (the elementwise kernel's loop)
-  int axis_hess(const HessParams& hs, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    const int TC = g_generic_tile, nth = nthreads();
-    cplx<T>* lds = lds_image(ax, TC);
-    run_generic_threads([&](int tid, auto sync) {
-      for (long long b = 0; b * TC < nlines; ++b) {
-        generic_axis_hess_block<T>(hs, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
-        sync();
-      }
-    });
-    return 0;
-  }
-  int hess_kspace(const HessParams& hs, const void* S, void* K) {
-    const int nzh = hs.nz / 2 + 1;
-    for (int ix = 0; ix < hs.nx; ++ix)
-      for (int iy = 0; iy < hs.ny; ++iy)
-        for (int iz = 0; iz < nzh; ++iz) {
-          const size_t row = (size_t)ix * hs.ny + iy;
-          ((cplx<T>*)K)[row * nzh + iz] = hess_cell<T>(hs, ((const cplx<T>*)S)[row * hs.pitch + iz], ix, iy, iz);
-        }
     return 0;
   }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
@@ -698,9 +662,11 @@ int generic_c2r_impl(int nx, int ny, int nz, const cplx<T>* K, T* W, double* s1,
   return rc;
 }
 
-// a realisation with the generation inside the x pass (rf_generic.h generic_realise_seq; an x axis beyond the cap: its unfused fallback)
-template <typename T>
-int generic_realise_impl(int nx, int ny, int nz, const GenParams& gp, T* W, double* s1, double* s2) {
+// generic_c2r_impl with the first pass taking its cells from a descriptor (rf_generic.h generic_c2r_from_seq; an x axis beyond the cap:
+// its unfused fallback): a realisation with the generation inside the x pass (GenParams), or one component of the gradient / Hessian of
+// the potential S as a field with the factor applied there (GradParams / HessParams)
+template <typename T, class From>
+int generic_c2r_from_impl(int nx, int ny, int nz, const From& from, const void* S, T* W, double* s1, double* s2) {
   GenericDims d;
   if (!emu_dims<T>(nx, ny, nz, true, d)) return -1;
   const long long nzh = nz / 2 + 1;
@@ -708,59 +674,38 @@ int generic_realise_impl(int nx, int ny, int nz, const GenParams& gp, T* W, doub
   std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
   EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
   ops.az = d.az;
-  const int rc = generic_realise_seq(ops, d, gp, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
+  const int rc = generic_c2r_from_seq(ops, d, from, S, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
   if (s1) *s1 = ops.s1;
   if (s2) *s2 = ops.s2;
   return rc;
 }
-
-// one component of the gradient of the potential as a field, the factor inside the x pass (rf_generic.h generic_gradient_c2r_seq; an x
-// axis beyond the cap: its unfused fallback)
-template <typename T>
-int generic_gradient_c2r_impl(int nx, int ny, int nz, const GradParams& gr, const cplx<T>* S, T* W, double* s1, double* s2) {
-  GenericDims d;
-  if (!emu_dims<T>(nx, ny, nz, true, d)) return -1;
-  const long long nzh = nz / 2 + 1;
-  auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
-  std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
-  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
-  ops.az = d.az;
-  const int rc = generic_gradient_c2r_seq(ops, d, gr, S, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
-  if (s1) *s1 = ops.s1;
-  if (s2) *s2 = ops.s2;
-  return rc;
+// the parameters of a component as the emulator's exports take them; false: refused (bad shape, axes, pitch, or divide without tables)
+template <class P>
+bool emu_deriv_params(int nx, int ny, int nz, int divide, const double* kx2, const double* ky2, const double* kz2, long long spitch, P& g) {
+  g.nx = nx; g.ny = ny; g.nz = nz; g.divide = divide != 0;
+  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2; g.pitch = spitch;
+  return nx >= 1 && ny >= 1 && nz >= 2 && !(nz & 1) && deriv_valid(g) && !(divide && !(kx2 && ky2 && kz2));
 }
 inline bool emu_grad_params(int nx, int ny, int nz, int axis, double scale, double dk, int divide, const double* kx2, const double* ky2, const double* kz2,
                             long long spitch, GradParams& g) {
-  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || axis < 0 || axis > 2 || spitch < nz / 2 + 1 || (divide && !(kx2 && ky2 && kz2))) return false;
   memset(&g, 0, sizeof(g));
-  g.nx = nx; g.ny = ny; g.nz = nz; g.axis = axis; g.divide = divide != 0; g.sdk = scale * dk;
-  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2; g.pitch = spitch;
-  return true;
-}
-
-// one component of the Hessian of the potential as a field (rf_generic.h generic_hessian_c2r_seq), as generic_gradient_c2r_impl
-template <typename T>
-int generic_hessian_c2r_impl(int nx, int ny, int nz, const HessParams& hs, const cplx<T>* S, T* W, double* s1, double* s2) {
-  GenericDims d;
-  if (!emu_dims<T>(nx, ny, nz, true, d)) return -1;
-  const long long nzh = nz / 2 + 1;
-  auto rx = make_twiddles<T>(nx), ry = make_twiddles<T>(ny), rz = make_twiddles<T>(nz);
-  std::vector<cplx<T>> G((size_t)nx * ny * nzh), G2((size_t)nx * ny * nzh);
-  EmuGenericOps<T> ops{rx.data(), ry.data(), rz.data(), nx, ny, nz, nz / 2, (long long)nx * ny, nullptr};
-  ops.az = d.az;
-  const int rc = generic_hessian_c2r_seq(ops, d, hs, S, G.data(), G2.data(), W, 1.0 / ((double)nx * ny * nz));
-  if (s1) *s1 = ops.s1;
-  if (s2) *s2 = ops.s2;
-  return rc;
+  g.axis = axis; g.sdk = scale * dk;
+  return emu_deriv_params(nx, ny, nz, divide, kx2, ky2, kz2, spitch, g);
 }
 inline bool emu_hess_params(int nx, int ny, int nz, int a, int b, double scale, double dk_a, double dk_b, int divide, const double* kx2, const double* ky2,
                             const double* kz2, long long spitch, HessParams& g) {
-  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || a < 0 || a > b || b > 2 || spitch < nz / 2 + 1 || (divide && !(kx2 && ky2 && kz2))) return false;
   memset(&g, 0, sizeof(g));
-  g.nx = nx; g.ny = ny; g.nz = nz; g.a = a; g.b = b; g.divide = divide != 0; g.sdk2 = -scale * dk_a * dk_b;
-  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2; g.pitch = spitch;
-  return true;
+  g.a = a; g.b = b; g.sdk2 = -scale * dk_a * dk_b;
+  return emu_deriv_params(nx, ny, nz, divide, kx2, ky2, kz2, spitch, g);
+}
+// K = the component alone, W = its field: the bodies of the four exports below
+template <class P> int emu_deriv_k(int f64, const P& g, const void* S, void* K) {
+  if (f64) { EmuGenericOps<double> ops{}; return ops.materialise(g, S, K); }
+  EmuGenericOps<float> ops{};
+  return ops.materialise(g, S, K);
+}
+template <class P> int emu_deriv_c2r(int f64, const P& g, const void* S, void* W, double* s1, double* s2) {
+  return f64 ? generic_c2r_from_impl<double>(g.nx, g.ny, g.nz, g, S, (double*)W, s1, s2) : generic_c2r_from_impl<float>(g.nx, g.ny, g.nz, g, S, (float*)W, s1, s2);
 }
 template <typename T>
 int lpt2_accumulate_impl(int step, T* H, T* Tacc, T* Sacc, long long n) {
@@ -1000,43 +945,34 @@ int emu_generic_realise(int f64, int nx, int ny, int nz, const double* kx2, cons
                         const double* noise, void* W, double* s1, double* s2) {
   GenHost h;
   fill_gen(h, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, noise_mode, seed, noise);
-  return f64 ? generic_realise_impl<double>(nx, ny, nz, h.gp, (double*)W, s1, s2) : generic_realise_impl<float>(nx, ny, nz, h.gp, (float*)W, s1, s2);
+  return f64 ? generic_c2r_from_impl<double>(nx, ny, nz, h.gp, nullptr, (double*)W, s1, s2)
+             : generic_c2r_from_impl<float>(nx, ny, nz, h.gp, nullptr, (float*)W, s1, s2);
 }
-// K [nx][ny][nz/2+1] = i k_axis S (rf_core.h grad_cell over an array, as the elementwise gradient kernel): S has rows of spitch cells and
+// K [nx][ny][nz/2+1] = i k_axis S (rf_core.h grad_cell over an array, as the elementwise derivative kernel): S has rows of spitch cells and
 // holds delta(k) / k^2, or delta(k) with divide != 0 (kx2, ky2, kz2: the k^2 tables; S == K is allowed)
 int emu_gradient_k(int f64, int nx, int ny, int nz, int axis, double scale, double dk, int divide, const double* kx2, const double* ky2,
                    const double* kz2, const void* S, long long spitch, void* K) {
   GradParams g;
-  if (!emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g)) return -1;
-  if (f64) { EmuGenericOps<double> ops{}; return ops.grad_kspace(g, S, K); }
-  EmuGenericOps<float> ops{};
-  return ops.grad_kspace(g, S, K);
+  return emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g) ? emu_deriv_k(f64, g, S, K) : -1;
 }
 // the field of that component with the factor applied inside the x pass (honours emu_set_generic_threads / _tile / _cap)
 int emu_generic_gradient_c2r(int f64, int nx, int ny, int nz, int axis, double scale, double dk, int divide, const double* kx2, const double* ky2,
                              const double* kz2, const void* S, long long spitch, void* W, double* s1, double* s2) {
   GradParams g;
-  if (!emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g)) return -1;
-  return f64 ? generic_gradient_c2r_impl<double>(nx, ny, nz, g, (const cplx<double>*)S, (double*)W, s1, s2)
-             : generic_gradient_c2r_impl<float>(nx, ny, nz, g, (const cplx<float>*)S, (float*)W, s1, s2);
+  return emu_grad_params(nx, ny, nz, axis, scale, dk, divide, kx2, ky2, kz2, spitch, g) ? emu_deriv_c2r(f64, g, S, W, s1, s2) : -1;
 }
-// K [nx][ny][nz/2+1] = D_a D_b S = -scale k_a k_b S (rf_core.h hess_cell over an array, as the elementwise Hessian kernel), 0 <= a <= b <= 2;
+// K [nx][ny][nz/2+1] = D_a D_b S = -scale k_a k_b S (rf_core.h hess_cell over an array, as the elementwise derivative kernel), 0 <= a <= b <= 2;
 // S, spitch, divide and S == K as emu_gradient_k
 int emu_hessian_k(int f64, int nx, int ny, int nz, int a, int b, double scale, double dk_a, double dk_b, int divide, const double* kx2,
                   const double* ky2, const double* kz2, const void* S, long long spitch, void* K) {
   HessParams g;
-  if (!emu_hess_params(nx, ny, nz, a, b, scale, dk_a, dk_b, divide, kx2, ky2, kz2, spitch, g)) return -1;
-  if (f64) { EmuGenericOps<double> ops{}; return ops.hess_kspace(g, S, K); }
-  EmuGenericOps<float> ops{};
-  return ops.hess_kspace(g, S, K);
+  return emu_hess_params(nx, ny, nz, a, b, scale, dk_a, dk_b, divide, kx2, ky2, kz2, spitch, g) ? emu_deriv_k(f64, g, S, K) : -1;
 }
 // the field of that component with the factor applied inside the x pass (honours emu_set_generic_threads / _tile / _cap)
 int emu_generic_hessian_c2r(int f64, int nx, int ny, int nz, int a, int b, double scale, double dk_a, double dk_b, int divide, const double* kx2,
                             const double* ky2, const double* kz2, const void* S, long long spitch, void* W, double* s1, double* s2) {
   HessParams g;
-  if (!emu_hess_params(nx, ny, nz, a, b, scale, dk_a, dk_b, divide, kx2, ky2, kz2, spitch, g)) return -1;
-  return f64 ? generic_hessian_c2r_impl<double>(nx, ny, nz, g, (const cplx<double>*)S, (double*)W, s1, s2)
-             : generic_hessian_c2r_impl<float>(nx, ny, nz, g, (const cplx<float>*)S, (float*)W, s1, s2);
+  return emu_hess_params(nx, ny, nz, a, b, scale, dk_a, dk_b, divide, kx2, ky2, kz2, spitch, g) ? emu_deriv_c2r(f64, g, S, W, s1, s2) : -1;
 }
 // one step (0 .. 4: FIRST, DIAG2, DIAG3, OFF, LAST) of the 2LPT source's sweep over n elements (rf_core.h lpt2_step, the function the
 // kernel calls per element): H the component, T and S the accumulators; LAST leaves the source in H

@@ -759,37 +759,30 @@ struct HipGenericOps {
     RF_HIP(launch_generic_axis(p->f64, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
     return 0;
   }
-  // the x pass with the generator as its source (rf_generic.h generic_realise_seq)
-  int axis_gen(const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+  // the x pass from a descriptor (rf_generic.h generic_c2r_from_seq): the generator (GenParams; no array), or one component of the
+  // gradient / Hessian of the array S (GradParams / HessParams) with its factor applied to the cells the pass loads
+  int axis_from(const GenParams& gp, const void*, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
     RF_HIP(launch_generic_axis_gen(p->f64, gp, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
     return 0;
   }
-  // ... and, for a plan whose x axis is split, the generation as a launch of its own into a scratch array (rf_kernel_ms: entry 4)
-  int gen_kspace(const GenParams& gp, void* K) {
+  template <class P>
+  int axis_from(const P& dp, const void* S, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
+    RF_HIP(launch_generic_axis_deriv(p->f64, dp, S, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
+    return 0;
+  }
+  // ... and, for a plan whose x axis is split, the same cells by a launch of its own into a scratch array (rf_kernel_ms: entry 4)
+  int materialised() {
+    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
+    return 0;
+  }
+  int materialise(const GenParams& gp, const void*, void* K) {
     RF_HIP(launch_gen_kspace(p->f64, K, gp, s));
-    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
-    return 0;
+    return materialised();
   }
-  // the x pass of a gradient component with i k_a applied to the cells it loads (rf_generic.h generic_gradient_c2r_seq), and the
-  // component as a sweep of its own for a plan whose x axis is split
-  int axis_grad(const GradParams& gr, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    RF_HIP(launch_generic_axis_grad(p->f64, gr, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
-    return 0;
-  }
-  int grad_kspace(const GradParams& gr, const void* S, void* K) {
-    RF_HIP(launch_gradient(p->f64, S, K, gr, s));
-    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }       // (rf_kernel_ms: entry 4, as the generation launch)
-    return 0;
-  }
-  // ... and of a Hessian component (generic_hessian_c2r_seq)
-  int axis_hess(const HessParams& hs, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    RF_HIP(launch_generic_axis_hess(p->f64, hs, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
-    return 0;
-  }
-  int hess_kspace(const HessParams& hs, const void* S, void* K) {
-    RF_HIP(launch_hessian(p->f64, S, K, hs, s));
-    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
-    return 0;
+  template <class P>
+  int materialise(const P& dp, const void* S, void* K) {
+    RF_HIP(launch_derivative(p->f64, S, K, dp, s));
+    return materialised();
   }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     if (int rc = enter(which)) return rc;
@@ -819,14 +812,16 @@ int ensure_g2(rf_plan* p) {
 
 // non-power-of-two grid: API-layout half spectrum K -> x pass into G -> y pass -> contiguous c2r pass into W (rf_generic.h
 // generic_c2r_seq: axes too long for one line of the LDS take the four-step form through the scratch arrays), (sum, sumsq) into stats_out.
-// gen != null (K is ignored): the x pass generates the half spectrum instead of loading it (RF_FLAG_FUSED_GENERIC_GENERATION,
-// generic_realise_seq).  timed: events ev[1] .. ev[3] behind the x pass, the y pass and the contiguous pass.
-int generic_c2r(rf_plan* p, const void* K, double* stats_out, bool timed = false, const GenParams* gen = nullptr) {
+// from != null: the x pass takes its cells from that descriptor instead of loading K (generic_c2r_from_seq) -- GenParams: it generates
+// the half spectrum (RF_FLAG_FUSED_GENERIC_GENERATION; K is ignored); GradParams / HessParams: K is the array whose gradient / Hessian
+// component is transformed, and is only read.  timed: events ev[1] .. ev[3] behind the x pass, the y pass and the contiguous pass.
+template <class From>
+int generic_c2r(rf_plan* p, const void* K, double* stats_out, bool timed, const From* from) {
   if (int rc = ensure_g(p)) return rc;
   if (int rc = ensure_g2(p)) return rc;
   HipGenericOps ops{p, p->stream, timed};
   const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-  if (gen) { if (int rc = generic_realise_seq(ops, p->gdims, *gen, p->G, p->G2, p->W, scale)) return rc; }
+  if (from) { if (int rc = generic_c2r_from_seq(ops, p->gdims, *from, K, p->G, p->G2, p->W, scale)) return rc; }
   else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G, p->G2, p->W, scale)) return rc;
   if (int rc = ops.enter(3)) return rc;
   RF_HIP(launch_reduce_partials(p->partials, p->npartials, stats_out, p->partials + 2 * p->npartials, p->stream));
@@ -1241,7 +1236,7 @@ int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
 
 int rf_plan_set_flag(rf_plan* p, int flag, int value) {
   RF_REQUIRE(p, "null plan");
-  if (flag == RF_FLAG_FUSED_GENERIC_GENERATION) {  // the x pass generates the half spectrum it transforms (rf_generic.h generic_realise_seq)
+  if (flag == RF_FLAG_FUSED_GENERIC_GENERATION) {  // the x pass generates the half spectrum it transforms (rf_generic.h generic_c2r_from_seq)
     RF_REQUIRE(p->generic && !p->unpacked && p->nranks == 1,
                "RF_FLAG_FUSED_GENERIC_GENERATION is for packed single-rank plans on the generic kernels (shapes that are not powers of two): "
                "the tiled kernels always generate inside their x pass");
@@ -1882,8 +1877,24 @@ int rf_load_potential(rf_plan* p, double scale) {
 
 }  // extern "C"
 namespace rfc {
-// what both gradient calls refuse, and the parameters of the component (rf_core.h GradParams): the source is the stored potential
-// (rows of ppitch cells) or the plan's k-space array in divide mode
+// What the gradient and the Hessian calls share once each has refused what only it refuses: the source must be there -- the stored
+// potential or the second-order one (rows of ppitch cells), or the plan's k-space array in divide mode -- and the fields that both
+// parameter structs have (rf_core.h GradParams, HessParams)
+template <class P>
+int derivative_source(rf_plan* p, int source, P& g, const void*& S) {
+  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
+  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L && p->p2_valid, "no second-order potential: call rf_lpt2_potential first");
+  else {
+    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+    RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  }
+  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
+  g.divide = source == RF_GRAD_FROM_KSPACE;
+  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
+  g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
+  S = g.divide ? p->K : (source == RF_GRAD_FROM_POTENTIAL2 ? p->L : p->P);
+  return 0;
+}
 int gradient_params(rf_plan* p, int axis, double scale, double dk, int source, GradParams& g, const void*& S) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
@@ -1891,23 +1902,11 @@ int gradient_params(rf_plan* p, int axis, double scale, double dk, int source, G
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
   RF_REQUIRE(source == RF_GRAD_FROM_POTENTIAL || source == RF_GRAD_FROM_KSPACE || source == RF_GRAD_FROM_POTENTIAL2,
              "source must be RF_GRAD_FROM_POTENTIAL, RF_GRAD_FROM_KSPACE or RF_GRAD_FROM_POTENTIAL2");
-  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
-  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L && p->p2_valid, "no second-order potential: call rf_lpt2_potential first");
-  else {
-    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
-    RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
-  }
   memset(&g, 0, sizeof(g));
-  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
   g.axis = axis;
-  g.divide = source == RF_GRAD_FROM_KSPACE;
   g.sdk = scale * dk;
-  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
-  g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
-  S = g.divide ? p->K : (source == RF_GRAD_FROM_POTENTIAL2 ? p->L : p->P);
-  return 0;
+  return derivative_source(p, source, g, S);
 }
-// the same for the Hessian calls (rf_core.h HessParams)
 int hessian_params(rf_plan* p, int a, int b, double scale, double dk_a, double dk_b, int source, HessParams& g, const void*& S) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
@@ -1915,19 +1914,45 @@ int hessian_params(rf_plan* p, int a, int b, double scale, double dk_a, double d
   RF_REQUIRE(a >= 0 && a <= 2 && b >= 0 && b <= 2, "axes must be 0, 1 or 2");
   RF_REQUIRE(a <= b, "axes must be given as a <= b");
   RF_REQUIRE(source == RF_GRAD_FROM_POTENTIAL || source == RF_GRAD_FROM_KSPACE, "source must be RF_GRAD_FROM_POTENTIAL or RF_GRAD_FROM_KSPACE");
-  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
-  else {
-    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
-    RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
-  }
   memset(&g, 0, sizeof(g));
-  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
   g.a = a; g.b = b;
-  g.divide = source == RF_GRAD_FROM_KSPACE;
   g.sdk2 = -scale * dk_a * dk_b;
-  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
-  g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
-  S = g.divide ? p->K : p->P;
+  return derivative_source(p, source, g, S);
+}
+// K = the component (rf_load_gradient / rf_load_hessian)
+template <class P>
+int load_derivative(rf_plan* p, const P& g, const void* S) {
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_k(p)) return rc;
+  RF_HIP(launch_derivative(p->f64, S, p->K, g, p->stream));
+  p->k_valid = true;
+  p->aux_valid = false;
+  return 0;
+}
+// the component as a real field (rf_execute_gradient_c2r / rf_execute_hessian_c2r).  RF_GRAD_FROM_KSPACE consumes K on either kind of
+// plan: a tiled plan overwrites it, and the generic form, which only reads it, keeps to the same contract.
+template <class P>
+int execute_derivative_c2r(rf_plan* p, const P& g, const void* S, int source) {
+  RF_HIP(hipSetDevice(p->device));
+  if (!p->generic) {    // the component as a sweep of its own, then the plan's inverse transform
+    if (int rc = load_derivative(p, g, S)) return rc;
+    const int rc = rf_execute_c2r(p);
+    if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
+    return rc;
+  }
+  // generic plans: the factor is applied by the x pass to the cells it loads (rf_generic.h generic_c2r_from_seq); K, P are only read
+  p->slab_timed = 0;
+  p->slab_merged = 0;
+  p->repair_timed = false;
+  p->timed = true;                                  // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
+  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  if (int rc = generic_c2r(p, S, p->stats, true, &g)) return rc;
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  p->cur = p->W;
+  p->stats_slot = 0;
+  p->real_valid = true;
+  p->stats_valid = true;
+  if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
   return 0;
 }
 // the accumulators of rf_lpt2_source, later the second-order potential
@@ -1957,90 +1982,28 @@ int rf_load_gradient(rf_plan* p, int axis, double scale, double dk, int source) 
   GradParams g;
   const void* S = nullptr;
   if (int rc = gradient_params(p, axis, scale, dk, source, g, S)) return rc;
-  RF_HIP(hipSetDevice(p->device));
-  if (int rc = ensure_k(p)) return rc;
-  RF_HIP(launch_gradient(p->f64, S, p->K, g, p->stream));
-  p->k_valid = true;
-  p->aux_valid = false;
-  return 0;
+  return load_derivative(p, g, S);
 }
 
 int rf_execute_gradient_c2r(rf_plan* p, int axis, double scale, double dk, int source) {
   GradParams g;
   const void* S = nullptr;
   if (int rc = gradient_params(p, axis, scale, dk, source, g, S)) return rc;
-  RF_HIP(hipSetDevice(p->device));
-  if (!p->generic) {    // the component as a sweep of its own, then the plan's inverse transform
-    if (int rc = rf_load_gradient(p, axis, scale, dk, source)) return rc;
-    const int rc = rf_execute_c2r(p);
-    if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;     // (K held delta(k) and was consumed; the fused form leaves it: one contract)
-    return rc;
-  }
-  // generic plans: i k_a is applied by the x pass to the cells it loads (rf_generic.h generic_gradient_c2r_seq); K, P are only read
-  if (int rc = ensure_g(p)) return rc;
-  if (int rc = ensure_g2(p)) return rc;
-  p->slab_timed = 0;
-  p->slab_merged = 0;
-  p->repair_timed = false;
-  p->timed = true;                                  // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  HipGenericOps ops{p, p->stream, true};
-  const double norm = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-  if (int rc = generic_gradient_c2r_seq(ops, p->gdims, g, S, p->G, p->G2, p->W, norm)) return rc;
-  if (int rc = ops.enter(3)) return rc;
-  RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->cur = p->W;
-  p->stats_slot = 0;
-  p->real_valid = true;
-  p->stats_valid = true;
-  if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
-  return 0;
+  return execute_derivative_c2r(p, g, S, source);
 }
 
 int rf_load_hessian(rf_plan* p, int a, int b, double scale, double dk_a, double dk_b, int source) {
   HessParams g;
   const void* S = nullptr;
   if (int rc = hessian_params(p, a, b, scale, dk_a, dk_b, source, g, S)) return rc;
-  RF_HIP(hipSetDevice(p->device));
-  if (int rc = ensure_k(p)) return rc;
-  RF_HIP(launch_hessian(p->f64, S, p->K, g, p->stream));
-  p->k_valid = true;
-  p->aux_valid = false;
-  return 0;
+  return load_derivative(p, g, S);
 }
 
 int rf_execute_hessian_c2r(rf_plan* p, int a, int b, double scale, double dk_a, double dk_b, int source) {
   HessParams g;
   const void* S = nullptr;
   if (int rc = hessian_params(p, a, b, scale, dk_a, dk_b, source, g, S)) return rc;
-  RF_HIP(hipSetDevice(p->device));
-  if (!p->generic) {    // the component as a sweep of its own, then the plan's inverse transform
-    if (int rc = rf_load_hessian(p, a, b, scale, dk_a, dk_b, source)) return rc;
-    const int rc = rf_execute_c2r(p);
-    if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;     // (as rf_execute_gradient_c2r: one contract for both kinds of plan)
-    return rc;
-  }
-  // generic plans: the factor is applied by the x pass to the cells it loads (rf_generic.h generic_hessian_c2r_seq); K, P are only read
-  if (int rc = ensure_g(p)) return rc;
-  if (int rc = ensure_g2(p)) return rc;
-  p->slab_timed = 0;
-  p->slab_merged = 0;
-  p->repair_timed = false;
-  p->timed = true;
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  HipGenericOps ops{p, p->stream, true};
-  const double norm = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-  if (int rc = generic_hessian_c2r_seq(ops, p->gdims, g, S, p->G, p->G2, p->W, norm)) return rc;
-  if (int rc = ops.enter(3)) return rc;
-  RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->cur = p->W;
-  p->stats_slot = 0;
-  p->real_valid = true;
-  p->stats_valid = true;
-  if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
-  return 0;
+  return execute_derivative_c2r(p, g, S, source);
 }
 
 // S(x) = sum_{a<b} (H_aa H_bb - H_ab^2) of the stored potential (rf_core.h lpt2_step): six Hessian transforms with scale 1 in the order

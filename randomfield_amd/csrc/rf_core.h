@@ -455,6 +455,14 @@ RF_HD cplx<T> hess_cell(const HessParams& g, cplx<T> v, int ix, int iy, int iz) 
   return mk<T>(f * v.x, f * v.y);
 }
 
+// Both cell functions under one name, chosen by the parameter struct, for the code that is written once for the two (the elementwise
+// kernel, the x pass of rf_generic.h, their launchers and the emulator) ...
+template <typename T> RF_HD cplx<T> deriv_cell(const GradParams& g, cplx<T> v, int ix, int iy, int iz) { return grad_cell<T>(g, v, ix, iy, iz); }
+template <typename T> RF_HD cplx<T> deriv_cell(const HessParams& g, cplx<T> v, int ix, int iy, int iz) { return hess_cell<T>(g, v, ix, iy, iz); }
+// ... and what every launch checks first: the axes name a component, and a row of the source holds at least the nz/2 + 1 cells read
+RF_HD bool deriv_valid(const GradParams& g) { return g.axis >= 0 && g.axis <= 2 && g.pitch >= g.nz / 2 + 1; }
+RF_HD bool deriv_valid(const HessParams& g) { return g.a >= 0 && g.a <= g.b && g.b <= 2 && g.pitch >= g.nz / 2 + 1; }
+
 // The real-space sweep that turns the six components into S = sum_{a<b} (H_aa H_bb - H_ab^2), one step per component h in the fixed
 // order xx, yy, zz, xy, xz, yz; t, s: the accumulators.  Explicit fma: host and device round the same number of times.
 //   FIRST  t = h                       DIAG2  s = t h; t = t + h            DIAG3  s = fma(t, h, s)

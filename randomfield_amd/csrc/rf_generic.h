@@ -372,38 +372,22 @@ template <typename T> struct GenericGenSource {
   RF_HD cplx<T> at(long long l, int e) const { return gen_cell<T>(gp, seed, e, (int)(l / nzh), (int)(l % nzh)); }
 };
 
-//   GenericGradSource: an array seen through grad_cell (rf_core.h) -- the x pass of one component of the potential's gradient.  Line
-//   l = iy * (nz/2 + 1) + iz of the half spectrum [nx][ny][nz/2+1], element e = cell (ix = e, iy, iz) of the source (the stored
-//   potential, whose rows may be padded, or the k-space array in divide mode: g.pitch cells per row either way), times i k_a: the very
-//   value the elementwise gradient kernel would have stored and the pass loaded.
-template <typename T> struct GenericGradSource {
+//   GenericDerivSource: an array seen through deriv_cell (rf_core.h; P = GradParams or HessParams) -- the x pass of one component of the
+//   potential's gradient or Hessian.  Line l = iy * (nz/2 + 1) + iz of the half spectrum [nx][ny][nz/2+1], element e = cell (ix = e, iy,
+//   iz) of the source (the stored potential, whose rows may be padded, or the k-space array in divide mode: g.pitch cells per row either
+//   way), times the component's factor: the very value the elementwise derivative kernel would have stored and the pass loaded.
+template <typename T, class P> struct GenericDerivSource {
   enum { INFLIGHT = 4 };
   const cplx<T>* src;
-  GradParams g;
+  P g;
   long long nzh, stride, base;
   int iy, iz;
-  RF_HD GenericGradSource(const GradParams& gp, const cplx<T>* s) : src(s), g(gp), nzh(gp.nz / 2 + 1), stride((long long)gp.ny * gp.pitch), base(0), iy(0), iz(0) {}
+  RF_HD GenericDerivSource(const P& dp, const cplx<T>* s) : src(s), g(dp), nzh(dp.nz / 2 + 1), stride((long long)dp.ny * dp.pitch), base(0), iy(0), iz(0) {}
   RF_HD void line(long long l, long long) { iy = (int)(l / nzh); iz = (int)(l % nzh); base = (long long)iy * g.pitch + iz; }
-  RF_HD cplx<T> at(int e) const { return grad_cell<T>(g, src[base + e * stride], e, iy, iz); }
+  RF_HD cplx<T> at(int e) const { return deriv_cell<T>(g, src[base + e * stride], e, iy, iz); }
   RF_HD cplx<T> at(long long l, int e) const {
     const int y = (int)(l / nzh), z = (int)(l % nzh);
-    return grad_cell<T>(g, src[(long long)y * g.pitch + z + e * stride], e, y, z);
-  }
-};
-
-//   GenericHessSource: the same array seen through hess_cell (rf_core.h) -- the x pass of one component of the potential's Hessian.
-template <typename T> struct GenericHessSource {
-  enum { INFLIGHT = 4 };
-  const cplx<T>* src;
-  HessParams g;
-  long long nzh, stride, base;
-  int iy, iz;
-  RF_HD GenericHessSource(const HessParams& hp, const cplx<T>* s) : src(s), g(hp), nzh(hp.nz / 2 + 1), stride((long long)hp.ny * hp.pitch), base(0), iy(0), iz(0) {}
-  RF_HD void line(long long l, long long) { iy = (int)(l / nzh); iz = (int)(l % nzh); base = (long long)iy * g.pitch + iz; }
-  RF_HD cplx<T> at(int e) const { return hess_cell<T>(g, src[base + e * stride], e, iy, iz); }
-  RF_HD cplx<T> at(long long l, int e) const {
-    const int y = (int)(l / nzh), z = (int)(l % nzh);
-    return hess_cell<T>(g, src[(long long)y * g.pitch + z + e * stride], e, y, z);
+    return deriv_cell<T>(g, src[(long long)y * g.pitch + z + e * stride], e, y, z);
   }
 };
 
@@ -499,24 +483,7 @@ RF_HD void generic_axis_gen_block(const GenParams& gp, uint64_t seed, cplx<T>* d
   generic_axis_block_from<T>(GenericGenSource<T>(gp, seed), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
                              tw_lds);
 }
-
-// the x pass of a gradient component with i k_a applied on the way in (GenericGradSource): same LDS positions, stages and stores
-template <typename T, class Sync>
-RF_HD void generic_axis_grad_block(const GradParams& gp, const cplx<T>* src, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
-                                   long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
-                                   cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
-  generic_axis_block_from<T>(GenericGradSource<T>(gp, src), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
-                             tw_lds);
-}
-
-// ... and of a Hessian component, D_a D_b applied on the way in (GenericHessSource)
-template <typename T, class Sync>
-RF_HD void generic_axis_hess_block(const HessParams& hp, const cplx<T>* src, cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner,
-                                   long long outer, long long nlines, int TC, const cplx<T>* root, int sign, T scale,
-                                   cplx<T>* lds, long long blk, int tid, int nth, Sync sync, int tw_lds = 0) {
-  generic_axis_block_from<T>(GenericHessSource<T>(hp, src), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, lds, blk, tid, nth, sync,
-                             tw_lds);
-}
+// (a component of the gradient or the Hessian: generic_axis_block_from with a GenericDerivSource, no wrapper)
 
 // Pitch of the LDS image of the contiguous passes (element e of row c at [e * pitch + c]).  Their threads walk ALONG a row on load and
 // store (that is what keeps the global accesses whole lines), i.e. with a stride of `pitch` elements in LDS: at pitch TR = 8 that is
@@ -830,9 +797,10 @@ RF_HD void generic_tangle_at(const cplx<T>* Z, cplx<T>* G, int M, const cplx<T>*
 //   row_c2r(G, W, scale) / row_r2c(W, G)                                   the fused contiguous passes of rows that fit the LDS
 //   untangle(G, Z) / tangle(Z, G) / moments(W)                             the pieces of the contiguous passes for long rows
 //   copy(dst, src, bytes)
-//   axis_gen(gen, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() whose source is the generator (generic_axis_gen_block)
-//   gen_kspace(gen, K)                                                     rows K,T,R,S into an API-layout array (generic_realise_seq only;
-//                                                                          `gen` is whatever the Ops' generator takes: the sequence hands it on)
+//   axis_from(from, S, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() whose source is the descriptor `from` over the
+//                                                                          array S (generic_axis_block_from with from's Source)
+//   materialise(from, S, K)                                                the same cells into an API-layout array
+//                                                                          (both for generic_c2r_from_seq only, which hands `from` and S on)
 // ---------------------------------------------------------------------------
 // Lines of a strided pass that go into one workgroup together (neighbours in memory: tc lines = segments of tc elements): the widest
 // tile up to 16 whose image(s) and stage table fit a CU's LDS (rf_k_generic.hip strided_shape launches exactly this).  Below 4 lines
@@ -863,7 +831,7 @@ int generic_long_pass(Ops& ops, const void* src, void* tmp, void* dst, const Gen
 }
 // half spectrum K [nx][ny][nz/2+1] -> dense reals W [nx][ny][nz] (np.fft.irfftn with `scale`); G, G2: scratch arrays of K's size (G2 is
 // touched only when an axis is long); the (sum, sumsq) partials are left by row_c2r / moments
-// (generic_c2r_after_x: everything behind the x pass, whose output is in G -- shared with generic_realise_seq)
+// (generic_c2r_after_x: everything behind the x pass, whose output is in G -- shared with generic_c2r_from_seq)
 template <class Ops>
 int generic_c2r_after_x(Ops& ops, const GenericDims& d, void* G, void* G2, void* W, double scale) {
   const long long nzh = d.nz / 2 + 1, M = d.nz / 2;
@@ -884,53 +852,24 @@ int generic_c2r_seq(Ops& ops, const GenericDims& d, const void* K, void* G, void
   else if (int rc = ops.axis(K, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
   return generic_c2r_after_x(ops, d, G, G2, W, scale);
 }
-// A realisation without its half spectrum in memory: generic_c2r_seq whose first pass GENERATES the cells it transforms
-// (GenericGenSource) instead of loading what a generation launch stored -- 5 sweeps of the half spectrum instead of 7, and no array K.
-// Same values in the same LDS positions through the same stages: the field and its moments are those of gen_kspace + generic_c2r_seq,
-// bit for bit.  Only an x axis that is ONE line of the LDS is fused (!d.lx.split()): the four-step form reads its input twice over
-// (sub-lines, then their transposes), so for such a plan the spectrum is generated into the scratch array G2 and the unfused
-// sequence runs from there.  G, G2: as generic_c2r_seq (G2 is touched only when an axis is long).
-template <class Ops, class Gen>
-int generic_realise_seq(Ops& ops, const GenericDims& d, const Gen& gen, void* G, void* G2, void* W, double scale) {
+// generic_c2r_seq of a half spectrum that is not in memory: the first pass forms the cells it transforms from the descriptor `from`
+// instead of loading what a launch of its own stored -- no sweep for that launch, and no array for its output.  `from` is
+//   GenParams (rf_core.h; S unused): a realisation, the pass GENERATES its cells (GenericGenSource) -- 5 sweeps of the half spectrum
+//     instead of 7;
+//   GradParams / HessParams: one component of the gradient / Hessian of the potential as a real field, the pass applies i k_a / D_a D_b to
+//     the cells of S it loads (GenericDerivSource; S: the stored potential, or k space in divide mode) and leaves S untouched.
+// Same values in the same LDS positions through the same stages: the field and its moments are those of materialise +
+// generic_c2r_seq, bit for bit.  Only an x axis that is ONE line of the LDS is fused (!d.lx.split()): the four-step form reads its
+// input twice over (sub-lines, then their transposes), so for such a plan the cells are materialised into the scratch array G2 and
+// the unfused sequence runs from there.  G, G2: as generic_c2r_seq (G2 is touched only when an axis is long).
+template <class Ops, class From>
+int generic_c2r_from_seq(Ops& ops, const GenericDims& d, const From& from, const void* S, void* G, void* G2, void* W, double scale) {
   const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
   if (d.lx.split()) {
-    if (int rc = ops.gen_kspace(gen, G2)) return rc;
+    if (int rc = ops.materialise(from, S, G2)) return rc;
     return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
   }
-  if (int rc = ops.axis_gen(gen, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
-  return generic_c2r_after_x(ops, d, G, G2, W, scale);
-}
-// One component of the gradient of the potential as a real field: generic_c2r_seq of i k_a S (S: the stored potential, or k space in
-// divide mode -- `grad` says which, rf_core.h GradParams) whose x pass applies the factor to the cells it loads (GenericGradSource)
-// instead of loading what the elementwise gradient kernel stored: no sweep of its own, S is left untouched.  Same values in the same
-// LDS positions through the same stages: the field and its moments are those of grad_kspace + generic_c2r_seq, bit for bit.  An x axis
-// in the four-step form reads its input twice over, so for such a plan the component goes into the scratch array G2 and the unfused
-// sequence runs from there (as generic_realise_seq).  Ops provides, besides the above:
-//   axis_grad(grad, S, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() through GenericGradSource (generic_axis_grad_block)
-//   grad_kspace(grad, S, K)                                                          i k_a S into an API-layout array
-template <class Ops>
-int generic_gradient_c2r_seq(Ops& ops, const GenericDims& d, const GradParams& grad, const void* S, void* G, void* G2, void* W, double scale) {
-  const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
-  if (d.lx.split()) {
-    if (int rc = ops.grad_kspace(grad, S, G2)) return rc;
-    return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
-  }
-  if (int rc = ops.axis_grad(grad, S, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
-  return generic_c2r_after_x(ops, d, G, G2, W, scale);
-}
-// One component of the Hessian of the potential as a real field: generic_gradient_c2r_seq with hess_cell for grad_cell (rf_core.h
-// HessParams, GenericHessSource) -- the field and its moments are those of hess_kspace + generic_c2r_seq, bit for bit; an x axis in the
-// four-step form takes the same fallback through G2.  Ops provides:
-//   axis_hess(hess, S, dst, ax, stride, inner, outer, nlines, which, sign, scale)   axis() through GenericHessSource (generic_axis_hess_block)
-//   hess_kspace(hess, S, K)                                                          D_a D_b S into an API-layout array
-template <class Ops>
-int generic_hessian_c2r_seq(Ops& ops, const GenericDims& d, const HessParams& hess, const void* S, void* G, void* G2, void* W, double scale) {
-  const long long Lx = (long long)d.ny * (d.nz / 2 + 1);
-  if (d.lx.split()) {
-    if (int rc = ops.hess_kspace(hess, S, G2)) return rc;
-    return generic_c2r_seq(ops, d, G2, G, G2, W, scale);
-  }
-  if (int rc = ops.axis_hess(hess, S, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
+  if (int rc = ops.axis_from(from, S, G, d.ax, Lx, Lx, 0, Lx, 0, +1, 1.0)) return rc;
   return generic_c2r_after_x(ops, d, G, G2, W, scale);
 }
 // dense reals W -> half spectrum K (np.fft.rfftn); W is left untouched

@@ -27,24 +27,15 @@ __global__ __launch_bounds__(1024) void generic_axis_gen_kernel(GenParams gp, cp
                             (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
 }
 
-// the x pass of one gradient component: the cells of `src` times i k_a on the way in (rf_generic.h GenericGradSource); src != dst
-template <typename T>
-__global__ __launch_bounds__(1024) void generic_axis_grad_kernel(GradParams gp, const cplx<T>* __restrict__ src, cplx<T>* __restrict__ dst, GenericAxis ax,
-                                                               long long stride, long long inner, long long outer, long long nlines, int TC,
-                                                               const cplx<T>* __restrict__ root, int sign, T scale, int tw_lds) {
+// the x pass of one derivative component (P = GradParams: i k_a, HessParams: -k_a k_b): the cells of `src` times that factor on the way
+// in (rf_generic.h GenericDerivSource); src != dst
+template <typename T, class P>
+__global__ __launch_bounds__(1024) void generic_axis_deriv_kernel(P dp, const cplx<T>* __restrict__ src, cplx<T>* __restrict__ dst, GenericAxis ax,
+                                                                long long stride, long long inner, long long outer, long long nlines, int TC,
+                                                                const cplx<T>* __restrict__ root, int sign, T scale, int tw_lds) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  generic_axis_grad_block<T>(gp, src, dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, reinterpret_cast<cplx<T>*>(lds_raw),
-                             (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
-}
-
-// the x pass of one Hessian component: the cells of `src` times -k_a k_b on the way in (rf_generic.h GenericHessSource); src != dst
-template <typename T>
-__global__ __launch_bounds__(1024) void generic_axis_hess_kernel(HessParams hp, const cplx<T>* __restrict__ src, cplx<T>* __restrict__ dst, GenericAxis ax,
-                                                               long long stride, long long inner, long long outer, long long nlines, int TC,
-                                                               const cplx<T>* __restrict__ root, int sign, T scale, int tw_lds) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  generic_axis_hess_block<T>(hp, src, dst, ax, stride, inner, outer, nlines, TC, root, sign, scale, reinterpret_cast<cplx<T>*>(lds_raw),
-                             (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
+  generic_axis_block_from<T>(GenericDerivSource<T, P>(dp, src), dst, ax, stride, inner, outer, nlines, TC, root, sign, scale,
+                             reinterpret_cast<cplx<T>*>(lds_raw), (long long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, BlockSync(), tw_lds);
 }
 
 template <typename T>
@@ -149,10 +140,13 @@ hipError_t lines_t(const void* src, void* dst, const GenericLines& L, const void
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t axis_t(const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
-                  long long nlines, const void* root, int sign, double scale, hipStream_t s) {
-  // lines that are neighbours in memory (inner > 1) are transformed 16 at a time: 128-byte (float32) segments
+// One strided pass, whatever its source: KERNEL(lead..., dst, ax, stride, inner, outer, nlines, tc, root, sign, scale, tw_lds).  Lines that
+// are neighbours in memory (inner > 1) are transformed 16 at a time: 128-byte (float32) segments.  The LDS attribute latch is one per
+// kernel (a static of this template's instantiation); it is set by the first call, which is never inside a capture: generic plans are
+// not graph-captured.
+template <auto KERNEL, typename T, class... Lead>
+hipError_t launch_axis(cplx<T>* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, const void* root,
+                       int sign, double scale, hipStream_t s, Lead... lead) {
   const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
   const int tc = sh.tc;
   const long long nblk = (nlines + tc - 1) / tc;
@@ -162,73 +156,31 @@ hipError_t axis_t(const void* src, void* dst, const GenericAxis& ax, long long s
   if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
   static LdsAttrLatch latch;
   if (lds > 65536)
-    if (hipError_t e = latch.ensure((const void*)generic_axis_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
-  hipLaunchKernelGGL(generic_axis_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride,
-                     inner, outer, nlines, tc, (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
+    if (hipError_t e = latch.ensure((const void*)KERNEL, GENERIC_LDS_MAX); e != hipSuccess) return e;
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)nblk), dim3(sh.threads), lds, s, lead..., dst, ax, stride, inner, outer, nlines, tc, (const cplx<T>*)root, sign,
+                     (T)scale, sh.tw_lds);
   return hipGetLastError();
 }
 
-// the same shape and LDS attribute latch as axis_t (the attribute is set by the first call, which is never inside a capture: generic
-// plans are not graph-captured)
+template <typename T>
+hipError_t axis_t(const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
+                  long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return launch_axis<generic_axis_kernel<T>, T>((cplx<T>*)dst, ax, stride, inner, outer, nlines, root, sign, scale, s, (const cplx<T>*)src);
+}
+
 template <typename T>
 hipError_t axis_gen_t(const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
                       long long nlines, const void* root, int sign, double scale, hipStream_t s) {
   if (ax.n != gp.nx || nlines != (long long)gp.ny * (gp.nz / 2 + 1)) return hipErrorInvalidValue;      // lines of the half spectrum along x, nothing else
-  const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
-  const int tc = sh.tc;
-  const long long nblk = (nlines + tc - 1) / tc;
-  if (nblk <= 0) return hipSuccess;
-  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  const size_t lds = sh.lds;
-  if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
-  static LdsAttrLatch latch;
-  if (lds > 65536)
-    if (hipError_t e = latch.ensure((const void*)generic_axis_gen_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
-  hipLaunchKernelGGL(generic_axis_gen_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, gp, (cplx<T>*)dst, ax, stride, inner, outer, nlines, tc,
-                     (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
-  return hipGetLastError();
+  return launch_axis<generic_axis_gen_kernel<T>, T>((cplx<T>*)dst, ax, stride, inner, outer, nlines, root, sign, scale, s, gp);
 }
 
-// the same shape and LDS attribute latch again
-template <typename T>
-hipError_t axis_grad_t(const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
-                       long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+template <typename T, class P>
+hipError_t axis_deriv_t(const P& dp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
+                        long long nlines, const void* root, int sign, double scale, hipStream_t s) {
   // lines of the half spectrum along x, out of place, nothing else
-  if (ax.n != gp.nx || nlines != (long long)gp.ny * (gp.nz / 2 + 1) || gp.pitch < gp.nz / 2 + 1 || gp.axis < 0 || gp.axis > 2 || src == dst) return hipErrorInvalidValue;
-  const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
-  const int tc = sh.tc;
-  const long long nblk = (nlines + tc - 1) / tc;
-  if (nblk <= 0) return hipSuccess;
-  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  const size_t lds = sh.lds;
-  if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
-  static LdsAttrLatch latch;
-  if (lds > 65536)
-    if (hipError_t e = latch.ensure((const void*)generic_axis_grad_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
-  hipLaunchKernelGGL(generic_axis_grad_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, gp, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner,
-                     outer, nlines, tc, (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
-  return hipGetLastError();
-}
-
-// ... and once more for the Hessian's x pass
-template <typename T>
-hipError_t axis_hess_t(const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer,
-                       long long nlines, const void* root, int sign, double scale, hipStream_t s) {
-  if (ax.n != hp.nx || nlines != (long long)hp.ny * (hp.nz / 2 + 1) || hp.pitch < hp.nz / 2 + 1 || hp.a < 0 || hp.a > hp.b || hp.b > 2 || src == dst)
-    return hipErrorInvalidValue;
-  const StridedShape sh = strided_shape(ax, (int)sizeof(cplx<T>), inner > 1);
-  const int tc = sh.tc;
-  const long long nblk = (nlines + tc - 1) / tc;
-  if (nblk <= 0) return hipSuccess;
-  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  const size_t lds = sh.lds;
-  if (lds > (size_t)GENERIC_LDS_MAX) return hipErrorInvalidValue;
-  static LdsAttrLatch latch;
-  if (lds > 65536)
-    if (hipError_t e = latch.ensure((const void*)generic_axis_hess_kernel<T>, GENERIC_LDS_MAX); e != hipSuccess) return e;
-  hipLaunchKernelGGL(generic_axis_hess_kernel<T>, dim3((unsigned)nblk), dim3(sh.threads), lds, s, hp, (const cplx<T>*)src, (cplx<T>*)dst, ax, stride, inner,
-                     outer, nlines, tc, (const cplx<T>*)root, sign, (T)scale, sh.tw_lds);
-  return hipGetLastError();
+  if (ax.n != dp.nx || nlines != (long long)dp.ny * (dp.nz / 2 + 1) || !deriv_valid(dp) || src == dst) return hipErrorInvalidValue;
+  return launch_axis<generic_axis_deriv_kernel<T, P>, T>((cplx<T>*)dst, ax, stride, inner, outer, nlines, root, sign, scale, s, dp, (const cplx<T>*)src);
 }
 
 template <typename T> int rows_per_block(const GenericAxis& ax) { return generic_lines_per_block(ax.n, (int)sizeof(cplx<T>), 8, 49152, generic_bufs(ax), true); }   // + the reduction's static LDS
@@ -247,16 +199,21 @@ hipError_t launch_generic_axis_gen(int f64, const GenParams& gp, void* dst, cons
              : axis_gen_t<float>(gp, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
 }
 
-hipError_t launch_generic_axis_grad(int f64, const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
-                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
-  return f64 ? axis_grad_t<double>(gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
-             : axis_grad_t<float>(gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
+namespace {
+template <class P>
+hipError_t launch_axis_deriv(int f64, const P& dp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                             long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return f64 ? axis_deriv_t<double>(dp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
+             : axis_deriv_t<float>(dp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
 }
-
-hipError_t launch_generic_axis_hess(int f64, const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
-                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
-  return f64 ? axis_hess_t<double>(hp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s)
-             : axis_hess_t<float>(hp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
+}  // namespace
+hipError_t launch_generic_axis_deriv(int f64, const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                     long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return launch_axis_deriv(f64, gp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
+}
+hipError_t launch_generic_axis_deriv(int f64, const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                     long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s) {
+  return launch_axis_deriv(f64, hp, src, dst, ax, stride, inner, outer, nlines, root, sign, scale, s);
 }
 
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s) {

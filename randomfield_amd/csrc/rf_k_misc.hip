@@ -227,34 +227,20 @@ __global__ __launch_bounds__(256) void scale_copy_kernel(const cplx<T>* __restri
   }
 }
 
-// K (rows of nzh = nz/2 + 1 cells) = i k_a S (rows of gp.pitch cells): one component of the gradient of the potential (rf_core.h
-// grad_cell).  Rows (ix, iy) as gen_kspace_kernel walks them: blockDim.x threads along kz -- whole lines loaded and stored --
-// blockDim.y rows per workgroup, a row's indices formed once with 32-bit divisions.  S == K is allowed (no __restrict__): a cell is
-// read and written by the same thread.
-template <typename T>
-__global__ __launch_bounds__(256) void gradient_kernel(const cplx<T>* S, cplx<T>* K, GradParams gp, unsigned nrows) {
-  const int nzh = gp.nz / 2 + 1;
+// K (rows of nzh = nz/2 + 1 cells) = the cell function of dp applied to S (rows of dp.pitch cells): one component of the gradient of the
+// potential (P = GradParams, i k_a) or of its Hessian (HessParams, D_a D_b) -- rf_core.h deriv_cell.  Rows (ix, iy) as gen_kspace_kernel
+// walks them: blockDim.x threads along kz -- whole lines loaded and stored -- blockDim.y rows per workgroup, a row's indices formed
+// once with 32-bit divisions.  S == K is allowed (no __restrict__): a cell is read and written by the same thread.
+template <typename T, class P>
+__global__ __launch_bounds__(256) void derivative_kernel(const cplx<T>* S, cplx<T>* K, P dp, unsigned nrows) {
+  const int nzh = dp.nz / 2 + 1;
   for (unsigned long long r0 = (unsigned long long)blockIdx.x * blockDim.y; r0 < nrows; r0 += (unsigned long long)gridDim.x * blockDim.y) {
     const unsigned long long rr = r0 + threadIdx.y;
     if (rr >= nrows) continue;
-    const unsigned row = (unsigned)rr, ix = row / (unsigned)gp.ny, iy = row - ix * (unsigned)gp.ny;
-    const cplx<T>* Sr = S + (long long)row * gp.pitch;
+    const unsigned row = (unsigned)rr, ix = row / (unsigned)dp.ny, iy = row - ix * (unsigned)dp.ny;
+    const cplx<T>* Sr = S + (long long)row * dp.pitch;
     cplx<T>* Kr = K + (long long)row * nzh;
-    for (int iz = threadIdx.x; iz < nzh; iz += blockDim.x) Kr[iz] = grad_cell<T>(gp, Sr[iz], (int)ix, (int)iy, iz);
-  }
-}
-
-// K = D_a D_b S: one component of the Hessian of the potential (rf_core.h hess_cell); rows, block shape and S == K as gradient_kernel
-template <typename T>
-__global__ __launch_bounds__(256) void hessian_kernel(const cplx<T>* S, cplx<T>* K, HessParams hp, unsigned nrows) {
-  const int nzh = hp.nz / 2 + 1;
-  for (unsigned long long r0 = (unsigned long long)blockIdx.x * blockDim.y; r0 < nrows; r0 += (unsigned long long)gridDim.x * blockDim.y) {
-    const unsigned long long rr = r0 + threadIdx.y;
-    if (rr >= nrows) continue;
-    const unsigned row = (unsigned)rr, ix = row / (unsigned)hp.ny, iy = row - ix * (unsigned)hp.ny;
-    const cplx<T>* Sr = S + (long long)row * hp.pitch;
-    cplx<T>* Kr = K + (long long)row * nzh;
-    for (int iz = threadIdx.x; iz < nzh; iz += blockDim.x) Kr[iz] = hess_cell<T>(hp, Sr[iz], (int)ix, (int)iy, iz);
+    for (int iz = threadIdx.x; iz < nzh; iz += blockDim.x) Kr[iz] = deriv_cell<T>(dp, Sr[iz], (int)ix, (int)iy, iz);
   }
 }
 
@@ -583,34 +569,23 @@ hipError_t launch_save_potential(int f64, const void* K, void* P, int nx, int ny
   return hipGetLastError();
 }
 
-hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s) {
-  const long long nrows = (long long)gp.nx * gp.ny;
-  const int nzh = gp.nz / 2 + 1;
-  if (nrows <= 0 || nrows > 0x7fffffffLL || gp.pitch < nzh || gp.axis < 0 || gp.axis > 2) return hipErrorInvalidValue;
+template <class P>
+static hipError_t launch_derivative_t(int f64, const void* S, void* K, const P& dp, hipStream_t s) {
+  const long long nrows = (long long)dp.nx * dp.ny;
+  const int nzh = dp.nz / 2 + 1;
+  if (nrows <= 0 || nrows > 0x7fffffffLL || !deriv_valid(dp)) return hipErrorInvalidValue;
   // the block shape of launch_gen_kspace; 16 workgroups per CU, grid-stride over the rest of the rows
   int tx = 1;
   while (tx < 256 && tx < nzh) tx <<= 1;
   const int ty = 256 / tx;
   const long long nblk = (nrows + ty - 1) / ty;
   const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);     // (more rows, and rows longer than tx: tests/test_gpu_at_scale.py)
-  if (f64) hipLaunchKernelGGL(gradient_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, gp, (unsigned)nrows);
-  else hipLaunchKernelGGL(gradient_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, gp, (unsigned)nrows);
+  if (f64) hipLaunchKernelGGL((derivative_kernel<double, P>), dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, dp, (unsigned)nrows);
+  else hipLaunchKernelGGL((derivative_kernel<float, P>), dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, dp, (unsigned)nrows);
   return hipGetLastError();
 }
-
-hipError_t launch_hessian(int f64, const void* S, void* K, const HessParams& hp, hipStream_t s) {
-  const long long nrows = (long long)hp.nx * hp.ny;
-  const int nzh = hp.nz / 2 + 1;
-  if (nrows <= 0 || nrows > 0x7fffffffLL || hp.pitch < nzh || hp.a < 0 || hp.a > hp.b || hp.b > 2) return hipErrorInvalidValue;
-  int tx = 1;                                        // (the block shape of launch_gradient)
-  while (tx < 256 && tx < nzh) tx <<= 1;
-  const int ty = 256 / tx;
-  const long long nblk = (nrows + ty - 1) / ty;
-  const unsigned grid = (unsigned)(nblk < 256 * 16 ? nblk : 256 * 16);     // (more rows, and rows longer than tx: tests/test_gpu_at_scale.py)
-  if (f64) hipLaunchKernelGGL(hessian_kernel<double>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<double>*)S, (cplx<double>*)K, hp, (unsigned)nrows);
-  else hipLaunchKernelGGL(hessian_kernel<float>, dim3(grid), dim3(tx, ty), 0, s, (const cplx<float>*)S, (cplx<float>*)K, hp, (unsigned)nrows);
-  return hipGetLastError();
-}
+hipError_t launch_derivative(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s) { return launch_derivative_t(f64, S, K, gp, s); }
+hipError_t launch_derivative(int f64, const void* S, void* K, const HessParams& hp, hipStream_t s) { return launch_derivative_t(f64, S, K, hp, s); }
 
 template <typename T, int VEC>
 static hipError_t lpt2_accumulate_t(int step, T* H, T* Tacc, T* Sacc, long long n, hipStream_t s) {

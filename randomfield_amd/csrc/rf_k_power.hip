@@ -7,7 +7,7 @@
 namespace rf {
 namespace {
 
-// Rows (ix, iy) of the half spectrum as gradient_kernel walks them: blockDim.x threads along kz, blockDim.y rows per workgroup.  Every
+// Rows (ix, iy) of the half spectrum as derivative_kernel walks them: blockDim.x threads along kz, blockDim.y rows per workgroup.  Every
 // wave owns a histogram in LDS ([waves][nbins] of sum_k, sum_p, count behind the nbins + 1 squared edges).  Per step of 64 cells the
 // bins of a wave are reduced in one of two fixed-order ways.  Rows of at least a wave (blockDim.x >= 64) whose kz2 table does not
 // decrease: equal bins are runs of neighbouring lanes, a segmented scan sums every run and the runs' last lanes add to the wave's

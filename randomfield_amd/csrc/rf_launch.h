@@ -138,12 +138,11 @@ hipError_t launch_save_potential(int f64, const void* K, void* P, int nx, int ny
                                  const double* ky2, const double* kz2, int zpitch, int zoff, int ppitch, hipStream_t s);
 // (n = cells of K; P's rows hold ppitch >= zpitch cells)
 hipError_t launch_scale_copy(int f64, const void* P, void* K, long long n, int zpitch, int ppitch, double scale, hipStream_t s);
-// K (rows of nz/2 + 1 cells) = i k_a S, S with rows of gp.pitch cells (rf_core.h grad_cell): the stored potential, or K itself in divide
-// mode (S == K is allowed: every cell is read and written by the same thread).  Single-rank layouts.
-hipError_t launch_gradient(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s);
-// K (rows of nz/2 + 1 cells) = D_a D_b S (rf_core.h hess_cell): one component of the Hessian of the potential; S, S == K and layouts as
-// launch_gradient
-hipError_t launch_hessian(int f64, const void* S, void* K, const HessParams& hp, hipStream_t s);
+// K (rows of nz/2 + 1 cells) = one component of the gradient (i k_a S, rf_core.h grad_cell) or of the Hessian (D_a D_b S, hess_cell) of
+// the potential.  S has rows of pitch cells: the stored potential, or K itself in divide mode (S == K is allowed: every cell is read and
+// written by the same thread).  Single-rank layouts; parameters that fail deriv_valid: hipErrorInvalidValue.
+hipError_t launch_derivative(int f64, const void* S, void* K, const GradParams& gp, hipStream_t s);
+hipError_t launch_derivative(int f64, const void* S, void* K, const HessParams& hp, hipStream_t s);
 // one step of the 2LPT source's real-space sweep (rf_core.h lpt2_step, step = LPT2_FIRST .. LPT2_LAST) over n elements of the dense
 // real arrays H (the component just transformed), T and S (the accumulators); n a multiple of 16 bytes' worth of elements and the
 // arrays 16-byte aligned, else hipErrorInvalidValue.  LPT2_LAST writes the source into H.
@@ -204,13 +203,13 @@ hipError_t launch_generic_axis(int f64, const void* src, void* dst, const Generi
 // half spectrum (rf_generic.h GenericGenSource); ax.n == gp.nx and nlines == gp.ny * (gp.nz/2 + 1), else hipErrorInvalidValue
 hipError_t launch_generic_axis_gen(int f64, const GenParams& gp, void* dst, const GenericAxis& ax, long long stride, long long inner,
                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
-// the x pass of one gradient component: element e of line l = cell (e, l / (nz/2+1), l % (nz/2+1)) of `src` (rows of gp.pitch cells) times
-// i k_a (rf_generic.h GenericGradSource); ax.n == gp.nx, nlines == gp.ny * (gp.nz/2 + 1) and src != dst, else hipErrorInvalidValue
-hipError_t launch_generic_axis_grad(int f64, const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
-                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
-// the x pass of one Hessian component (rf_generic.h GenericHessSource): as launch_generic_axis_grad
-hipError_t launch_generic_axis_hess(int f64, const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
-                                    long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
+// the x pass of one gradient or Hessian component: element e of line l = cell (e, l / (nz/2+1), l % (nz/2+1)) of `src` (rows of pitch cells)
+// times the component's factor (rf_generic.h GenericDerivSource); ax.n == nx, nlines == ny * (nz/2 + 1), deriv_valid parameters and
+// src != dst, else hipErrorInvalidValue
+hipError_t launch_generic_axis_deriv(int f64, const GradParams& gp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                     long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
+hipError_t launch_generic_axis_deriv(int f64, const HessParams& hp, const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner,
+                                     long long outer, long long nlines, const void* root, int sign, double scale, hipStream_t s);
 // axes too long for the LDS (rf_generic.h GenericLong): one step of the four-step transform (lines with sub-lines); the Hermitian
 // (un)tangle of long rows as passes of their own; (sum, sum of squares) of a real array into nblocks partial pairs
 hipError_t launch_generic_lines(int f64, const void* src, void* dst, const GenericLines& L, const void* root, hipStream_t s);

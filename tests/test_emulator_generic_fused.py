@@ -1,4 +1,4 @@
-"""Generic grids with the generation inside the first FFT pass (csrc/rf_generic.h generic_realise_seq, GenericGenSource), on the CPU
+"""Generic grids with the generation inside the first FFT pass (csrc/rf_generic.h generic_c2r_from_seq, GenericGenSource), on the CPU
 emulator: the fused sequence must give the field and the moments of generation + generic_c2r_seq bit for bit -- the same gen_cell
 values in the same LDS positions through the same stages -- for every thread walk the kernels and the emulator have.  Plus the ABI
 surface of the option (flag 64, feature bit 13), which needs no GPU either."""

@@ -1,6 +1,6 @@
 """The gradient of the saved potential, psi_a(k) = i k_a delta(k) / k^2 (csrc/rf_core.h grad_cell), on the CPU emulator: the cell function
 over an array from both sources (emu_gradient_k, the elementwise kernel's loop), the generic sequence that applies it inside the x pass
-(rf_generic.h generic_gradient_c2r_seq, GenericGradSource) against "elementwise, then generic_c2r_seq" bit for bit, the float64 oracle
+(rf_generic.h generic_c2r_from_seq, GenericDerivSource) against "elementwise, then generic_c2r_seq" bit for bit, the float64 oracle
 np.fft.irfftn(1j * k_a * Phat), the divergence identity, the numpy backend of Generator.calculate_displacement_field and the ABI
 surface (5.5, feature bit 14).  No GPU needed.
 

@@ -1,5 +1,5 @@
 """The second-order (2LPT) displacement on the CPU: the Hessian cell function over an array from both sources (emu_hessian_k, rf_core.h
-hess_cell), the generic sequence that applies it inside the x pass (rf_generic.h generic_hessian_c2r_seq, GenericHessSource) against
+hess_cell), the generic sequence that applies it inside the x pass (rf_generic.h generic_c2r_from_seq, GenericDerivSource) against
 "elementwise, then generic_c2r_seq" bit for bit, the accumulate step function (emu_lpt2_accumulate, rf_core.h lpt2_step), the numpy
 backend of Generator.lpt2_source / calculate_displacement_field(order=2) against tests/lpt2_oracle.py, and the ABI surface (feature
 bit 16, version still 5.5).  No GPU needed.

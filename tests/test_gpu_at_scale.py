@@ -3,9 +3,9 @@ that reach them -- run with -m gpu on an MI355X.  The four per-feature files (te
 test_gpu_power_measure.py, test_gpu_particles.py) stay below every cap in this table; the 512^3 and 1024^3 configurations live above it:
 
     kernel                                               launch cap (source)                               a second stride needs
-    gradient_kernel, hessian_kernel                      min(nblk, 4096) workgroups of ty = 256 / tx rows, nx ny / ty > 4096
+    derivative_kernel (gradient and Hessian)             min(nblk, 4096) workgroups of ty = 256 / tx rows, nx ny / ty > 4096
                                                          tx the power of two covering nz/2 + 1, <= 256
-                                                         (rf_k_misc.hip launch_gradient / launch_hessian)
+                                                         (rf_k_misc.hip launch_derivative)
     save_potential_kernel, scale_copy_kernel             4096 x 256 threads (rf_k_misc.hip grid_for)       > 1 048 576 cells
     cic_convert_kernel, cic_paint_global_kernel          4096 x 256 threads (rf_k_particles.hip sweep_grid) > 1 048 576 cells / particles
     lpt2_accumulate_kernel, particles_accumulate_kernel  4096 x 256 threads of 16 bytes                    > 4 194 304 cells (float32, 4 per
@@ -13,7 +13,7 @@ test_gpu_power_measure.py, test_gpu_particles.py) stay below every cap in this t
     power_sweep_kernel                                   2048 workgroups up to 128 bins, else 1024         nx ny > cap ty
                                                          (rf_k_power.hip power_launch_shape)
 
-    the kz loop inside a row of gradient_kernel, hessian_kernel and power_sweep_kernel takes a second step when nz/2 + 1 > tx.
+    the kz loop inside a row of derivative_kernel and power_sweep_kernel takes a second step when nz/2 + 1 > tx.
     float32 plans with nz >= 512 keep the potential in rows of nz/2 + 64 cells (rf_capi.hip rf_plan_create), below that nz/2 + 2.
 
 Every test opens with a regime guard: a plain assert, from the shape and the literal cap, that the launch it is named for strides --
@@ -39,7 +39,7 @@ import test_gpu_power_measure as tpm
 pytestmark = pytest.mark.gpu
 
 C64, C128 = np.complex64, np.complex128
-CAP = 4096                       # workgroups of grid_for, sweep_grid, launch_gradient and launch_hessian (256 * 16)
+CAP = 4096                       # workgroups of grid_for, sweep_grid and launch_derivative (256 * 16)
 THREADS = CAP * 256              # ... of 256 threads: cells, particles or 16-byte vectors per stride
 SPACING = tl.SPACING
 assert tg.SPACING == SPACING

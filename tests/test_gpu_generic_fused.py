@@ -1,4 +1,4 @@
-"""Generic grids with the generation inside the first FFT pass (RF_FLAG_FUSED_GENERIC_GENERATION; rf_generic.h generic_realise_seq,
+"""Generic grids with the generation inside the first FFT pass (RF_FLAG_FUSED_GENERIC_GENERATION; rf_generic.h generic_c2r_from_seq,
 rf_k_generic.hip generic_axis_gen_kernel) -- run with -m gpu on an MI355X.
 
 The fused realisation must be the unfused one bit for bit: the same gen_cell values go to the same LDS positions and through the same

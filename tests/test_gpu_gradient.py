@@ -1,5 +1,5 @@
-"""The gradient of the saved potential on the device (rf_load_gradient, rf_execute_gradient_c2r; rf_k_misc.hip gradient_kernel,
-rf_k_generic.hip generic_axis_grad_kernel) and Generator.calculate_displacement_field -- run with -m gpu on an MI355X.
+"""The gradient of the saved potential on the device (rf_load_gradient, rf_execute_gradient_c2r; rf_k_misc.hip derivative_kernel,
+rf_k_generic.hip generic_axis_deriv_kernel) and Generator.calculate_displacement_field -- run with -m gpu on an MI355X.
 
 Oracle: numpy in float64, np.fft.irfftn(1j * k_a * Phat) with the axis' Nyquist entry of k_a set to 0, Phat being the k space the
 device itself holds (download_k) or the uploaded array.  Tolerances: k space after load_gradient within 4 eps per component of the

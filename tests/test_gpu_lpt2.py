@@ -1,5 +1,5 @@
 """The second-order (2LPT) displacement on the device (rf_load_hessian, rf_execute_hessian_c2r, rf_lpt2_source, rf_lpt2_potential,
-RF_GRAD_FROM_POTENTIAL2; rf_k_misc.hip hessian_kernel / lpt2_accumulate_kernel, rf_k_generic.hip generic_axis_hess_kernel) and
+RF_GRAD_FROM_POTENTIAL2; rf_k_misc.hip derivative_kernel / lpt2_accumulate_kernel, rf_k_generic.hip generic_axis_deriv_kernel) and
 Generator.calculate_displacement_field(order=2) / lpt2_source -- run with -m gpu on an MI355X.
 
 Oracle: tests/lpt2_oracle.py, float64 numpy, applied to what the device itself holds (the downloaded potential, the downloaded S).
@@ -10,8 +10,8 @@ per product, at most 11 roundings of eps/2 A in the sweep); psi2 against the ora
 (two transforms).  Generic plans apply the Hessian factor inside their x pass: that field must be load_hessian + execute_c2r bit for
 bit, the four-step fallback of (16384, 4, 6) included.  Shapes: those of tests/test_gpu_gradient.py, one per launch class, its three
 nz >= 512 shapes among them ((16, 16, 512) complex64, (8, 8, 512) complex128, (6, 10, 520) complex64: the second kz step of
-hessian_kernel, and Hessian, source and second-order potential on the padded potential pitch).  The grid-stride loops of
-hessian_kernel and lpt2_accumulate_kernel: tests/test_gpu_at_scale.py."""
+derivative_kernel, and Hessian, source and second-order potential on the padded potential pitch).  The grid-stride loops of
+derivative_kernel and lpt2_accumulate_kernel: tests/test_gpu_at_scale.py."""
 import numpy as np
 import pytest
 
