@@ -173,7 +173,7 @@ int upload_noise(rf_plan* p, int mode, const double* noise_host) {
   return 0;
 }
 
-FastGenParams make_fast(rf_plan* p, uint64_t seed, bool seed_from_dev, const uint64_t* seed_ptr) {
+FastGenParams make_fast(rf_plan* p, const CallDesc& cd, uint64_t seed, bool seed_from_dev, const uint64_t* seed_ptr) {
   FastGenParams f;
   f.nx = p->nx; f.ny = p->ny; f.nz = p->nz;
   f.dkx = p->fdkx; f.dky = p->fdky; f.dkz = p->fdkz;
@@ -182,7 +182,7 @@ FastGenParams make_fast(rf_plan* p, uint64_t seed, bool seed_from_dev, const uin
   f.noise = nullptr; f.noise32 = nullptr;
   f.rowtab = nullptr; f.seg_cap = 0;
   f.zpitch = p->nzl + 1; f.zoff = p->kz0; f.ppitch = p->ppitch;
-  f.pscale = p->emit_pscale; f.emit_potential = p->emit_potential ? 1 : 0;
+  f.pscale = cd.emit_pscale; f.emit_potential = cd.emit_potential ? 1 : 0;
   return f;
 }
 
@@ -247,12 +247,12 @@ int slab_chunks(const rf_plan* p) {
 size_t chunk_bytes(const rf_plan* p) { return p->w_bytes / (size_t)slab_chunks(p); }
 
 // (kz0c, nzlc >= 0: a sub-slab of this rank's planes instead of all of them -- W then points at the sub-slab's own region)
-int queue_x(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, bool timed, int kz0c, int nzlc) {
+int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, bool timed, int kz0c, int nzlc) {
   // resident deviates (the numpy stream replayed by rf_noise_mt19937) take the fast float32 sigma path too; host-supplied
   // deviates (RF_NOISE_EXTERNAL, the parity mode) keep the exact reference dtype chain
   // (float32 copies of the deviates exist for this path only, and it can store the potential too; float64 ones cannot)
-  const bool fast_noise = !kspace && gp.noise_mode == NOISE_EXTERNAL && p->resident_fast && p->have_fast && !p->exact_gen &&
-                          !p->f64 && !(p->replicate && p->nranks > 1) && (p->noise32_resident || !p->pot_target);
+  const bool fast_noise = !kspace && gp.noise_mode == NOISE_EXTERNAL && cd.resident_fast && p->have_fast && !p->exact_gen &&
+                          !p->f64 && !(p->replicate && p->nranks > 1) && (p->noise32_resident || !cd.pot_target);
   RF_REQUIRE(kspace || gp.noise_mode != NOISE_EXTERNAL || fast_noise || p->noise_resident,
              "only float32 copies of the deviates are resident: this path (exact chain / float64 plan) needs rf_noise_mt19937's float64 ones");
   const bool fast = (!kspace && gp.noise_mode == NOISE_PHILOX && p->have_fast && !p->exact_gen) || fast_noise;
@@ -266,7 +266,7 @@ int queue_x(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStr
                          ? xblock_x_geom(p->nx, p->ny, nzl, col_gen_tile_cols(p->f64, p->nx), xpose_row_block(p))
                          : ColGeom{(long long)p->ny * nzl, 0, (long long)p->ny * nzl};
   if (timed) { RF_HIP(hipEventRecord(p->ev[5], sx)); p->repair_timed = fast; }   // overwritten by the launcher if it splits
-  FastGenParams fgp = make_fast(p, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
+  FastGenParams fgp = make_fast(p, cd, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
   if (fast_noise && p->noise32_resident) {
     fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch);      // (a later float64 replay reuses the scratch: it clears noise32_resident)
     fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt_rowtab); fgp.seg_cap = p->seg_cap;
@@ -275,7 +275,7 @@ int queue_x(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStr
   if (fast)
     RF_HIP(launch_col_fastgen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, fgp,
                               kz0, (int)nzl, p->tw_x, sx, false, timed ? p->ev[5] : nullptr,
-                              rep ? p->rank * p->nxl : 0, rep ? (p->rank + 1) * p->nxl : 1 << 30, p->pot_target, p->fixbuf));
+                              rep ? p->rank * p->nxl : 0, rep ? (p->rank + 1) * p->nxl : 1 << 30, cd.pot_target, p->fixbuf));
   else
     RF_HIP(launch_col_gen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, gp, kspace, kz0, (int)nzl, p->tw_x, sx));
   return 0;
@@ -331,17 +331,22 @@ int queue_y_direct(rf_plan* p, const void* W, int rbuf, hipStream_t s, int c) {
   return 0;
 }
 
+// grow a vector of events to n (flags as hipEventCreateWithFlags takes them)
+int ensure_events(std::vector<hipEvent_t>& ev, size_t n, unsigned flags) {
+  while (ev.size() < n) { hipEvent_t e; RF_HIP(hipEventCreateWithFlags(&e, flags)); ev.push_back(e); }
+  return 0;
+}
+
 // The forward half of a plan in direct mode: sub-slab by sub-slab the x pass on stream A and the storing y pass on stream Y (Y == A: one
 // stream; Y != A: the stores of sub-slab c -- link-bound on a real job -- run beside the x pass of sub-slab c + 1).  The caller has
 // put the barrier that frees the receive buffers in front of it on Y.  `timed` (Y == A only): ev[5] / ev[1] / ev[2] as queue_xy.
-int direct_forward(rf_plan* p, const GenParams& gp, const void* kspace, void* W, int rbuf, hipStream_t A, hipStream_t Y, bool timed) {
+int direct_forward(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, int rbuf, hipStream_t A, hipStream_t Y, bool timed) {
   const int C = slab_chunks(p);
   const long long nzc_ = p->nzl / C;
-  if (Y != A)
-    while ((int)p->chunk_ev.size() < C + 1) { hipEvent_t e; RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); p->chunk_ev.push_back(e); }
+  if (Y != A) if (int rc = ensure_events(p->chunk_ev, C + 1, hipEventDisableTiming)) return rc;
   for (int c = 0; c < C; ++c) {
-    if (C == 1) { if (int rc = queue_x(p, gp, kspace, W, A, timed)) return rc; }
-    else if (int rc = queue_x(p, gp, kspace, (char*)W + (size_t)c * chunk_bytes(p), A, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
+    if (C == 1) { if (int rc = queue_x(p, cd, gp, kspace, W, A, timed)) return rc; }
+    else if (int rc = queue_x(p, cd, gp, kspace, (char*)W + (size_t)c * chunk_bytes(p), A, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
     if (timed && C == 1) RF_HIP(hipEventRecord(p->ev[1], A));
     if (Y != A) { RF_HIP(hipEventRecord(p->chunk_ev[c], A)); RF_HIP(hipStreamWaitEvent(Y, p->chunk_ev[c], 0)); }
     if (int rc = queue_y_direct(p, W, rbuf, Y, c)) return rc;
@@ -354,29 +359,29 @@ int direct_forward(rf_plan* p, const GenParams& gp, const void* kspace, void* W,
 // x pass (generation or API k-space fused into its load) + y pass of buffer W on stream s.
 // Records ev[1] (after x) and ev[2] (after y) when `timed`.
 // the forward half of ONE sub-slab c of a plan that exchanges in chunks: x pass + y pass on its nzl / xchunks planes (region c of W)
-int queue_xy_chunk(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStream_t s, int c) {
+int queue_xy_chunk(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, int c) {
   const int C = slab_chunks(p);
   const long long nzc_ = p->nzl / C;
   char* Wc = (char*)W + (size_t)c * chunk_bytes(p);
-  if (int rc = queue_x(p, gp, kspace, Wc, s, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
+  if (int rc = queue_x(p, cd, gp, kspace, Wc, s, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
   const ColGeom gy{nzc_, (long long)p->ny * nzc_, nzc_};
   RF_HIP(launch_col_plain(p->f64, p->ny, +1, Wc, gy, (long long)p->nx * nzc_, p->tw_y, s));
   return 0;
 }
 
 // (a plan in direct mode: the y pass stores into the peers' receive buffers `rbuf`, and what follows is the z pass, not an exchange)
-int queue_xy(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStream_t s, bool timed, int rbuf) {
-  if (direct_active(p)) return direct_forward(p, gp, kspace, W, rbuf, s, s, timed);
+int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, bool timed, int rbuf) {
+  if (direct_active(p)) return direct_forward(p, cd, gp, kspace, W, rbuf, s, s, timed);
   if (slab_chunks(p) > 1) {
     for (int c = 0; c < slab_chunks(p); ++c)
-      if (int rc = queue_xy_chunk(p, gp, kspace, W, s, c)) return rc;
+      if (int rc = queue_xy_chunk(p, cd, gp, kspace, W, s, c)) return rc;
     if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = false; RF_HIP(hipEventRecord(p->ev[1], s)); RF_HIP(hipEventRecord(p->ev[2], s)); }
     return 0;
   }
   const bool rep = p->replicate && p->nranks > 1;
   const long long nzl = rep ? p->nzc : p->nzl, nxp = rep ? p->nxl : p->nx;      // the local array is [nxp][ny][nzl]
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
-  if (int rc = queue_x(p, gp, kspace, W, s, timed)) return rc;
+  if (int rc = queue_x(p, cd, gp, kspace, W, s, timed)) return rc;
   if (timed) RF_HIP(hipEventRecord(p->ev[1], s));
   RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, nxp * nzl, p->tw_y, s));
   if (timed) RF_HIP(hipEventRecord(p->ev[2], s));
@@ -480,7 +485,7 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
     const int b = i & 1, pb = (i - 1) & 1;
     if (i < n) {
       // (sub-slab by sub-slab when the plan chunks: x(c) on A, the stores of sub-slab c on Y behind an event)
-      if (int rc = direct_forward(p, make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, A, Y, false)) return rc;
+      if (int rc = direct_forward(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, A, Y, false)) return rc;
       (void)ev_fwd;
     }
     if (i >= 1) {
@@ -509,6 +514,26 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
   return 0;
 }
 
+// The plan holds the real-space field of its last call in W, and that field's (sum, sumsq) in pair `slot` of `stats`
+void field_ready(rf_plan* p, int slot) {
+  p->cur = p->W;
+  p->stats_slot = slot;
+  p->real_valid = true;
+  p->stats_valid = true;
+}
+
+// room for the (sum, sumsq) pairs of n realisations (captured batch graphs carry the array's address: they go)
+int ensure_stats(rf_plan* p, int n) {
+  if (p->stats_cap >= n) return 0;
+  RF_HIP(hipStreamSynchronize(p->stream));
+  drop_graphs(p);
+  if (p->stats) RF_HIP(hipFree(p->stats));
+  p->stats = nullptr; p->stats_cap = 0;
+  RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
+  p->stats_cap = n + 64;
+  return 0;
+}
+
 // Pipelined batch on the slab path: realisation i+1's generation + x + y passes (compute stream) run
 // while realisation i's all-to-all is in flight (exchange stream); two (send, receive) buffer pairs.
 //   compute: x,y(0) | x,y(1)   z(0) | x,y(2)   z(1) | ...            (in order on p->stream)
@@ -516,39 +541,22 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
 // z(i) waits for exch(i); exch(i) waits for x,y(i) and -- because it overwrites R[i%2] -- for z(i-2).
 // One all-reduce of all n (sum, sumsq) pairs at the end.
 int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
+  if (int rc = ensure_stats(p, n)) return rc;
   if (p->replicate && p->nranks > 1) {          // no exchange to overlap: realisations back to back, one all-reduce at the end
-    if (p->stats_cap < n) {
-      RF_HIP(hipStreamSynchronize(p->stream));
-      if (p->stats) RF_HIP(hipFree(p->stats));
-      p->stats = nullptr;
-      RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
-      p->stats_cap = n + 64;
-    }
     const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
     for (int i = 0; i < n; ++i) {
-      if (int rc = queue_xy(p, make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W, p->stream, false)) return rc;
+      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W, p->stream, false)) return rc;
       RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W, (long long)p->nxl * p->ny, scale, p->tw_z, p->partials, p->stream));
       RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats + 2 * i, p->partials + 2 * p->npartials, p->stream));
     }
     if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, p->stream));
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->cur = p->W;
-    p->stats_slot = n - 1;
     p->timed = false;
-    p->real_valid = true;
-    p->stats_valid = true;
+    field_ready(p, n - 1);
     return 0;
   }
   if (int rc = ensure_batch_buffers(p)) return rc;
-  if (p->stats_cap < n) {
-    RF_HIP(hipStreamSynchronize(p->stream));
-    drop_graphs(p);
-    if (p->stats) RF_HIP(hipFree(p->stats));
-    p->stats = nullptr;
-    RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
-    p->stats_cap = n + 64;
-  }
   if (direct_active(p)) return slab_batch_direct(p, seeds, n);
   void* Wb[2] = {p->W, p->W2};
   void* Rb[2] = {p->R, p->R2};
@@ -558,7 +566,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
   for (int i = 0; i <= n; ++i) {
     if (i < n) {
       const int b = i & 1;
-      if (int rc = queue_xy(p, make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], A, false)) return rc;
+      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], A, false)) return rc;
       RF_HIP(hipEventRecord(ev_fwd[b], A));
       RF_HIP(hipStreamWaitEvent(C, ev_fwd[b], 0));
       if (i >= 2) RF_HIP(hipStreamWaitEvent(C, ev_z[b], 0));          // R[b] still being read by z(i-2)?
@@ -616,7 +624,7 @@ int yz_slab_planes(const rf_plan* p) {
 // on X, z pass gathering X -> W).
 // Host sink (rf_set_host_sink).  The z pass of a slab of x planes has been queued on s: mark that point with an event ...
 int sink_mark(rf_plan* p, int slab, hipStream_t s) {
-  while ((int)p->sink_ev.size() <= slab) { hipEvent_t e; RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); p->sink_ev.push_back(e); }
+  if (int rc = ensure_events(p->sink_ev, slab + 1, hipEventDisableTiming)) return rc;
   RF_HIP(hipEventRecord(p->sink_ev[slab], s));
   return 0;
 }
@@ -640,9 +648,9 @@ int sink_finish(rf_plan* p) {
   return 0;
 }
 
-int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed) {
+int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, bool timed) {
   const long long nzl = p->nzl;
-  bool sink = p->sink_host != nullptr && !p->zscale;
+  bool sink = p->sink_host != nullptr && !cd.zscale;
   if (sink) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cap);
@@ -658,7 +666,7 @@ int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed) 
   const int nslab = (int)((p->nx + B - 1) / B);
   const long long plane = (long long)p->ny * nzl * (long long)p->csize, tiles_per_plane = p->npartials / p->nx;
   if (timed) {
-    while ((int)p->slab_ev.size() < 2 * nslab) { hipEvent_t e; RF_HIP(hipEventCreate(&e)); p->slab_ev.push_back(e); }
+    if (int rc = ensure_events(p->slab_ev, 2 * nslab, hipEventDefault)) return rc;
     p->slab_timed = nslab;
   }
   // untimed single-rank float32 realisations at the sizes rf_k_yz.hip serves: the z pass of slab i and the y pass of slab i + 1 share a
@@ -667,11 +675,11 @@ int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed) 
   // (rf_set_merged_yz(2) merges timed calls too, with an event behind every launch: rf_merged_yz_ms)
   // (the last slab may be smaller -- a slab size that does not divide nx: RF_FLAG_YZ_SLAB_PLANES -- as long as both sizes fit the kernel)
   const long long Blast = p->nx - (long long)(nslab - 1) * B;
-  if ((timed ? p->yz_merge >= 2 : p->yz_merge >= 1) && !xp && !p->zscale && nslab > 1 &&
+  if ((timed ? p->yz_merge >= 2 : p->yz_merge >= 1) && !xp && !cd.zscale && nslab > 1 &&
       yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, B * nzl) &&
       (Blast == B || yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, Blast * nzl))) {
     if (timed) {
-      while ((int)p->slab_ev.size() < nslab + 1) { hipEvent_t e; RF_HIP(hipEventCreate(&e)); p->slab_ev.push_back(e); }
+      if (int rc = ensure_events(p->slab_ev, nslab + 1, hipEventDefault)) return rc;
       p->slab_merged = nslab;
       p->slab_timed = 0;       // (rf_kernel_ms: the merged form's events apply, the per-pass pairs of slab_ev were not recorded by this call)
     }
@@ -709,7 +717,7 @@ int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed) 
     if (timed) RF_HIP(hipEventRecord(p->slab_ev[2 * i], s));
     double* part = p->partials + 2 * x0 * tiles_per_plane;
     if (xp) RF_HIP(launch_row_c2r_xgather(p->f64, (int)p->nzc, Xs, Ws, nb * p->ny, scale, (int)tc, (int)rb, p->ny, p->tw_z, part, s));
-    else if (p->zscale) RF_HIP(launch_row_c2r_zscale(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->zscale, p->tw_z, part, s));
+    else if (cd.zscale) RF_HIP(launch_row_c2r_zscale(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, cd.zscale, p->tw_z, part, s));
     else RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z, part, s));
     if (timed) RF_HIP(hipEventRecord(p->slab_ev[2 * i + 1], s));
     if (sink) {
@@ -730,15 +738,15 @@ int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed) 
 
 // the whole single-rank pipeline: x pass (generation or API k-space fused into its load; into the transposed intermediate
 // when the plan uses it), then queue_yz
-int queue_xyz(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStream_t s, double* stats_out, bool timed) {
+int queue_xyz(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, double* stats_out, bool timed) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(s, &cap);
   if (cap == hipStreamCaptureStatusNone)           // (no allocation inside a graph capture: batch_prepare() has done it)
     if (int rc = ensure_x(p)) return rc;
   const bool xp = p->X && xpose_ok(p);
-  if (int rc = queue_x(p, gp, kspace, xp ? p->X : W, s, timed)) return rc;
+  if (int rc = queue_x(p, cd, gp, kspace, xp ? p->X : W, s, timed)) return rc;
   if (timed) RF_HIP(hipEventRecord(p->ev[1], s));
-  return queue_yz(p, W, s, stats_out, timed);
+  return queue_yz(p, cd, W, s, stats_out, timed);
 }
 
 // the launches behind the sequences of rf_generic.h (generic_c2r_seq / generic_r2c_seq / generic_c2c_seq) on the plan's stream
@@ -828,8 +836,31 @@ int generic_c2r(rf_plan* p, const void* K, double* stats_out, bool timed, const 
   return 0;
 }
 
+// the k-space side array K holds a half spectrum (and no auxiliary real field any more)
+void kspace_ready(rf_plan* p) {
+  p->k_valid = true;
+  p->aux_valid = false;
+}
+
+// What the exchanging branches of queue_c2r end with, the receive buffer being complete for stream A: the gathering z pass on A, then
+// the all-reduce of the moments on S, the stream that drives the communicator in this call (S != A: behind an event hop each way)
+int gather_and_reduce(rf_plan* p, hipStream_t A, hipStream_t S) {
+  hipEvent_t hop = S != A ? p->chunk_ev[slab_chunks(p)] : nullptr;
+  if (int rc = queue_z_slab(p, p->R, p->W, p->stats, A)) return rc;
+  if (p->timed) RF_HIP(hipEventRecord(p->ev[3], A));
+  if (p->nranks > 1 && p->comm) {       // global (sum, sumsq): one 2-double all-reduce
+    if (hop) { RF_HIP(hipEventRecord(hop, A)); RF_HIP(hipStreamWaitEvent(S, hop, 0)); }
+    RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, S));
+    if (hop) { RF_HIP(hipEventRecord(hop, S)); RF_HIP(hipStreamWaitEvent(A, hop, 0)); }
+  }
+  if (p->timed) RF_HIP(hipEventRecord(p->ev[4], A));
+  p->stats_slot = 0;
+  p->stats_valid = true;
+  return 0;
+}
+
 // one realisation / transform on the plan's stream into the primary buffer
-int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
+int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace) {
   if (p->generic) {
     // per-kernel times (rf_kernel_ms): ev[0] | generation launch | ev[5] | x | ev[1] | y | ev[2] | contiguous | ev[3] | reduce | ev[4]
     p->slab_timed = 0;
@@ -842,27 +873,20 @@ int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
       if (int rc = ensure_k(p)) return rc;
       RF_HIP(launch_gen_kspace(p->f64, p->K, gp, p->stream));
       if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], p->stream)); p->repair_timed = true; }
-      p->k_valid = true;
-      p->aux_valid = false;
+      kspace_ready(p);
       kspace = p->K;
     }
     if (int rc = generic_c2r(p, kspace, p->stats, p->timed, fused ? &gp : nullptr)) return rc;
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->cur = p->W;
-    p->stats_slot = 0;
-    p->real_valid = true;
-    p->stats_valid = true;
+    field_ready(p, 0);
     return 0;
   }
   p->slab_timed = 0;                            // (set again by queue_yz when this call runs the y / z passes slab by slab, timed)
   p->slab_merged = 0;
   if (p->timed) RF_HIP(hipEventRecord(p->ev[0], p->stream));
   if (p->nranks == 1 && !p->force_slab) {       // one GPU: x pass, then the y / z passes (slab by slab on large grids)
-    if (int rc = queue_xyz(p, gp, kspace, p->W, p->stream, p->stats, p->timed)) return rc;
-    p->cur = p->W;
-    p->stats_slot = 0;
-    p->real_valid = true;
-    p->stats_valid = true;
+    if (int rc = queue_xyz(p, cd, gp, kspace, p->W, p->stream, p->stats, p->timed)) return rc;
+    field_ready(p, 0);
     return 0;
   }
   if (direct_active(p)) {
@@ -874,23 +898,14 @@ int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
     const int C = slab_chunks(p);
     const bool two = p->direct_overlap != 0 && C > 1;
     if (int rc = ensure_comm_stream(p)) return rc;
-    while ((int)p->chunk_ev.size() < C + 1) { hipEvent_t e; RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); p->chunk_ev.push_back(e); }
+    if (int rc = ensure_events(p->chunk_ev, C + 1, hipEventDisableTiming)) return rc;
     hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
     if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], A)); RF_HIP(hipStreamWaitEvent(Y, p->chunk_ev[C], 0)); }
     if (int rc = direct_barrier(p, Y)) return rc;
-    if (int rc = direct_forward(p, gp, kspace, p->W, 0, A, Y, p->timed)) return rc;
+    if (int rc = direct_forward(p, cd, gp, kspace, p->W, 0, A, Y, p->timed)) return rc;
     if (int rc = direct_barrier(p, Y)) return rc;
     if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], Y)); RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0)); }
-    if (int rc = queue_z_slab(p, p->R, p->W, p->stats, A)) return rc;
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[3], A));
-    if (p->nranks > 1 && p->comm) {
-      if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], A)); RF_HIP(hipStreamWaitEvent(Y, p->chunk_ev[C], 0)); }
-      RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, Y));
-      if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], Y)); RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0)); }
-    }
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[4], A));
-    p->stats_slot = 0;
-    p->stats_valid = true;
+    if (int rc = gather_and_reduce(p, A, Y)) return rc;
     if (p->direct_standin) p->real_valid = false;       // (the stores went to this rank's own buffers: no field came out)
     return 0;
   }
@@ -901,12 +916,12 @@ int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
     // only, the final all-reduce of the moments too.)
     const int C = slab_chunks(p);
     if (int rc = ensure_comm_stream(p)) return rc;
-    while ((int)p->chunk_ev.size() < C + 1) { hipEvent_t e; RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); p->chunk_ev.push_back(e); }
+    if (int rc = ensure_events(p->chunk_ev, C + 1, hipEventDisableTiming)) return rc;
     hipStream_t A = p->stream, X = p->comm_stream;
     RF_HIP(hipEventRecord(p->chunk_ev[C], A));                 // (whatever used R / the communicator before on the plan's stream)
     RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[C], 0));
     for (int c = 0; c < C; ++c) {
-      if (int rc = queue_xy_chunk(p, gp, kspace, p->W, A, c)) return rc;
+      if (int rc = queue_xy_chunk(p, cd, gp, kspace, p->W, A, c)) return rc;
       RF_HIP(hipEventRecord(p->chunk_ev[c], A));
       RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[c], 0));
       if (int rc = queue_exchange_rccl(p, p->W, p->R, X, c)) return rc;
@@ -914,22 +929,11 @@ int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
     if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], A)); p->repair_timed = false; RF_HIP(hipEventRecord(p->ev[1], A)); RF_HIP(hipEventRecord(p->ev[2], A)); }
     RF_HIP(hipEventRecord(p->chunk_ev[C], X));
     RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0));
-    if (int rc = queue_z_slab(p, p->R, p->W, p->stats, A)) return rc;
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[3], A));
-    if (p->nranks > 1 && p->comm) {
-      RF_HIP(hipEventRecord(p->chunk_ev[C], A));
-      RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[C], 0));
-      RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, X));
-      RF_HIP(hipEventRecord(p->chunk_ev[C], X));
-      RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0));
-    }
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[4], A));
-    p->stats_slot = 0;
-    p->stats_valid = true;
+    if (int rc = gather_and_reduce(p, A, X)) return rc;
     if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
     return 0;
   }
-  if (int rc = queue_xy(p, gp, kspace, p->W, p->stream, p->timed)) return rc;
+  if (int rc = queue_xy(p, cd, gp, kspace, p->W, p->stream, p->timed)) return rc;
   if (p->replicate && p->nranks > 1) {          // the local array already is this rank's x slab [nxl][ny][nz/2]
     const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
     RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W, (long long)p->nxl * p->ny, scale, p->tw_z, p->partials, p->stream));
@@ -937,21 +941,12 @@ int queue_c2r(rf_plan* p, const GenParams& gp, const void* kspace) {
     if (p->timed) RF_HIP(hipEventRecord(p->ev[3], p->stream));
     if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, p->stream));
     if (p->timed) RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->cur = p->W;
-    p->real_valid = true;
-    p->stats_slot = 0;
-    p->stats_valid = true;
+    field_ready(p, 0);
     return 0;
   }
   if (p->nranks > 1 || p->force_slab) {
     if (int rc = queue_exchange_rccl(p, p->W, p->R, p->stream)) return rc;
-    if (int rc = queue_z_slab(p, p->R, p->W, p->stats, p->stream)) return rc;
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[3], p->stream));
-    // global (sum, sumsq): one 2-double all-reduce
-    if (p->nranks > 1 && p->comm) RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, p->stream));
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->stats_slot = 0;
-    p->stats_valid = true;
+    if (int rc = gather_and_reduce(p, p->stream, p->stream)) return rc;
     if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
     return 0;
   }
@@ -1354,8 +1349,7 @@ int rf_generate(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   RF_REQUIRE(mode != RF_NOISE_RESIDENT || p->noise_resident, "rf_generate needs float64 deviates: only float32 copies are resident");
   RF_HIP(launch_gen_kspace(p->f64, p->K, make_gen(p, seed, mode, false), p->stream));
   if (mode == RF_NOISE_EXTERNAL) RF_HIP(hipStreamSynchronize(p->stream));  // host noise buffer may be released by the caller
-  p->k_valid = true;
-  p->aux_valid = false;
+  kspace_ready(p);
   return 0;
 }
 
@@ -1366,7 +1360,7 @@ int rf_execute_c2r(rf_plan* p) {
   RF_REQUIRE(!(p->replicate && p->nranks > 1), "replicated-generation plans have no distributed k-space buffer");
   RF_HIP(hipSetDevice(p->device));
   p->timed = true;
-  return queue_c2r(p, make_gen(p, 0, RF_NOISE_NATIVE, false), p->K);
+  return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K);
 }
 
 }  // extern "C"
@@ -1391,8 +1385,7 @@ int queue_r2c_slab_cols(rf_plan* p, hipStream_t s) {
   RF_HIP(launch_unpack_kspace(p->f64, p->W, p->K, p->nx, p->ny, (int)nzl, p->kz0, s));
   p->real_valid = false;      // the field buffer now holds packed k space
   p->stats_valid = false;
-  p->k_valid = true;
-  p->aux_valid = false;
+  kspace_ready(p);
   return 0;
 }
 // single-rank forward transform of the field in W.  Generic plans: rows -> half spectrum in K, then the y and x forward passes
@@ -1406,8 +1399,7 @@ int queue_r2c_single(rf_plan* p, bool unpack) {
     if (generic_any_long(p)) { if (int rc = ensure_g(p)) return rc; if (int rc = ensure_g2(p)) return rc; }
     HipGenericOps ops{p, p->stream};
     if (int rc = generic_r2c_seq(ops, p->gdims, p->W, p->K, p->G, p->G2)) return rc;
-    p->k_valid = true;          // the real field in W is untouched on this path
-    p->aux_valid = false;
+    kspace_ready(p);            // the real field in W is untouched on this path
     return 0;
   }
   if (unpack) { if (int rc = ensure_k(p)) return rc; }
@@ -1418,8 +1410,7 @@ int queue_r2c_single(rf_plan* p, bool unpack) {
   p->stats_valid = false;
   if (unpack) {
     RF_HIP(launch_unpack_kspace(p->f64, p->W, p->K, p->nx, p->ny, (int)nzc, 0, p->stream));
-    p->k_valid = true;
-    p->aux_valid = false;
+    kspace_ready(p);
   }
   return 0;
 }
@@ -1459,10 +1450,9 @@ int rf_realise(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
   p->timed = true;
-  p->resident_fast = (mode == RF_NOISE_RESIDENT);
-  int rc = queue_c2r(p, make_gen(p, seed, mode, false), nullptr);
-  p->resident_fast = false;
-  if (rc) return rc;
+  CallDesc cd;
+  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
+  if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
   if (mode == RF_NOISE_EXTERNAL) RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -1488,9 +1478,10 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, nullptr)) return rc;
   p->timed = true;
-  p->resident_fast = (mode == RF_NOISE_RESIDENT);
-  p->emit_potential = true;
-  p->emit_pscale = p->f64 ? scale : (double)(float)scale;
+  CallDesc cd;
+  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
+  cd.emit_potential = true;
+  cd.emit_pscale = p->f64 ? scale : (double)(float)scale;
   // the light-cone factor per plane z (generate.py:344-347): in the z pass's own store where the plan runs the plain single-rank
   // passes, else by the sweep rf_scale_z would make -- the same two roundings either way
   // (decided from the plan's FLAG: the blocked intermediate X is allocated lazily inside queue_c2r, and its gathering z pass has no
@@ -1498,12 +1489,8 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   if (int rc = ensure_x(p)) return rc;
   const bool fuse_z = factor_z && p->nranks == 1 && !p->force_slab && !xpose_ok(p);
   if (factor_z) RF_HIP(hipMemcpyAsync(p->ztab, factor_z, (size_t)p->nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  p->zscale = fuse_z ? p->ztab : nullptr;
-  int rc = queue_c2r(p, make_gen(p, seed, mode, false), nullptr);
-  p->zscale = nullptr;
-  p->emit_potential = false;
-  p->resident_fast = false;
-  if (rc) return rc;
+  cd.zscale = fuse_z ? p->ztab : nullptr;
+  if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
   if (factor_z && !fuse_z) {
     RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, p->nz, p->ztab, 0.0, p->stream));
     p->stats_valid = false;
@@ -1514,6 +1501,24 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
 
 }  // extern "C"
 namespace rfc {
+// mean and standard deviation of a field of the plan from its (sum, sumsq) pair
+void mean_std(const rf_plan* p, const double* st, double* mean, double* std_out) {
+  const double cnt = (double)p->nx * p->ny * p->nz;
+  const double m = st[0] / cnt;
+  const double v = st[1] / cnt - m * m;
+  if (mean) *mean = m;
+  if (std_out) *std_out = v > 0 ? std::sqrt(v) : 0.0;
+}
+
+// the rms of the first n realisations of a batch, from their pairs in `stats` (waits for the plan's stream)
+int rms_from_stats(rf_plan* p, int n, double* rms_out) {
+  std::vector<double> st(2 * (size_t)n);
+  RF_HIP(hipMemcpyAsync(st.data(), p->stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  for (int i = 0; i < n; ++i) mean_std(p, &st[2 * i], nullptr, rms_out + i);
+  return 0;
+}
+
 // generate_delta_field(save_potential=True) (generate.py:191-219): the field as rf_realise, plus delta(k) / k^2 in the
 // plan's potential buffer.  With the native generator (or resident float32 deviates) the potential is a second store
 // stream of the generation pass; every other case runs the unfused sequence generate -> save_potential -> c2r.
@@ -1531,18 +1536,16 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
     if (int rc = rf_generate(p, seed, mode, noise_host)) return rc;
     if (int rc = rf_save_potential(p)) return rc;
     if (whole) return rf_execute_c2r(p);
-    return queue_xy(p, make_gen(p, 0, RF_NOISE_NATIVE, false), p->K, p->W, p->stream, false);
+    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K, p->W, p->stream, false);
   }
   if (int rc = ensure_p(p)) return rc;
   p->p2_valid = false;                               // (P is rewritten: a second-order potential made from the old one is stale)
   p->timed = whole;
-  p->pot_target = p->P;
-  p->resident_fast = (mode == RF_NOISE_RESIDENT);
+  CallDesc cd;
+  cd.pot_target = p->P;
+  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   const GenParams gp = make_gen(p, seed, mode, false);
-  const int rc = whole ? queue_c2r(p, gp, nullptr) : queue_xy(p, gp, nullptr, p->W, p->stream, false);
-  p->pot_target = nullptr;
-  p->resident_fast = false;
-  return rc;
+  return whole ? queue_c2r(p, cd, gp, nullptr) : queue_xy(p, cd, gp, nullptr, p->W, p->stream, false);
 }
 }  // namespace rfc
 extern "C" {
@@ -1558,7 +1561,7 @@ static int batch_issue(rf_plan* p, int n) {
   for (int i = 0; i < n; ++i) {
     GenParams gp = make_gen(p, 0, RF_NOISE_NATIVE, true);
     gp.seed_dev = p->seeds_dev + i;
-    if (int rc = queue_xyz(p, gp, nullptr, p->W, p->stream, p->stats + 2 * i, false)) return rc;
+    if (int rc = queue_xyz(p, CallDesc(), gp, nullptr, p->W, p->stream, p->stats + 2 * i, false)) return rc;
   }
   return 0;
 }
@@ -1587,14 +1590,11 @@ static int batch_prepare(rf_plan* p, int n) {
   }
   if (p->graphs.count(n)) return 0;
   if (int rc = ensure_x(p)) return rc;
-  const bool timed_save = p->timed;
-  p->timed = false;
   RF_HIP(hipStreamSynchronize(p->stream));
   rf_plan::BatchGraph bg;
   RF_HIP(hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal));
   const int rc = batch_issue(p, n);
   hipError_t e2 = hipStreamEndCapture(p->stream, &bg.graph);
-  p->timed = timed_save;
   if (rc) return rc;
   RF_HIP(e2);
   RF_HIP(hipGraphInstantiate(&bg.exec, bg.graph, nullptr, nullptr, 0));
@@ -1617,28 +1617,12 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
     RF_HIP(hipSetDevice(p->device));
     if (int rc = slab_batch(p, seeds, n)) return rc;
-    if (rms_out) {
-      std::vector<double> st(2 * (size_t)n);
-      RF_HIP(hipMemcpyAsync(st.data(), p->stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-      RF_HIP(hipStreamSynchronize(p->stream));
-      const double cnt = (double)p->nx * p->ny * p->nz;
-      for (int i = 0; i < n; ++i) {
-        const double m = st[2 * i] / cnt, v = st[2 * i + 1] / cnt - m * m;
-        rms_out[i] = v > 0 ? std::sqrt(v) : 0.0;
-      }
-    }
-    return 0;
+    return rms_out ? rms_from_stats(p, n, rms_out) : 0;
   }
   if (p->generic) {             // no graph: realisations one after the other
     RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
     RF_HIP(hipSetDevice(p->device));
-    if (p->stats_cap < n) {
-      RF_HIP(hipStreamSynchronize(p->stream));
-      if (p->stats) RF_HIP(hipFree(p->stats));
-      p->stats = nullptr;
-      RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
-      p->stats_cap = n + 64;
-    }
+    if (int rc = ensure_stats(p, n)) return rc;
     const bool fused = p->fused_generic;        // generation inside the x pass: no K, k_valid as it was (queue_c2r)
     if (!fused) { if (int rc = ensure_k(p)) return rc; }
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
@@ -1648,20 +1632,10 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
       if (int rc = generic_c2r(p, p->K, p->stats + 2 * i, false, fused ? &gp : nullptr)) return rc;
     }
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->cur = p->W; p->timed = false; p->real_valid = true; p->stats_valid = true;
-    if (!fused) { p->k_valid = true; p->aux_valid = false; }
-    p->stats_slot = n - 1;
-    if (rms_out) {
-      std::vector<double> st(2 * (size_t)n);
-      RF_HIP(hipMemcpyAsync(st.data(), p->stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-      RF_HIP(hipStreamSynchronize(p->stream));
-      const double cnt = (double)p->nx * p->ny * p->nz;
-      for (int i = 0; i < n; ++i) {
-        const double m = st[2 * i] / cnt, v = st[2 * i + 1] / cnt - m * m;
-        rms_out[i] = v > 0 ? std::sqrt(v) : 0.0;
-      }
-    }
-    return 0;
+    p->timed = false;
+    field_ready(p, n - 1);
+    if (!fused) kspace_ready(p);
+    return rms_out ? rms_from_stats(p, n, rms_out) : 0;
   }
   if (int rc = batch_prepare(p, n)) return rc;
   if (p->seeds_pin_cap < n) {
@@ -1683,23 +1657,9 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
   RF_HIP(hipGraphLaunch(p->graphs[n].exec, p->stream));
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->cur = p->W;
   p->timed = false;
-  p->real_valid = true;
-  p->stats_valid = true;
-  p->stats_slot = n - 1;
-  if (rms_out) {
-    std::vector<double> st(2 * (size_t)n);
-    RF_HIP(hipMemcpyAsync(st.data(), p->stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    RF_HIP(hipStreamSynchronize(p->stream));
-    const double cnt = (double)p->nx * p->ny * p->nz;
-    for (int i = 0; i < n; ++i) {
-      const double m = st[2 * i] / cnt;
-      const double v = st[2 * i + 1] / cnt - m * m;
-      rms_out[i] = v > 0 ? std::sqrt(v) : 0.0;
-    }
-  }
-  return 0;
+  field_ready(p, n - 1);
+  return rms_out ? rms_from_stats(p, n, rms_out) : 0;
 }
 
 int rf_moments(rf_plan* p, double* mean, double* std_out) {
@@ -1710,11 +1670,7 @@ int rf_moments(rf_plan* p, double* mean, double* std_out) {
   double st[2];
   RF_HIP(hipMemcpyAsync(st, p->stats + 2 * p->stats_slot, sizeof(st), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  const double cnt = (double)p->nx * p->ny * p->nz;
-  const double m = st[0] / cnt;
-  const double v = st[1] / cnt - m * m;
-  if (mean) *mean = m;
-  if (std_out) *std_out = v > 0 ? std::sqrt(v) : 0.0;
+  mean_std(p, st, mean, std_out);
   return 0;
 }
 
@@ -1759,7 +1715,8 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   RF_REQUIRE(mode == RF_NOISE_NATIVE || mode == RF_NOISE_EXTERNAL || mode == RF_NOISE_RESIDENT, "unknown noise mode");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  p->resident_fast = (mode == RF_NOISE_RESIDENT);
+  CallDesc cd;
+  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   const long long nzl = p->nzl, ntiles = (long long)p->nx * nzl / col_tile_cols(p->f64, p->ny);
   if (p->nypart < ntiles) {
     if (p->ypart) RF_HIP(hipFree(p->ypart));
@@ -1773,14 +1730,11 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   const double n3 = (double)p->nx * (double)p->ny * (double)p->nz, scale = 1.0 / n3;
   double *growth = p->lntab, *dens = p->lntab + p->nz, *A = p->lntab + 2 * p->nz, *B = p->lntab + 3 * p->nz, *sig = p->lntab + 4 * p->nz;
   RF_HIP(hipEventRecord(p->ev[0], s));
-  void* Xsave = p->X;
-  p->X = nullptr;                                    // plain layout: the accumulating y pass runs in place on W
   p->slab_timed = 0;
   p->slab_merged = 0;
-  int rc = queue_x(p, gp, nullptr, p->W, s, true);   // (timed: rf_kernel_ms reports x, y + tables, z + map, reduce of this call too)
-  p->X = Xsave;
-  p->resident_fast = false;
-  if (rc) return rc;
+  // into W, the plain layout whatever RF_FLAG_TRANSPOSED_INTERMEDIATE says: the accumulating y pass runs in place on W
+  // (timed: rf_kernel_ms reports x, y + tables, z + map, reduce of this call too)
+  if (int rc = queue_x(p, cd, gp, nullptr, p->W, s, true)) return rc;
   RF_HIP(hipEventRecord(p->ev[1], s));
   RF_HIP(launch_col_plain_acc(p->f64, p->ny, p->W, gy, (long long)p->nx * nzl, p->kz0, (int)nzl, p->ypart, p->tw_y, s));
   // rms = sqrt(S / (nx ny)) / N3  (rf_fft.h AccColIO)
@@ -1792,10 +1746,7 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, s));
   RF_HIP(hipEventRecord(p->ev[4], s));
   p->timed = true;
-  p->cur = p->W;
-  p->stats_slot = 0;
-  p->real_valid = true;
-  p->stats_valid = true;                             // (the moments of the DENSITY field now)
+  field_ready(p, 0);                                 // (the moments of the DENSITY field now)
   p->k_valid = false;
   if (sigma_out) {
     RF_HIP(hipMemcpyAsync(sigma_out, sig, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1870,8 +1821,7 @@ int rf_load_potential(rf_plan* p, double scale) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
   RF_HIP(launch_scale_copy(p->f64, p->P, p->K, (long long)p->nx * p->ny * (p->nzl + 1), (int)p->nzl + 1, p->ppitch, scale, p->stream));
-  p->k_valid = true;
-  p->aux_valid = false;
+  kspace_ready(p);
   return 0;
 }
 
@@ -1925,8 +1875,7 @@ int load_derivative(rf_plan* p, const P& g, const void* S) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
   RF_HIP(launch_derivative(p->f64, S, p->K, g, p->stream));
-  p->k_valid = true;
-  p->aux_valid = false;
+  kspace_ready(p);
   return 0;
 }
 // the component as a real field (rf_execute_gradient_c2r / rf_execute_hessian_c2r).  RF_GRAD_FROM_KSPACE consumes K on either kind of
@@ -1948,10 +1897,7 @@ int execute_derivative_c2r(rf_plan* p, const P& g, const void* S, int source) {
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
   if (int rc = generic_c2r(p, S, p->stats, true, &g)) return rc;
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->cur = p->W;
-  p->stats_slot = 0;
-  p->real_valid = true;
-  p->stats_valid = true;
+  field_ready(p, 0);
   if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
   return 0;
 }
@@ -2205,8 +2151,7 @@ int rf_upload_k(rf_plan* p, const void* host) {
   if (int rc = ensure_k(p)) return rc;
   RF_HIP(hipMemcpyAsync(p->K, host, p->k_bytes, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  p->k_valid = true;
-  p->aux_valid = false;
+  kspace_ready(p);
   return 0;
 }
 

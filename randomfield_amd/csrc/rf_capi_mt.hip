@@ -445,13 +445,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   if (int rc = mt_ensure_buffers(p, g)) return rc;
   if (int rc = ensure_x(p)) return rc;
   RF_HIP(hipStreamSynchronize(p->stream));
-  if (p->stats_cap < n) {
-    drop_graphs(p);
-    if (p->stats) RF_HIP(hipFree(p->stats));
-    p->stats = nullptr;
-    RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
-    p->stats_cap = n + 64;
-  }
+  if (int rc = ensure_stats(p, n)) return rc;
   if (!p->aux_stream) {
     RF_HIP(hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking));
     for (auto& e : p->bev) RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -487,6 +481,8 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     RF_HIP(hipEventRecord(p->bev[0], R));
     return 0;
   };
+  CallDesc cd;
+  cd.resident_fast = true;
   auto issue = [&]() -> int {
     RF_HIP(hipEventRecord(p->ev[0], S));
     RF_HIP(hipEventRecord(p->bev[1], S));
@@ -494,31 +490,30 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     if (int rc = replay(0)) return rc;
     for (int i = 0; i < n; ++i) {
       RF_HIP(hipStreamWaitEvent(S, p->bev[0], 0));        // the runs of seed i are complete
-      p->resident_fast = true;
       p->noise32_resident = true;                         // (queue_x selects the float32-pair kernel by it; cleared again on failure)
       const bool xp = p->X && xpose_ok(p);
-      const int rc = queue_x(p, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X : p->W, S, false);
-      p->resident_fast = false;
-      if (rc) return rc;
+      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X : p->W, S, false)) return rc;
       RF_HIP(hipEventRecord(p->bev[1], S));               // the generation pass of seed i has read the runs
       if (i + 1 < n) {
         RF_HIP(hipStreamWaitEvent(R, p->bev[1], 0));
         if (int rc2 = replay(i + 1)) return rc2;
       }
-      if (int rc3 = queue_yz(p, p->W, S, p->stats + 2 * i, false)) return rc3;
+      if (int rc3 = queue_yz(p, cd, p->W, S, p->stats + 2 * i, false)) return rc3;
     }
     RF_HIP(hipEventRecord(p->ev[4], S));
     return 0;
   };
   std::vector<unsigned long long> totals((size_t)n);
   std::vector<int> flags((size_t)n);
-  std::vector<double> st(2 * (size_t)n);
+  std::vector<double> rms((size_t)n);                      // (handed out only once every replay has been checked)
   int rc = issue();
   if (!rc) {
     hipError_t e = hipStreamSynchronize(R);
-    if (e == hipSuccess) e = hipMemcpyAsync(st.data(), p->stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, S);
-    if (e == hipSuccess) e = hipStreamSynchronize(S);
-    if (e == hipSuccess) e = hipMemcpy(totals.data(), dtotals, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(2, std::string("rf_realise_batch_reference: ") + hipGetErrorString(e));
+  }
+  if (!rc) rc = rms_from_stats(p, n, rms.data());          // (waits for S)
+  if (!rc) {
+    hipError_t e = hipMemcpy(totals.data(), dtotals, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(flags.data(), dflags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(2, std::string("rf_realise_batch_reference: ") + hipGetErrorString(e));
   }
@@ -532,14 +527,10 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     return drain(rc);
   }
   p->noise32_resident = true;                             // the last seed's deviates, as float32 pairs in the runs
-  p->cur = p->W; p->timed = false; p->real_valid = true; p->stats_valid = true; p->stats_slot = n - 1; p->k_valid = false;
-  if (rms_out) {
-    const double cnt = (double)p->nx * p->ny * p->nz;
-    for (int i = 0; i < n; ++i) {
-      const double m = st[2 * i] / cnt, v = st[2 * i + 1] / cnt - m * m;
-      rms_out[i] = v > 0 ? std::sqrt(v) : 0.0;
-    }
-  }
+  p->timed = false;
+  field_ready(p, n - 1);
+  p->k_valid = false;
+  if (rms_out) memcpy(rms_out, rms.data(), (size_t)n * sizeof(double));
   return 0;
 }
 

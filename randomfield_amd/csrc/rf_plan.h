@@ -194,11 +194,6 @@ struct rf_plan {
   uint64_t* seeds_pin[2] = {nullptr, nullptr};
   hipEvent_t seeds_ev[2] = {nullptr, nullptr};
   int seeds_pin_cap = 0, seeds_turn = 0;
-  bool resident_fast = false;             // the current call draws from the device-resident deviates (RF_NOISE_RESIDENT)
-  bool emit_potential = false;            // the current call transforms emit_pscale * delta(k) / k^2 instead of delta(k) (rf_realise_scaled_potential)
-  double emit_pscale = 0.0;
-  const double* zscale = nullptr;         // the current call's z pass multiplies plane z by zscale[z] (device table: ztab)
-  void* pot_target = nullptr;             // non-null while rf_realise_potential queues its x pass: where delta(k)/k^2 goes
   double* coll_scratch = nullptr;         // 2 doubles on the device for host-side all-reduces (never aliases `stats`)
   void* br_tmp = nullptr;                 // rf_realise_batch_reference: [start states n x 624][accepted totals n][flags n], kept between calls
   int br_cap = 0;                         // (allocating and freeing them cost a device synchronisation per call: one-seed batches are the Generator's call)
@@ -231,6 +226,16 @@ struct rf_plan {
 };
 
 namespace rfc {
+// What ONE call asks of the passes it queues.  The entry point builds it on its stack and hands it down by const reference
+// (queue_c2r ... queue_x / queue_yz / make_fast); a default-constructed one is a plain realisation.  Nothing of it outlives the call.
+struct CallDesc {
+  bool resident_fast = false;             // draw from the device-resident deviates (RF_NOISE_RESIDENT)
+  bool emit_potential = false;            // transform emit_pscale * delta(k) / k^2 instead of delta(k) (rf_realise_scaled_potential)
+  double emit_pscale = 0.0;
+  const double* zscale = nullptr;         // the z pass multiplies plane z by zscale[z] (device table: ztab)
+  void* pot_target = nullptr;             // the x pass also stores delta(k) / k^2 there (rf_realise_potential)
+};
+
 // (defined in rf_capi.hip)
 void drop_graphs(rf_plan* p);
 int ensure_k(rf_plan* p);
@@ -240,12 +245,15 @@ bool xpose_ok(const rf_plan* p);
 int slab_chunks(const rf_plan* p);
 GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev);
 int upload_noise(rf_plan* p, int mode, const double* noise_host);
-int queue_x(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, bool timed = false, int kz0c = -1, int nzlc = -1);
-int queue_xy(rf_plan* p, const GenParams& gp, const void* kspace, void* W, hipStream_t s, bool timed, int rbuf = 0);
+int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, bool timed = false, int kz0c = -1, int nzlc = -1);
+int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, bool timed, int rbuf = 0);
 int ensure_batch_buffers(rf_plan* p);
 int rebuild_peer_tab(rf_plan* p);
 int direct_barrier(rf_plan* p, hipStream_t s);
-int queue_yz(rf_plan* p, void* W, hipStream_t s, double* stats_out, bool timed);
+int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, bool timed);
+int ensure_stats(rf_plan* p, int n);
+int rms_from_stats(rf_plan* p, int n, double* rms_out);
+void field_ready(rf_plan* p, int slot);
 int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStream_t s);
 int queue_r2c_slab_rows(rf_plan* p, hipStream_t s);
 int queue_r2c_slab_cols(rf_plan* p, hipStream_t s);

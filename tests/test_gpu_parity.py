@@ -1328,6 +1328,98 @@ def test_fused_lognormal_realisation(hip, dpower, shape, dtype):
     plan.close()
 
 
+def _call_native(plan):
+    plan.realise(seed=21)
+
+
+def _call_resident32(plan):
+    plan.reference_noise(99, single=True)
+    assert plan.can_regenerate_potential("resident")                 # (the float32 pairs, not the float64 fallback of a short segment)
+    plan.realise(noise="resident")
+
+
+def _call_potential(plan):
+    plan.realise_potential(seed=22)
+
+
+def _call_scaled_potential(plan):
+    plan.realise_scaled_potential(seed=23, scale=-2.5e-3, factor_z=np.exp(-0.01 * np.arange(plan.nz)))
+
+
+def _call_lognormal(plan):
+    return plan.realise_lognormal(seed=24)
+
+
+def _call_batch(plan):
+    return tuple(plan.realise_batch([25, 26]))
+
+
+def _call_refused(plan):
+    with pytest.raises(RuntimeError):
+        plan.realise(noise="resident")                               # no deviates on this plan (yet)
+
+
+_CALLS = [_call_native, _call_resident32, _call_potential, _call_scaled_potential, _call_lognormal, _call_batch]
+
+
+def test_one_call_leaves_nothing_behind_for_the_next(hip, dpower):
+    """What one entry point asks of the passes (resident deviates, the scaled potential and its scale, the z table of the z pass,
+    the target of the stored potential) belongs to that call alone: for every ordered pair (A, B) of realise (native; resident
+    float32 pairs), realise_potential, realise_scaled_potential(factor_z), realise_lognormal, realise_batch and -- as A only -- a
+    refused realise(noise='resident'), B straight after A on one plan gives bit for bit the field, the moments and the return
+    value that B gives as the first call of a plan."""
+    from randomfield_amd import powertools
+    k, Pk = dpower
+    n = 64
+    kgrid = powertools.ksq_axes(n, n, n, SPACING)
+    table = cpu_ref.sigma_table(k, Pk, n, n, n, SPACING)
+    growth, dens = np.exp(-0.5 * np.arange(n) / n), 0.5 + np.arange(n) / n
+
+    def run(calls):
+        plan = hip.DevicePlan(n, n, n, np.complex64)
+        plan.set_kgrid(*kgrid)
+        plan.set_power(*table)
+        plan.set_z_tables(growth, dens)
+        for call in calls:
+            ret = call(plan)
+        out = (ret, plan.moments(), plan.download_real())
+        plan.close()
+        return out
+
+    fresh = [run([b]) for b in _CALLS]
+    for a in _CALLS + [_call_refused]:
+        for b, want in zip(_CALLS, fresh):
+            ret, moments, field = run([a, b])
+            what = "%s after %s" % (b.__name__, a.__name__)
+            assert ret == want[0] and moments == want[1], what
+            assert np.array_equal(field, want[2]), what
+
+
+def test_fused_lognormal_ignores_and_preserves_the_blocked_intermediate(hip, dpower):
+    """rf_realise_lognormal runs its accumulating y pass in place on W, whatever RF_FLAG_TRANSPOSED_INTERMEDIATE says: on a plan that
+    has allocated the blocked intermediate X it gives the flag-off plan's density field and sigma bit for bit, and the plain
+    realisation that follows goes through X as the one before did."""
+    k, Pk = dpower
+    n, seed = 64, 21
+    growth, dens = np.exp(-0.5 * np.arange(n) / n), 0.5 + np.arange(n) / n
+    plain = make_plan(hip, (n, n, n), np.complex64, k, Pk)
+    plain.set_z_tables(growth, dens)
+    sigma = plain.realise_lognormal(seed=seed)
+    want, want_moments = plain.download_real(), plain.moments()
+    plan = make_plan(hip, (n, n, n), np.complex64, k, Pk)
+    plan.set_z_tables(growth, dens)
+    plan.set_transposed_intermediate(True)
+    plan.realise(seed=seed)
+    assert plan.nbytes > plain.nbytes                       # (X is there)
+    first, first_moments = plan.download_real(), plan.moments()
+    assert plan.realise_lognormal(seed=seed) == sigma
+    assert np.array_equal(plan.download_real(), want) and plan.moments() == want_moments
+    plan.realise(seed=seed)
+    assert np.array_equal(plan.download_real(), first) and plan.moments() == first_moments
+    plain.close()
+    plan.close()
+
+
 def test_reference_rng_array_and_none_seeds(hip, dpower):
     """random.py:24 hands the seed to np.random.RandomState: array seeds (init_by_array) and None are replayed on the
     GPU like integer seeds -- no host deviates are drawn or uploaded."""
