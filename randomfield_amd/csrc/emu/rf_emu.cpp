@@ -327,7 +327,7 @@ int dispatch_row_c2c(int M, cplx<T>* base, long long nrows, double scale) {
   ScaledRowIO<T> io; io.base = base; io.M_of = M; io.scale = (T)scale;
   switch (M) {
 #define X(MM) case MM: run_row_c2c<typename RowSel<T, MM>::type, DIR>(io, nrows, tw.data()); return 0;
-    RF_ROW_SIZES(X)
+    RF_ROWC_SIZES(X)
 #undef X
     default: return -1;
   }
