@@ -57,6 +57,11 @@ int rf_particles_set_paint_form(rf_plan* plan, int form);
 /* the tiled kernel's brick (lattice cells per axis, brick3[3]) and halo (cells on every side): the tile is brick + 2 halo per axis */
 int rf_particles_paint_geometry(rf_plan* plan, int* brick3, int* halo);
 
+/* What the plans of this process hold right now: bytes of device memory, HIP events, HIP streams (every allocation a plan makes is an
+ * owning member of it, csrc/rf_owned.h).  Back at their earlier values once the plans made in between are destroyed: "freed with the plan",
+ * testable without the device-wide free memory that other processes change. */
+int rf_diag_live_resources(size_t* device_bytes, int* events, int* streams);
+
 /* ---- virtual ranks: the multi-GPU pipeline step by step on one device ------ */
 /* The slab pipeline in separate steps, for tests and custom exchanges: forward = generation + x and y
  * passes on this rank's kz slab; backward = z pass on this rank's x slab + local (sum, sumsq).

@@ -1,17 +1,6 @@
 // rf_capi.hip -- the C-ABI of include/randomfield_hip.h: plan object, device buffers, stream / graph orchestration of the HIP kernels
 // (plans, inputs, realisations, transforms, host <-> device, timing; the replay of numpy's stream: rf_capi_mt.hip; the communicator
 // and the slab pipeline step by step: rf_capi_slab.hip; shared helpers: rf_plan.h).
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include <rccl/rccl.h>
-
 #include "rf_plan.h"
 
 using namespace rf;
@@ -66,27 +55,16 @@ void drop_graphs(rf_plan* p) {
   p->graphs.clear();
 }
 
-int ensure_k(rf_plan* p) {
-  if (!p->K) RF_HIP(hipMalloc(&p->K, p->k_bytes));
-  return 0;
-}
+int ensure_k(rf_plan* p) { RF_HIP(p->K.reserve(p->k_bytes)); return 0; }
 
 // The saved potential is written by a second store stream of the generation pass, row for row next to the field's.  The time of
 // that pass is bimodal -- 5.2 or 5.75 ms for the whole default call at 1024^3 -- and tools/pot_offset.py shows what decides it:
 // NOT the virtual addresses (45 plans at identical virtual addresses of both arrays and 15 offsets of the potential inside its
 // allocation, 256 B ... 4 MiB: either mode at every offset, the same offset in both modes) but the physical pages the driver
 // happens to back them with, which user space neither sees nor chooses: the array sits at offset 0 of its allocation.
-int ensure_p(rf_plan* p) {
-  if (p->P) return 0;
-  RF_HIP(hipMalloc(&p->P_base, p->p_bytes));
-  p->P = p->P_base;
-  return 0;
-}
+int ensure_p(rf_plan* p) { RF_HIP(p->P.reserve(p->p_bytes)); return 0; }
 
-int ensure_g(rf_plan* p) {
-  if (!p->G) RF_HIP(hipMalloc(&p->G, p->k_bytes));
-  return 0;
-}
+int ensure_g(rf_plan* p) { RF_HIP(p->G.reserve(p->k_bytes)); return 0; }
 
 // May the plan hand the x pass's output to the y and z passes through the blocked intermediate X (rf_fft.h xblock_*_geom)?
 // Single-rank tiled plans whose x and y passes use tiles of the same width, whose kz runs are whole tiles and whose z pass
@@ -98,7 +76,7 @@ bool xpose_ok(const rf_plan* p) {
   return tcx > 0 && tcx == tcy && p->nzl >= tcx && p->nzl % tcx == 0 && row_c2r_xgather_ok(p->f64, (int)p->nzc, tcx, xpose_row_block(p));
 }
 int ensure_x(rf_plan* p) {
-  if (!p->X && xpose_ok(p)) RF_HIP(hipMalloc(&p->X, p->w_bytes));
+  if (xpose_ok(p)) RF_HIP(p->X.reserve(p->w_bytes));
   return 0;
 }
 
@@ -131,23 +109,19 @@ bool generic_shape(int nx, int ny, int nz, int f64, GenericAxis& ax, GenericAxis
 GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev) {
   GenParams g;
   g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
-  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
-  g.xt = p->xt; g.st = p->st; g.sl = p->sl; g.bin = p->bin;
+  g.kx2 = p->kx2.get(); g.ky2 = p->ky2.get(); g.kz2 = p->kz2.get();
+  g.xt = p->xt.get(); g.st = p->st.get(); g.sl = p->sl.get(); g.bin = p->bin.get();
   g.nt = p->nt; g.nbins = p->nbins; g.x0 = p->x0; g.inv_dx = p->inv_dx;
   g.noise_mode = (mode == RF_NOISE_RESIDENT) ? (int)RF_NOISE_EXTERNAL : mode; g.seed = seed; g.seed_dev = nullptr; (void)seed_from_dev;   // graph batches point seed_dev at seeds_dev[i]
-  g.noise = p->noise;
+  g.noise = p->noise.get();
   g.zpitch = p->nzl + 1; g.zoff = p->kz0;      // side arrays (noise, K, P) hold this rank's planes + the Nyquist plane
   return g;
 }
 
 int ensure_noise(rf_plan* p) {
-  const size_t n = 2 * (size_t)p->nx * p->ny * (p->nzl + 1);       // this rank's planes + the Nyquist plane
-  if (p->noise_cap < n) {
-    if (p->noise) RF_HIP(hipFree(p->noise));
-    p->noise = nullptr; p->noise_cap = 0; p->noise_resident = false;
-    RF_HIP(hipMalloc((void**)&p->noise, n * sizeof(double)));
-    p->noise_cap = n;
-  }
+  const size_t need = 2 * (size_t)p->nx * p->ny * (p->nzl + 1) * sizeof(double);       // this rank's planes + the Nyquist plane
+  if (p->noise.bytes < need) p->noise_resident = false;
+  RF_HIP(p->noise.reserve(need));
   return 0;
 }
 
@@ -163,10 +137,10 @@ int upload_noise(rf_plan* p, int mode, const double* noise_host) {
   // planes and the Nyquist plane (one rank: everything, one contiguous copy)
   const size_t cell = 2 * sizeof(double), hp = (size_t)(p->nzc + 1) * cell, dp = (size_t)(p->nzl + 1) * cell, rows = (size_t)p->nx * p->ny;
   if (p->nranks == 1) {
-    RF_HIP(hipMemcpyAsync(p->noise, noise_host, rows * hp, hipMemcpyHostToDevice, p->stream));
+    RF_HIP(hipMemcpyAsync(p->noise.get(), noise_host, rows * hp, hipMemcpyHostToDevice, p->stream));
   } else {
-    RF_HIP(hipMemcpy2DAsync(p->noise, dp, (const char*)noise_host + (size_t)p->kz0 * cell, hp, (size_t)p->nzl * cell, rows, hipMemcpyHostToDevice, p->stream));
-    RF_HIP(hipMemcpy2DAsync((char*)p->noise + (size_t)p->nzl * cell, dp, (const char*)noise_host + (size_t)p->nzc * cell, hp, cell, rows, hipMemcpyHostToDevice, p->stream));
+    RF_HIP(hipMemcpy2DAsync(p->noise.get(), dp, (const char*)noise_host + (size_t)p->kz0 * cell, hp, (size_t)p->nzl * cell, rows, hipMemcpyHostToDevice, p->stream));
+    RF_HIP(hipMemcpy2DAsync((char*)p->noise.get() + (size_t)p->nzl * cell, dp, (const char*)noise_host + (size_t)p->nzc * cell, hp, cell, rows, hipMemcpyHostToDevice, p->stream));
   }
   p->noise_resident = true;
   p->noise32_resident = false;
@@ -177,7 +151,7 @@ FastGenParams make_fast(rf_plan* p, const CallDesc& cd, uint64_t seed, bool seed
   FastGenParams f;
   f.nx = p->nx; f.ny = p->ny; f.nz = p->nz;
   f.dkx = p->fdkx; f.dky = p->fdky; f.dkz = p->fdkz;
-  f.rec = p->frec; f.nbins = p->fnbins; f.u_scale = p->fu_scale; f.u_off = p->fu_off;
+  f.rec = p->frec.get(); f.nbins = p->fnbins; f.u_scale = p->fu_scale; f.u_off = p->fu_off;
   f.seed = seed; f.seed_dev = seed_from_dev ? seed_ptr : nullptr;
   f.noise = nullptr; f.noise32 = nullptr;
   f.rowtab = nullptr; f.seg_cap = 0;
@@ -222,14 +196,13 @@ int build_fast(rf_plan* p) {
     return 0;
   p->fu_scale = (float)(0.5 * std::log10(2.0) / dx);
   p->fu_off = (float)(-x0 / dx);
-  if (p->frec) RF_HIP(hipFree(p->frec));
-  p->frec = nullptr;
-  RF_HIP(hipMalloc((void**)&p->frec, rec.size() * sizeof(FastRec)));
-  RF_HIP(hipMemcpy(p->frec, rec.data(), rec.size() * sizeof(FastRec), hipMemcpyHostToDevice));
+  RF_HIP(p->frec.release());                    // (always a fresh table, as long as the new records)
+  RF_HIP(p->frec.reserve(rec.size() * sizeof(FastRec)));
+  RF_HIP(hipMemcpy(p->frec.get(), rec.data(), rec.size() * sizeof(FastRec), hipMemcpyHostToDevice));
   p->fnbins = (int)rec.size();
   // side buffer of the repaired kz = 0 slots (one complex per mode (ix, iy): 8 MB at 1024^2 float32), filled and read inside the
   // generation pass by the rank that owns kz = 0 -- every rank in replicated-generation mode
-  if (!p->fixbuf) RF_HIP(hipMalloc(&p->fixbuf, (size_t)p->nx * p->ny * p->csize));
+  RF_HIP(p->fixbuf.reserve((size_t)p->nx * p->ny * p->csize));
   p->have_fast = true;
   return 0;
 }
@@ -262,22 +235,22 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   const int kz0 = kz0c >= 0 ? kz0c : (rep ? 0 : p->kz0);
   // W == p->X: the blocked intermediate [x block][kz tile][ny][rb][TC] -- a tile (all nx rows of TC adjacent kz of one iy) is
   // nx / rb contiguous chunks of rb * TC cells there
-  const ColGeom gx = (W == p->X && W != nullptr)
+  const ColGeom gx = (W == p->X.ptr && W != nullptr)
                          ? xblock_x_geom(p->nx, p->ny, nzl, col_gen_tile_cols(p->f64, p->nx), xpose_row_block(p))
                          : ColGeom{(long long)p->ny * nzl, 0, (long long)p->ny * nzl};
   if (timed) { RF_HIP(hipEventRecord(p->ev[5], sx)); p->repair_timed = fast; }   // overwritten by the launcher if it splits
   FastGenParams fgp = make_fast(p, cd, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
   if (fast_noise && p->noise32_resident) {
-    fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch);      // (a later float64 replay reuses the scratch: it clears noise32_resident)
-    fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt_rowtab); fgp.seg_cap = p->seg_cap;
+    fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch.ptr);      // (a later float64 replay reuses the scratch: it clears noise32_resident)
+    fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt_rowtab.ptr); fgp.seg_cap = p->seg_cap;
   }
   else if (fast_noise) fgp.noise = gp.noise;
   if (fast)
     RF_HIP(launch_col_fastgen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, fgp,
-                              kz0, (int)nzl, p->tw_x, sx, false, timed ? p->ev[5] : nullptr,
-                              rep ? p->rank * p->nxl : 0, rep ? (p->rank + 1) * p->nxl : 1 << 30, cd.pot_target, p->fixbuf));
+                              kz0, (int)nzl, p->tw_x.ptr, sx, false, timed ? p->ev[5] : nullptr,
+                              rep ? p->rank * p->nxl : 0, rep ? (p->rank + 1) * p->nxl : 1 << 30, cd.pot_target, p->fixbuf.ptr));
   else
-    RF_HIP(launch_col_gen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, gp, kspace, kz0, (int)nzl, p->tw_x, sx));
+    RF_HIP(launch_col_gen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, gp, kspace, kz0, (int)nzl, p->tw_x.ptr, sx));
   return 0;
 }
 
@@ -301,10 +274,10 @@ int rebuild_peer_tab(rf_plan* p) {
         h_tab[((size_t)b * C + c) * P + h] = p->peer_R[b][h] ? (char*)p->peer_R[b][h] + ((long long)p->rank * C + c - h) * blk_c : nullptr;
   RF_HIP(hipStreamSynchronize(p->stream));
   if (p->comm_stream) RF_HIP(hipStreamSynchronize(p->comm_stream));
-  if (p->peer_tab) RF_HIP(hipFree(p->peer_tab));
-  p->peer_tab = nullptr;
-  RF_HIP(hipMalloc((void**)&p->peer_tab, h_tab.size() * sizeof(void*)));
-  RF_HIP(hipMemcpy(p->peer_tab, h_tab.data(), h_tab.size() * sizeof(void*), hipMemcpyHostToDevice));
+  p->peer_tab_chunks = 0;
+  RF_HIP(p->peer_tab.release());
+  RF_HIP(p->peer_tab.reserve(h_tab.size() * sizeof(void*)));
+  RF_HIP(hipMemcpy(p->peer_tab.get(), h_tab.data(), h_tab.size() * sizeof(void*), hipMemcpyHostToDevice));
   p->peer_tab_chunks = C;
   return 0;
 }
@@ -313,27 +286,21 @@ int rebuild_peer_tab(rf_plan* p) {
 // buffer and the next stores into it): a 2-double all-reduce on its own scratch words.  Virtual ranks (no communicator) are ordered
 // by the host that drives them.
 int direct_barrier(rf_plan* p, hipStream_t s) {
-  if (p->nranks > 1 && p->comm) RF_NCCL(g_rccl.AllReduce(p->coll_scratch + 2, p->coll_scratch + 2, 2, ncclFloat64, ncclSum, p->comm, s));
+  if (p->nranks > 1 && p->comm) RF_NCCL(g_rccl.AllReduce(p->coll_scratch.get() + 2, p->coll_scratch.get() + 2, 2, ncclFloat64, ncclSum, p->comm, s));
   return 0;
 }
 
 // the y pass of sub-slab c (the whole kz slab when the plan does not chunk) out of W into the peers' receive buffers number `rbuf`
 int queue_y_direct(rf_plan* p, const void* W, int rbuf, hipStream_t s, int c) {
   const int C = slab_chunks(p);
-  RF_REQUIRE(p->peer_tab && p->peer_tab_chunks == C && c >= 0 && c < C, "direct exchange: the destination table does not match the plan's exchange chunks");
+  RF_REQUIRE(p->peer_tab.get() && p->peer_tab_chunks == C && c >= 0 && c < C, "direct exchange: the destination table does not match the plan's exchange chunks");
   RF_REQUIRE(p->peer_R[rbuf][p->rank] != nullptr, "direct exchange: the second receive buffer does not exist");
   const long long nzc_ = p->nzl / C;
   const ColGeom gy{nzc_, (long long)p->ny * nzc_, nzc_};
   int shift = 0;
   while ((1 << shift) < p->nxl) ++shift;
-  RF_HIP(launch_col_direct(p->f64, p->ny, (const char*)W + (size_t)c * chunk_bytes(p), gy, p->peer_tab + ((size_t)rbuf * C + c) * p->nranks, shift,
-                           (long long)p->nx * nzc_, p->tw_y, s));
-  return 0;
-}
-
-// grow a vector of events to n (flags as hipEventCreateWithFlags takes them)
-int ensure_events(std::vector<hipEvent_t>& ev, size_t n, unsigned flags) {
-  while (ev.size() < n) { hipEvent_t e; RF_HIP(hipEventCreateWithFlags(&e, flags)); ev.push_back(e); }
+  RF_HIP(launch_col_direct(p->f64, p->ny, (const char*)W + (size_t)c * chunk_bytes(p), gy, p->peer_tab.get() + ((size_t)rbuf * C + c) * p->nranks, shift,
+                           (long long)p->nx * nzc_, p->tw_y.ptr, s));
   return 0;
 }
 
@@ -343,7 +310,7 @@ int ensure_events(std::vector<hipEvent_t>& ev, size_t n, unsigned flags) {
 int direct_forward(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, int rbuf, hipStream_t A, hipStream_t Y, bool timed) {
   const int C = slab_chunks(p);
   const long long nzc_ = p->nzl / C;
-  if (Y != A) if (int rc = ensure_events(p->chunk_ev, C + 1, hipEventDisableTiming)) return rc;
+  if (Y != A) RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
   for (int c = 0; c < C; ++c) {
     if (C == 1) { if (int rc = queue_x(p, cd, gp, kspace, W, A, timed)) return rc; }
     else if (int rc = queue_x(p, cd, gp, kspace, (char*)W + (size_t)c * chunk_bytes(p), A, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
@@ -365,7 +332,7 @@ int queue_xy_chunk(rf_plan* p, const CallDesc& cd, const GenParams& gp, const vo
   char* Wc = (char*)W + (size_t)c * chunk_bytes(p);
   if (int rc = queue_x(p, cd, gp, kspace, Wc, s, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
   const ColGeom gy{nzc_, (long long)p->ny * nzc_, nzc_};
-  RF_HIP(launch_col_plain(p->f64, p->ny, +1, Wc, gy, (long long)p->nx * nzc_, p->tw_y, s));
+  RF_HIP(launch_col_plain(p->f64, p->ny, +1, Wc, gy, (long long)p->nx * nzc_, p->tw_y.ptr, s));
   return 0;
 }
 
@@ -383,7 +350,7 @@ int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ks
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
   if (int rc = queue_x(p, cd, gp, kspace, W, s, timed)) return rc;
   if (timed) RF_HIP(hipEventRecord(p->ev[1], s));
-  RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, nxp * nzl, p->tw_y, s));
+  RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, nxp * nzl, p->tw_y.ptr, s));
   if (timed) RF_HIP(hipEventRecord(p->ev[2], s));
   return 0;
 }
@@ -394,8 +361,8 @@ int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStrea
   const long long nrows = (long long)p->nxl * p->ny;
   const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
   const long long nzseg = p->nzl / slab_chunks(p);            // planes per received segment: nranks * chunks of them make a row
-  RF_HIP(launch_row_c2r_gather(p->f64, p->nzc, R, W, nrows, scale, (int)nzseg, nrows * nzseg, p->tw_z, p->partials, s));
-  RF_HIP(launch_reduce_partials(p->partials, p->npartials, stats_out, p->partials + 2 * p->npartials, s));
+  RF_HIP(launch_row_c2r_gather(p->f64, p->nzc, R, W, nrows, scale, (int)nzseg, nrows * nzseg, p->tw_z.ptr, p->partials.get(), s));
+  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
   p->cur = W;
   p->real_valid = true;
   return 0;
@@ -425,7 +392,7 @@ int queue_exchange_rccl(rf_plan* p, const void* W, void* R, hipStream_t s, int c
       const void* sp[16]; void* dp[16];
       int nb = 0;
       for (int h = 0; h < p->nranks; ++h) if (h != p->rank) { sp[nb] = src(c, h); dp[nb] = dst(c, h); ++nb; }
-      RF_HIP(launch_exchange_standin(sp, dp, nb, blk, p->standin_wg, p->standin_read_pct, p->standin_write_pct, (unsigned*)p->coll_scratch, s));
+      RF_HIP(launch_exchange_standin(sp, dp, nb, blk, p->standin_wg, p->standin_read_pct, p->standin_write_pct, (unsigned*)p->coll_scratch.get(), s));
     }
     return 0;
   }
@@ -445,19 +412,13 @@ int queue_exchange_rccl(rf_plan* p, const void* W, void* R, hipStream_t s, int c
   return 0;
 }
 
-int ensure_comm_stream(rf_plan* p) {
-  if (!p->comm_stream) RF_HIP(hipStreamCreateWithFlags(&p->comm_stream, hipStreamNonBlocking));
-  return 0;
-}
-
-// second (send, receive) buffer pair, exchange stream and events of the pipelined batches
+// second (send, receive) buffer pair, exchange stream and events of the pipelined batches (each step idempotent: whatever failed is
+// tried again by the next call)
 int ensure_batch_buffers(rf_plan* p) {
-  if (!p->W2) {
-    RF_HIP(hipMalloc(&p->W2, p->w_bytes));
-    RF_HIP(hipMalloc(&p->R2, p->w_bytes));
-    if (int rc = ensure_comm_stream(p)) return rc;
-    for (auto& e : p->pev) RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  RF_HIP(p->W2.reserve(p->w_bytes));
+  RF_HIP(p->R2.reserve(p->w_bytes));
+  RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
+  RF_HIP(p->pev.ensure(6, hipEventDisableTiming));
   return 0;
 }
 
@@ -473,9 +434,9 @@ int ensure_batch_buffers(rf_plan* p) {
 // (direct_overlap = 0: everything on A in the order x(i) y(i) z(i - 1) B(i).)
 int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
   RF_REQUIRE(p->nranks == 1 || p->comm || p->direct_standin, "virtual ranks linked for the direct exchange run step by step (rf_slab_forward, rf_slab_backward)");
-  void* Wb[2] = {p->W, p->W2};
-  void* Rb[2] = {p->R, p->R2};
-  hipEvent_t *ev_fwd = p->pev, *ev_bar = p->pev + 2, *ev_z = p->pev + 4;
+  void* Wb[2] = {p->W.ptr, p->W2.ptr};
+  void* Rb[2] = {p->R.ptr, p->R2.ptr};
+  const hipEvent_t *ev_fwd = p->pev.ev.data(), *ev_bar = ev_fwd + 2, *ev_z = ev_fwd + 4;
   const bool two = p->direct_overlap != 0;
   hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
   RF_HIP(hipEventRecord(p->ev[0], A));
@@ -490,7 +451,7 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
     }
     if (i >= 1) {
       if (two) RF_HIP(hipStreamWaitEvent(A, ev_bar[pb], 0));
-      if (int rc = queue_z_slab(p, Rb[pb], Wb[pb], p->stats + 2 * (i - 1), A)) return rc;
+      if (int rc = queue_z_slab(p, Rb[pb], Wb[pb], p->stats.get() + 2 * (i - 1), A)) return rc;
       if (two) RF_HIP(hipEventRecord(ev_z[pb], A));
     }
     if (i < n) {
@@ -502,7 +463,7 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
   if (p->nranks > 1 && p->comm) {                                 // the moments of all n realisations: one all-reduce, on the stream that drives the communicator
     const int lb = (n - 1) & 1;
     if (two) RF_HIP(hipStreamWaitEvent(Y, ev_z[lb], 0));
-    RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, Y));
+    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, Y));
     if (two) { RF_HIP(hipEventRecord(ev_bar[lb], Y)); RF_HIP(hipStreamWaitEvent(A, ev_bar[lb], 0)); }
   }
   RF_HIP(hipEventRecord(p->ev[4], A));
@@ -516,7 +477,7 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
 
 // The plan holds the real-space field of its last call in W, and that field's (sum, sumsq) in pair `slot` of `stats`
 void field_ready(rf_plan* p, int slot) {
-  p->cur = p->W;
+  p->cur = p->W.ptr;
   p->stats_slot = slot;
   p->real_valid = true;
   p->stats_valid = true;
@@ -524,13 +485,10 @@ void field_ready(rf_plan* p, int slot) {
 
 // room for the (sum, sumsq) pairs of n realisations (captured batch graphs carry the array's address: they go)
 int ensure_stats(rf_plan* p, int n) {
-  if (p->stats_cap >= n) return 0;
+  if (p->stats.bytes >= 2 * (size_t)n * sizeof(double)) return 0;
   RF_HIP(hipStreamSynchronize(p->stream));
   drop_graphs(p);
-  if (p->stats) RF_HIP(hipFree(p->stats));
-  p->stats = nullptr; p->stats_cap = 0;
-  RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)(n + 64) * sizeof(double)));
-  p->stats_cap = n + 64;
+  RF_HIP(p->stats.reserve(2 * (size_t)(n + 64) * sizeof(double)));
   return 0;
 }
 
@@ -546,11 +504,11 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
     const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
     for (int i = 0; i < n; ++i) {
-      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W, p->stream, false)) return rc;
-      RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W, (long long)p->nxl * p->ny, scale, p->tw_z, p->partials, p->stream));
-      RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats + 2 * i, p->partials + 2 * p->npartials, p->stream));
+      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W.ptr, p->stream, false)) return rc;
+      RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nxl * p->ny, scale, p->tw_z.ptr, p->partials.get(), p->stream));
+      RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get() + 2 * i, p->partials.get() + 2 * p->npartials, p->stream));
     }
-    if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, p->stream));
+    if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, p->stream));
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
     p->timed = false;
     field_ready(p, n - 1);
@@ -558,9 +516,9 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
   }
   if (int rc = ensure_batch_buffers(p)) return rc;
   if (direct_active(p)) return slab_batch_direct(p, seeds, n);
-  void* Wb[2] = {p->W, p->W2};
-  void* Rb[2] = {p->R, p->R2};
-  hipEvent_t *ev_fwd = p->pev, *ev_exch = p->pev + 2, *ev_z = p->pev + 4;
+  void* Wb[2] = {p->W.ptr, p->W2.ptr};
+  void* Rb[2] = {p->R.ptr, p->R2.ptr};
+  const hipEvent_t *ev_fwd = p->pev.ev.data(), *ev_exch = ev_fwd + 2, *ev_z = ev_fwd + 4;
   hipStream_t A = p->stream, C = p->comm_stream;
   RF_HIP(hipEventRecord(p->ev[0], A));
   for (int i = 0; i <= n; ++i) {
@@ -576,7 +534,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
     if (i >= 1) {
       const int pb = (i - 1) & 1;
       RF_HIP(hipStreamWaitEvent(A, ev_exch[pb], 0));
-      if (int rc = queue_z_slab(p, Rb[pb], Wb[pb], p->stats + 2 * (i - 1), A)) return rc;
+      if (int rc = queue_z_slab(p, Rb[pb], Wb[pb], p->stats.get() + 2 * (i - 1), A)) return rc;
       RF_HIP(hipEventRecord(ev_z[pb], A));
     }
   }
@@ -585,7 +543,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
     // stream too, behind the last z pass (event), and the compute stream waits for it
     const int lb = (n - 1) & 1;
     RF_HIP(hipStreamWaitEvent(C, ev_z[lb], 0));
-    RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, C));
+    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, C));
     RF_HIP(hipEventRecord(ev_exch[lb], C));
     RF_HIP(hipStreamWaitEvent(A, ev_exch[lb], 0));
   }
@@ -624,7 +582,7 @@ int yz_slab_planes(const rf_plan* p) {
 // on X, z pass gathering X -> W).
 // Host sink (rf_set_host_sink).  The z pass of a slab of x planes has been queued on s: mark that point with an event ...
 int sink_mark(rf_plan* p, int slab, hipStream_t s) {
-  if (int rc = ensure_events(p->sink_ev, slab + 1, hipEventDisableTiming)) return rc;
+  RF_HIP(p->sink_ev.ensure(slab + 1, hipEventDisableTiming));
   RF_HIP(hipEventRecord(p->sink_ev[slab], s));
   return 0;
 }
@@ -657,7 +615,7 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
     sink = cap == hipStreamCaptureStatusNone;      // (a captured batch keeps its fields on the device)
   }
   const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-  const bool xp = p->X && xpose_ok(p);
+  const bool xp = p->X.ptr && xpose_ok(p);
   const long long rb = xpose_row_block(p), tc = col_tile_cols(p->f64, p->ny);
   const ColGeom gy = xp ? xblock_y_geom(p->nx, p->ny, nzl, tc, rb) : ColGeom{nzl, (long long)p->ny * nzl, nzl};
   long long B = yz_slab_planes(p);
@@ -666,7 +624,7 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
   const int nslab = (int)((p->nx + B - 1) / B);
   const long long plane = (long long)p->ny * nzl * (long long)p->csize, tiles_per_plane = p->npartials / p->nx;
   if (timed) {
-    if (int rc = ensure_events(p->slab_ev, 2 * nslab, hipEventDefault)) return rc;
+    RF_HIP(p->slab_ev.ensure(2 * nslab, hipEventDefault));
     p->slab_timed = nslab;
   }
   // untimed single-rank float32 realisations at the sizes rf_k_yz.hip serves: the z pass of slab i and the y pass of slab i + 1 share a
@@ -679,20 +637,20 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
       yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, B * nzl) &&
       (Blast == B || yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, Blast * nzl))) {
     if (timed) {
-      if (int rc = ensure_events(p->slab_ev, nslab + 1, hipEventDefault)) return rc;
+      RF_HIP(p->slab_ev.ensure(nslab + 1, hipEventDefault));
       p->slab_merged = nslab;
       p->slab_timed = 0;       // (rf_kernel_ms: the merged form's events apply, the per-pass pairs of slab_ev were not recorded by this call)
     }
-    RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, B * nzl, p->tw_y, s));
+    RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, B * nzl, p->tw_y.ptr, s));
     if (timed) RF_HIP(hipEventRecord(p->slab_ev[0], s));
     for (int i = 0; i < nslab; ++i) {
       char* Ws = (char*)W + (long long)i * B * plane;
-      double* part = p->partials + 2 * (long long)i * B * tiles_per_plane;
+      double* part = p->partials.get() + 2 * (long long)i * B * tiles_per_plane;
       const long long nb = i + 1 < nslab ? B : Blast, nb_next = i + 2 < nslab ? B : Blast;       // planes of slab i / of slab i + 1
       if (i + 1 < nslab)
-        RF_HIP(launch_yz_merged(p->f64, p->ny, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z, part, Ws + B * plane, gy, nb_next * nzl, p->tw_y, s));
+        RF_HIP(launch_yz_merged(p->f64, p->ny, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, Ws + B * plane, gy, nb_next * nzl, p->tw_y.ptr, s));
       else
-        RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z, part, s));
+        RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, s));
       if (timed) RF_HIP(hipEventRecord(p->slab_ev[i + 1], s));
       if (sink) {
         if (int rc = sink_mark(p, i, s)) return rc;
@@ -700,7 +658,7 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
       }
     }
     if (timed) { RF_HIP(hipEventRecord(p->ev[2], s)); RF_HIP(hipEventRecord(p->ev[3], s)); }
-    RF_HIP(launch_reduce_partials(p->partials, p->npartials, stats_out, p->partials + 2 * p->npartials, s));
+    RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
     if (timed) RF_HIP(hipEventRecord(p->ev[4], s));
     if (sink) {
       if (int rc = sink_copy(p, W, (long long)(nslab - 1) * B, Blast, nslab - 1)) return rc;
@@ -711,14 +669,14 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
   for (int i = 0; i < nslab; ++i) {
     const long long x0 = (long long)i * B, nb = x0 + B <= p->nx ? B : p->nx - x0;      // planes [x0, x0 + nb)
     char* Ws = (char*)W + x0 * plane;
-    char* Xs = xp ? (char*)p->X + x0 * plane : nullptr;        // (x blocks are contiguous and as large as their planes)
-    if (xp) RF_HIP(launch_col_xpose(p->f64, p->ny, Xs, gy, Xs, gy, nb * nzl, p->tw_y, s));
-    else RF_HIP(launch_col_plain(p->f64, p->ny, +1, Ws, gy, nb * nzl, p->tw_y, s));
+    char* Xs = xp ? (char*)p->X.ptr + x0 * plane : nullptr;        // (x blocks are contiguous and as large as their planes)
+    if (xp) RF_HIP(launch_col_xpose(p->f64, p->ny, Xs, gy, Xs, gy, nb * nzl, p->tw_y.ptr, s));
+    else RF_HIP(launch_col_plain(p->f64, p->ny, +1, Ws, gy, nb * nzl, p->tw_y.ptr, s));
     if (timed) RF_HIP(hipEventRecord(p->slab_ev[2 * i], s));
-    double* part = p->partials + 2 * x0 * tiles_per_plane;
-    if (xp) RF_HIP(launch_row_c2r_xgather(p->f64, (int)p->nzc, Xs, Ws, nb * p->ny, scale, (int)tc, (int)rb, p->ny, p->tw_z, part, s));
-    else if (cd.zscale) RF_HIP(launch_row_c2r_zscale(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, cd.zscale, p->tw_z, part, s));
-    else RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z, part, s));
+    double* part = p->partials.get() + 2 * x0 * tiles_per_plane;
+    if (xp) RF_HIP(launch_row_c2r_xgather(p->f64, (int)p->nzc, Xs, Ws, nb * p->ny, scale, (int)tc, (int)rb, p->ny, p->tw_z.ptr, part, s));
+    else if (cd.zscale) RF_HIP(launch_row_c2r_zscale(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, cd.zscale, p->tw_z.ptr, part, s));
+    else RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, s));
     if (timed) RF_HIP(hipEventRecord(p->slab_ev[2 * i + 1], s));
     if (sink) {
       if (int rc = sink_mark(p, i, s)) return rc;
@@ -726,7 +684,7 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
     }
   }
   if (timed) { RF_HIP(hipEventRecord(p->ev[2], s)); RF_HIP(hipEventRecord(p->ev[3], s)); }   // (rf_kernel_ms sums the slab events)
-  RF_HIP(launch_reduce_partials(p->partials, p->npartials, stats_out, p->partials + 2 * p->npartials, s));
+  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
   if (timed) RF_HIP(hipEventRecord(p->ev[4], s));
   if (sink) {
     const long long xl = (long long)(nslab - 1) * B;
@@ -743,8 +701,8 @@ int queue_xyz(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
   (void)hipStreamIsCapturing(s, &cap);
   if (cap == hipStreamCaptureStatusNone)           // (no allocation inside a graph capture: batch_prepare() has done it)
     if (int rc = ensure_x(p)) return rc;
-  const bool xp = p->X && xpose_ok(p);
-  if (int rc = queue_x(p, cd, gp, kspace, xp ? p->X : W, s, timed)) return rc;
+  const bool xp = p->X.ptr && xpose_ok(p);
+  if (int rc = queue_x(p, cd, gp, kspace, xp ? p->X.ptr : W, s, timed)) return rc;
   if (timed) RF_HIP(hipEventRecord(p->ev[1], s));
   return queue_yz(p, cd, W, s, stats_out, timed);
 }
@@ -761,7 +719,7 @@ struct HipGenericOps {
     if (timed) while (phase < ph) RF_HIP(hipEventRecord(p->ev[++phase], s));
     return 0;
   }
-  const void* root(int which) const { return which == 0 ? p->tw_x : (which == 1 ? p->tw_y : p->tw_z); }
+  const void* root(int which) const { return which == 0 ? p->tw_x.ptr : (which == 1 ? p->tw_y.ptr : p->tw_z.ptr); }
   int axis(const void* src, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
     if (int rc = enter(which)) return rc;
     RF_HIP(launch_generic_axis(p->f64, src, dst, ax, stride, inner, outer, nlines, root(which), sign, scale, s));
@@ -799,22 +757,22 @@ struct HipGenericOps {
   }
   int row_c2r(const void* G, void* W, double scale) {
     if (int rc = enter(2)) return rc;
-    RF_HIP(launch_generic_row_c2r(p->f64, G, W, p->gdims.az, (long long)p->nx * p->ny, p->tw_z, scale, p->partials, s));
+    RF_HIP(launch_generic_row_c2r(p->f64, G, W, p->gdims.az, (long long)p->nx * p->ny, p->tw_z.ptr, scale, p->partials.get(), s));
     return 0;
   }
   int row_r2c(const void* W, void* G) {
-    RF_HIP(launch_generic_row_r2c(p->f64, W, G, p->gdims.az, (long long)p->nx * p->ny, p->tw_z, s));
+    RF_HIP(launch_generic_row_r2c(p->f64, W, G, p->gdims.az, (long long)p->nx * p->ny, p->tw_z.ptr, s));
     return 0;
   }
-  int untangle(const void* G, void* Z) { if (int rc = enter(2)) return rc; RF_HIP(launch_generic_untangle(p->f64, G, Z, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z, s)); return 0; }
-  int tangle(const void* Z, void* G) { RF_HIP(launch_generic_tangle(p->f64, Z, G, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z, s)); return 0; }
-  int moments(const void* W) { RF_HIP(launch_generic_moments(p->f64, W, (long long)p->nx * p->ny * p->nz, p->partials, p->npartials, s)); return 0; }
+  int untangle(const void* G, void* Z) { if (int rc = enter(2)) return rc; RF_HIP(launch_generic_untangle(p->f64, G, Z, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z.ptr, s)); return 0; }
+  int tangle(const void* Z, void* G) { RF_HIP(launch_generic_tangle(p->f64, Z, G, (int)p->nzc, (long long)p->nx * p->ny, p->tw_z.ptr, s)); return 0; }
+  int moments(const void* W) { RF_HIP(launch_generic_moments(p->f64, W, (long long)p->nx * p->ny * p->nz, p->partials.get(), p->npartials, s)); return 0; }
   int copy(void* dst, const void* src, size_t bytes) { RF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); return 0; }
 };
 bool generic_any_long(const rf_plan* p) { return p->gdims.lx.split() || p->gdims.ly.split() || p->gdims.lz.split(); }
 // the second scratch array, for plans with an axis in the four-step form
 int ensure_g2(rf_plan* p) {
-  if (!p->G2 && generic_any_long(p)) RF_HIP(hipMalloc(&p->G2, p->unpacked ? p->w_bytes : p->k_bytes));
+  if (generic_any_long(p)) RF_HIP(p->G2.reserve(p->unpacked ? p->w_bytes : p->k_bytes));
   return 0;
 }
 
@@ -829,10 +787,10 @@ int generic_c2r(rf_plan* p, const void* K, double* stats_out, bool timed, const 
   if (int rc = ensure_g2(p)) return rc;
   HipGenericOps ops{p, p->stream, timed};
   const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-  if (from) { if (int rc = generic_c2r_from_seq(ops, p->gdims, *from, K, p->G, p->G2, p->W, scale)) return rc; }
-  else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G, p->G2, p->W, scale)) return rc;
+  if (from) { if (int rc = generic_c2r_from_seq(ops, p->gdims, *from, K, p->G.ptr, p->G2.ptr, p->W.ptr, scale)) return rc; }
+  else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G.ptr, p->G2.ptr, p->W.ptr, scale)) return rc;
   if (int rc = ops.enter(3)) return rc;
-  RF_HIP(launch_reduce_partials(p->partials, p->npartials, stats_out, p->partials + 2 * p->npartials, p->stream));
+  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, p->stream));
   return 0;
 }
 
@@ -846,11 +804,11 @@ void kspace_ready(rf_plan* p) {
 // the all-reduce of the moments on S, the stream that drives the communicator in this call (S != A: behind an event hop each way)
 int gather_and_reduce(rf_plan* p, hipStream_t A, hipStream_t S) {
   hipEvent_t hop = S != A ? p->chunk_ev[slab_chunks(p)] : nullptr;
-  if (int rc = queue_z_slab(p, p->R, p->W, p->stats, A)) return rc;
+  if (int rc = queue_z_slab(p, p->R.ptr, p->W.ptr, p->stats.get(), A)) return rc;
   if (p->timed) RF_HIP(hipEventRecord(p->ev[3], A));
   if (p->nranks > 1 && p->comm) {       // global (sum, sumsq): one 2-double all-reduce
     if (hop) { RF_HIP(hipEventRecord(hop, A)); RF_HIP(hipStreamWaitEvent(S, hop, 0)); }
-    RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, S));
+    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2, ncclFloat64, ncclSum, p->comm, S));
     if (hop) { RF_HIP(hipEventRecord(hop, S)); RF_HIP(hipStreamWaitEvent(A, hop, 0)); }
   }
   if (p->timed) RF_HIP(hipEventRecord(p->ev[4], A));
@@ -871,12 +829,12 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and k_valid stay as they are
     if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
       if (int rc = ensure_k(p)) return rc;
-      RF_HIP(launch_gen_kspace(p->f64, p->K, gp, p->stream));
+      RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
       if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], p->stream)); p->repair_timed = true; }
       kspace_ready(p);
-      kspace = p->K;
+      kspace = p->K.ptr;
     }
-    if (int rc = generic_c2r(p, kspace, p->stats, p->timed, fused ? &gp : nullptr)) return rc;
+    if (int rc = generic_c2r(p, kspace, p->stats.get(), p->timed, fused ? &gp : nullptr)) return rc;
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
     field_ready(p, 0);
     return 0;
@@ -885,7 +843,7 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
   p->slab_merged = 0;
   if (p->timed) RF_HIP(hipEventRecord(p->ev[0], p->stream));
   if (p->nranks == 1 && !p->force_slab) {       // one GPU: x pass, then the y / z passes (slab by slab on large grids)
-    if (int rc = queue_xyz(p, cd, gp, kspace, p->W, p->stream, p->stats, p->timed)) return rc;
+    if (int rc = queue_xyz(p, cd, gp, kspace, p->W.ptr, p->stream, p->stats.get(), p->timed)) return rc;
     field_ready(p, 0);
     return 0;
   }
@@ -897,12 +855,12 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     RF_REQUIRE(p->nranks == 1 || p->comm || p->direct_standin, "virtual ranks linked for the direct exchange run step by step (rf_slab_forward, rf_slab_backward)");
     const int C = slab_chunks(p);
     const bool two = p->direct_overlap != 0 && C > 1;
-    if (int rc = ensure_comm_stream(p)) return rc;
-    if (int rc = ensure_events(p->chunk_ev, C + 1, hipEventDisableTiming)) return rc;
+    RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
+    RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
     hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
     if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], A)); RF_HIP(hipStreamWaitEvent(Y, p->chunk_ev[C], 0)); }
     if (int rc = direct_barrier(p, Y)) return rc;
-    if (int rc = direct_forward(p, cd, gp, kspace, p->W, 0, A, Y, p->timed)) return rc;
+    if (int rc = direct_forward(p, cd, gp, kspace, p->W.ptr, 0, A, Y, p->timed)) return rc;
     if (int rc = direct_barrier(p, Y)) return rc;
     if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], Y)); RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0)); }
     if (int rc = gather_and_reduce(p, A, Y)) return rc;
@@ -915,16 +873,16 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     // at once; the gathering z pass waits for the last sub-slab's exchange.  (The communicator is driven from the exchange stream
     // only, the final all-reduce of the moments too.)
     const int C = slab_chunks(p);
-    if (int rc = ensure_comm_stream(p)) return rc;
-    if (int rc = ensure_events(p->chunk_ev, C + 1, hipEventDisableTiming)) return rc;
+    RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
+    RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
     hipStream_t A = p->stream, X = p->comm_stream;
     RF_HIP(hipEventRecord(p->chunk_ev[C], A));                 // (whatever used R / the communicator before on the plan's stream)
     RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[C], 0));
     for (int c = 0; c < C; ++c) {
-      if (int rc = queue_xy_chunk(p, cd, gp, kspace, p->W, A, c)) return rc;
+      if (int rc = queue_xy_chunk(p, cd, gp, kspace, p->W.ptr, A, c)) return rc;
       RF_HIP(hipEventRecord(p->chunk_ev[c], A));
       RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[c], 0));
-      if (int rc = queue_exchange_rccl(p, p->W, p->R, X, c)) return rc;
+      if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, X, c)) return rc;
     }
     if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], A)); p->repair_timed = false; RF_HIP(hipEventRecord(p->ev[1], A)); RF_HIP(hipEventRecord(p->ev[2], A)); }
     RF_HIP(hipEventRecord(p->chunk_ev[C], X));
@@ -933,19 +891,19 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
     return 0;
   }
-  if (int rc = queue_xy(p, cd, gp, kspace, p->W, p->stream, p->timed)) return rc;
+  if (int rc = queue_xy(p, cd, gp, kspace, p->W.ptr, p->stream, p->timed)) return rc;
   if (p->replicate && p->nranks > 1) {          // the local array already is this rank's x slab [nxl][ny][nz/2]
     const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-    RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W, (long long)p->nxl * p->ny, scale, p->tw_z, p->partials, p->stream));
-    RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, p->stream));
+    RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nxl * p->ny, scale, p->tw_z.ptr, p->partials.get(), p->stream));
+    RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get(), p->partials.get() + 2 * p->npartials, p->stream));
     if (p->timed) RF_HIP(hipEventRecord(p->ev[3], p->stream));
-    if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats, p->stats, 2, ncclFloat64, ncclSum, p->comm, p->stream));
+    if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2, ncclFloat64, ncclSum, p->comm, p->stream));
     if (p->timed) RF_HIP(hipEventRecord(p->ev[4], p->stream));
     field_ready(p, 0);
     return 0;
   }
   if (p->nranks > 1 || p->force_slab) {
-    if (int rc = queue_exchange_rccl(p, p->W, p->R, p->stream)) return rc;
+    if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, p->stream)) return rc;
     if (int rc = gather_and_reduce(p, p->stream, p->stream)) return rc;
     if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
     return 0;
@@ -953,12 +911,37 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
   return fail(1, "queue_c2r: unreachable");
 }
 
-template <typename T> int upload_twiddles(void** dst, int n) {
+template <typename T> int upload_twiddles(DevBuf<>& dst, int n) {
   auto w = make_twiddles<T>(n);
-  hipError_t e = hipMalloc(dst, w.size() * sizeof(cplx<T>));
+  hipError_t e = dst.reserve(w.size() * sizeof(cplx<T>));
   if (e != hipSuccess) return fail(2, std::string("hipMalloc twiddles: ") + hipGetErrorString(e));
-  e = hipMemcpy(*dst, w.data(), w.size() * sizeof(cplx<T>), hipMemcpyHostToDevice);
+  e = hipMemcpy(dst.ptr, w.data(), w.size() * sizeof(cplx<T>), hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(2, std::string("hipMemcpy twiddles: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// What rf_plan_create and rf_plan_create_c2c share, in the order of the allocations: the plan's stream, the field buffer W (and R on
+// multi-rank plans), the twiddle tables of the three axes, the workspace of a packed plan (p->npartials is set), the timing events
+int create_common(rf_plan* p, bool packed) {
+  hipError_t e;
+  if ((e = p->own_stream.create(hipStreamNonBlocking)) != hipSuccess) return fail(2, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  p->stream = p->own_stream;
+  if ((e = p->W.reserve(p->w_bytes)) != hipSuccess || (p->nranks > 1 && (e = p->R.reserve(p->w_bytes)) != hipSuccess))
+    return fail(2, std::string("hipMalloc field buffer: ") + hipGetErrorString(e));
+  const int n[3] = {p->nx, p->ny, p->nz};
+  DevBuf<>* tw[3] = {&p->tw_x, &p->tw_y, &p->tw_z};
+  for (int a = 0; a < 3; ++a)
+    if (int rc = p->f64 ? upload_twiddles<double>(*tw[a], n[a]) : upload_twiddles<float>(*tw[a], n[a])) return rc;
+  if (packed &&
+      ((e = p->partials.reserve((2 * p->npartials + 512) * sizeof(double))) != hipSuccess ||
+       (e = p->stats.reserve(2 * 64 * sizeof(double))) != hipSuccess ||
+       (e = p->coll_scratch.reserve(4 * sizeof(double))) != hipSuccess ||      // [0..1] host-side all-reduces, [2..3] the direct exchange's barriers
+       (e = p->kx2.reserve(p->nx * sizeof(double))) != hipSuccess ||
+       (e = p->ky2.reserve(p->ny * sizeof(double))) != hipSuccess ||
+       (e = p->kz2.reserve((p->nzc + 1) * sizeof(double))) != hipSuccess ||
+       (e = p->ztab.reserve(2 * p->nz * sizeof(double))) != hipSuccess))
+    return fail(2, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
+  if ((e = p->ev.ensure(6, hipEventDefault)) != hipSuccess) return fail(2, std::string("hipEventCreate: ") + hipGetErrorString(e));
   return 0;
 }
 
@@ -1043,59 +1026,32 @@ int rf_plan_create(rf_plan** out, int nx, int ny, int nz, int dtype, int device,
   // nz/2 + 2; 5.5 / 6.1 / 6.0 ms with nz/2 + 64), which a row stride further from the field's 4 MiB softens
   p->ppitch = dtype ? (int)p->nzl + 1 : (int)p->nzl + (p->nzl >= 256 ? 64 : 2);
   p->p_bytes = (size_t)nx * ny * p->ppitch * p->csize;
-  auto cleanup = [&](int rc) { rf_plan_destroy(p); return rc; };
+  auto cleanup = [&](int rc) { delete p; return rc; };
   hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking)) != hipSuccess)
-    return cleanup(fail(2, std::string("hipStreamCreate: ") + hipGetErrorString(e)));
-  p->stream = p->own_stream;
-  if ((e = hipMalloc(&p->W, p->w_bytes)) != hipSuccess || (nranks > 1 && (e = hipMalloc(&p->R, p->w_bytes)) != hipSuccess))
-    return cleanup(fail(2, std::string("hipMalloc field buffer: ") + hipGetErrorString(e)));
-  int rc = 0;
-  if (dtype) {
-    rc = upload_twiddles<double>(&p->tw_x, nx);
-    if (!rc) rc = upload_twiddles<double>(&p->tw_y, ny);
-    if (!rc) rc = upload_twiddles<double>(&p->tw_z, nz);
-  } else {
-    rc = upload_twiddles<float>(&p->tw_x, nx);
-    if (!rc) rc = upload_twiddles<float>(&p->tw_y, ny);
-    if (!rc) rc = upload_twiddles<float>(&p->tw_z, nz);
-  }
-  if (rc) return cleanup(rc);
   p->npartials = generic ? (gd.lz.split() ? 1024 : generic_row_blocks(dtype, gd.az, (long long)nx * ny))      // (long rows: the moments are a pass of their own, 1024 blocks)
                : nranks > 1 ? row_c2r_tiles(dtype, p->nzc, (long long)p->nxl * ny) : row_c2r_tiles(dtype, p->nzc, (long long)nx * ny);
-  p->stats_cap = 64;
-  if ((e = hipMalloc((void**)&p->partials, (2 * p->npartials + 512) * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void**)&p->stats, 2 * p->stats_cap * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void**)&p->coll_scratch, 4 * sizeof(double))) != hipSuccess ||      // [0..1] host-side all-reduces, [2..3] the direct exchange's barriers
-     
-      (e = hipMalloc((void**)&p->kx2, nx * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void**)&p->ky2, ny * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void**)&p->kz2, (p->nzc + 1) * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void**)&p->ztab, 2 * nz * sizeof(double))) != hipSuccess)
-    return cleanup(fail(2, std::string("hipMalloc workspace: ") + hipGetErrorString(e)));
-  for (auto& ev : p->ev)
-    if ((e = hipEventCreate(&ev)) != hipSuccess) return cleanup(fail(2, std::string("hipEventCreate: ") + hipGetErrorString(e)));
+  if (int rc = create_common(p, true)) return cleanup(rc);
   if (!generic) {  // function attributes (dynamic LDS above 64 KB) are set here, never inside a graph capture
     GenParams gp0; memset(&gp0, 0, sizeof(gp0)); gp0.nx = nx; gp0.ny = ny; gp0.nz = nz;
     const long long nzc = p->nzc, nzl = p->nzl;
     const ColGeom gx{(long long)ny * nzl, 0, (long long)ny * nzl}, gy{nzl, (long long)ny * nzl, nzl};
     FastGenParams fp0; memset(&fp0, 0, sizeof(fp0)); fp0.nx = nx; fp0.ny = ny; fp0.nz = nz;
-    if ((e = launch_col_gen(dtype, nx, p->W, gx, (long long)ny * nzl, gp0, nullptr, 0, (int)nzl, p->tw_x, p->stream, true)) != hipSuccess ||
-        (e = launch_col_fastgen(dtype, nx, p->W, gx, (long long)ny * nzl, fp0, 0, (int)nzl, p->tw_x, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, ny, +1, p->W, gy, (long long)nx * nzl, p->tw_y, p->stream, true)) != hipSuccess ||
-        (e = launch_col_xpose(dtype, ny, p->W, gy, p->W, gy, (long long)nx * nzl, p->tw_y, p->stream, true)) != hipSuccess ||
-        (e = launch_col_direct(dtype, ny, p->W, gy, nullptr, 0, (long long)nx * nzl, p->tw_y, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain_acc(dtype, ny, p->W, gy, (long long)nx * nzl, 0, (int)nzl, nullptr, p->tw_y, p->stream, true)) != hipSuccess ||
-        (e = launch_row_c2r_lognormal(dtype, (int)nzc, p->W, (long long)p->nxl * ny, 1.0, nullptr, nullptr, p->tw_z, p->partials, p->stream, true)) != hipSuccess ||
-        (yz_merged_supported(dtype, ny, (int)nzc) && (e = launch_yz_merged(dtype, ny, (int)nzc, p->W, 8, 1.0, p->tw_z, p->partials, p->W, ColGeom{p->nzl, (long long)ny * p->nzl, p->nzl}, 8, p->tw_y, p->stream, true)) != hipSuccess) ||
-        (e = launch_row_c2r(dtype, (int)nzc, p->W, (long long)p->nxl * ny, 1.0, p->tw_z, p->partials, p->stream, true)) != hipSuccess ||
-        (e = launch_row_c2r_zscale(dtype, (int)nzc, p->W, (long long)p->nxl * ny, 1.0, nullptr, p->tw_z, p->partials, p->stream, true)) != hipSuccess ||
-        (e = launch_row_c2r_xgather(dtype, (int)nzc, p->W, p->W, (long long)p->nxl * ny, 1.0, 8, 8, ny, p->tw_z, p->partials, p->stream, true)) != hipSuccess ||
-        (e = launch_row_r2c(dtype, (int)nzc, p->W, (long long)p->nxl * ny, p->tw_z, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, ny, -1, p->W, gy, (long long)nx * nzl, p->tw_y, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, nx, -1, p->W, gx, (long long)ny * nzl, p->tw_x, p->stream, true)) != hipSuccess ||
-        ((e = launch_row_c2r_gather(dtype, (int)nzc, p->W, p->W, (long long)p->nxl * ny, 1.0, (int)nzl, (long long)p->nxl * ny * nzl,
-                                                  p->tw_z, p->partials, p->stream, true)) != hipSuccess))
+    if ((e = launch_col_gen(dtype, nx, p->W.ptr, gx, (long long)ny * nzl, gp0, nullptr, 0, (int)nzl, p->tw_x.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_fastgen(dtype, nx, p->W.ptr, gx, (long long)ny * nzl, fp0, 0, (int)nzl, p->tw_x.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_plain(dtype, ny, +1, p->W.ptr, gy, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_xpose(dtype, ny, p->W.ptr, gy, p->W.ptr, gy, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_direct(dtype, ny, p->W.ptr, gy, nullptr, 0, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_plain_acc(dtype, ny, p->W.ptr, gy, (long long)nx * nzl, 0, (int)nzl, nullptr, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_row_c2r_lognormal(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, 1.0, nullptr, nullptr, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
+        (yz_merged_supported(dtype, ny, (int)nzc) && (e = launch_yz_merged(dtype, ny, (int)nzc, p->W.ptr, 8, 1.0, p->tw_z.ptr, p->partials.get(), p->W.ptr, ColGeom{p->nzl, (long long)ny * p->nzl, p->nzl}, 8, p->tw_y.ptr, p->stream, true)) != hipSuccess) ||
+        (e = launch_row_c2r(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, 1.0, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
+        (e = launch_row_c2r_zscale(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, 1.0, nullptr, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
+        (e = launch_row_c2r_xgather(dtype, (int)nzc, p->W.ptr, p->W.ptr, (long long)p->nxl * ny, 1.0, 8, 8, ny, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
+        (e = launch_row_r2c(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, p->tw_z.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_plain(dtype, ny, -1, p->W.ptr, gy, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_plain(dtype, nx, -1, p->W.ptr, gx, (long long)ny * nzl, p->tw_x.ptr, p->stream, true)) != hipSuccess ||
+        ((e = launch_row_c2r_gather(dtype, (int)nzc, p->W.ptr, p->W.ptr, (long long)p->nxl * ny, 1.0, (int)nzl, (long long)p->nxl * ny * nzl,
+                                                  p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess))
       return cleanup(fail(2, std::string("kernel preparation: ") + hipGetErrorString(e)));
   }
   *out = p;
@@ -1124,26 +1080,17 @@ int rf_plan_create_c2c(rf_plan** out, int nx, int ny, int nz, int dtype, int dev
   p->unpacked = true;
   p->w_bytes = (size_t)nx * ny * nz * p->csize;
   p->k_bytes = 0;
-  auto cleanup = [&](int rc) { rf_plan_destroy(p); return rc; };
+  auto cleanup = [&](int rc) { delete p; return rc; };
   hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking)) != hipSuccess)
-    return cleanup(fail(2, std::string("hipStreamCreate: ") + hipGetErrorString(e)));
-  p->stream = p->own_stream;
-  if ((e = hipMalloc(&p->W, p->w_bytes)) != hipSuccess) return cleanup(fail(2, std::string("hipMalloc field buffer: ") + hipGetErrorString(e)));
-  int rc = dtype ? upload_twiddles<double>(&p->tw_x, nx) : upload_twiddles<float>(&p->tw_x, nx);
-  if (!rc) rc = dtype ? upload_twiddles<double>(&p->tw_y, ny) : upload_twiddles<float>(&p->tw_y, ny);
-  if (!rc) rc = dtype ? upload_twiddles<double>(&p->tw_z, nz) : upload_twiddles<float>(&p->tw_z, nz);
-  if (rc) return cleanup(rc);
-  for (auto& ev : p->ev)
-    if ((e = hipEventCreate(&ev)) != hipSuccess) return cleanup(fail(2, std::string("hipEventCreate: ") + hipGetErrorString(e)));
+  if (int rc = create_common(p, false)) return cleanup(rc);
   const ColGeom gx{(long long)ny * nz, 0, (long long)ny * nz}, gy{nz, (long long)ny * nz, nz};
   if (!generic && (!col_plain_addressable(dtype, nx, gx) || !col_plain_addressable(dtype, ny, gy)))
     return cleanup(fail(1, "unsupported shape for a c2c plan: an axis shorter than 1024 with rows more than 4 GiB apart "
                            "(32-bit lane offsets); make that axis >= 1024 or the others smaller"));
   for (int dir = -1; dir <= 1 && !generic; dir += 2)
-    if ((e = launch_row_c2c(dtype, nz, dir, p->W, (long long)nx * ny, 1.0, p->tw_z, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, ny, dir, p->W, gy, (long long)nx * nz, p->tw_y, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, nx, dir, p->W, gx, (long long)ny * nz, p->tw_x, p->stream, true)) != hipSuccess)
+    if ((e = launch_row_c2c(dtype, nz, dir, p->W.ptr, (long long)nx * ny, 1.0, p->tw_z.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_plain(dtype, ny, dir, p->W.ptr, gy, (long long)nx * nz, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
+        (e = launch_col_plain(dtype, nx, dir, p->W.ptr, gx, (long long)ny * nz, p->tw_x.ptr, p->stream, true)) != hipSuccess)
       return cleanup(fail(2, std::string("kernel preparation: ") + hipGetErrorString(e)));
   *out = p;
   return 0;
@@ -1153,7 +1100,7 @@ int rf_upload_c(rf_plan* p, const void* host) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(p->unpacked, "rf_upload_c is for plans made by rf_plan_create_c2c");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(p->W, host, p->w_bytes, hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(p->W.ptr, host, p->w_bytes, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -1162,7 +1109,7 @@ int rf_download_c(rf_plan* p, void* host) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(p->unpacked, "rf_download_c is for plans made by rf_plan_create_c2c");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, p->W, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(host, p->W.ptr, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -1178,54 +1125,42 @@ int rf_execute_c2c(rf_plan* p, int direction) {
   const double scale = direction > 0 ? 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz) : 1.0;
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
   if (p->generic) {
-    if (generic_any_long(p) && !p->G) RF_HIP(hipMalloc(&p->G, p->w_bytes));        // scratch of the four-step form
+    if (generic_any_long(p)) RF_HIP(p->G.reserve(p->w_bytes));        // scratch of the four-step form
     HipGenericOps ops{p, p->stream};
-    if (int rc = generic_c2c_seq(ops, p->gdims, p->W, p->G, direction, scale)) return rc;
+    if (int rc = generic_c2c_seq(ops, p->gdims, p->W.ptr, p->G.ptr, direction, scale)) return rc;
   } else {
-    RF_HIP(launch_col_plain(p->f64, p->nx, direction, p->W, gx, (long long)p->ny * nz, p->tw_x, p->stream));
-    RF_HIP(launch_col_plain(p->f64, p->ny, direction, p->W, gy, (long long)p->nx * nz, p->tw_y, p->stream));
-    RF_HIP(launch_row_c2c(p->f64, (int)nz, direction, p->W, (long long)p->nx * p->ny, scale, p->tw_z, p->stream));
+    RF_HIP(launch_col_plain(p->f64, p->nx, direction, p->W.ptr, gx, (long long)p->ny * nz, p->tw_x.ptr, p->stream));
+    RF_HIP(launch_col_plain(p->f64, p->ny, direction, p->W.ptr, gy, (long long)p->nx * nz, p->tw_y.ptr, p->stream));
+    RF_HIP(launch_row_c2c(p->f64, (int)nz, direction, p->W.ptr, (long long)p->nx * p->ny, scale, p->tw_z.ptr, p->stream));
   }
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   p->timed = false;
   return 0;
 }
 
+// (the owning members free everything; the streams are the first members of rf_plan and so the last to go)
 int rf_plan_destroy(rf_plan* p) {
   if (!p) return 0;
   (void)hipSetDevice(p->device);
-  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  for (hipStream_t s : {p->stream, (hipStream_t)p->comm_stream, (hipStream_t)p->dl_stream, (hipStream_t)p->aux_stream})
+    if (s) (void)hipStreamSynchronize(s);
   drop_graphs(p);
   if (p->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(p->comm);
-  if (p->comm_stream) { (void)hipStreamSynchronize(p->comm_stream); (void)hipStreamDestroy(p->comm_stream); }
-  for (auto& e : p->pev) if (e) (void)hipEventDestroy(e);
   for (void* m : p->ipc_open) (void)hipIpcCloseMemHandle(m);
-  if (p->dl_stream) { (void)hipStreamSynchronize(p->dl_stream); (void)hipStreamDestroy(p->dl_stream); }
-  for (auto& e : p->sink_ev) (void)hipEventDestroy(e);
-  void* bufs[] = {p->peer_tab, p->W, p->R, p->W2, p->R2, p->K, p->P_base, p->G, p->G2, p->tw_x, p->tw_y, p->tw_z, p->kx2, p->ky2, p->kz2, p->xt, p->st, p->sl, p->bin,
-                  p->X, p->lntab, p->ypart, p->noise, p->mt_scratch, p->mt_send, p->mt_recv, p->mt_sbase, p->mt_first, p->mt_pos, p->mt_npos_dev, p->mt_states, p->mt_counts, p->mt_offsets, p->mt_rowtab, p->mt_flags, p->br_tmp, p->fixbuf, p->partials, p->stats, p->seeds_dev, p->ztab, p->frec, p->coll_scratch, p->pw_buf, p->L, p->Q, p->A, p->pa_drop};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (int i = 0; i < 2; ++i) {
-    if (p->seeds_pin[i]) (void)hipHostFree(p->seeds_pin[i]);
-    if (p->seeds_ev[i]) (void)hipEventDestroy(p->seeds_ev[i]);
-  }
-  for (auto& ev : p->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : p->slab_ev) (void)hipEventDestroy(ev);
-  for (auto& ev : p->chunk_ev) (void)hipEventDestroy(ev);
-  for (auto& ev : p->bev)
-    if (ev) (void)hipEventDestroy(ev);
-  if (p->aux_stream) (void)hipStreamDestroy(p->aux_stream);
-  if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
   delete p;
   return 0;
 }
 
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
-  *nbytes = p->w_bytes * (1 + (p->R ? 1 : 0) + (p->W2 ? 2 : 0) + (p->X ? 1 : 0)) + (p->K ? p->k_bytes : 0) + (p->P ? p->p_bytes : 0) + (p->L ? p->l_bytes : 0) + (p->Q ? 3 * p->w_bytes : 0) + (p->A ? (size_t)p->nx * p->ny * p->nz * 8 : 0) + ((p->G ? 1 : 0) + (p->G2 ? 1 : 0)) * (p->unpacked ? p->w_bytes : p->k_bytes) +
-            p->noise_cap * sizeof(double) + p->mt_scratch_bytes;      // + resident deviates and the replay's scratch runs
+  *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes +
+            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes;      // (+ resident deviates and the replay's scratch runs)
+  return 0;
+}
+
+int rf_diag_live_resources(size_t* device_bytes, int* events, int* streams) {
+  RF_REQUIRE(device_bytes && events && streams, "null argument");
+  *device_bytes = rfo::live().device_bytes; *events = rfo::live().events; *streams = rfo::live().streams;
   return 0;
 }
 
@@ -1268,7 +1203,7 @@ int rf_plan_set_flag(rf_plan* p, int flag, int value) {
   if (flag == RF_FLAG_TRANSPOSED_INTERMEDIATE) {
     p->xposed = value != 0;
     drop_graphs(p);
-    if (!p->xposed && p->X) { RF_HIP(hipFree(p->X)); p->X = nullptr; }
+    if (!p->xposed) RF_HIP(p->X.release());
     return 0;
   }
   if (flag == RF_FLAG_REPLICATED_GENERATION) {
@@ -1281,7 +1216,7 @@ int rf_plan_set_flag(rf_plan* p, int flag, int value) {
   if (flag == RF_FLAG_FORCE_SLAB_PATH) {
     RF_REQUIRE(p->nranks == 1, "RF_FLAG_FORCE_SLAB_PATH is for single-rank plans");
     RF_REQUIRE(!p->generic, "RF_FLAG_FORCE_SLAB_PATH needs power-of-two axes");
-    if (value && !p->R) RF_HIP(hipMalloc(&p->R, p->w_bytes));
+    if (value) RF_HIP(p->R.reserve(p->w_bytes));
     p->force_slab = value != 0;
     drop_graphs(p);
     return 0;
@@ -1303,9 +1238,9 @@ int rf_set_kgrid(rf_plan* p, const double* kx2, const double* ky2, const double*
   RF_REQUIRE(p && kx2 && ky2 && kz2, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(p->kx2, kx2, p->nx * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(hipMemcpyAsync(p->ky2, ky2, p->ny * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(hipMemcpyAsync(p->kz2, kz2, (p->nzc + 1) * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(p->kx2.get(), kx2, p->nx * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(p->ky2.get(), ky2, p->ny * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(p->kz2.get(), kz2, (p->nzc + 1) * sizeof(double), hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   p->h_kx2.assign(kx2, kx2 + p->nx); p->h_ky2.assign(ky2, ky2 + p->ny); p->h_kz2.assign(kz2, kz2 + p->nzc + 1);
   p->have_kgrid = true;
@@ -1321,17 +1256,16 @@ int rf_set_power(rf_plan* p, const double* log10k, const double* sigma, int n) {
   RF_HIP(hipStreamSynchronize(p->stream));
   SigmaTableHost t;
   build_sigma_table(log10k, sigma, n, t);
-  for (void* b : {(void*)p->xt, (void*)p->st, (void*)p->sl, (void*)p->bin})
-    if (b) RF_HIP(hipFree(b));
-  p->xt = p->st = p->sl = nullptr; p->bin = nullptr; p->have_power = false;
-  RF_HIP(hipMalloc((void**)&p->xt, n * sizeof(double)));
-  RF_HIP(hipMalloc((void**)&p->st, n * sizeof(double)));
-  RF_HIP(hipMalloc((void**)&p->sl, t.sl.size() * sizeof(double)));
-  RF_HIP(hipMalloc((void**)&p->bin, t.bin.size() * sizeof(int)));
-  RF_HIP(hipMemcpy(p->xt, t.xt.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  RF_HIP(hipMemcpy(p->st, t.st.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  RF_HIP(hipMemcpy(p->sl, t.sl.data(), t.sl.size() * sizeof(double), hipMemcpyHostToDevice));
-  RF_HIP(hipMemcpy(p->bin, t.bin.data(), t.bin.size() * sizeof(int), hipMemcpyHostToDevice));
+  p->have_power = false;
+  RF_HIP(p->xt.release()); RF_HIP(p->st.release()); RF_HIP(p->sl.release()); RF_HIP(p->bin.release());      // (always fresh tables)
+  RF_HIP(p->xt.reserve(n * sizeof(double)));
+  RF_HIP(p->st.reserve(n * sizeof(double)));
+  RF_HIP(p->sl.reserve(t.sl.size() * sizeof(double)));
+  RF_HIP(p->bin.reserve(t.bin.size() * sizeof(int)));
+  RF_HIP(hipMemcpy(p->xt.get(), t.xt.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  RF_HIP(hipMemcpy(p->st.get(), t.st.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  RF_HIP(hipMemcpy(p->sl.get(), t.sl.data(), t.sl.size() * sizeof(double), hipMemcpyHostToDevice));
+  RF_HIP(hipMemcpy(p->bin.get(), t.bin.data(), t.bin.size() * sizeof(int), hipMemcpyHostToDevice));
   p->nt = n; p->nbins = (int)t.bin.size(); p->x0 = t.x0; p->inv_dx = t.inv_dx;
   p->have_power = true;
   p->h_tab = t;
@@ -1347,7 +1281,7 @@ int rf_generate(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   if (int rc = ensure_k(p)) return rc;        // a kz-slab rank holds (and generates) its own planes + the Nyquist plane
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
   RF_REQUIRE(mode != RF_NOISE_RESIDENT || p->noise_resident, "rf_generate needs float64 deviates: only float32 copies are resident");
-  RF_HIP(launch_gen_kspace(p->f64, p->K, make_gen(p, seed, mode, false), p->stream));
+  RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, make_gen(p, seed, mode, false), p->stream));
   if (mode == RF_NOISE_EXTERNAL) RF_HIP(hipStreamSynchronize(p->stream));  // host noise buffer may be released by the caller
   kspace_ready(p);
   return 0;
@@ -1356,11 +1290,11 @@ int rf_generate(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
 int rf_execute_c2r(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+  RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
   RF_REQUIRE(!(p->replicate && p->nranks > 1), "replicated-generation plans have no distributed k-space buffer");
   RF_HIP(hipSetDevice(p->device));
   p->timed = true;
-  return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K);
+  return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr);
 }
 
 }  // extern "C"
@@ -1369,10 +1303,10 @@ namespace rfc {
 // [nxl][ny][nzl] of R (block g = the kz planes of rank g) -- the reverse of what the gathering z pass reads
 int queue_r2c_slab_rows(rf_plan* p, hipStream_t s) {
   const long long nrows = (long long)p->nxl * p->ny;
-  RF_HIP(launch_row_r2c(p->f64, (int)p->nzc, p->W, nrows, p->tw_z, s));
+  RF_HIP(launch_row_r2c(p->f64, (int)p->nzc, p->W.ptr, nrows, p->tw_z.ptr, s));
   const size_t seg = (size_t)p->nzl * p->csize, blk = (size_t)nrows * seg;
   for (int g = 0; g < p->nranks; ++g)
-    RF_HIP(hipMemcpy2DAsync((char*)p->R + g * blk, seg, (const char*)p->W + g * seg, (size_t)p->nzc * p->csize, seg, (size_t)nrows,
+    RF_HIP(hipMemcpy2DAsync((char*)p->R.ptr + g * blk, seg, (const char*)p->W.ptr + g * seg, (size_t)p->nzc * p->csize, seg, (size_t)nrows,
                             hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -1380,9 +1314,9 @@ int queue_r2c_slab_rows(rf_plan* p, hipStream_t s) {
 int queue_r2c_slab_cols(rf_plan* p, hipStream_t s) {
   const long long nzl = p->nzl;
   const ColGeom gx{(long long)p->ny * nzl, 0, (long long)p->ny * nzl}, gy{nzl, (long long)p->ny * nzl, nzl};
-  RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W, gy, (long long)p->nx * nzl, p->tw_y, s));
-  RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W, gx, (long long)p->ny * nzl, p->tw_x, s));
-  RF_HIP(launch_unpack_kspace(p->f64, p->W, p->K, p->nx, p->ny, (int)nzl, p->kz0, s));
+  RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W.ptr, gy, (long long)p->nx * nzl, p->tw_y.ptr, s));
+  RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W.ptr, gx, (long long)p->ny * nzl, p->tw_x.ptr, s));
+  RF_HIP(launch_unpack_kspace(p->f64, p->W.ptr, p->K.ptr, p->nx, p->ny, (int)nzl, p->kz0, s));
   p->real_valid = false;      // the field buffer now holds packed k space
   p->stats_valid = false;
   kspace_ready(p);
@@ -1398,18 +1332,18 @@ int queue_r2c_single(rf_plan* p, bool unpack) {
     if (int rc = ensure_k(p)) return rc;
     if (generic_any_long(p)) { if (int rc = ensure_g(p)) return rc; if (int rc = ensure_g2(p)) return rc; }
     HipGenericOps ops{p, p->stream};
-    if (int rc = generic_r2c_seq(ops, p->gdims, p->W, p->K, p->G, p->G2)) return rc;
+    if (int rc = generic_r2c_seq(ops, p->gdims, p->W.ptr, p->K.ptr, p->G.ptr, p->G2.ptr)) return rc;
     kspace_ready(p);            // the real field in W is untouched on this path
     return 0;
   }
   if (unpack) { if (int rc = ensure_k(p)) return rc; }
-  RF_HIP(launch_row_r2c(p->f64, (int)nzc, p->W, (long long)p->nx * p->ny, p->tw_z, p->stream));     // z, in place
-  RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W, gy, (long long)p->nx * nzc, p->tw_y, p->stream));   // y forward
-  RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W, gx, (long long)p->ny * nzc, p->tw_x, p->stream));   // x forward
+  RF_HIP(launch_row_r2c(p->f64, (int)nzc, p->W.ptr, (long long)p->nx * p->ny, p->tw_z.ptr, p->stream));     // z, in place
+  RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W.ptr, gy, (long long)p->nx * nzc, p->tw_y.ptr, p->stream));   // y forward
+  RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W.ptr, gx, (long long)p->ny * nzc, p->tw_x.ptr, p->stream));   // x forward
   p->real_valid = false;      // the field buffer now holds packed k space
   p->stats_valid = false;
   if (unpack) {
-    RF_HIP(launch_unpack_kspace(p->f64, p->W, p->K, p->nx, p->ny, (int)nzc, 0, p->stream));
+    RF_HIP(launch_unpack_kspace(p->f64, p->W.ptr, p->K.ptr, p->nx, p->ny, (int)nzc, 0, p->stream));
     kspace_ready(p);
   }
   return 0;
@@ -1420,7 +1354,7 @@ extern "C" {
 int rf_execute_r2c(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->real_valid && p->cur == p->W, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
   if (p->nranks > 1) {
@@ -1429,7 +1363,7 @@ int rf_execute_r2c(rf_plan* p) {
     RF_REQUIRE(!p->generic && !p->replicate, "the multi-rank forward transform runs on the tiled kernels of exchange-mode plans");
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
     if (int rc = queue_r2c_slab_rows(p, p->stream)) return rc;
-    if (int rc = queue_exchange_rccl(p, p->R, p->W, p->stream, -1, true)) return rc;
+    if (int rc = queue_exchange_rccl(p, p->R.ptr, p->W.ptr, p->stream, -1, true)) return rc;
     if (int rc = queue_r2c_slab_cols(p, p->stream)) return rc;
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
     p->timed = false;
@@ -1488,11 +1422,11 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   // per-z factor -- testing p->X here dropped the factor on the first call after RF_FLAG_TRANSPOSED_INTERMEDIATE was set)
   if (int rc = ensure_x(p)) return rc;
   const bool fuse_z = factor_z && p->nranks == 1 && !p->force_slab && !xpose_ok(p);
-  if (factor_z) RF_HIP(hipMemcpyAsync(p->ztab, factor_z, (size_t)p->nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  cd.zscale = fuse_z ? p->ztab : nullptr;
+  if (factor_z) RF_HIP(hipMemcpyAsync(p->ztab.get(), factor_z, (size_t)p->nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  cd.zscale = fuse_z ? p->ztab.get() : nullptr;
   if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
   if (factor_z && !fuse_z) {
-    RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, p->nz, p->ztab, 0.0, p->stream));
+    RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, p->nz, p->ztab.get(), 0.0, p->stream));
     p->stats_valid = false;
   }
   if (factor_z) RF_HIP(hipStreamSynchronize(p->stream));     // (factor_z is the caller's memory)
@@ -1513,7 +1447,7 @@ void mean_std(const rf_plan* p, const double* st, double* mean, double* std_out)
 // the rms of the first n realisations of a batch, from their pairs in `stats` (waits for the plan's stream)
 int rms_from_stats(rf_plan* p, int n, double* rms_out) {
   std::vector<double> st(2 * (size_t)n);
-  RF_HIP(hipMemcpyAsync(st.data(), p->stats, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(st.data(), p->stats.get(), st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   for (int i = 0; i < n; ++i) mean_std(p, &st[2 * i], nullptr, rms_out + i);
   return 0;
@@ -1536,16 +1470,16 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
     if (int rc = rf_generate(p, seed, mode, noise_host)) return rc;
     if (int rc = rf_save_potential(p)) return rc;
     if (whole) return rf_execute_c2r(p);
-    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K, p->W, p->stream, false);
+    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, false);
   }
   if (int rc = ensure_p(p)) return rc;
   p->p2_valid = false;                               // (P is rewritten: a second-order potential made from the old one is stale)
   p->timed = whole;
   CallDesc cd;
-  cd.pot_target = p->P;
+  cd.pot_target = p->P.ptr;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   const GenParams gp = make_gen(p, seed, mode, false);
-  return whole ? queue_c2r(p, cd, gp, nullptr) : queue_xy(p, cd, gp, nullptr, p->W, p->stream, false);
+  return whole ? queue_c2r(p, cd, gp, nullptr) : queue_xy(p, cd, gp, nullptr, p->W.ptr, p->stream, false);
 }
 }  // namespace rfc
 extern "C" {
@@ -1560,8 +1494,8 @@ int rf_realise_potential(rf_plan* p, uint64_t seed, int mode, const double* nois
 static int batch_issue(rf_plan* p, int n) {
   for (int i = 0; i < n; ++i) {
     GenParams gp = make_gen(p, 0, RF_NOISE_NATIVE, true);
-    gp.seed_dev = p->seeds_dev + i;
-    if (int rc = queue_xyz(p, CallDesc(), gp, nullptr, p->W, p->stream, p->stats + 2 * i, false)) return rc;
+    gp.seed_dev = p->seeds_dev.get() + i;
+    if (int rc = queue_xyz(p, CallDesc(), gp, nullptr, p->W.ptr, p->stream, p->stats.get() + 2 * i, false)) return rc;
   }
   return 0;
 }
@@ -1574,19 +1508,15 @@ static int batch_prepare(rf_plan* p, int n) {
   RF_REQUIRE(p->nranks == 1, "graph-captured batches are single-GPU; loop rf_realise on multi-GPU plans");
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
   RF_HIP(hipSetDevice(p->device));
-  if (p->seeds_cap < n || p->stats_cap < n) {
-    // device arrays are baked into the captured graphs: grow them (generously) and start over
+  if (p->seeds_dev.bytes < n * sizeof(uint64_t) || p->stats.bytes < 2 * n * sizeof(double)) {
+    // device arrays are baked into the captured graphs: grow them (generously) and start over -- BOTH, each at exactly `cap` entries
     RF_HIP(hipStreamSynchronize(p->stream));
     drop_graphs(p);
-    const int cap = n > 64 ? n : 64;
-    if (p->seeds_dev) RF_HIP(hipFree(p->seeds_dev));
-    p->seeds_dev = nullptr;
-    RF_HIP(hipMalloc((void**)&p->seeds_dev, cap * sizeof(uint64_t)));
-    p->seeds_cap = cap;
-    if (p->stats) RF_HIP(hipFree(p->stats));
-    p->stats = nullptr;
-    RF_HIP(hipMalloc((void**)&p->stats, 2 * (size_t)cap * sizeof(double)));
-    p->stats_cap = cap;
+    const size_t cap = n > 64 ? n : 64;
+    RF_HIP(p->seeds_dev.release());
+    RF_HIP(p->seeds_dev.reserve(cap * sizeof(uint64_t)));
+    RF_HIP(p->stats.release());
+    RF_HIP(p->stats.reserve(2 * cap * sizeof(double)));
   }
   if (p->graphs.count(n)) return 0;
   if (int rc = ensure_x(p)) return rc;
@@ -1628,8 +1558,8 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     RF_HIP(hipEventRecord(p->ev[0], p->stream));
     for (int i = 0; i < n; ++i) {
       const GenParams gp = make_gen(p, seeds[i], RF_NOISE_NATIVE, false);
-      if (!fused) RF_HIP(launch_gen_kspace(p->f64, p->K, gp, p->stream));
-      if (int rc = generic_c2r(p, p->K, p->stats + 2 * i, false, fused ? &gp : nullptr)) return rc;
+      if (!fused) RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
+      if (int rc = generic_c2r(p, p->K.ptr, p->stats.get() + 2 * i, false, fused ? &gp : nullptr)) return rc;
     }
     RF_HIP(hipEventRecord(p->ev[4], p->stream));
     p->timed = false;
@@ -1638,21 +1568,16 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     return rms_out ? rms_from_stats(p, n, rms_out) : 0;
   }
   if (int rc = batch_prepare(p, n)) return rc;
-  if (p->seeds_pin_cap < n) {
+  if (p->seeds_pin[0].bytes < n * sizeof(uint64_t) || p->seeds_pin[1].bytes < n * sizeof(uint64_t)) {
     RF_HIP(hipStreamSynchronize(p->stream));
-    for (int i = 0; i < 2; ++i) {
-      if (p->seeds_pin[i]) RF_HIP(hipHostFree(p->seeds_pin[i]));
-      p->seeds_pin[i] = nullptr;
-      RF_HIP(hipHostMalloc((void**)&p->seeds_pin[i], (size_t)(n + 64) * sizeof(uint64_t), hipHostMallocDefault));
-      if (!p->seeds_ev[i]) RF_HIP(hipEventCreateWithFlags(&p->seeds_ev[i], hipEventDisableTiming));
-    }
-    p->seeds_pin_cap = n + 64;
+    for (auto& slot : p->seeds_pin) RF_HIP(slot.reserve((size_t)(n + 64) * sizeof(uint64_t)));
   }
+  RF_HIP(p->seeds_ev.ensure(2, hipEventDisableTiming));
   const int slot = p->seeds_turn;
   p->seeds_turn ^= 1;
   RF_HIP(hipEventSynchronize(p->seeds_ev[slot]));        // returns at once for an event that was never recorded
-  std::memcpy(p->seeds_pin[slot], seeds, n * sizeof(uint64_t));
-  RF_HIP(hipMemcpyAsync(p->seeds_dev, p->seeds_pin[slot], n * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+  std::memcpy(p->seeds_pin[slot].get(), seeds, n * sizeof(uint64_t));
+  RF_HIP(hipMemcpyAsync(p->seeds_dev.get(), p->seeds_pin[slot].get(), n * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipEventRecord(p->seeds_ev[slot], p->stream));
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
   RF_HIP(hipGraphLaunch(p->graphs[n].exec, p->stream));
@@ -1668,7 +1593,7 @@ int rf_moments(rf_plan* p, double* mean, double* std_out) {
   RF_REQUIRE(p->stats_valid, "no realisation has been computed");
   RF_HIP(hipSetDevice(p->device));
   double st[2];
-  RF_HIP(hipMemcpyAsync(st, p->stats + 2 * p->stats_slot, sizeof(st), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(st, p->stats.get() + 2 * p->stats_slot, sizeof(st), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   mean_std(p, st, mean, std_out);
   return 0;
@@ -1681,9 +1606,9 @@ int rf_lognormal(rf_plan* p, const double* a_z, const double* b_z, int nz, doubl
   RF_REQUIRE(p->real_valid, "no real-space field on the device");
   RF_REQUIRE(sigma > 0, "sigma must be positive");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(p->ztab, a_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(hipMemcpyAsync(p->ztab + nz, b_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(launch_lognormal(p->f64, p->cur, (long long)p->nxl * p->ny, nz, p->ztab, p->ztab + nz, sigma, p->stream));
+  RF_HIP(hipMemcpyAsync(p->ztab.get(), a_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(p->ztab.get() + nz, b_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(launch_lognormal(p->f64, p->cur, (long long)p->nxl * p->ny, nz, p->ztab.get(), p->ztab.get() + nz, sigma, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));  // host tables may go away
   p->stats_valid = false;
   return 0;
@@ -1695,9 +1620,9 @@ int rf_set_z_tables(rf_plan* p, const double* growth_z, const double* density_z,
   RF_REQUIRE(nz == p->nz, "table length must equal nz");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipStreamSynchronize(p->stream));
-  if (!p->lntab) RF_HIP(hipMalloc((void**)&p->lntab, (4 * (size_t)nz + 8) * sizeof(double)));
-  RF_HIP(hipMemcpy(p->lntab, growth_z, nz * sizeof(double), hipMemcpyHostToDevice));
-  if (density_z) RF_HIP(hipMemcpy(p->lntab + nz, density_z, nz * sizeof(double), hipMemcpyHostToDevice));
+  RF_HIP(p->lntab.reserve((4 * (size_t)nz + 8) * sizeof(double)));
+  RF_HIP(hipMemcpy(p->lntab.get(), growth_z, nz * sizeof(double), hipMemcpyHostToDevice));
+  if (density_z) RF_HIP(hipMemcpy(p->lntab.get() + nz, density_z, nz * sizeof(double), hipMemcpyHostToDevice));
   p->ln_tables = true;
   p->ln_density = density_z != nullptr;
   return 0;
@@ -1718,32 +1643,27 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   CallDesc cd;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   const long long nzl = p->nzl, ntiles = (long long)p->nx * nzl / col_tile_cols(p->f64, p->ny);
-  if (p->nypart < ntiles) {
-    if (p->ypart) RF_HIP(hipFree(p->ypart));
-    p->ypart = nullptr; p->nypart = 0;
-    RF_HIP(hipMalloc((void**)&p->ypart, ntiles * sizeof(double)));
-    p->nypart = ntiles;
-  }
+  RF_HIP(p->ypart.reserve(ntiles * sizeof(double)));
   hipStream_t s = p->stream;
   const GenParams gp = make_gen(p, seed, mode, false);
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
   const double n3 = (double)p->nx * (double)p->ny * (double)p->nz, scale = 1.0 / n3;
-  double *growth = p->lntab, *dens = p->lntab + p->nz, *A = p->lntab + 2 * p->nz, *B = p->lntab + 3 * p->nz, *sig = p->lntab + 4 * p->nz;
+  double *growth = p->lntab.get(), *dens = p->lntab.get() + p->nz, *A = p->lntab.get() + 2 * p->nz, *B = p->lntab.get() + 3 * p->nz, *sig = p->lntab.get() + 4 * p->nz;
   RF_HIP(hipEventRecord(p->ev[0], s));
   p->slab_timed = 0;
   p->slab_merged = 0;
   // into W, the plain layout whatever RF_FLAG_TRANSPOSED_INTERMEDIATE says: the accumulating y pass runs in place on W
   // (timed: rf_kernel_ms reports x, y + tables, z + map, reduce of this call too)
-  if (int rc = queue_x(p, cd, gp, nullptr, p->W, s, true)) return rc;
+  if (int rc = queue_x(p, cd, gp, nullptr, p->W.ptr, s, true)) return rc;
   RF_HIP(hipEventRecord(p->ev[1], s));
-  RF_HIP(launch_col_plain_acc(p->f64, p->ny, p->W, gy, (long long)p->nx * nzl, p->kz0, (int)nzl, p->ypart, p->tw_y, s));
+  RF_HIP(launch_col_plain_acc(p->f64, p->ny, p->W.ptr, gy, (long long)p->nx * nzl, p->kz0, (int)nzl, p->ypart.get(), p->tw_y.ptr, s));
   // rms = sqrt(S / (nx ny)) / N3  (rf_fft.h AccColIO)
-  RF_HIP(launch_lognormal_tables(p->ypart, ntiles, 1.0 / ((double)p->nx * (double)p->ny * n3 * n3), growth, p->ln_density ? dens : nullptr, p->nz,
+  RF_HIP(launch_lognormal_tables(p->ypart.get(), ntiles, 1.0 / ((double)p->nx * (double)p->ny * n3 * n3), growth, p->ln_density ? dens : nullptr, p->nz,
                                  p->f64 ? 0 : 1, p->f64 ? lognormal_ap_unit<double>(scale) : 1.0, sig, A, B, s));
   RF_HIP(hipEventRecord(p->ev[2], s));
-  RF_HIP(launch_row_c2r_lognormal(p->f64, (int)p->nzc, p->W, (long long)p->nx * p->ny, scale, A, B, p->tw_z, p->partials, s));
+  RF_HIP(launch_row_c2r_lognormal(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nx * p->ny, scale, A, B, p->tw_z.ptr, p->partials.get(), s));
   RF_HIP(hipEventRecord(p->ev[3], s));
-  RF_HIP(launch_reduce_partials(p->partials, p->npartials, p->stats, p->partials + 2 * p->npartials, s));
+  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get(), p->partials.get() + 2 * p->npartials, s));
   RF_HIP(hipEventRecord(p->ev[4], s));
   p->timed = true;
   field_ready(p, 0);                                 // (the moments of the DENSITY field now)
@@ -1761,8 +1681,8 @@ int rf_affine_z(rf_plan* p, const double* mul_z, int nz, double add) {
   RF_REQUIRE(nz == p->nz, "table length must equal nz");
   RF_REQUIRE(p->real_valid, "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(p->ztab, mul_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, nz, p->ztab, add, p->stream));
+  RF_HIP(hipMemcpyAsync(p->ztab.get(), mul_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, nz, p->ztab.get(), add, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   p->stats_valid = false;
   return 0;
@@ -1781,8 +1701,8 @@ int rf_lensing_potential(rf_plan* p, const double* cot_z, int nz, double spacing
   RF_REQUIRE(p->real_valid, "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;            // (nx ny (nz/2+1)) complex >= (nx ny nz) real
-  RF_HIP(hipMemcpyAsync(p->ztab, cot_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(launch_lensing(p->f64, p->cur, p->K, (long long)p->nxl * p->ny, nz, p->ztab, spacing, i_min, p->stream));   // rows are local: x slab
+  RF_HIP(hipMemcpyAsync(p->ztab.get(), cot_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(launch_lensing(p->f64, p->cur, p->K.ptr, (long long)p->nxl * p->ny, nz, p->ztab.get(), spacing, i_min, p->stream));   // rows are local: x slab
   RF_HIP(hipStreamSynchronize(p->stream));
   p->k_valid = false;
   p->aux_valid = true;
@@ -1793,11 +1713,11 @@ int rf_lensing_potential(rf_plan* p, const double* cot_z, int nz, double spacing
 int rf_download_aux(rf_plan* p, void* host, int x0, int x1) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K && p->aux_valid, "no auxiliary field on the device");
+  RF_REQUIRE(p->K.ptr && p->aux_valid, "no auxiliary field on the device");
   RF_REQUIRE(0 <= x0 && x0 < x1 && x1 <= p->nxl, "invalid x range (multi-GPU plans hold nx/ranks local planes)");
   RF_HIP(hipSetDevice(p->device));
   const size_t plane = (size_t)p->ny * p->nz * (p->csize / 2);
-  RF_HIP(hipMemcpyAsync(host, (const char*)p->K + (size_t)x0 * plane, (size_t)(x1 - x0) * plane, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(host, (const char*)p->K.ptr + (size_t)x0 * plane, (size_t)(x1 - x0) * plane, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -1805,22 +1725,22 @@ int rf_download_aux(rf_plan* p, void* host, int x0, int x1) {
 int rf_save_potential(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K && p->k_valid, "no k-space data");
+  RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data");
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_p(p)) return rc;
   p->p2_valid = false;
-  RF_HIP(launch_save_potential(p->f64, p->K, p->P, p->nx, p->ny, p->nz, p->kx2, p->ky2, p->kz2, p->nzl + 1, p->kz0, p->ppitch, p->stream));
+  RF_HIP(launch_save_potential(p->f64, p->K.ptr, p->P.ptr, p->nx, p->ny, p->nz, p->kx2.get(), p->ky2.get(), p->kz2.get(), p->nzl + 1, p->kz0, p->ppitch, p->stream));
   return 0;
 }
 
 int rf_load_potential(rf_plan* p, double scale) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->P, "no saved potential");
+  RF_REQUIRE(p->P.ptr, "no saved potential");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
-  RF_HIP(launch_scale_copy(p->f64, p->P, p->K, (long long)p->nx * p->ny * (p->nzl + 1), (int)p->nzl + 1, p->ppitch, scale, p->stream));
+  RF_HIP(launch_scale_copy(p->f64, p->P.ptr, p->K.ptr, (long long)p->nx * p->ny * (p->nzl + 1), (int)p->nzl + 1, p->ppitch, scale, p->stream));
   kspace_ready(p);
   return 0;
 }
@@ -1832,17 +1752,17 @@ namespace rfc {
 // parameter structs have (rf_core.h GradParams, HessParams)
 template <class P>
 int derivative_source(rf_plan* p, int source, P& g, const void*& S) {
-  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P, "no saved potential");
-  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L && p->p2_valid, "no second-order potential: call rf_lpt2_potential first");
+  if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P.ptr, "no saved potential");
+  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L.ptr && p->p2_valid, "no second-order potential: call rf_lpt2_potential first");
   else {
-    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+    RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
     RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   }
   g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
   g.divide = source == RF_GRAD_FROM_KSPACE;
-  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
+  g.kx2 = p->kx2.get(); g.ky2 = p->ky2.get(); g.kz2 = p->kz2.get();
   g.pitch = g.divide ? p->nzc + 1 : p->ppitch;
-  S = g.divide ? p->K : (source == RF_GRAD_FROM_POTENTIAL2 ? p->L : p->P);
+  S = g.divide ? p->K.ptr : (source == RF_GRAD_FROM_POTENTIAL2 ? p->L.ptr : p->P.ptr);
   return 0;
 }
 int gradient_params(rf_plan* p, int axis, double scale, double dk, int source, GradParams& g, const void*& S) {
@@ -1874,7 +1794,7 @@ template <class P>
 int load_derivative(rf_plan* p, const P& g, const void* S) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
-  RF_HIP(launch_derivative(p->f64, S, p->K, g, p->stream));
+  RF_HIP(launch_derivative(p->f64, S, p->K.ptr, g, p->stream));
   kspace_ready(p);
   return 0;
 }
@@ -1895,30 +1815,25 @@ int execute_derivative_c2r(rf_plan* p, const P& g, const void* S, int source) {
   p->repair_timed = false;
   p->timed = true;                                  // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  if (int rc = generic_c2r(p, S, p->stats, true, &g)) return rc;
+  if (int rc = generic_c2r(p, S, p->stats.get(), true, &g)) return rc;
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   field_ready(p, 0);
   if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
   return 0;
 }
 // the accumulators of rf_lpt2_source, later the second-order potential
-int ensure_l(rf_plan* p) {
-  if (p->L) return 0;
-  p->l_bytes = 2 * p->w_bytes > p->p_bytes ? 2 * p->w_bytes : p->p_bytes;
-  RF_HIP(hipMalloc(&p->L, p->l_bytes));
-  return 0;
-}
+int ensure_l(rf_plan* p) { RF_HIP(p->L.reserve(2 * p->w_bytes > p->p_bytes ? 2 * p->w_bytes : p->p_bytes)); return 0; }
 // the particle buffers (rf_particles_*): the displacements, zeroed once, and the paint's accumulator grid with its drop counter
 size_t particle_cells(const rf_plan* p) { return (size_t)p->nx * p->ny * p->nz; }
 int ensure_q(rf_plan* p) {
   if (p->Q) return 0;
-  RF_HIP(hipMalloc(&p->Q, 3 * p->w_bytes));
-  RF_HIP(hipMemsetAsync(p->Q, 0, 3 * p->w_bytes, p->stream));
+  RF_HIP(p->Q.reserve(3 * p->w_bytes));
+  RF_HIP(hipMemsetAsync(p->Q.ptr, 0, 3 * p->w_bytes, p->stream));
   return 0;
 }
 int ensure_a(rf_plan* p) {
-  if (!p->pa_drop) RF_HIP(hipMalloc(&p->pa_drop, 8));
-  if (!p->A) RF_HIP(hipMalloc(&p->A, particle_cells(p) * 8));
+  RF_HIP(p->pa_drop.reserve(8));
+  RF_HIP(p->A.reserve(particle_cells(p) * 8));
   return 0;
 }
 }  // namespace rfc
@@ -1958,21 +1873,21 @@ int rf_lpt2_source(rf_plan* p, const double* dk) {
   RF_REQUIRE(p && dk, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->nranks == 1, "the second-order source runs on single-rank plans");
-  RF_REQUIRE(p->P, "no saved potential");
+  RF_REQUIRE(p->P.ptr, "no saved potential");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_l(p)) return rc;
   p->p2_valid = false;                               // (the accumulators take the memory of the second-order potential)
   static const int comp[6][3] = {{0, 0, LPT2_FIRST}, {1, 1, LPT2_DIAG2}, {2, 2, LPT2_DIAG3}, {0, 1, LPT2_OFF}, {0, 2, LPT2_OFF}, {1, 2, LPT2_LAST}};
-  void* T = p->L;
-  void* S = (char*)p->L + p->w_bytes;
+  void* T = p->L.ptr;
+  void* S = (char*)p->L.ptr + p->w_bytes;
   const long long n = (long long)p->nx * p->ny * p->nz;
   for (const auto& c : comp) {
     if (int rc = rf_execute_hessian_c2r(p, c[0], c[1], 1.0, dk[c[0]], dk[c[1]], RF_GRAD_FROM_POTENTIAL)) return rc;
-    RF_HIP(launch_lpt2_accumulate(p->f64, c[2], p->W, T, S, n, p->stream));
+    RF_HIP(launch_lpt2_accumulate(p->f64, c[2], p->W.ptr, T, S, n, p->stream));
   }
   RF_HIP(hipEventRecord(p->ev[4], p->stream));       // (rf_elapsed_ms: the last component's transform and the last step)
   p->timed = false;
-  p->cur = p->W;
+  p->cur = p->W.ptr;
   p->real_valid = true;
   p->stats_valid = false;
   p->k_valid = false;                                // (tiled plans left a Hessian component there: one contract)
@@ -1985,11 +1900,11 @@ int rf_lpt2_potential(rf_plan* p, const double* dk) {
   RF_REQUIRE(p && dk, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->nranks == 1, "the second-order potential runs on single-rank plans");
-  RF_REQUIRE(p->P, "no saved potential");
+  RF_REQUIRE(p->P.ptr, "no saved potential");
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   if (int rc = rf_lpt2_source(p, dk)) return rc;
   if (int rc = rf_execute_r2c(p)) return rc;
-  RF_HIP(launch_save_potential(p->f64, p->K, p->L, p->nx, p->ny, p->nz, p->kx2, p->ky2, p->kz2, p->nzl + 1, p->kz0, p->ppitch, p->stream));
+  RF_HIP(launch_save_potential(p->f64, p->K.ptr, p->L.ptr, p->nx, p->ny, p->nz, p->kx2.get(), p->ky2.get(), p->kz2.get(), p->nzl + 1, p->kz0, p->ppitch, p->stream));
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   p->p2_valid = true;
   return 0;
@@ -2009,7 +1924,7 @@ int rf_particles_accumulate(rf_plan* p, int axis, double coeff, int first) {
   RF_REQUIRE(p->real_valid && p->cur, "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_q(p)) return rc;
-  RF_HIP(launch_particles_accumulate(p->f64, p->cur, (char*)p->Q + (size_t)axis * p->w_bytes, coeff, first, (long long)particle_cells(p), p->stream));
+  RF_HIP(launch_particles_accumulate(p->f64, p->cur, (char*)p->Q.ptr + (size_t)axis * p->w_bytes, coeff, first, (long long)particle_cells(p), p->stream));
   return 0;
 }
 
@@ -2019,7 +1934,7 @@ int rf_particles_upload(rf_plan* p, int axis, const void* host) {
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_q(p)) return rc;
-  RF_HIP(hipMemcpyAsync((char*)p->Q + (size_t)axis * p->w_bytes, host, p->w_bytes, hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync((char*)p->Q.ptr + (size_t)axis * p->w_bytes, host, p->w_bytes, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -2028,9 +1943,9 @@ int rf_particles_download(rf_plan* p, int axis, void* host) {
   if (int rc = particles_check(p, "the particle displacements live on single-rank plans")) return rc;
   RF_REQUIRE(host, "null argument");
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
-  RF_REQUIRE(p->Q, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
+  RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, (char*)p->Q + (size_t)axis * p->w_bytes, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(host, (char*)p->Q.ptr + (size_t)axis * p->w_bytes, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -2039,7 +1954,7 @@ int rf_particles_download(rf_plan* p, int axis, void* host) {
 int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* dropped) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(inv_h && dropped, "null argument");
-  RF_REQUIRE(p->Q, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
+  RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
   for (int a = 0; a < 3; ++a) RF_REQUIRE(inv_h[a] > 0 && inv_h[a] <= 1.7976931348623157e308, "inv_h must be positive and finite");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_a(p)) return rc;
@@ -2052,20 +1967,20 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
   p->slab_merged = 0;
   p->repair_timed = false;
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  RF_HIP(hipMemsetAsync(p->A, 0, n * 8, p->stream));
-  RF_HIP(hipMemsetAsync(p->pa_drop, 0, 8, p->stream));
+  RF_HIP(hipMemsetAsync(p->A.ptr, 0, n * 8, p->stream));
+  RF_HIP(hipMemsetAsync(p->pa_drop.ptr, 0, 8, p->stream));
   RF_HIP(hipEventRecord(p->ev[1], p->stream));
-  RF_HIP(launch_cic_paint(p->f64, form, p->Q, (unsigned long long*)p->A, (unsigned long long*)p->pa_drop, p->nx, p->ny, p->nz, inv_h, p->stream));
+  RF_HIP(launch_cic_paint(p->f64, form, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
   RF_HIP(hipEventRecord(p->ev[2], p->stream));
-  RF_HIP(launch_cic_convert(p->f64, (const unsigned long long*)p->A, p->W, (long long)n, p->stream));
+  RF_HIP(launch_cic_convert(p->f64, (const unsigned long long*)p->A.ptr, p->W.ptr, (long long)n, p->stream));
   RF_HIP(hipEventRecord(p->ev[3], p->stream));
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   p->timed = true;
-  p->cur = p->W;
+  p->cur = p->W.ptr;
   p->real_valid = true;
   p->stats_valid = false;
   p->pa_valid = true;
-  RF_HIP(hipMemcpyAsync(dropped, p->pa_drop, 8, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(dropped, p->pa_drop.ptr, 8, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -2073,9 +1988,9 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
 int rf_particles_download_counts(rf_plan* p, unsigned long long* host) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(host, "null argument");
-  RF_REQUIRE(p->A && p->pa_valid, "no painted counts: call rf_particles_paint first");
+  RF_REQUIRE(p->A.ptr && p->pa_valid, "no painted counts: call rf_particles_paint first");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, p->A, particle_cells(p) * 8, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(host, p->A.ptr, particle_cells(p) * 8, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -2103,22 +2018,18 @@ int rf_measure_power(rf_plan* p, int source, const double* k_edges, int nbins, u
   RF_REQUIRE(k_edges[0] >= 0.0, "bad k_edges: the first edge must not be negative");
   for (int b = 0; b < nbins; ++b) RF_REQUIRE(k_edges[b] < k_edges[b + 1], "bad k_edges: the edges must be strictly increasing");
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
-  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
-  else RF_REQUIRE(p->real_valid && p->cur == p->W, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+  else RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
   // one lazy buffer: [squared edges, 1025 slots][result 3 x 1024][three planes of per-workgroup partials]
   const PowerLaunch L = power_launch_shape(p->nx, p->ny, p->nz, nbins);
   const long long plane_words = (long long)L.grid * nbins;
   const size_t head_words = 1025 + 3 * 1024, need = (head_words + 3 * (size_t)plane_words) * 8;
-  if (p->pw_bytes < need) {
-    RF_HIP(hipStreamSynchronize(p->stream));
-    if (p->pw_buf) { RF_HIP(hipFree(p->pw_buf)); p->pw_buf = nullptr; p->pw_bytes = 0; }
-    RF_HIP(hipMalloc(&p->pw_buf, need));
-    p->pw_bytes = need;
-  }
-  double* e2_dev = (double*)p->pw_buf;
-  unsigned long long* out_dev = (unsigned long long*)p->pw_buf + 1025;
-  unsigned long long* part_dev = (unsigned long long*)p->pw_buf + head_words;
+  if (p->pw_buf.bytes < need) RF_HIP(hipStreamSynchronize(p->stream));
+  RF_HIP(p->pw_buf.reserve(need));
+  double* e2_dev = (double*)p->pw_buf.ptr;
+  unsigned long long* out_dev = (unsigned long long*)p->pw_buf.ptr + 1025;
+  unsigned long long* part_dev = (unsigned long long*)p->pw_buf.ptr + head_words;
   std::vector<double> e2((size_t)nbins + 1);
   for (int b = 0; b <= nbins; ++b) e2[b] = k_edges[b] * k_edges[b];
   RF_HIP(hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
@@ -2131,8 +2042,8 @@ int rf_measure_power(rf_plan* p, int source, const double* k_edges, int nbins, u
   g.packed = source == RF_POWER_FROM_FIELD && !p->generic;
   g.kz_sorted = 1;
   for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) g.kz_sorted = 0;
-  g.kx2 = p->kx2; g.ky2 = p->ky2; g.kz2 = p->kz2;
-  RF_HIP(launch_power(p->f64, g.packed ? p->W : p->K, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
+  g.kx2 = p->kx2.get(); g.ky2 = p->ky2.get(); g.kz2 = p->kz2.get();
+  RF_HIP(launch_power(p->f64, g.packed ? p->W.ptr : p->K.ptr, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   p->timed = false;
   std::vector<unsigned long long> out(3 * (size_t)nbins);
@@ -2149,7 +2060,7 @@ int rf_upload_k(rf_plan* p, const void* host) {
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
-  RF_HIP(hipMemcpyAsync(p->K, host, p->k_bytes, hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(p->K.ptr, host, p->k_bytes, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   kspace_ready(p);
   return 0;
@@ -2158,9 +2069,9 @@ int rf_upload_k(rf_plan* p, const void* host) {
 int rf_download_k(rf_plan* p, void* host) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K && p->k_valid, "no k-space data");
+  RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, p->K, p->k_bytes, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(host, p->K.ptr, p->k_bytes, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -2174,9 +2085,9 @@ int rf_upload_real(rf_plan* p, const void* host, int layout) {
   const size_t width = (size_t)p->nz * rsize;
   const size_t hpitch = layout == RF_LAYOUT_PADDED ? (size_t)(p->nz + 2) * rsize : width;
   // (a multi-rank plan takes its own nx / ranks planes)
-  RF_HIP(hipMemcpy2DAsync(p->W, width, host, hpitch, width, (size_t)p->nxl * p->ny, hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpy2DAsync(p->W.ptr, width, host, hpitch, width, (size_t)p->nxl * p->ny, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  p->cur = p->W;
+  p->cur = p->W.ptr;
   p->real_valid = true;
   p->stats_valid = false;
   return 0;
@@ -2214,7 +2125,7 @@ int rf_set_host_sink(rf_plan* p, void* host, int layout) {
   if (p->f64 && (p->sink_host == nullptr) != (host == nullptr)) drop_graphs(p);      // (a float64 plan runs its y / z passes slab by slab only for a sink)
   p->sink_host = host;
   p->sink_layout = layout;
-  if (host && !p->dl_stream) RF_HIP(hipStreamCreateWithFlags(&p->dl_stream, hipStreamNonBlocking));
+  if (host) RF_HIP(p->dl_stream.create(hipStreamNonBlocking));
   return 0;
 }
 
@@ -2229,8 +2140,8 @@ int rf_host_sink_delivered(rf_plan* p, int* delivered) {
 
 int rf_device_ptr(rf_plan* p, void** real_field, void** kspace) {
   RF_REQUIRE(p, "null plan");
-  if (real_field) *real_field = p->cur ? p->cur : p->W;
-  if (kspace) *kspace = p->K;
+  if (real_field) *real_field = p->cur ? p->cur : p->W.ptr;
+  if (kspace) *kspace = p->K.ptr;
   return 0;
 }
 
@@ -2320,7 +2231,7 @@ int rf_yz_slabs(rf_plan* p, int* nslab, int* planes) {
   RF_REQUIRE(p && nslab && planes, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   long long B = yz_slab_planes(p);
-  if (p->X && xpose_ok(p) && B > 0 && (B % xpose_row_block(p) || (B & (B - 1)) || p->nx % B)) B = 0;
+  if (p->X.ptr && xpose_ok(p) && B > 0 && (B % xpose_row_block(p) || (B & (B - 1)) || p->nx % B)) B = 0;
   *planes = B > 0 ? (int)B : p->nxl;
   *nslab = B > 0 ? (int)((p->nx + B - 1) / B) : 1;
   return 0;

@@ -12,10 +12,8 @@ int rf_mt_set_jump(rf_plan* p, int npolys, const uint16_t* pos, const int* npos,
   RF_REQUIRE(npolys >= 1 && stride >= 1 && blocks_per_segment >= 1 && radix >= 2 && npolys % (radix - 1) == 0, "invalid jump table");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipStreamSynchronize(p->stream));
-  if (p->mt_pos) RF_HIP(hipFree(p->mt_pos));
-  if (p->mt_npos_dev) RF_HIP(hipFree(p->mt_npos_dev));
-  p->mt_pos = nullptr;
-  p->mt_npos_dev = nullptr;
+  RF_HIP(p->mt_pos.release());                    // (always fresh tables)
+  RF_HIP(p->mt_npos_dev.release());
   // device rows (rf_k_mt.hip mt_jump_kernel): four lists, one per class c = position mod 4, each padded to a multiple of 8 entries;
   // an entry is the byte offset 4 (position - c) of an aligned 16-byte read; the padding points into the block of zero words
   // behind the 33-block window (33 * 624 words); four padded counts per polynomial
@@ -37,10 +35,10 @@ int rf_mt_set_jump(rf_plan* p, int npolys, const uint16_t* pos, const int* npos,
     }
     for (int c = 0; c < 4; ++c) counts[4 * l + c] = padded[c];
   }
-  RF_HIP(hipMalloc((void**)&p->mt_pos, wide.size() * sizeof(uint32_t)));
-  RF_HIP(hipMemcpy(p->mt_pos, wide.data(), wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  RF_HIP(hipMalloc((void**)&p->mt_npos_dev, counts.size() * sizeof(int)));
-  RF_HIP(hipMemcpy(p->mt_npos_dev, counts.data(), counts.size() * sizeof(int), hipMemcpyHostToDevice));
+  RF_HIP(p->mt_pos.reserve(wide.size() * sizeof(uint32_t)));
+  RF_HIP(hipMemcpy(p->mt_pos.get(), wide.data(), wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  RF_HIP(p->mt_npos_dev.reserve(counts.size() * sizeof(int)));
+  RF_HIP(hipMemcpy(p->mt_npos_dev.get(), counts.data(), counts.size() * sizeof(int), hipMemcpyHostToDevice));
   p->mt_npos.assign(npos, npos + npolys);
   p->mt_stride = wstride;
   p->mt_bps = blocks_per_segment;
@@ -78,29 +76,17 @@ int mt_geom(rf_plan* p, int single, MtGeom& g) {
   return 0;
 }
 int mt_ensure_buffers(rf_plan* p, const MtGeom& g) {
-  const size_t nstates = (size_t)g.nseg;
-  if (p->mt_states_cap < nstates) {
-    if (p->mt_states) RF_HIP(hipFree(p->mt_states));
-    p->mt_states = nullptr;
-    RF_HIP(hipMalloc((void**)&p->mt_states, nstates * 624 * sizeof(uint32_t)));
-    p->mt_states_cap = nstates;
+  RF_HIP(p->mt_states.reserve((size_t)g.nseg * 624 * sizeof(uint32_t)));
+  const size_t seg = ((size_t)g.nseg + 1) * sizeof(unsigned long long);
+  if (p->mt_counts.bytes < seg || p->mt_offsets.bytes < seg) {      // the pair grows together: both freed, then both allocated
+    RF_HIP(p->mt_counts.release());
+    RF_HIP(p->mt_offsets.release());
   }
-  if (p->mt_seg_cap < (size_t)g.nseg + 1) {
-    if (p->mt_counts) RF_HIP(hipFree(p->mt_counts));
-    if (p->mt_offsets) RF_HIP(hipFree(p->mt_offsets));
-    p->mt_counts = p->mt_offsets = nullptr;
-    RF_HIP(hipMalloc((void**)&p->mt_counts, ((size_t)g.nseg + 1) * sizeof(unsigned long long)));
-    RF_HIP(hipMalloc((void**)&p->mt_offsets, ((size_t)g.nseg + 1) * sizeof(unsigned long long)));
-    p->mt_seg_cap = (size_t)g.nseg + 1;
-  }
-  if (!p->mt_rowtab) RF_HIP(hipMalloc(&p->mt_rowtab, (size_t)p->nx * p->ny * sizeof(RowLoc)));
-  if (!p->mt_flags) RF_HIP(hipMalloc((void**)&p->mt_flags, sizeof(int)));
-  if (p->mt_scratch_bytes < g.need) {
-    if (p->mt_scratch) RF_HIP(hipFree(p->mt_scratch));
-    p->mt_scratch = nullptr; p->mt_scratch_bytes = 0;
-    RF_HIP(hipMalloc(&p->mt_scratch, g.need));
-    p->mt_scratch_bytes = g.need;
-  }
+  RF_HIP(p->mt_counts.reserve(seg));
+  RF_HIP(p->mt_offsets.reserve(seg));
+  RF_HIP(p->mt_rowtab.reserve((size_t)p->nx * p->ny * sizeof(RowLoc)));
+  RF_HIP(p->mt_flags.reserve(sizeof(int)));
+  RF_HIP(p->mt_scratch.reserve(g.need));
   return 0;
 }
 // the replay itself on stream s, from the start state in p->mt_states[0 .. 624): jump tree, ONE generation pass, scan (and the
@@ -111,7 +97,7 @@ int mt_queue(rf_plan* p, const MtGeom& g, int single, hipStream_t s) {
   long long dist = 1;
   for (int t = 0; t < g.stages; ++t, dist *= R) {
     const int nsrc = (int)(dist < g.nseg ? dist : g.nseg);
-    RF_HIP(launch_mt_jump(p->mt_states, p->mt_pos + (size_t)t * (R - 1) * p->mt_stride, p->mt_npos_dev + 4 * t * (R - 1), p->mt_stride, nsrc,
+    RF_HIP(launch_mt_jump(p->mt_states.get(), p->mt_pos.get() + (size_t)t * (R - 1) * p->mt_stride, p->mt_npos_dev.get() + 4 * t * (R - 1), p->mt_stride, nsrc,
                           dist, R - 1, g.nseg, s));
   }
   // ONE generation pass: every segment writes its accepted pairs densely into its own run of the scratch array
@@ -119,16 +105,16 @@ int mt_queue(rf_plan* p, const MtGeom& g, int single, hipStream_t s) {
   // moves the runs into place.  (Round 1 generated every block twice -- a count pass, then a fill pass that knew the
   // offsets: 2.5 + 3.3 ms against 3.3 + 1.x ms for fill + move.)  A kz-slab rank replays the WHOLE stream (where a
   // deviate goes depends on every earlier acceptance) and keeps the deviates of its own planes while moving.
-  RF_HIP(launch_mt_polar(single != 0, p->mt_states, g.nseg, p->mt_bps, g.total_blocks, p->mt_counts, p->mt_scratch, g.cap, s));
-  RF_HIP(launch_mt_scan(p->mt_counts, p->mt_offsets, g.nseg, s));
+  RF_HIP(launch_mt_polar(single != 0, p->mt_states.get(), g.nseg, p->mt_bps, g.total_blocks, p->mt_counts.get(), p->mt_scratch.ptr, g.cap, s));
+  RF_HIP(launch_mt_scan(p->mt_counts.get(), p->mt_offsets.get(), g.nseg, s));
   // float64 deviates are moved into cell order (and cut to this rank's planes); float32 ones stay in the segments' runs:
   // the generation pass finds cell c through the scan (slack_cell), which saves the 1.7 ms copy per 1024^3
   if (single) {
-    RF_HIP(hipMemsetAsync(p->mt_flags, 0, sizeof(int), s));
-    RF_HIP(launch_mt_rowtab(p->mt_offsets, g.nseg, p->mt_rowtab, p->nx, p->ny, (int)p->nzc + 1, p->mt_flags, s));
+    RF_HIP(hipMemsetAsync(p->mt_flags.get(), 0, sizeof(int), s));
+    RF_HIP(launch_mt_rowtab(p->mt_offsets.get(), g.nseg, p->mt_rowtab.ptr, p->nx, p->ny, (int)p->nzc + 1, p->mt_flags.get(), s));
   }
   if (!single)
-    RF_HIP(launch_mt_compact(false, p->mt_scratch, p->mt_counts, p->mt_offsets, g.nseg, g.cap, p->noise, g.ncells, (int)p->nzc + 1,
+    RF_HIP(launch_mt_compact(false, p->mt_scratch.ptr, p->mt_counts.get(), p->mt_offsets.get(), g.nseg, g.cap, p->noise.get(), g.ncells, (int)p->nzc + 1,
                              (int)p->nzl + 1, p->kz0, s));
   return 0;
 }
@@ -140,7 +126,7 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
   // flag, tables too dense for the per-bin records) read float64 deviates and get them
   if (single && (p->f64 || p->generic || !p->have_fast || p->exact_gen)) single = 0;
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->mt_pos && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
+  RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
   RF_HIP(hipSetDevice(p->device));
   if (!single)
     if (int rc = ensure_noise(p)) return rc;
@@ -155,15 +141,15 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
   }
   if (int rc = mt_ensure_buffers(p, g)) return rc;
   hipStream_t s = p->stream;
-  RF_HIP(hipMemcpyAsync(p->mt_states, state624, 624 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  RF_HIP(hipMemcpyAsync(p->mt_states.get(), state624, 624 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   if (int rc = mt_queue(p, g, single, s)) return rc;
   const int nseg = g.nseg;
   unsigned long long total = 0;
   int flags = 0;
   p->noise_resident = false;
   p->noise32_resident = false;
-  RF_HIP(hipMemcpyAsync(&total, p->mt_offsets + nseg, sizeof(total), hipMemcpyDeviceToHost, s));
-  if (single) RF_HIP(hipMemcpyAsync(&flags, p->mt_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
+  RF_HIP(hipMemcpyAsync(&total, p->mt_offsets.get() + nseg, sizeof(total), hipMemcpyDeviceToHost, s));
+  if (single) RF_HIP(hipMemcpyAsync(&flags, p->mt_flags.get(), sizeof(flags), hipMemcpyDeviceToHost, s));
   RF_HIP(hipStreamSynchronize(s));
   p->nseg = nseg;
   p->seg_cap = g.cap;
@@ -179,9 +165,7 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
     // and releasing 11 GB costs ~0.5 s per call, a hundred times the replay).  (float32 deviates live IN the runs and keep them.)
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < total_b / 3) {
-      RF_HIP(hipFree(p->mt_scratch));
-      p->mt_scratch = nullptr;
-      p->mt_scratch_bytes = 0;
+      RF_HIP(p->mt_scratch.release());
     }
   }
   return 0;
@@ -204,7 +188,7 @@ inline int sh_seg_begin(int r, int nseg, int nranks) { return (int)((long long)r
 int rf_mt_share_segments(rf_plan* p, int* nseg_total, int* seg_first, int* seg_count) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked && !p->generic, "the distributed replay serves packed plans on the tiled kernels");
-  RF_REQUIRE(p->mt_pos && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
+  RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
   MtGeom g;
   if (int rc = mt_geom(p, 1, g)) return rc;
   const int a = sh_seg_begin(p->rank, g.nseg, p->nranks), b = sh_seg_begin(p->rank + 1, g.nseg, p->nranks);
@@ -218,7 +202,7 @@ int rf_mt_share_begin(rf_plan* p, const uint32_t* state624, int single, unsigned
   RF_REQUIRE(p && state624 && counts_out, "null argument");
   RF_REQUIRE(!p->unpacked && !p->generic, "the distributed replay serves packed plans on the tiled kernels");
   RF_REQUIRE(!p->replicate, "replicated-generation plans draw native deviates only");
-  RF_REQUIRE(p->mt_pos && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
+  RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
   RF_REQUIRE(p->nranks >= 1 && p->nranks <= 64, "unsupported number of ranks");
   if (single && p->f64) single = 0;                      // float64 cells: keep the exact deviates
   RF_HIP(hipSetDevice(p->device));
@@ -237,7 +221,7 @@ int rf_mt_share_begin(rf_plan* p, const uint32_t* state624, int single, unsigned
   // the start state of segment `first`: one jump per non-zero radix-R digit of `first` (digit d of weight R^t: polynomial
   // t (R - 1) + d - 1 of the table), hopping through the spare slots behind the local states
   int slot = nloc;
-  RF_HIP(hipMemcpyAsync(p->mt_states + (size_t)slot * 624, state624, 624 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  RF_HIP(hipMemcpyAsync(p->mt_states.get() + (size_t)slot * 624, state624, 624 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   {
     int rest = first;
     for (int t = 0; rest > 0; ++t, rest /= R) {
@@ -245,21 +229,21 @@ int rf_mt_share_begin(rf_plan* p, const uint32_t* state624, int single, unsigned
       if (d == 0) continue;
       RF_REQUIRE(t < g.stages && slot + 1 < nloc + 8, "segment index beyond the uploaded jump table");
       const int row = t * (R - 1) + d - 1;
-      RF_HIP(launch_mt_jump(p->mt_states + (size_t)slot * 624, p->mt_pos + (size_t)row * p->mt_stride, p->mt_npos_dev + 4 * row, p->mt_stride,
+      RF_HIP(launch_mt_jump(p->mt_states.get() + (size_t)slot * 624, p->mt_pos.get() + (size_t)row * p->mt_stride, p->mt_npos_dev.get() + 4 * row, p->mt_stride,
                             1, 1, 1, 2, s));
       ++slot;
     }
   }
-  RF_HIP(hipMemcpyAsync(p->mt_states, p->mt_states + (size_t)slot * 624, 624 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  RF_HIP(hipMemcpyAsync(p->mt_states.get(), p->mt_states.get() + (size_t)slot * 624, 624 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   // the local tree and the generation pass over the local segments (mt_queue with a shifted origin)
   long long dist = 1;
   for (int t = 0; dist < nloc; ++t, dist *= R) {
     const int nsrc = (int)(dist < nloc ? dist : nloc);
-    RF_HIP(launch_mt_jump(p->mt_states, p->mt_pos + (size_t)t * (R - 1) * p->mt_stride, p->mt_npos_dev + 4 * t * (R - 1), p->mt_stride, nsrc,
+    RF_HIP(launch_mt_jump(p->mt_states.get(), p->mt_pos.get() + (size_t)t * (R - 1) * p->mt_stride, p->mt_npos_dev.get() + 4 * t * (R - 1), p->mt_stride, nsrc,
                           dist, R - 1, nloc, s));
   }
-  RF_HIP(launch_mt_polar(single != 0, p->mt_states, nloc, p->mt_bps, g.total_blocks - (long long)first * p->mt_bps, p->mt_counts, p->mt_scratch, g.cap, s));
-  RF_HIP(hipMemcpyAsync(counts_out, p->mt_counts, (size_t)nloc * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  RF_HIP(launch_mt_polar(single != 0, p->mt_states.get(), nloc, p->mt_bps, g.total_blocks - (long long)first * p->mt_bps, p->mt_counts.get(), p->mt_scratch.ptr, g.cap, s));
+  RF_HIP(hipMemcpyAsync(counts_out, p->mt_counts.get(), (size_t)nloc * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   RF_HIP(hipStreamSynchronize(s));
   p->sh_single = single; p->sh_first = first; p->sh_nloc = nloc;
   p->noise_resident = false;                              // (p->noise is about to be overwritten)
@@ -278,15 +262,15 @@ int rf_mt_share_gather(rf_plan* p, unsigned long long* counts_all) {
   MtGeom g;
   if (int rc = mt_geom(p, p->sh_single, g)) return rc;
   if (p->comm_stream) RF_HIP(hipStreamSynchronize(p->comm_stream));          // (the communicator is used from one stream at a time)
-  unsigned long long* tmp = nullptr;
-  RF_HIP(hipMalloc((void**)&tmp, (size_t)g.nseg * sizeof(unsigned long long)));
+  DevBuf<unsigned long long> tmp_buf;
+  RF_HIP(tmp_buf.reserve((size_t)g.nseg * sizeof(unsigned long long)));
+  unsigned long long* tmp = tmp_buf.get();
   hipStream_t s = p->stream;
   hipError_t e = hipMemsetAsync(tmp, 0, (size_t)g.nseg * sizeof(unsigned long long), s);
-  if (e == hipSuccess) e = hipMemcpyAsync(tmp + p->sh_first, p->mt_counts, (size_t)p->sh_nloc * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tmp + p->sh_first, p->mt_counts.get(), (size_t)p->sh_nloc * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess && p->comm && g_rccl.AllReduce(tmp, tmp, (size_t)g.nseg, ncclUint64, ncclSum, p->comm, s) != ncclSuccess) e = hipErrorUnknown;
   if (e == hipSuccess) e = hipMemcpyAsync(counts_all, tmp, (size_t)g.nseg * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(tmp);
   RF_HIP(e);
   return 0;
 }
@@ -333,31 +317,15 @@ int rf_mt_share_pack(rf_plan* p, const unsigned long long* counts_all) {
   const size_t es = p->sh_single ? 2 * sizeof(float) : 2 * sizeof(double);
   const size_t send_bytes = (size_t)(p->sh_sendoff[P] > 0 ? p->sh_sendoff[P] : 1) * es;
   const size_t recv_pairs = (size_t)p->nx * p->ny * (nzl + 1);
-  if (p->mt_send_bytes < send_bytes) {
-    if (p->mt_send) RF_HIP(hipFree(p->mt_send));
-    p->mt_send = nullptr; p->mt_send_bytes = 0;
-    const size_t want = send_bytes + send_bytes / 64;    // (the shares differ from seed to seed by the counts' binomial noise)
-    RF_HIP(hipMalloc(&p->mt_send, want));
-    p->mt_send_bytes = want;
-  }
-  if (p->sh_single && p->mt_recv_bytes < recv_pairs * es) {
-    if (p->mt_recv) RF_HIP(hipFree(p->mt_recv));
-    p->mt_recv = nullptr; p->mt_recv_bytes = 0;
-    RF_HIP(hipMalloc(&p->mt_recv, recv_pairs * es));
-    p->mt_recv_bytes = recv_pairs * es;
-  }
-  if (!p->mt_sbase) RF_HIP(hipMalloc((void**)&p->mt_sbase, 64 * sizeof(long long)));
-  if (p->mt_first_cap < (size_t)p->sh_nloc) {
-    if (p->mt_first) RF_HIP(hipFree(p->mt_first));
-    p->mt_first = nullptr; p->mt_first_cap = 0;
-    RF_HIP(hipMalloc((void**)&p->mt_first, (size_t)p->sh_nloc * sizeof(unsigned long long)));
-    p->mt_first_cap = (size_t)p->sh_nloc;
-  }
+  if (p->mt_send.bytes < send_bytes) RF_HIP(p->mt_send.reserve(send_bytes + send_bytes / 64));    // (the shares differ from seed to seed by the counts' binomial noise)
+  if (p->sh_single) RF_HIP(p->mt_recv.reserve(recv_pairs * es));
+  RF_HIP(p->mt_sbase.reserve(64 * sizeof(long long)));
+  RF_HIP(p->mt_first.reserve((size_t)p->sh_nloc * sizeof(unsigned long long)));
   hipStream_t s = p->stream;
-  RF_HIP(hipMemcpyAsync(p->mt_sbase, sbase.data(), (size_t)P * sizeof(long long), hipMemcpyHostToDevice, s));
-  RF_HIP(hipMemcpyAsync(p->mt_first, off.data() + p->sh_first, (size_t)p->sh_nloc * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-  RF_HIP(launch_mt_share_pack(p->sh_single != 0, p->mt_scratch, p->mt_counts, p->mt_first, p->sh_nloc, g.cap, p->mt_send, g.ncells, nzh, nzl, P,
-                              p->mt_sbase, s));
+  RF_HIP(hipMemcpyAsync(p->mt_sbase.get(), sbase.data(), (size_t)P * sizeof(long long), hipMemcpyHostToDevice, s));
+  RF_HIP(hipMemcpyAsync(p->mt_first.get(), off.data() + p->sh_first, (size_t)p->sh_nloc * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  RF_HIP(launch_mt_share_pack(p->sh_single != 0, p->mt_scratch.ptr, p->mt_counts.get(), p->mt_first.get(), p->sh_nloc, g.cap, p->mt_send.ptr, g.ncells, nzh, nzl, P,
+                              p->mt_sbase.get(), s));
   RF_HIP(hipStreamSynchronize(s));                        // (sbase / off are host temporaries)
   p->sh_state = 2;
   return 0;
@@ -365,7 +333,7 @@ int rf_mt_share_pack(rf_plan* p, const unsigned long long* counts_all) {
 
 namespace {
 // where rank p's stream arrives: the resident deviates themselves (float64) or the float32 staging buffer
-inline char* sh_recv_base(rf_plan* p) { return p->sh_single ? (char*)p->mt_recv : (char*)p->noise; }
+inline char* sh_recv_base(rf_plan* p) { return p->sh_single ? (char*)p->mt_recv.ptr : (char*)p->noise.get(); }
 }
 
 int rf_mt_share_exchange(rf_plan* p) {
@@ -376,13 +344,13 @@ int rf_mt_share_exchange(rf_plan* p) {
   const size_t es = p->sh_single ? 2 * sizeof(float) : 2 * sizeof(double);
   hipStream_t s = p->stream;
   const int me = p->rank;
-  RF_HIP(hipMemcpyAsync(sh_recv_base(p) + p->sh_recvoff[me] * es, (const char*)p->mt_send + p->sh_sendoff[me] * es, p->sh_sendcnt[me] * es,
+  RF_HIP(hipMemcpyAsync(sh_recv_base(p) + p->sh_recvoff[me] * es, (const char*)p->mt_send.ptr + p->sh_sendoff[me] * es, p->sh_sendcnt[me] * es,
                         hipMemcpyDeviceToDevice, s));
   if (p->nranks > 1) {
     RF_NCCL(g_rccl.GroupStart());
     for (int h = 0; h < p->nranks; ++h) {
       if (h == me) continue;
-      if (p->sh_sendcnt[h]) RF_NCCL(g_rccl.Send((const char*)p->mt_send + p->sh_sendoff[h] * es, p->sh_sendcnt[h] * es, ncclUint8, h, p->comm, s));
+      if (p->sh_sendcnt[h]) RF_NCCL(g_rccl.Send((const char*)p->mt_send.ptr + p->sh_sendoff[h] * es, p->sh_sendcnt[h] * es, ncclUint8, h, p->comm, s));
       if (p->sh_recvcnt[h]) RF_NCCL(g_rccl.Recv(sh_recv_base(p) + p->sh_recvoff[h] * es, p->sh_recvcnt[h] * es, ncclUint8, h, p->comm, s));
     }
     RF_NCCL(g_rccl.GroupEnd());
@@ -404,7 +372,7 @@ int rf_mt_share_exchange_local(rf_plan** plans, int n) {
     for (int h = 0; h < n; ++h) {
       RF_REQUIRE(plans[g]->sh_sendcnt[h] == plans[h]->sh_recvcnt[g], "send / receive counts disagree");
       if (plans[g]->sh_sendcnt[h])
-        RF_HIP(hipMemcpy(sh_recv_base(plans[h]) + plans[h]->sh_recvoff[g] * es, (const char*)plans[g]->mt_send + plans[g]->sh_sendoff[h] * es,
+        RF_HIP(hipMemcpy(sh_recv_base(plans[h]) + plans[h]->sh_recvoff[g] * es, (const char*)plans[g]->mt_send.ptr + plans[g]->sh_sendoff[h] * es,
                          plans[g]->sh_sendcnt[h] * es, hipMemcpyDeviceToDevice));
     }
   RF_HIP(hipDeviceSynchronize());       // (see rf_slab_exchange_local)
@@ -417,7 +385,7 @@ int rf_mt_share_finish(rf_plan* p, unsigned long long* accepted) {
   RF_REQUIRE(p->sh_state == 3, "the exchange must have run first");
   RF_HIP(hipSetDevice(p->device));
   if (p->sh_single)
-    RF_HIP(launch_mt_share_widen(p->mt_recv, p->noise, (long long)p->nx * p->ny * (p->nzl + 1), p->stream));
+    RF_HIP(launch_mt_share_widen(p->mt_recv.ptr, p->noise.get(), (long long)p->nx * p->ny * (p->nzl + 1), p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   p->noise_resident = true;
   p->noise32_resident = false;
@@ -435,7 +403,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(n >= 1, "need at least one seed");
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
-  RF_REQUIRE(p->mt_pos && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
+  RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
   RF_REQUIRE(p->nranks == 1 && !p->force_slab && !p->generic && !p->f64 && p->have_fast && !p->exact_gen,
              "rf_realise_batch_reference is for single-GPU complex64 plans on the fast generation path; loop rf_noise_mt19937 + rf_realise otherwise");
   RF_HIP(hipSetDevice(p->device));
@@ -446,20 +414,18 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   if (int rc = ensure_x(p)) return rc;
   RF_HIP(hipStreamSynchronize(p->stream));
   if (int rc = ensure_stats(p, n)) return rc;
-  if (!p->aux_stream) {
-    RF_HIP(hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking));
-    for (auto& e : p->bev) RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  RF_HIP(p->aux_stream.create(hipStreamNonBlocking));
+  RF_HIP(p->bev.ensure(2, hipEventDisableTiming));
   // all start states and the per-seed accepted totals live on the device for the length of the batch (the plan keeps the block)
-  if (p->br_cap < n) {
-    if (p->br_tmp) RF_HIP(hipFree(p->br_tmp));
-    p->br_tmp = nullptr; p->br_cap = 0;
+  if (p->br_cap < n) {                                    // (br_cap: the block's layout is computed from it)
+    p->br_cap = 0;
+    RF_HIP(p->br_tmp.release());
     const int cap = n > 16 ? n : 16;
-    RF_HIP(hipMalloc(&p->br_tmp, (size_t)cap * (624 * sizeof(uint32_t) + sizeof(unsigned long long) + sizeof(int) + 4)));
+    RF_HIP(p->br_tmp.reserve((size_t)cap * (624 * sizeof(uint32_t) + sizeof(unsigned long long) + sizeof(int) + 4)));
     p->br_cap = cap;
   }
-  uint32_t* dstates = (uint32_t*)p->br_tmp;
-  unsigned long long* dtotals = (unsigned long long*)((char*)p->br_tmp + (size_t)p->br_cap * 624 * sizeof(uint32_t));
+  uint32_t* dstates = (uint32_t*)p->br_tmp.ptr;
+  unsigned long long* dtotals = (unsigned long long*)((char*)p->br_tmp.ptr + (size_t)p->br_cap * 624 * sizeof(uint32_t));
   int* dflags = (int*)(dtotals + p->br_cap);
   RF_HIP(hipMemcpy(dstates, states, (size_t)n * 624 * sizeof(uint32_t), hipMemcpyHostToDevice));
   hipStream_t S = p->stream, R = p->aux_stream;
@@ -474,10 +440,10 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   // both streams are drained before any return from here on
   auto drain = [&](int rc) { (void)hipStreamSynchronize(R); (void)hipStreamSynchronize(S); return rc; };
   auto replay = [&](int i) -> int {
-    RF_HIP(hipMemcpyAsync(p->mt_states, dstates + (size_t)i * 624, 624 * sizeof(uint32_t), hipMemcpyDeviceToDevice, R));
+    RF_HIP(hipMemcpyAsync(p->mt_states.get(), dstates + (size_t)i * 624, 624 * sizeof(uint32_t), hipMemcpyDeviceToDevice, R));
     if (int r = mt_queue(p, g, 1, R)) return r;
-    RF_HIP(hipMemcpyAsync(dtotals + i, p->mt_offsets + g.nseg, sizeof(unsigned long long), hipMemcpyDeviceToDevice, R));
-    RF_HIP(hipMemcpyAsync(dflags + i, p->mt_flags, sizeof(int), hipMemcpyDeviceToDevice, R));
+    RF_HIP(hipMemcpyAsync(dtotals + i, p->mt_offsets.get() + g.nseg, sizeof(unsigned long long), hipMemcpyDeviceToDevice, R));
+    RF_HIP(hipMemcpyAsync(dflags + i, p->mt_flags.get(), sizeof(int), hipMemcpyDeviceToDevice, R));
     RF_HIP(hipEventRecord(p->bev[0], R));
     return 0;
   };
@@ -491,14 +457,14 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     for (int i = 0; i < n; ++i) {
       RF_HIP(hipStreamWaitEvent(S, p->bev[0], 0));        // the runs of seed i are complete
       p->noise32_resident = true;                         // (queue_x selects the float32-pair kernel by it; cleared again on failure)
-      const bool xp = p->X && xpose_ok(p);
-      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X : p->W, S, false)) return rc;
+      const bool xp = p->X.ptr && xpose_ok(p);
+      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X.ptr : p->W.ptr, S, false)) return rc;
       RF_HIP(hipEventRecord(p->bev[1], S));               // the generation pass of seed i has read the runs
       if (i + 1 < n) {
         RF_HIP(hipStreamWaitEvent(R, p->bev[1], 0));
         if (int rc2 = replay(i + 1)) return rc2;
       }
-      if (int rc3 = queue_yz(p, cd, p->W, S, p->stats + 2 * i, false)) return rc3;
+      if (int rc3 = queue_yz(p, cd, p->W.ptr, S, p->stats.get() + 2 * i, false)) return rc3;
     }
     RF_HIP(hipEventRecord(p->ev[4], S));
     return 0;
@@ -536,7 +502,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
 
 int rf_can_batch_reference(rf_plan* p) {
   if (!p || p->unpacked || p->nranks != 1 || p->force_slab || p->generic || p->f64 || !p->have_fast || p->exact_gen || !p->have_kgrid ||
-      !p->have_power || !p->mt_pos || p->mt_npos.empty())
+      !p->have_power || !p->mt_pos.get() || p->mt_npos.empty())
     return 0;
   MtGeom g;
   if (mt_geom(p, 1, g)) return 0;
@@ -549,7 +515,7 @@ int rf_download_noise(rf_plan* p, double* host, unsigned long long first, unsign
   RF_REQUIRE(p->noise_resident, "no float64 deviates resident on the device");
   RF_REQUIRE(first + count <= 2ull * p->nx * p->ny * (p->nzl + 1), "range outside the noise buffer");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, p->noise + first, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(host, p->noise.get() + first, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }

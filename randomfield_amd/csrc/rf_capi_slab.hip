@@ -31,9 +31,9 @@ int rf_comm_init(rf_plan* p, const void* id128) {
   memcpy(&id, id128, sizeof(id));
   RF_NCCL(g_rccl.CommInitRank(&p->comm, p->nranks, id, p->rank));
   // one tiny collective now: a broken communicator should fail here, not inside a timed region
-  RF_HIP(hipMemsetAsync(p->coll_scratch, 0, 4 * sizeof(double), p->stream));
+  RF_HIP(hipMemsetAsync(p->coll_scratch.get(), 0, 4 * sizeof(double), p->stream));
   p->standin_wg = 0;                       // (a stand-in exchange is a thing of ranks without a communicator)
-  RF_NCCL(g_rccl.AllReduce(p->coll_scratch, p->coll_scratch, 2, ncclFloat64, ncclSum, p->comm, p->stream));
+  RF_NCCL(g_rccl.AllReduce(p->coll_scratch.get(), p->coll_scratch.get(), 2, ncclFloat64, ncclSum, p->comm, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -55,7 +55,7 @@ int rf_comm_allreduce_f64(rf_plan* p, double* inout, int n, int op) {
   RF_HIP(hipSetDevice(p->device));
   if (!p->comm) { RF_HIP(hipStreamSynchronize(p->stream)); return 0; }     // a one-rank communicator still runs the collective
   if (p->comm_stream) RF_HIP(hipStreamSynchronize(p->comm_stream));          // (the communicator is used from one stream at a time)
-  double* d = p->coll_scratch;            // its own two doubles: `stats` holds the moments of up to stats_cap realisations
+  double* d = p->coll_scratch.get();            // its own two doubles: `stats` holds the moments of up to stats_cap realisations
   RF_HIP(hipMemcpyAsync(d, inout, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
   RF_NCCL(g_rccl.AllReduce(d, d, n, ncclFloat64, op == 0 ? ncclSum : ncclMax, p->comm, p->stream));
   RF_HIP(hipMemcpyAsync(inout, d, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
@@ -73,7 +73,7 @@ int rf_slab_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_hos
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
   CallDesc cd;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
-  if (int rc = queue_xy(p, cd, make_gen(p, seed, mode, false), nullptr, p->W, p->stream, false)) return rc;
+  if (int rc = queue_xy(p, cd, make_gen(p, seed, mode, false), nullptr, p->W.ptr, p->stream, false)) return rc;
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -89,8 +89,8 @@ int rf_slab_forward_ex(rf_plan* p, uint64_t seed, int mode, const double* noise_
   if (source == RF_SLAB_GENERATE_SAVE_POTENTIAL) {
     if (int rc = potential_forward(p, seed, mode, noise_host, false)) return rc;
   } else {
-    RF_REQUIRE(p->K && p->k_valid, "no k-space data: call rf_generate, rf_load_potential or rf_upload_k first");
-    if (int rc = queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K, p->W, p->stream, false)) return rc;
+    RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate, rf_load_potential or rf_upload_k first");
+    if (int rc = queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, false)) return rc;
   }
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
@@ -110,7 +110,7 @@ int rf_slab_exchange_local(rf_plan** plans, int n) {
   for (int g = 0; g < n; ++g)        // sender g, receiver h: block h of sub-slab c of W_g -> segment (g, c) of R_h
     for (int h = 0; h < n; ++h)
       for (int c = 0; c < C; ++c)
-        RF_HIP(hipMemcpy((char*)plans[h]->R + ((size_t)g * C + c) * blk, (char*)plans[g]->W + (size_t)c * cb + (size_t)h * blk, blk, hipMemcpyDeviceToDevice));
+        RF_HIP(hipMemcpy((char*)plans[h]->R.ptr + ((size_t)g * C + c) * blk, (char*)plans[g]->W.ptr + (size_t)c * cb + (size_t)h * blk, blk, hipMemcpyDeviceToDevice));
   // a device-to-device hipMemcpy may return before the copy has run (it is only ordered on the null stream), and the
   // plans' streams do not synchronise with the null stream: without this the gathering z pass of a large grid read
   // blocks that had not arrived yet (caught by the full-size config-4 test; small grids happened to win the race)
@@ -123,7 +123,7 @@ int rf_slab_r2c_rows(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked && !p->generic, "this call applies to packed plans on the tiled kernels");
   RF_REQUIRE(p->nranks > 1, "rf_slab_* are for multi-rank plans");
-  RF_REQUIRE(p->real_valid && p->cur == p->W, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = queue_r2c_slab_rows(p, p->stream)) return rc;
   p->real_valid = false;
@@ -141,7 +141,7 @@ int rf_slab_exchange_local_reverse(rf_plan** plans, int n) {
   const size_t blk = (size_t)p0->nxl * p0->ny * p0->nzl * p0->csize;
   for (int h = 0; h < n; ++h)        // sender h (x slab), receiver g (kz slab): block g of R_h -> block h of W_g
     for (int g = 0; g < n; ++g)
-      RF_HIP(hipMemcpy((char*)plans[g]->W + h * blk, (const char*)plans[h]->R + g * blk, blk, hipMemcpyDeviceToDevice));
+      RF_HIP(hipMemcpy((char*)plans[g]->W.ptr + h * blk, (const char*)plans[h]->R.ptr + g * blk, blk, hipMemcpyDeviceToDevice));
   RF_HIP(hipDeviceSynchronize());       // (see rf_slab_exchange_local)
   return 0;
 }
@@ -166,8 +166,8 @@ int direct_reset(rf_plan* p) {
   for (void* m : p->ipc_open) (void)hipIpcCloseMemHandle(m);
   p->ipc_open.clear();
   p->peer_R[0].clear(); p->peer_R[1].clear();
-  if (p->peer_tab) { RF_HIP(hipFree(p->peer_tab)); p->peer_tab = nullptr; }
   p->peer_tab_chunks = 0;
+  RF_HIP(p->peer_tab.release());
   return 0;
 }
 bool direct_shape_ok(const rf_plan* p) {
@@ -181,7 +181,7 @@ bool direct_fill_record(rf_plan* p, unsigned char* mine) {
   memset(mine, 0, DIRECT_REC);
   if (!(direct_shape_ok(p) && !p->replicate) || ensure_batch_buffers(p) != 0) return false;
   hipIpcMemHandle_t hd[2];
-  if (hipIpcGetMemHandle(&hd[0], p->R) != hipSuccess || hipIpcGetMemHandle(&hd[1], p->R2) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (hipIpcGetMemHandle(&hd[0], p->R.ptr) != hipSuccess || hipIpcGetMemHandle(&hd[1], p->R2.ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
   memcpy(mine, hd, sizeof(hd));
   mine[2 * sizeof(hipIpcMemHandle_t)] = 1;
   // where the buffers live, so that a peer can ask the runtime BEFORE it maps them whether its device reaches this one at all
@@ -195,7 +195,7 @@ bool direct_map_peers(rf_plan* p, const unsigned char* rec, std::vector<void*>& 
   for (int h = 0; h < P; ++h)
     if (rec[DIRECT_REC * h + 2 * sizeof(hipIpcMemHandle_t)] != 1) return false;
   R0.assign(P, nullptr); R1.assign(P, nullptr);
-  R0[p->rank] = p->R; R1[p->rank] = p->R2;
+  R0[p->rank] = p->R.ptr; R1[p->rank] = p->R2.ptr;
   for (int h = 0; h < P; ++h) {
     if (h == p->rank) continue;
     hipIpcMemHandle_t ph[2];
@@ -223,9 +223,9 @@ bool direct_map_peers(rf_plan* p, const unsigned char* rec, std::vector<void*>& 
 // min over the communicator's ranks of a flag (1 = fine here), on the plan's stream
 int agree(rf_plan* p, bool mine, bool* all) {
   double v[2] = {mine ? 1.0 : 0.0, 0.0};
-  RF_HIP(hipMemcpyAsync(p->coll_scratch, v, sizeof(v), hipMemcpyHostToDevice, p->stream));
-  RF_NCCL(g_rccl.AllReduce(p->coll_scratch, p->coll_scratch, 2, ncclFloat64, ncclMin, p->comm, p->stream));
-  RF_HIP(hipMemcpyAsync(v, p->coll_scratch, sizeof(v), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(p->coll_scratch.get(), v, sizeof(v), hipMemcpyHostToDevice, p->stream));
+  RF_NCCL(g_rccl.AllReduce(p->coll_scratch.get(), p->coll_scratch.get(), 2, ncclFloat64, ncclMin, p->comm, p->stream));
+  RF_HIP(hipMemcpyAsync(v, p->coll_scratch.get(), sizeof(v), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   *all = v[0] > 0.5;
   return 0;
@@ -253,7 +253,7 @@ int rf_comm_enable_direct(rf_plan* p, int enable, int* enabled) {
   if (ok && ensure_batch_buffers(p) != 0) ok = false;
   if (P == 1) {                                  // the forced slab path of a single rank: its own buffers are all there is
     if (!ok) return 0;
-    p->peer_R[0].assign(1, p->R); p->peer_R[1].assign(1, p->R2);
+    p->peer_R[0].assign(1, p->R.ptr); p->peer_R[1].assign(1, p->R2.ptr);
     if (int rc = rebuild_peer_tab(p)) return rc;
     p->direct = true; *enabled = 1;
     return 0;
@@ -263,39 +263,40 @@ int rf_comm_enable_direct(rf_plan* p, int enable, int* enabled) {
   std::vector<unsigned char> rec(REC * P, 0);
   unsigned char* mine = rec.data() + REC * p->rank;
   ok = ok && direct_fill_record(p, mine);
-  unsigned char* dev = nullptr;
-  RF_HIP(hipMalloc((void**)&dev, REC * P));
-  auto done = [&](int rc) { (void)hipFree(dev); return rc; };
-  if (hipMemcpyAsync(dev + REC * p->rank, mine, REC, hipMemcpyHostToDevice, p->stream) != hipSuccess) return done(fail(2, "hipMemcpyAsync of the IPC handles failed"));
-  if (g_rccl.AllGather(dev + REC * p->rank, dev, REC, ncclUint8, p->comm, p->stream) != ncclSuccess) return done(fail(5, "ncclAllGather of the IPC handles failed"));
+  DevBuf<unsigned char> dev_buf;                 // (freed when this call returns, whichever way)
+  RF_HIP(dev_buf.reserve(REC * P));
+  unsigned char* dev = dev_buf.get();
+  if (hipMemcpyAsync(dev + REC * p->rank, mine, REC, hipMemcpyHostToDevice, p->stream) != hipSuccess) return fail(2, "hipMemcpyAsync of the IPC handles failed");
+  if (g_rccl.AllGather(dev + REC * p->rank, dev, REC, ncclUint8, p->comm, p->stream) != ncclSuccess) return fail(5, "ncclAllGather of the IPC handles failed");
   if (hipMemcpyAsync(rec.data(), dev, REC * P, hipMemcpyDeviceToHost, p->stream) != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess)
-    return done(fail(2, "reading back the gathered IPC handles failed"));
+    return fail(2, "reading back the gathered IPC handles failed");
   // 2. map the peers' buffers
   std::vector<void*> R0, R1;
   ok = ok && direct_map_peers(p, rec.data(), R0, R1);
   bool all = false;
-  if (int rc = agree(p, ok, &all)) return done(rc);
-  if (!all) { (void)hipFree(dev); return direct_reset(p); }
+  if (int rc = agree(p, ok, &all)) return rc;
+  if (!all) { (void)dev_buf.release(); return direct_reset(p); }
   // 3. prove it: rank g stores the marker (tag + g) into slot g of every rank's two buffers, from a kernel, as the y pass will;
   //    behind a barrier every rank must find all P markers in its own buffers (which are scratch between realisations)
   p->peer_R[0] = R0; p->peer_R[1] = R1;
-  void** tabs = nullptr;
-  if (hipMalloc((void**)&tabs, 2 * P * sizeof(void*)) != hipSuccess) return done(fail(2, "hipMalloc failed"));
+  DevBuf<void*> tabs_buf;
+  if (tabs_buf.reserve(2 * P * sizeof(void*)) != hipSuccess) return fail(2, "hipMalloc failed");
+  void** tabs = tabs_buf.get();
   std::vector<void*> both(R0); both.insert(both.end(), R1.begin(), R1.end());
   const unsigned long long tag = 0x5246444952000000ull;          // "RFDIR"
-  bool good = hipMemsetAsync(p->R, 0, 8 * P, p->stream) == hipSuccess && hipMemsetAsync(p->R2, 0, 8 * P, p->stream) == hipSuccess &&
+  bool good = hipMemsetAsync(p->R.ptr, 0, 8 * P, p->stream) == hipSuccess && hipMemsetAsync(p->R2.ptr, 0, 8 * P, p->stream) == hipSuccess &&
               hipMemcpyAsync(tabs, both.data(), 2 * P * sizeof(void*), hipMemcpyHostToDevice, p->stream) == hipSuccess;
-  if (int rc = direct_barrier(p, p->stream)) { (void)hipFree(tabs); return done(rc); }          // every rank has cleared its slots
+  if (int rc = direct_barrier(p, p->stream)) return rc;          // every rank has cleared its slots
   good = good && launch_peer_mark(tabs, 2 * P, p->rank, tag + (unsigned)p->rank, p->stream) == hipSuccess;
-  if (int rc = direct_barrier(p, p->stream)) { (void)hipFree(tabs); return done(rc); }          // every rank's markers are on their way ... and have landed
+  if (int rc = direct_barrier(p, p->stream)) return rc;          // every rank's markers are on their way ... and have landed
   std::vector<unsigned long long> got(2 * P, 0);
-  good = good && hipMemcpyAsync(got.data(), p->R, 8 * P, hipMemcpyDeviceToHost, p->stream) == hipSuccess &&
-         hipMemcpyAsync(got.data() + P, p->R2, 8 * P, hipMemcpyDeviceToHost, p->stream) == hipSuccess && hipStreamSynchronize(p->stream) == hipSuccess;
+  good = good && hipMemcpyAsync(got.data(), p->R.ptr, 8 * P, hipMemcpyDeviceToHost, p->stream) == hipSuccess &&
+         hipMemcpyAsync(got.data() + P, p->R2.ptr, 8 * P, hipMemcpyDeviceToHost, p->stream) == hipSuccess && hipStreamSynchronize(p->stream) == hipSuccess;
   for (int g = 0; g < P && good; ++g) good = got[g] == tag + (unsigned)g && got[P + g] == tag + (unsigned)g;
-  (void)hipFree(tabs);
+  (void)tabs_buf.release();
   (void)hipGetLastError();
-  if (int rc = agree(p, good, &all)) return done(rc);
-  (void)hipFree(dev);
+  if (int rc = agree(p, good, &all)) return rc;
+  (void)dev_buf.release();
   if (!all) return direct_reset(p);
   if (int rc = rebuild_peer_tab(p)) { (void)direct_reset(p); return rc; }
   p->direct = true;
@@ -326,7 +327,7 @@ int rf_slab_link_direct(rf_plan** plans, int n, int enable) {
   for (int g = 0; g < n; ++g) {
     rf_plan* p = plans[g];
     p->peer_R[0].resize(n); p->peer_R[1].resize(n);
-    for (int h = 0; h < n; ++h) { p->peer_R[0][h] = plans[h]->R; p->peer_R[1][h] = plans[h]->R2; }
+    for (int h = 0; h < n; ++h) { p->peer_R[0][h] = plans[h]->R.ptr; p->peer_R[1][h] = plans[h]->R2.ptr; }
     if (int rc = rebuild_peer_tab(p)) return rc;
     p->direct = true;
     p->standin_wg = 0;
@@ -381,8 +382,8 @@ int rf_slab_set_direct_standin(rf_plan* p, int on, int overlap) {
   const long long blk = (long long)p->nxl * p->ny * p->nzl * (long long)p->csize;
   p->peer_R[0].resize(p->nranks); p->peer_R[1].resize(p->nranks);
   for (int h = 0; h < p->nranks; ++h) {
-    p->peer_R[0][h] = (char*)p->R + (long long)(h - p->rank) * blk;
-    p->peer_R[1][h] = (char*)p->R2 + (long long)(h - p->rank) * blk;
+    p->peer_R[0][h] = (char*)p->R.ptr + (long long)(h - p->rank) * blk;
+    p->peer_R[1][h] = (char*)p->R2.ptr + (long long)(h - p->rank) * blk;
   }
   if (int rc = rebuild_peer_tab(p)) return rc;
   p->direct = true;
@@ -397,7 +398,7 @@ int rf_slab_backward(rf_plan* p) {
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->nranks > 1, "rf_slab_* are for multi-rank plans");
   RF_HIP(hipSetDevice(p->device));
-  if (int rc = queue_z_slab(p, p->R, p->W, p->stats, p->stream)) return rc;
+  if (int rc = queue_z_slab(p, p->R.ptr, p->W.ptr, p->stats.get(), p->stream)) return rc;
   p->stats_slot = 0;
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
@@ -433,7 +434,7 @@ int rf_slab_stats(rf_plan* p, double* sum, double* sumsq) {
   RF_REQUIRE(p && sum && sumsq, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   double st[2];
-  RF_HIP(hipMemcpyAsync(st, p->stats, sizeof(st), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(st, p->stats.get(), sizeof(st), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   *sum = st[0]; *sumsq = st[1];
   return 0;
