@@ -45,7 +45,9 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * minor number -- the version stays 5.5 -- and is announced by its feature bit alone: ask rf_abi_features() & RF_FEATURE_POWER_MEASURE.
  * The same holds for the second-order (2LPT) calls: rf_abi_features() & RF_FEATURE_LPT2.
  * And for the particle calls -- the resident displacement buffer and the cloud-in-cell paint, rf_particles_accumulate, rf_particles_upload,
- * rf_particles_download, rf_particles_paint: rf_abi_features() & RF_FEATURE_PARTICLES, the version stays 5.5. */
+ * rf_particles_download, rf_particles_paint: rf_abi_features() & RF_FEATURE_PARTICLES, the version stays 5.5.
+ * And for rf_measure_multipoles, the redshift-space multipole moments of the binned power spectrum with an optional window compensation:
+ * rf_abi_features() & RF_FEATURE_POWER_MULTIPOLES, the version stays 5.5. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -73,8 +75,9 @@ enum {
   RF_FEATURE_POWER_MEASURE = 1 << 15,      /* rf_measure_power: the binned power spectrum of the k buffer or of the field */
   RF_FEATURE_LPT2 = 1 << 16,               /* rf_load_hessian, rf_execute_hessian_c2r, rf_lpt2_source, rf_lpt2_potential, RF_GRAD_FROM_POTENTIAL2:
                                               the second-order Lagrangian displacement */
-  RF_FEATURE_PARTICLES = 1 << 17           /* rf_particles_accumulate, rf_particles_upload, rf_particles_download, rf_particles_paint: the three
+  RF_FEATURE_PARTICLES = 1 << 17,          /* rf_particles_accumulate, rf_particles_upload, rf_particles_download, rf_particles_paint: the three
                                               displacement components resident on the device, painted back onto the grid (cloud in cell) */
+  RF_FEATURE_POWER_MULTIPOLES = 1 << 18    /* rf_measure_multipoles: the moments of mu^2 behind P0, P2, P4 along a grid axis, window compensation */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -354,6 +357,22 @@ int rf_particles_paint(rf_plan* plan, const double* inv_h, unsigned long long* d
  * refused with nothing queued.  Blocks until the three arrays (nbins entries each) are on the host; rf_elapsed_ms covers the call. */
 enum { RF_POWER_FROM_KSPACE = 0, RF_POWER_FROM_FIELD = 1 };
 int rf_measure_power(rf_plan* plan, int source, const double* k_edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p);
+
+/* ---- power spectrum multipoles (rf_abi_features() & RF_FEATURE_POWER_MULTIPOLES) -- */
+/* The same sweep with a line of sight along grid axis los_axis (0, 1, 2: plane-parallel) and an optional window compensation.  Cells, k^2,
+ * bins, weights w, source, preconditions, blocking and rf_elapsed_ms are exactly rf_measure_power's.  mu^2 = k_los^2 / k^2, k_los^2 the
+ * entry of that axis' own table of rf_set_kgrid (one float64 division).  comp_x, comp_y, comp_z: float64 tables of nx, ny, nz/2 + 1
+ * entries, each may be NULL (= all ones); c = (comp_x[ix] comp_y[iy]) comp_z[iz] and e = c |delta(k)|^2 (for a mass-assignment window
+ * of order p: sinc(pi m / n)^(-2p) per axis, m the signed frequency index).  Per bin, nbins entries each: count = sum of w (exact),
+ * sum_k = sum of w sqrt(k^2), m0 = sum of w e, m2 = sum of w (e mu^2), m4 = sum of w ((e mu^2) mu^2) -- moments of mu^2, every term
+ * non-negative, summed in float64 in a fixed order: the same plan, data, edges and tables give the same bits on every call.  With
+ * Mj = (V / N^2) mj / count the multipoles are P0 = M0, P2 = (5/2)(3 M2 - M0), P4 = (9/8)(35 M4 - 30 M2 + 3 M0).  With NULL tables
+ * the terms of count, sum_k and m0 are those of rf_measure_power's count, sum_k and sum_p (the float sums agree to summation order).
+ * Refused with nothing queued: what rf_measure_power refuses, a los_axis outside 0..2, and a compensation entry that is not finite and
+ * positive.  The call's lazy buffer (edges, result, tables, per-workgroup partials) is counted by rf_plan_nbytes. */
+int rf_measure_multipoles(rf_plan* plan, int source, int los_axis, const double* k_edges, int nbins,
+                          const double* comp_x, const double* comp_y, const double* comp_z,
+                          unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4);
 
 /* ---- host <-> device (layout conversion to/from the reference's arrays) -- */
 int rf_upload_k(rf_plan* plan, const void* host);            /* (nx, ny, nz/2+1) complex */

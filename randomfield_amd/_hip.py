@@ -34,7 +34,7 @@ ABI_MAJOR, ABI_MINOR = 5, 5
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
-            "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17}
+            "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17, "power_multipoles": 1 << 18}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -93,6 +93,8 @@ SIGNATURES = {
     "rf_particles_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rf_particles_paint": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
+    "rf_measure_multipoles": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp,
+                                            ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp, _c_dp, _c_dp]),
     "rf_lensing_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "rf_download_aux": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "rf_upload_k": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -741,6 +743,29 @@ class DevicePlan(object):
         check(self._lib.rf_measure_power(self._h, int(source), _dp(e), nbins, count.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
                                          _dp(sum_k), _dp(sum_p)), "rf_measure_power")
         return count, sum_k, sum_p
+
+    def measure_multipoles(self, edges, los, source=RF_POWER_FROM_KSPACE, compensation=None):
+        """Per-bin sums of the power spectrum multipoles along grid axis ``los`` (rf_measure_multipoles): ``edges`` and ``source`` as
+        :meth:`measure_power`; ``compensation``: None or three float64 tables of nx, ny, nz/2 + 1 finite positive entries (each may be
+        None = all ones) multiplied onto |delta(k)|^2.  Returns ``(count, sum_k, m0, m2, m4)``: the uint64 sum of the weights and the
+        float64 sums of w |k|, w e, w e mu^2, w e mu^4 with e the compensated |delta(k)|^2."""
+        e = _f64(np.asarray(edges, np.float64).ravel())
+        nbins = len(e) - 1
+        lengths = (self.nx, self.ny, self.nz // 2 + 1)
+        tabs = [None] * 3 if compensation is None else list(compensation)
+        if len(tabs) != 3:
+            raise ValueError("measure_multipoles: compensation is three per-axis tables")
+        for a in range(3):
+            if tabs[a] is not None:
+                tabs[a] = _f64(np.asarray(tabs[a], np.float64).ravel())
+                if len(tabs[a]) != lengths[a]:
+                    raise ValueError("measure_multipoles: compensation table %d needs %d entries" % (a, lengths[a]))
+        count = np.zeros(max(nbins, 1), np.uint64)
+        sums = [np.zeros(max(nbins, 1), np.float64) for _ in range(4)]
+        check(self._lib.rf_measure_multipoles(self._h, int(source), int(los), _dp(e), nbins, *[None if t is None else _dp(t) for t in tabs],
+                                              count.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), *[_dp(v) for v in sums]),
+              "rf_measure_multipoles")
+        return (count,) + tuple(sums)
 
     # -- host <-> device --------------------------------------------------
     @property

@@ -1040,6 +1040,38 @@ int emu_measure_power(int f64, int nx, int ny, int nz, int packed, const double*
       }
   return 0;
 }
+// the power spectrum multipoles (rf_core.h power_load / multipole_cell over an array in array order, as rf_measure_multipoles' sweep): S,
+// packed and edges as emu_measure_power's; los 0, 1, 2; cx, cy, cz: tables of nx, ny, nz/2 + 1 finite positive entries, or null
+int emu_measure_multipoles(int f64, int nx, int ny, int nz, int packed, int los, const double* kx2, const double* ky2, const double* kz2,
+                           const void* S, const double* edges, int nbins, const double* cx, const double* cy, const double* cz,
+                           unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4) {
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || nbins < 1 || nbins > 1024 || los < 0 || los > 2 || !(kx2 && ky2 && kz2 && S && edges) ||
+      !(count && sum_k && m0 && m2 && m4) || !(edges[0] >= 0.0)) return -1;
+  for (int b = 0; b < nbins; ++b) if (!(edges[b] < edges[b + 1])) return -1;
+  const double* comp[3] = {cx, cy, cz};
+  const int clen[3] = {nx, ny, nz / 2 + 1};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; comp[a] && i < clen[a]; ++i) if (!(std::isfinite(comp[a][i]) && comp[a][i] > 0.0)) return -1;
+  MultipoleParams g;
+  memset(&g, 0, sizeof(g));
+  g.p.nx = nx; g.p.ny = ny; g.p.nz = nz; g.p.nbins = nbins; g.p.packed = packed != 0;
+  g.p.kx2 = kx2; g.p.ky2 = ky2; g.p.kz2 = kz2;
+  g.los = los; g.cx = cx; g.cy = cy; g.cz = cz;
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = edges[b] * edges[b];
+  for (int b = 0; b < nbins; ++b) { count[b] = 0; sum_k[b] = 0.0; m0[b] = 0.0; m2[b] = 0.0; m4[b] = 0.0; }
+  for (int ix = 0; ix < nx; ++ix)
+    for (int iy = 0; iy < ny; ++iy)
+      for (int iz = 0; iz <= nz / 2; ++iz) {
+        int w = 0;
+        double wk = 0.0, m[3];
+        const int b = f64 ? multipole_cell<double>(g, e2.data(), power_load<double>(g.p, (const cplx<double>*)S, ix, iy, iz), ix, iy, iz, w, wk, m)
+                          : multipole_cell<float>(g, e2.data(), power_load<float>(g.p, (const cplx<float>*)S, ix, iy, iz), ix, iy, iz, w, wk, m);
+        if (b < 0) continue;
+        count[b] += (unsigned long long)w; sum_k[b] += wk; m0[b] += m[0]; m2[b] += m[1]; m4[b] += m[2];
+      }
+  return 0;
+}
 int emu_generic_r2c(int f64, int nx, int ny, int nz, const void* W, void* K) {
   return f64 ? generic_r2c_impl<double>(nx, ny, nz, (const double*)W, (cplx<double>*)K)
              : generic_r2c_impl<float>(nx, ny, nz, (const float*)W, (cplx<float>*)K);

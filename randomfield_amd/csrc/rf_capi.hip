@@ -971,7 +971,7 @@ unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
          RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE | RF_FEATURE_LPT2 |
-         RF_FEATURE_PARTICLES;
+         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1154,7 +1154,7 @@ int rf_plan_destroy(rf_plan* p) {
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
   *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes +
-            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes;      // (+ resident deviates and the replay's scratch runs)
+            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes;      // (+ resident deviates and the replay's scratch runs)
   return 0;
 }
 
@@ -2052,6 +2052,76 @@ int rf_measure_power(rf_plan* p, int source, const double* k_edges, int nbins, u
   memcpy(count, out.data(), (size_t)nbins * 8);
   memcpy(sum_k, out.data() + nbins, (size_t)nbins * 8);
   memcpy(sum_p, out.data() + 2 * (size_t)nbins, (size_t)nbins * 8);
+  return 0;
+}
+
+int rf_measure_multipoles(rf_plan* p, int source, int los_axis, const double* k_edges, int nbins, const double* comp_x, const double* comp_y,
+                          const double* comp_z, unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4) {
+  RF_REQUIRE(p, "null plan");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the power spectrum measurement runs on single-rank plans");
+  RF_REQUIRE(source == RF_POWER_FROM_KSPACE || source == RF_POWER_FROM_FIELD, "source must be RF_POWER_FROM_KSPACE or RF_POWER_FROM_FIELD");
+  RF_REQUIRE(los_axis >= 0 && los_axis <= 2, "los_axis must be 0, 1 or 2");
+  RF_REQUIRE(k_edges && count && sum_k && m0 && m2 && m4, "null argument");
+  RF_REQUIRE(nbins >= 1 && nbins <= 1024, "nbins must be between 1 and 1024");
+  RF_REQUIRE(k_edges[0] >= 0.0, "bad k_edges: the first edge must not be negative");
+  for (int b = 0; b < nbins; ++b) RF_REQUIRE(k_edges[b] < k_edges[b + 1], "bad k_edges: the edges must be strictly increasing");
+  const int nzh = p->nz / 2 + 1;
+  const double* comp[3] = {comp_x, comp_y, comp_z};
+  const int clen[3] = {p->nx, p->ny, nzh};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; comp[a] && i < clen[a]; ++i)
+      RF_REQUIRE(std::isfinite(comp[a][i]) && comp[a][i] > 0.0, "bad compensation table: every entry must be finite and positive");
+  RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+  else RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  RF_HIP(hipSetDevice(p->device));
+  // one lazy buffer: [squared edges, 1025 slots][result 5 x 1024][cx nx][cy ny][cz nz/2+1][five planes of per-workgroup partials]
+  const MultipoleLaunch L = multipole_launch_shape(p->nx, p->ny, p->nz, nbins);
+  const long long plane_words = (long long)L.grid * nbins;
+  const size_t tab_words = (size_t)p->nx + p->ny + nzh, head_words = 1025 + MULTIPOLE_PLANES * 1024 + tab_words;
+  const size_t need = (head_words + MULTIPOLE_PLANES * (size_t)plane_words) * 8;
+  if (p->mp_buf.bytes < need) RF_HIP(hipStreamSynchronize(p->stream));
+  RF_HIP(p->mp_buf.reserve(need));
+  double* e2_dev = (double*)p->mp_buf.ptr;
+  unsigned long long* out_dev = (unsigned long long*)p->mp_buf.ptr + 1025;
+  double* tab_dev = (double*)p->mp_buf.ptr + 1025 + MULTIPOLE_PLANES * 1024;
+  unsigned long long* part_dev = (unsigned long long*)p->mp_buf.ptr + head_words;
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = k_edges[b] * k_edges[b];
+  RF_HIP(hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  MultipoleParams g;
+  memset(&g, 0, sizeof(g));
+  const double** gtab[3] = {&g.cx, &g.cy, &g.cz};
+  size_t off = 0;
+  for (int a = 0; a < 3; ++a) {
+    if (comp[a]) {
+      RF_HIP(hipMemcpyAsync(tab_dev + off, comp[a], (size_t)clen[a] * sizeof(double), hipMemcpyHostToDevice, p->stream));
+      *gtab[a] = tab_dev + off;
+    }
+    off += (size_t)clen[a];
+  }
+  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false)) return rc; }     // tiled plans: W packed, no K
+  g.p.nx = p->nx; g.p.ny = p->ny; g.p.nz = p->nz;
+  g.p.nbins = nbins;
+  g.p.packed = source == RF_POWER_FROM_FIELD && !p->generic;
+  g.p.kz_sorted = 1;
+  for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) g.p.kz_sorted = 0;
+  g.p.kx2 = p->kx2.get(); g.p.ky2 = p->ky2.get(); g.p.kz2 = p->kz2.get();
+  g.los = los_axis;
+  RF_HIP(launch_multipoles(p->f64, g.p.packed ? p->W.ptr : p->K.ptr, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
+  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  p->timed = false;
+  std::vector<unsigned long long> out(MULTIPOLE_PLANES * (size_t)nbins);
+  RF_HIP(hipMemcpyAsync(out.data(), out_dev, out.size() * 8, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  const size_t nb8 = (size_t)nbins * 8;
+  memcpy(count, out.data(), nb8);
+  memcpy(sum_k, out.data() + nbins, nb8);
+  memcpy(m0, out.data() + 2 * (size_t)nbins, nb8);
+  memcpy(m2, out.data() + 3 * (size_t)nbins, nb8);
+  memcpy(m4, out.data() + 4 * (size_t)nbins, nb8);
   return 0;
 }
 

@@ -533,6 +533,42 @@ RF_HD cplx<T> power_load(const PowerParams& g, const cplx<T>* S, int ix, int iy,
   return mk<T>((T)0.5 * (a.y + b.y), (T)0.5 * (b.x - a.x));
 }
 
+// ------------------------------------------ binned power spectrum multipoles --
+// The estimator of rf_measure_multipoles: the cell, its k^2, bin and weight are power_cell's (same sum order, same power_bin, the DC cell
+// and cells outside all bins dropped).  mu^2 = k_los^2 / k^2 with k_los^2 the entry of the line-of-sight axis' own table (kx2[ix],
+// ky2[iy] or kz2[iz] for los = 0, 1, 2): one float64 division (a non-DC cell whose tables sum to 0 -- not a k grid -- takes mu^2 = 0).
+// Window compensation c = (cx[ix] cy[iy]) cz[iz], float64 tables of nx, ny, nz/2 + 1 entries, a null table = all ones.
+// e = c (re^2 + im^2), values widened to float64 first.  A bin sums w, w sqrt(k^2), w e, w (e mu^2) and w ((e mu^2) mu^2): moments of
+// mu^2, every term non-negative; the Legendre combinations are the host's.  With null tables w, wk and m[0] are power_cell's w, wk, wp.
+struct MultipoleParams {
+  PowerParams p;
+  int los;                    // 0, 1, 2: the axis mu is measured against
+  const double* cx;
+  const double* cy;
+  const double* cz;
+};
+template <typename T>
+RF_HD int multipole_cell(const MultipoleParams& g, const double* e2, cplx<T> v, int ix, int iy, int iz, int& w, double& wk, double (&m)[3]) {
+  w = 0; wk = 0.0; m[0] = 0.0; m[1] = 0.0; m[2] = 0.0;
+  if (ix == 0 && iy == 0 && iz == 0) return -1;
+  const double ax = g.p.kx2[ix], ay = g.p.ky2[iy], az = g.p.kz2[iz];
+  const double k2 = (ax + ay) + az;
+  const int b = power_bin(e2, g.p.nbins, k2);
+  if (b < 0) return -1;
+  w = (iz == 0 || 2 * iz == g.p.nz) ? 1 : 2;
+  const double re = (double)v.x, im = (double)v.y;
+  wk = (double)w * sqrt(k2);
+  double e = re * re + im * im;
+  if (g.cx || g.cy || g.cz) e = (((g.cx ? g.cx[ix] : 1.0) * (g.cy ? g.cy[iy] : 1.0)) * (g.cz ? g.cz[iz] : 1.0)) * e;
+  const double klos2 = g.los == 0 ? ax : (g.los == 1 ? ay : az);
+  const double mu2 = k2 > 0.0 ? klos2 / k2 : 0.0;
+  const double e2m = e * mu2, e4m = e2m * mu2;
+  m[0] = (double)w * e;
+  m[1] = (double)w * e2m;
+  m[2] = (double)w * e4m;
+  return b;
+}
+
 // ------------------------------------------- particles: cloud-in-cell paint --
 // One particle of unit mass per lattice cell q = (ix, iy, iz), displaced by s_a(q) (length units); inv_h[a] = 1 / (grid spacing).
 // Per axis, all in float64:

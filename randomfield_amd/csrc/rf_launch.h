@@ -168,6 +168,15 @@ struct PowerLaunch { int tx = 1, ty = 1; unsigned grid = 1; size_t lds = 0; };
 PowerLaunch power_launch_shape(int nx, int ny, int nz, int nbins);
 hipError_t launch_power(int f64, const void* S, const PowerParams& gp, const double* e2_dev, unsigned long long* partials, long long plane_words,
                         unsigned long long* out, hipStream_t s);
+// the power spectrum multipoles of a half spectrum (rf_core.h multipole_cell; rf_k_multipole.hip).  S and e2_dev as launch_power's;
+// gm.cx / cy / cz: device tables or null.  partials: MULTIPOLE_PLANES planes of plane_words 8-byte words each (count, sum_k, m0, m2, m4 per workgroup
+// and bin: plane_words >= grid * nbins of multipole_launch_shape, else hipErrorInvalidValue);
+// out: [count nbins][sum_k nbins][m0 nbins][m2 nbins][m4 nbins], 8-byte words
+enum { MULTIPOLE_PLANES = 5 };
+struct MultipoleLaunch : PowerLaunch { int cells = 1; };      // cells: consecutive cells of a row per lane (4 on rows of at least 256 cells)
+MultipoleLaunch multipole_launch_shape(int nx, int ny, int nz, int nbins);
+hipError_t launch_multipoles(int f64, const void* S, const MultipoleParams& gm, const double* e2_dev, unsigned long long* partials,
+                             long long plane_words, unsigned long long* out, hipStream_t s);
 
 // on-GPU replay of RandomState(seed).normal (rf_k_mt.hip)
 // one stage of the jump tree: states[i + m * dist] = states[i] advanced by m * dist segments, i < nsrc, m = 1 .. nmult

@@ -229,6 +229,7 @@ struct rf_plan {
   rf::GenericDims gdims;               // the same + the split of the long axes, as the sequences of rf_generic.h take them
   bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; k_valid untouched)
   rfc::DevBuf<> pw_buf;                 // lazy, rf_measure_power: squared edges, result, per-workgroup partials
+  rfc::DevBuf<> mp_buf;                 // lazy, rf_measure_multipoles: squared edges, result, compensation tables, per-workgroup partials (counted by rf_plan_nbytes)
   bool timed = false;
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations

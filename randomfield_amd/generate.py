@@ -410,7 +410,7 @@ class Generator(object):
             self._field_on_host = True
         return self.plan_c2r.data_out
 
-    def measure_power_spectrum(self, field=None, *, k_edges=None, nbins=None):
+    def measure_power_spectrum(self, field=None, *, k_edges=None, nbins=None, window=None):
         """
         Binned power spectrum of a field on this grid (an extension; the reference has no such method): the estimator that
         closes P(k) -> delta(x) -> P^(k).
@@ -431,9 +431,60 @@ class Generator(object):
         a later :meth:`download_field` needs the field to be on the host already (it is after ``generate_delta_field()`` with
         the default ``download=True`` and after passing ``field``); other shapes keep the field on the device.
         ``distributed=True`` raises ``NotImplementedError``.
+
+        ``window`` (None, ``'ngp'`` / ``'cic'`` / ``'tsc'``, or three per-axis tables as ``powertools.window_compensation`` makes
+        them) divides a mass-assignment window out of |delta(k)|**2: ``'Pk'`` is then the compensated monopole of
+        :meth:`measure_power_multipoles` (``rf_measure_multipoles``).  With the default nothing changes.
         """
         if self.distributed:
             raise NotImplementedError("measure_power_spectrum runs on single-GPU plans.")
+        if window is not None:
+            res = self.measure_power_multipoles(field, los=2, k_edges=k_edges, nbins=nbins, window=window)
+            out = np.empty(len(res), [("k", float), ("Pk", float), ("nmodes", np.uint64)])
+            out["k"], out["Pk"], out["nmodes"] = res["k"], res["P0"], res["nmodes"]
+            return out
+        shape, k_edges = self._power_inputs(field, k_edges, nbins)
+        if self.backend == "numpy":
+            kdata = np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
+            sums = powertools.bin_power(kdata, self.grid_spacing_Mpc_h, k_edges)
+        else:
+            from . import _hip
+            sums = self.plan_c2r.device.measure_power(k_edges, _hip.RF_POWER_FROM_FIELD)
+        return powertools.power_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
+
+    def measure_power_multipoles(self, field=None, *, los=2, k_edges=None, nbins=None, window=None):
+        """
+        Monopole, quadrupole and hexadecapole of the binned power spectrum with the line of sight along grid axis ``los`` (0, 1, 2:
+        plane-parallel) -- what a mock painted in redshift space (:meth:`particle_displacements` with ``rsd_axis``) is measured with.
+
+        ``field``, ``k_edges``, ``nbins``, the binning, the weights, the normalisation and what happens to the device copy of the
+        field are those of :meth:`measure_power_spectrum`.  Per bin the moments M0, M2, M4 of mu**2 = k_los**2 / k**2 weighted by
+        |delta(k)|**2 are summed (every term non-negative) and combined as P0 = M0, P2 = (5/2)(3 M2 - M0),
+        P4 = (9/8)(35 M4 - 30 M2 + 3 M0).  ``window``: None, a scheme name (``'ngp'``, ``'cic'``, ``'tsc'``:
+        ``powertools.window_compensation``) or three per-axis tables of nx, ny, nz/2 + 1 finite positive factors multiplied onto
+        |delta(k)|**2 (each may be None).  The compensation is the standard one for well-mixed particles, not an exact inverse of
+        the paint of a cold lattice.  Returns a structured array with the fields ``'k'``, ``'P0'``, ``'P2'``, ``'P4'``, ``'nmodes'``;
+        empty bins hold NaN.  hip backend: one sweep on the device (``rf_measure_multipoles``), the same bits on every call.
+        """
+        if self.distributed:
+            raise NotImplementedError("measure_power_multipoles runs on single-GPU plans.")
+        if los not in (0, 1, 2):
+            raise ValueError("Invalid los: {0!r} (expected 0, 1 or 2).".format(los))
+        if isinstance(window, str):
+            window = powertools.window_compensation(tuple(self.plan_c2r.shape), window)
+        elif window is not None:
+            window = powertools._compensation_tables(window, tuple(self.plan_c2r.shape))
+        shape, k_edges = self._power_inputs(field, k_edges, nbins)
+        if self.backend == "numpy":
+            kdata = np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
+            sums = powertools.bin_multipoles(kdata, self.grid_spacing_Mpc_h, k_edges, los, window)
+        else:
+            from . import _hip
+            sums = self.plan_c2r.device.measure_multipoles(k_edges, los, _hip.RF_POWER_FROM_FIELD, window)
+        return powertools.multipole_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
+
+    def _power_inputs(self, field, k_edges, nbins):
+        """the edges of a power spectrum measurement, and ``field`` (if given) made the current field: (shape, k_edges)"""
         shape = tuple(self.plan_c2r.shape)
         if k_edges is None:
             k_edges = powertools.default_k_edges(shape, self.grid_spacing_Mpc_h, nbins)
@@ -448,13 +499,7 @@ class Generator(object):
             self._field_on_host = True
             if self.backend == "hip":
                 self.plan_c2r.device.upload_real(self.plan_c2r.data_out_padded, padded=True)
-        if self.backend == "numpy":
-            kdata = np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
-            sums = powertools.bin_power(kdata, self.grid_spacing_Mpc_h, k_edges)
-        else:
-            from . import _hip
-            sums = self.plan_c2r.device.measure_power(k_edges, _hip.RF_POWER_FROM_FIELD)
-        return powertools.power_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
+        return shape, k_edges
 
     def _need_table(self, name):
         value = getattr(self, name)
@@ -725,7 +770,7 @@ class Generator(object):
         return self.download_field() if download else None
 
     # ---- particles: the displaced lattice and its cloud-in-cell paint ---------
-    def particle_displacements(self, order=2, D1=1.0, download=True):
+    def particle_displacements(self, order=2, D1=1.0, download=True, *, rsd_axis=None, f1=0.0, f2=None):
         """
         The Lagrangian displacements s = D1 psi1 (``order=1``) or D1 psi1 + D1**2 psi2 (``order=2``) of the lattice particles, one
         per cell, in Mpc/h -- from :meth:`calculate_displacement_field`, whose ``order=2`` term already carries the 3/7.  The three
@@ -733,26 +778,39 @@ class Generator(object):
         and :meth:`particle_positions`, until the next field is generated (``generate_delta_field`` / ``generate_density_field``
         drop them).  Returns a new ``(3, nx, ny, nz)`` array of the plan's real type, or None with ``download=False``.  The field
         buffer is left holding the last component transformed.
+
+        Redshift space: with ``rsd_axis = a`` (0, 1, 2) the component along grid axis a alone takes the coefficients D1 (1 + f1) and
+        D1**2 (1 + f2) -- formed in float64, then handled as the plain coefficients are -- which moves the particles along that one
+        axis by their peculiar velocity in units of the Hubble flow: a plane-parallel line of sight.  ``f1`` is the linear growth
+        rate d ln D1 / d ln a, ``f2`` the second-order one (``None``: 2 f1).  The two other components, the default call and the
+        displacement fields of :meth:`calculate_displacement_field` are untouched.
         """
         if order not in (1, 2):
             raise ValueError("Invalid order: {0!r} (expected 1 or 2).".format(order))
+        if rsd_axis is not None and rsd_axis not in (0, 1, 2):
+            raise ValueError("Invalid rsd_axis: {0!r} (expected None, 0, 1 or 2).".format(rsd_axis))
         rtype = self.plan_c2r.data_out.dtype.type
         d1, d2 = float(D1), float(D1) * float(D1)
+        coeffs = [(d1, d2)] * 3
+        if rsd_axis is not None:
+            g1 = float(f1)
+            g2 = 2.0 * g1 if f2 is None else float(f2)
+            coeffs[rsd_axis] = (d1 * (1.0 + g1), d2 * (1.0 + g2))
         if self.backend == "numpy":
             Q = np.empty((3,) + tuple(self.plan_c2r.shape), rtype)
             for axis in range(3):
-                Q[axis] = rtype(d1) * self.calculate_displacement_field(axis, order=1)
+                Q[axis] = rtype(coeffs[axis][0]) * self.calculate_displacement_field(axis, order=1)
                 if order == 2:
-                    Q[axis] += rtype(d2) * self.calculate_displacement_field(axis, order=2)
+                    Q[axis] += rtype(coeffs[axis][1]) * self.calculate_displacement_field(axis, order=2)
             self._particles = Q
             return self._download_particles() if download else None
         for axis in range(3):
             self.calculate_displacement_field(axis, order=1, download=False)
             dev = self.plan_c2r.device
-            dev.particles_accumulate(axis, d1, first=True)
+            dev.particles_accumulate(axis, coeffs[axis][0], first=True)
             if order == 2:
                 self.calculate_displacement_field(axis, order=2, download=False)
-                dev.particles_accumulate(axis, d2, first=False)
+                dev.particles_accumulate(axis, coeffs[axis][1], first=False)
         self._particles = True
         return self._download_particles() if download else None
 

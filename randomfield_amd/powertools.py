@@ -18,7 +18,7 @@ from . import transform
 
 __all__ = ["get_k_bounds", "create_ksq_grids", "ksq_axes", "fill_with_log10k", "validate_power", "filter_power",
            "sigma_table", "tabulate_sigmas", "load_default_power", "make_power", "bin_power", "default_k_edges",
-           "power_estimate"]
+           "power_estimate", "bin_multipoles", "multipole_estimate", "window_compensation"]
 
 
 def grid_k_range(shape, spacing):
@@ -113,6 +113,105 @@ def power_estimate(count, sum_k, sum_p, shape, spacing):
     with np.errstate(divide="ignore", invalid="ignore"):
         out["k"] = np.where(c > 0, np.asarray(sum_k) / c, np.nan)
         out["Pk"] = np.where(c > 0, (spacing ** 3 / n) * np.asarray(sum_p) / c, np.nan)
+    out["nmodes"] = count
+    return out
+
+
+_WINDOW_ORDER = {"ngp": 1, "cic": 2, "tsc": 3}
+
+
+def window_compensation(shape, scheme):
+    """The three per-axis float64 tables ``sinc(pi m / n)**(-2 p)`` (lengths nx, ny, nz/2 + 1) that divide the mass-assignment window
+    out of |delta(k)|**2: m the signed frequency index, sinc(0) = 1, p = 1, 2, 3 for ``'ngp'``, ``'cic'``, ``'tsc'``; the entry at
+    Nyquist is ``(pi / 2)**(2 p)``.  This is the standard correction for well-mixed particles; on a cold lattice with sub-cell
+    displacements the paint is a finite difference of the displacement and the window is not this one."""
+    if scheme not in _WINDOW_ORDER:
+        raise ValueError("Invalid window scheme: {0!r} (expected 'ngp', 'cic' or 'tsc').".format(scheme))
+    p = _WINDOW_ORDER[scheme]
+    nx, ny, nz = (int(n) for n in shape)
+    tabs = []
+    for n, count in ((nx, nx), (ny, ny), (nz, nz // 2 + 1)):
+        m = np.rint(np.fft.fftfreq(n) * n)[:count]            # signed index (the Nyquist entry's sign does not matter: sinc is even)
+        tabs.append(np.sinc(m / n) ** (-2.0 * p))              # np.sinc(x) = sin(pi x) / (pi x)
+    return tuple(tabs)
+
+
+def _compensation_tables(compensation, shape):
+    lengths = (shape[0], shape[1], shape[2] // 2 + 1)
+    tabs = [None] * 3 if compensation is None else list(compensation)
+    if len(tabs) != 3:
+        raise ValueError("compensation must be three per-axis tables (each may be None).")
+    out = []
+    for t, n in zip(tabs, lengths):
+        if t is not None:
+            t = np.asarray(t, np.float64).ravel()
+            if len(t) != n or not np.all(np.isfinite(t) & (t > 0)):
+                raise ValueError("a compensation table must hold {0} finite positive values.".format(n))
+        out.append(t)
+    return out
+
+
+def bin_multipoles(kdata, spacing, edges, los, compensation=None):
+    """Per-bin sums of the power spectrum multipoles of a half spectrum along grid axis ``los`` (0, 1, 2) -- the numpy statement of the
+    definition the device call ``rf_measure_multipoles`` implements (csrc/rf_core.h multipole_cell).
+
+    Cells, k2, bins and weights w as in :func:`bin_power`.  ``mu2 = klos2 / k2`` with klos2 the line-of-sight axis' own table entry;
+    ``compensation``: None or three tables (nx, ny, nz/2 + 1 finite positive values, each may be None = ones), c = (cx[ix] cy[iy])
+    cz[iz]; e = c |delta(k)|**2.  Returns ``(count, sum_k, m0, m2, m4)``: the uint64 sum of w and the float64 sums of ``w sqrt(k2)``,
+    ``w e``, ``w (e mu2)`` and ``w ((e mu2) mu2)`` per bin."""
+    edges = np.asarray(edges, np.float64).ravel()
+    nbins = len(edges) - 1
+    if not 1 <= nbins <= 1024 or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+        raise ValueError("edges must be 2 ... 1025 strictly increasing non-negative values.")
+    if los not in (0, 1, 2):
+        raise ValueError("Invalid los: {0!r} (expected 0, 1 or 2).".format(los))
+    if kdata.ndim != 3 or kdata.shape[2] < 2:
+        raise ValueError("kdata must be an (nx, ny, nz/2 + 1) half spectrum.")
+    nx, ny, nz = kdata.shape[0], kdata.shape[1], 2 * (kdata.shape[2] - 1)      # (any even nz: the generic plans' shapes too)
+    cx, cy, cz = _compensation_tables(compensation, (nx, ny, nz))
+    kx2, ky2, kz2 = ksq_axes(nx, ny, nz, spacing)
+    k2 = (kx2[:, None, None] + ky2[None, :, None]) + kz2[None, None, :]
+    klos2 = np.broadcast_to((kx2[:, None, None], ky2[None, :, None], kz2[None, None, :])[los], k2.shape)
+    b = np.searchsorted(edges * edges, k2.ravel(), side="right") - 1
+    w = np.full(k2.shape, 2, np.int64)
+    w[:, :, 0] = 1
+    w[:, :, nz // 2] = 1
+    w = w.ravel()
+    keep = (b >= 0) & (b < nbins)
+    keep[0] = False                          # the DC cell
+    b, w = b[keep], w[keep]
+    k2k = k2.ravel()[keep]
+    re = kdata.real.astype(np.float64).ravel()[keep]
+    im = kdata.imag.astype(np.float64).ravel()[keep]
+    e = re * re + im * im
+    if compensation is not None:
+        one = np.ones(1)
+        c = ((one if cx is None else cx)[:, None, None] * (one if cy is None else cy)[None, :, None]) * (one if cz is None else cz)[None, None, :]
+        e = np.broadcast_to(c, k2.shape).ravel()[keep] * e
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu2 = np.where(k2k > 0, klos2.ravel()[keep] / k2k, 0.0)
+    e2m = e * mu2
+    count = np.bincount(b, weights=w, minlength=nbins).astype(np.uint64)      # (exact: integers far below 2**53)
+    sum_k = np.bincount(b, weights=w * np.sqrt(k2k), minlength=nbins)
+    m0 = np.bincount(b, weights=w * e, minlength=nbins)
+    m2 = np.bincount(b, weights=w * e2m, minlength=nbins)
+    m4 = np.bincount(b, weights=w * (e2m * mu2), minlength=nbins)
+    return count, sum_k, m0, m2, m4
+
+
+def multipole_estimate(count, sum_k, m0, m2, m4, shape, spacing):
+    """The structured array ('k', 'P0', 'P2', 'P4', 'nmodes') of the sums of :func:`bin_multipoles` /
+    ``DevicePlan.measure_multipoles``: with Mj = (V / N**2) mj / count, ``P0 = M0``, ``P2 = (5/2)(3 M2 - M0)`` and
+    ``P4 = (9/8)(35 M4 - 30 M2 + 3 M0)`` (the Legendre polynomials in mu, (2l + 1) normalisation); NaN in empty bins."""
+    n = float(shape[0]) * float(shape[1]) * float(shape[2])
+    out = np.empty(len(count), [("k", float), ("P0", float), ("P2", float), ("P4", float), ("nmodes", np.uint64)])
+    c = np.asarray(count, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        M0, M2, M4 = (np.where(c > 0, (spacing ** 3 / n) * np.asarray(m, np.float64) / c, np.nan) for m in (m0, m2, m4))
+        out["k"] = np.where(c > 0, np.asarray(sum_k) / c, np.nan)
+    out["P0"] = M0
+    out["P2"] = 2.5 * (3.0 * M2 - M0)
+    out["P4"] = 1.125 * (35.0 * M4 - 30.0 * M2 + 3.0 * M0)
     out["nmodes"] = count
     return out
 
