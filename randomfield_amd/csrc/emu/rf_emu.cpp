@@ -912,6 +912,38 @@ int c2r_lognormal_impl(int nx, int ny, int nz, const cplx<T>* kspace, const doub
     default: return -1;
   }
 }
+
+// The loop behind emu_measure_power and emu_measure_multipoles (rf_core.h power_load / bin_cell over an array in array order, as the
+// device sweep's cells).  g arrives cleared but for the estimator's own fields; edges: nbins + 1 edges in k, squared here as the host
+// side of the device calls squares them.
+template <typename P>
+int measure_bins(int f64, int nx, int ny, int nz, int packed, const double* kx2, const double* ky2, const double* kz2, const void* S,
+                 const double* edges, int nbins, P& g, unsigned long long* count, double* const (&sums)[BinSums<P>::N]) {
+  constexpr int NS = BinSums<P>::N;
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || nbins < 1 || nbins > 1024 || !(kx2 && ky2 && kz2 && S && edges) || !(edges[0] >= 0.0)) return -1;
+  for (int b = 0; b < nbins; ++b) if (!(edges[b] < edges[b + 1])) return -1;
+  PowerParams& gp = bin_geom(g);
+  gp.nx = nx; gp.ny = ny; gp.nz = nz; gp.nbins = nbins; gp.packed = packed != 0;
+  gp.kx2 = kx2; gp.ky2 = ky2; gp.kz2 = kz2;
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = edges[b] * edges[b];
+  for (int b = 0; b < nbins; ++b) {
+    count[b] = 0;
+    for (int j = 0; j < NS; ++j) sums[j][b] = 0.0;
+  }
+  for (int ix = 0; ix < nx; ++ix)
+    for (int iy = 0; iy < ny; ++iy)
+      for (int iz = 0; iz <= nz / 2; ++iz) {
+        int w = 0;
+        double d[NS] = {};
+        const int b = f64 ? bin_cell<double>(g, e2.data(), power_load<double>(gp, (const cplx<double>*)S, ix, iy, iz), ix, iy, iz, w, d)
+                          : bin_cell<float>(g, e2.data(), power_load<float>(gp, (const cplx<float>*)S, ix, iy, iz), ix, iy, iz, w, d);
+        if (b < 0) continue;
+        count[b] += (unsigned long long)w;
+        for (int j = 0; j < NS; ++j) sums[j][b] += d[j];
+      }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1014,63 +1046,30 @@ int emu_particles_delta(int f64, const unsigned long long* A, void* W, long long
   }
   return 0;
 }
-// the binned power spectrum (rf_core.h power_load / power_cell over an array, as rf_measure_power's sweep; cells in array order): S is
-// the API-layout half spectrum [nx][ny][nz/2+1], or with packed != 0 the array [nx][ny][nz/2] the tiled forward passes leave (slot
-// kz = 0 = A0 + i A_nyq).  edges: nbins + 1 edges in k, squared here as the host side of the call squares them.
+// the binned power spectrum (measure_bins with rf_core.h power_cell, as rf_measure_power's sweep): S is the API-layout half spectrum
+// [nx][ny][nz/2+1], or with packed != 0 the array [nx][ny][nz/2] the tiled forward passes leave (slot kz = 0 = A0 + i A_nyq)
 int emu_measure_power(int f64, int nx, int ny, int nz, int packed, const double* kx2, const double* ky2, const double* kz2, const void* S,
                       const double* edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p) {
-  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || nbins < 1 || nbins > 1024 || !(kx2 && ky2 && kz2 && S && edges) || !(edges[0] >= 0.0)) return -1;
-  for (int b = 0; b < nbins; ++b) if (!(edges[b] < edges[b + 1])) return -1;
   PowerParams g;
   memset(&g, 0, sizeof(g));
-  g.nx = nx; g.ny = ny; g.nz = nz; g.nbins = nbins; g.packed = packed != 0;
-  g.kx2 = kx2; g.ky2 = ky2; g.kz2 = kz2;
-  std::vector<double> e2((size_t)nbins + 1);
-  for (int b = 0; b <= nbins; ++b) e2[b] = edges[b] * edges[b];
-  for (int b = 0; b < nbins; ++b) { count[b] = 0; sum_k[b] = 0.0; sum_p[b] = 0.0; }
-  for (int ix = 0; ix < nx; ++ix)
-    for (int iy = 0; iy < ny; ++iy)
-      for (int iz = 0; iz <= nz / 2; ++iz) {
-        int w = 0;
-        double wk = 0.0, wp = 0.0;
-        const int b = f64 ? power_cell<double>(g, e2.data(), power_load<double>(g, (const cplx<double>*)S, ix, iy, iz), ix, iy, iz, w, wk, wp)
-                          : power_cell<float>(g, e2.data(), power_load<float>(g, (const cplx<float>*)S, ix, iy, iz), ix, iy, iz, w, wk, wp);
-        if (b < 0) continue;
-        count[b] += (unsigned long long)w; sum_k[b] += wk; sum_p[b] += wp;
-      }
-  return 0;
+  double* const sums[2] = {sum_k, sum_p};
+  return measure_bins(f64, nx, ny, nz, packed, kx2, ky2, kz2, S, edges, nbins, g, count, sums);
 }
-// the power spectrum multipoles (rf_core.h power_load / multipole_cell over an array in array order, as rf_measure_multipoles' sweep): S,
-// packed and edges as emu_measure_power's; los 0, 1, 2; cx, cy, cz: tables of nx, ny, nz/2 + 1 finite positive entries, or null
+// the power spectrum multipoles (measure_bins with multipole_cell, as rf_measure_multipoles' sweep): S, packed and edges as
+// emu_measure_power's; los 0, 1, 2; cx, cy, cz: tables of nx, ny, nz/2 + 1 finite positive entries, or null
 int emu_measure_multipoles(int f64, int nx, int ny, int nz, int packed, int los, const double* kx2, const double* ky2, const double* kz2,
                            const void* S, const double* edges, int nbins, const double* cx, const double* cy, const double* cz,
                            unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4) {
-  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || nbins < 1 || nbins > 1024 || los < 0 || los > 2 || !(kx2 && ky2 && kz2 && S && edges) ||
-      !(count && sum_k && m0 && m2 && m4) || !(edges[0] >= 0.0)) return -1;
-  for (int b = 0; b < nbins; ++b) if (!(edges[b] < edges[b + 1])) return -1;
+  if (los < 0 || los > 2 || !(count && sum_k && m0 && m2 && m4)) return -1;
   const double* comp[3] = {cx, cy, cz};
   const int clen[3] = {nx, ny, nz / 2 + 1};
   for (int a = 0; a < 3; ++a)
     for (int i = 0; comp[a] && i < clen[a]; ++i) if (!(std::isfinite(comp[a][i]) && comp[a][i] > 0.0)) return -1;
   MultipoleParams g;
   memset(&g, 0, sizeof(g));
-  g.p.nx = nx; g.p.ny = ny; g.p.nz = nz; g.p.nbins = nbins; g.p.packed = packed != 0;
-  g.p.kx2 = kx2; g.p.ky2 = ky2; g.p.kz2 = kz2;
   g.los = los; g.cx = cx; g.cy = cy; g.cz = cz;
-  std::vector<double> e2((size_t)nbins + 1);
-  for (int b = 0; b <= nbins; ++b) e2[b] = edges[b] * edges[b];
-  for (int b = 0; b < nbins; ++b) { count[b] = 0; sum_k[b] = 0.0; m0[b] = 0.0; m2[b] = 0.0; m4[b] = 0.0; }
-  for (int ix = 0; ix < nx; ++ix)
-    for (int iy = 0; iy < ny; ++iy)
-      for (int iz = 0; iz <= nz / 2; ++iz) {
-        int w = 0;
-        double wk = 0.0, m[3];
-        const int b = f64 ? multipole_cell<double>(g, e2.data(), power_load<double>(g.p, (const cplx<double>*)S, ix, iy, iz), ix, iy, iz, w, wk, m)
-                          : multipole_cell<float>(g, e2.data(), power_load<float>(g.p, (const cplx<float>*)S, ix, iy, iz), ix, iy, iz, w, wk, m);
-        if (b < 0) continue;
-        count[b] += (unsigned long long)w; sum_k[b] += wk; m0[b] += m[0]; m2[b] += m[1]; m4[b] += m[2];
-      }
-  return 0;
+  double* const sums[4] = {sum_k, m0, m2, m4};
+  return measure_bins(f64, nx, ny, nz, packed, kx2, ky2, kz2, S, edges, nbins, g, count, sums);
 }
 int emu_generic_r2c(int f64, int nx, int ny, int nz, const void* W, void* K) {
   return f64 ? generic_r2c_impl<double>(nx, ny, nz, (const double*)W, (cplx<double>*)K)

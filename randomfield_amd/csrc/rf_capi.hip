@@ -2008,121 +2008,108 @@ int rf_particles_set_paint_form(rf_plan* p, int form) {
   return 0;
 }
 
-int rf_measure_power(rf_plan* p, int source, const double* k_edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p) {
+}  // extern "C"
+namespace rfc {
+// What rf_measure_power and rf_measure_multipoles share (P = PowerParams or MultipoleParams; rf_core.h bin_cell).  The refusals come in
+// three runs with the estimator's own between them, in the order the calls have always checked: the plan and the source; the arrays and
+// the edges; then, in measure_bins, what the source needs.
+int bins_refuse_plan(rf_plan* p, int source) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->nranks == 1, "the power spectrum measurement runs on single-rank plans");
   RF_REQUIRE(source == RF_POWER_FROM_KSPACE || source == RF_POWER_FROM_FIELD, "source must be RF_POWER_FROM_KSPACE or RF_POWER_FROM_FIELD");
-  RF_REQUIRE(k_edges && count && sum_k && sum_p, "null argument");
-  RF_REQUIRE(nbins >= 1 && nbins <= 1024, "nbins must be between 1 and 1024");
-  RF_REQUIRE(k_edges[0] >= 0.0, "bad k_edges: the first edge must not be negative");
-  for (int b = 0; b < nbins; ++b) RF_REQUIRE(k_edges[b] < k_edges[b + 1], "bad k_edges: the edges must be strictly increasing");
-  RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
-  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
-  else RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
-  RF_HIP(hipSetDevice(p->device));
-  // one lazy buffer: [squared edges, 1025 slots][result 3 x 1024][three planes of per-workgroup partials]
-  const PowerLaunch L = power_launch_shape(p->nx, p->ny, p->nz, nbins);
-  const long long plane_words = (long long)L.grid * nbins;
-  const size_t head_words = 1025 + 3 * 1024, need = (head_words + 3 * (size_t)plane_words) * 8;
-  if (p->pw_buf.bytes < need) RF_HIP(hipStreamSynchronize(p->stream));
-  RF_HIP(p->pw_buf.reserve(need));
-  double* e2_dev = (double*)p->pw_buf.ptr;
-  unsigned long long* out_dev = (unsigned long long*)p->pw_buf.ptr + 1025;
-  unsigned long long* part_dev = (unsigned long long*)p->pw_buf.ptr + head_words;
-  std::vector<double> e2((size_t)nbins + 1);
-  for (int b = 0; b <= nbins; ++b) e2[b] = k_edges[b] * k_edges[b];
-  RF_HIP(hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false)) return rc; }     // tiled plans: W packed, no K
-  PowerParams g;
-  memset(&g, 0, sizeof(g));
-  g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
-  g.nbins = nbins;
-  g.packed = source == RF_POWER_FROM_FIELD && !p->generic;
-  g.kz_sorted = 1;
-  for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) g.kz_sorted = 0;
-  g.kx2 = p->kx2.get(); g.ky2 = p->ky2.get(); g.kz2 = p->kz2.get();
-  RF_HIP(launch_power(p->f64, g.packed ? p->W.ptr : p->K.ptr, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->timed = false;
-  std::vector<unsigned long long> out(3 * (size_t)nbins);
-  RF_HIP(hipMemcpyAsync(out.data(), out_dev, out.size() * 8, hipMemcpyDeviceToHost, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  memcpy(count, out.data(), (size_t)nbins * 8);
-  memcpy(sum_k, out.data() + nbins, (size_t)nbins * 8);
-  memcpy(sum_p, out.data() + 2 * (size_t)nbins, (size_t)nbins * 8);
   return 0;
 }
-
-int rf_measure_multipoles(rf_plan* p, int source, int los_axis, const double* k_edges, int nbins, const double* comp_x, const double* comp_y,
-                          const double* comp_z, unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4) {
-  RF_REQUIRE(p, "null plan");
-  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->nranks == 1, "the power spectrum measurement runs on single-rank plans");
-  RF_REQUIRE(source == RF_POWER_FROM_KSPACE || source == RF_POWER_FROM_FIELD, "source must be RF_POWER_FROM_KSPACE or RF_POWER_FROM_FIELD");
-  RF_REQUIRE(los_axis >= 0 && los_axis <= 2, "los_axis must be 0, 1 or 2");
-  RF_REQUIRE(k_edges && count && sum_k && m0 && m2 && m4, "null argument");
+int bins_refuse_args(const double* k_edges, int nbins, const unsigned long long* count, double* const* sums, int ns) {
+  bool all = k_edges && count;
+  for (int j = 0; j < ns; ++j) all = all && sums[j];
+  RF_REQUIRE(all, "null argument");
   RF_REQUIRE(nbins >= 1 && nbins <= 1024, "nbins must be between 1 and 1024");
   RF_REQUIRE(k_edges[0] >= 0.0, "bad k_edges: the first edge must not be negative");
   for (int b = 0; b < nbins; ++b) RF_REQUIRE(k_edges[b] < k_edges[b + 1], "bad k_edges: the edges must be strictly increasing");
-  const int nzh = p->nz / 2 + 1;
-  const double* comp[3] = {comp_x, comp_y, comp_z};
-  const int clen[3] = {p->nx, p->ny, nzh};
-  for (int a = 0; a < 3; ++a)
-    for (int i = 0; comp[a] && i < clen[a]; ++i)
-      RF_REQUIRE(std::isfinite(comp[a][i]) && comp[a][i] > 0.0, "bad compensation table: every entry must be finite and positive");
+  return 0;
+}
+// The measurement itself.  g arrives cleared but for the estimator's own fields; its geometry is filled here.  buf is the call's lazy
+// buffer: [squared edges, 1025 slots][result planes x 1024][tables: nx, ny, nz/2 + 1 slots, only with comp][planes of per-workgroup
+// partials].  comp: three host tables (null entries = all ones) uploaded behind the result, their device addresses stored through
+// comp_dev -- or null for an estimator without tables.
+template <typename P>
+int measure_bins(rf_plan* p, int source, const double* k_edges, int nbins, DevBuf<>& buf, P& g, const double* const* comp, const double** const* comp_dev,
+                 unsigned long long* count, double* const (&sums)[BinSums<P>::N]) {
+  constexpr BinTable T = bin_table<P>();
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
   else RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
-  // one lazy buffer: [squared edges, 1025 slots][result 5 x 1024][cx nx][cy ny][cz nz/2+1][five planes of per-workgroup partials]
-  const MultipoleLaunch L = multipole_launch_shape(p->nx, p->ny, p->nz, nbins);
+  const BinLaunch L = bin_launch_shape(T, p->nx, p->ny, p->nz, nbins);
   const long long plane_words = (long long)L.grid * nbins;
-  const size_t tab_words = (size_t)p->nx + p->ny + nzh, head_words = 1025 + MULTIPOLE_PLANES * 1024 + tab_words;
-  const size_t need = (head_words + MULTIPOLE_PLANES * (size_t)plane_words) * 8;
-  if (p->mp_buf.bytes < need) RF_HIP(hipStreamSynchronize(p->stream));
-  RF_HIP(p->mp_buf.reserve(need));
-  double* e2_dev = (double*)p->mp_buf.ptr;
-  unsigned long long* out_dev = (unsigned long long*)p->mp_buf.ptr + 1025;
-  double* tab_dev = (double*)p->mp_buf.ptr + 1025 + MULTIPOLE_PLANES * 1024;
-  unsigned long long* part_dev = (unsigned long long*)p->mp_buf.ptr + head_words;
+  const int clen[3] = {p->nx, p->ny, p->nz / 2 + 1};
+  const size_t tab_words = comp ? (size_t)clen[0] + clen[1] + clen[2] : 0, head_words = 1025 + T.planes * 1024 + tab_words;
+  const size_t need = (head_words + T.planes * (size_t)plane_words) * 8;
+  if (buf.bytes < need) RF_HIP(hipStreamSynchronize(p->stream));
+  RF_HIP(buf.reserve(need));
+  double* e2_dev = (double*)buf.ptr;
+  unsigned long long* out_dev = (unsigned long long*)buf.ptr + 1025;
+  double* tab_dev = (double*)buf.ptr + 1025 + T.planes * 1024;
+  unsigned long long* part_dev = (unsigned long long*)buf.ptr + head_words;
   std::vector<double> e2((size_t)nbins + 1);
   for (int b = 0; b <= nbins; ++b) e2[b] = k_edges[b] * k_edges[b];
   RF_HIP(hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  MultipoleParams g;
-  memset(&g, 0, sizeof(g));
-  const double** gtab[3] = {&g.cx, &g.cy, &g.cz};
-  size_t off = 0;
-  for (int a = 0; a < 3; ++a) {
+  for (int a = 0; comp && a < 3; ++a) {
     if (comp[a]) {
-      RF_HIP(hipMemcpyAsync(tab_dev + off, comp[a], (size_t)clen[a] * sizeof(double), hipMemcpyHostToDevice, p->stream));
-      *gtab[a] = tab_dev + off;
+      RF_HIP(hipMemcpyAsync(tab_dev, comp[a], (size_t)clen[a] * sizeof(double), hipMemcpyHostToDevice, p->stream));
+      *comp_dev[a] = tab_dev;
     }
-    off += (size_t)clen[a];
+    tab_dev += clen[a];
   }
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
   if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false)) return rc; }     // tiled plans: W packed, no K
-  g.p.nx = p->nx; g.p.ny = p->ny; g.p.nz = p->nz;
-  g.p.nbins = nbins;
-  g.p.packed = source == RF_POWER_FROM_FIELD && !p->generic;
-  g.p.kz_sorted = 1;
-  for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) g.p.kz_sorted = 0;
-  g.p.kx2 = p->kx2.get(); g.p.ky2 = p->ky2.get(); g.p.kz2 = p->kz2.get();
-  g.los = los_axis;
-  RF_HIP(launch_multipoles(p->f64, g.p.packed ? p->W.ptr : p->K.ptr, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
+  PowerParams& gp = bin_geom(g);
+  gp.nx = p->nx; gp.ny = p->ny; gp.nz = p->nz;
+  gp.nbins = nbins;
+  gp.packed = source == RF_POWER_FROM_FIELD && !p->generic;
+  gp.kz_sorted = 1;
+  for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) gp.kz_sorted = 0;
+  gp.kx2 = p->kx2.get(); gp.ky2 = p->ky2.get(); gp.kz2 = p->kz2.get();
+  RF_HIP(launch_bins(p->f64, gp.packed ? p->W.ptr : p->K.ptr, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
   RF_HIP(hipEventRecord(p->ev[4], p->stream));
   p->timed = false;
-  std::vector<unsigned long long> out(MULTIPOLE_PLANES * (size_t)nbins);
+  std::vector<unsigned long long> out(T.planes * (size_t)nbins);
   RF_HIP(hipMemcpyAsync(out.data(), out_dev, out.size() * 8, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   const size_t nb8 = (size_t)nbins * 8;
   memcpy(count, out.data(), nb8);
-  memcpy(sum_k, out.data() + nbins, nb8);
-  memcpy(m0, out.data() + 2 * (size_t)nbins, nb8);
-  memcpy(m2, out.data() + 3 * (size_t)nbins, nb8);
-  memcpy(m4, out.data() + 4 * (size_t)nbins, nb8);
+  for (int j = 0; j < BinSums<P>::N; ++j) memcpy(sums[j], out.data() + (j + 1) * (size_t)nbins, nb8);
   return 0;
+}
+}  // namespace rfc
+extern "C" {
+
+int rf_measure_power(rf_plan* p, int source, const double* k_edges, int nbins, unsigned long long* count, double* sum_k, double* sum_p) {
+  double* const sums[2] = {sum_k, sum_p};
+  if (int rc = bins_refuse_plan(p, source)) return rc;
+  if (int rc = bins_refuse_args(k_edges, nbins, count, sums, 2)) return rc;
+  PowerParams g;
+  memset(&g, 0, sizeof(g));
+  return measure_bins(p, source, k_edges, nbins, p->pw_buf, g, nullptr, nullptr, count, sums);
+}
+
+int rf_measure_multipoles(rf_plan* p, int source, int los_axis, const double* k_edges, int nbins, const double* comp_x, const double* comp_y,
+                          const double* comp_z, unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4) {
+  double* const sums[4] = {sum_k, m0, m2, m4};
+  if (int rc = bins_refuse_plan(p, source)) return rc;
+  RF_REQUIRE(los_axis >= 0 && los_axis <= 2, "los_axis must be 0, 1 or 2");
+  if (int rc = bins_refuse_args(k_edges, nbins, count, sums, 4)) return rc;
+  const double* comp[3] = {comp_x, comp_y, comp_z};
+  const int clen[3] = {p->nx, p->ny, p->nz / 2 + 1};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; comp[a] && i < clen[a]; ++i)
+      RF_REQUIRE(std::isfinite(comp[a][i]) && comp[a][i] > 0.0, "bad compensation table: every entry must be finite and positive");
+  MultipoleParams g;
+  memset(&g, 0, sizeof(g));
+  g.los = los_axis;
+  const double** const comp_dev[3] = {&g.cx, &g.cy, &g.cz};
+  return measure_bins(p, source, k_edges, nbins, p->mp_buf, g, comp, comp_dev, count, sums);
 }
 
 int rf_upload_k(rf_plan* p, const void* host) {

@@ -569,6 +569,28 @@ RF_HD int multipole_cell(const MultipoleParams& g, const double* e2, cplx<T> v, 
   return b;
 }
 
+// Both estimators under one name, chosen by the parameter struct, for the code that is written once for the two (the kernels and the
+// launcher of rf_k_power.hip, measure_bins of rf_capi.hip and the emulator): the number of float64 sums a bin carries beside its count,
+// the cell's contributions as one array (sum 0 is sum_k in both), and the geometry both structs hold.
+template <typename P> struct BinSums;
+template <> struct BinSums<PowerParams> { enum { N = 2 }; };         // sum_k, sum_p
+template <> struct BinSums<MultipoleParams> { enum { N = 4 }; };     // sum_k, m0, m2, m4
+RF_HD const PowerParams& bin_geom(const PowerParams& g) { return g; }
+RF_HD const PowerParams& bin_geom(const MultipoleParams& g) { return g.p; }
+RF_HD PowerParams& bin_geom(PowerParams& g) { return g; }
+RF_HD PowerParams& bin_geom(MultipoleParams& g) { return g.p; }
+template <typename T>
+RF_HD int bin_cell(const PowerParams& g, const double* e2, cplx<T> v, int ix, int iy, int iz, int& w, double (&d)[2]) {
+  return power_cell<T>(g, e2, v, ix, iy, iz, w, d[0], d[1]);
+}
+template <typename T>
+RF_HD int bin_cell(const MultipoleParams& g, const double* e2, cplx<T> v, int ix, int iy, int iz, int& w, double (&d)[4]) {
+  double m[3];
+  const int b = multipole_cell<T>(g, e2, v, ix, iy, iz, w, d[0], m);
+  d[1] = m[0]; d[2] = m[1]; d[3] = m[2];
+  return b;
+}
+
 // ------------------------------------------- particles: cloud-in-cell paint --
 // One particle of unit mass per lattice cell q = (ix, iy, iz), displaced by s_a(q) (length units); inv_h[a] = 1 / (grid spacing).
 // Per axis, all in float64:

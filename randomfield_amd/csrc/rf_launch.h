@@ -160,23 +160,26 @@ hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long
 void cic_paint_geometry(int* brick3, int* halo);
 // W = (double)A 2^-48 - 1, rounded once to the real type (rf_core.h cic_delta)
 hipError_t launch_cic_convert(int f64, const unsigned long long* A, void* W, long long n, hipStream_t s);
-// the binned power spectrum of a half spectrum (rf_core.h power_cell; rf_k_power.hip).  S: API layout, or the packed array of the tiled
-// forward passes (gp.packed); e2_dev: the gp.nbins + 1 squared edges.  partials: three planes of plane_words 8-byte words each
-// (count, sum_k, sum_p per workgroup and bin: plane_words >= grid * nbins of power_launch_shape, else hipErrorInvalidValue);
-// out: [count nbins][sum_k nbins][sum_p nbins], 8-byte words
-struct PowerLaunch { int tx = 1, ty = 1; unsigned grid = 1; size_t lds = 0; };
-PowerLaunch power_launch_shape(int nx, int ny, int nz, int nbins);
-hipError_t launch_power(int f64, const void* S, const PowerParams& gp, const double* e2_dev, unsigned long long* partials, long long plane_words,
-                        unsigned long long* out, hipStream_t s);
-// the power spectrum multipoles of a half spectrum (rf_core.h multipole_cell; rf_k_multipole.hip).  S and e2_dev as launch_power's;
-// gm.cx / cy / cz: device tables or null.  partials: MULTIPOLE_PLANES planes of plane_words 8-byte words each (count, sum_k, m0, m2, m4 per workgroup
-// and bin: plane_words >= grid * nbins of multipole_launch_shape, else hipErrorInvalidValue);
-// out: [count nbins][sum_k nbins][m0 nbins][m2 nbins][m4 nbins], 8-byte words
-enum { MULTIPOLE_PLANES = 5 };
-struct MultipoleLaunch : PowerLaunch { int cells = 1; };      // cells: consecutive cells of a row per lane (4 on rows of at least 256 cells)
-MultipoleLaunch multipole_launch_shape(int nx, int ny, int nz, int nbins);
-hipError_t launch_multipoles(int f64, const void* S, const MultipoleParams& gm, const double* e2_dev, unsigned long long* partials,
-                             long long plane_words, unsigned long long* out, hipStream_t s);
+// the binned sums of a half spectrum (rf_k_power.hip): the power spectrum (rf_core.h power_cell; P = PowerParams) or its multipoles
+// (multipole_cell; MultipoleParams, g.cx / cy / cz device tables or null) -- rf_core.h bin_cell.  S: API layout, or the packed array of
+// the tiled forward passes (packed); e2_dev: the nbins + 1 squared edges.  What differs between the estimators beside the cell function
+// is this table: the planes (the count and BinSums<P>::N float64 sums), the bin counts up to which a workgroup has 256 and 128 threads
+// (64 above) -- tabulated, not derived from the 64 KB of LDS: power would fit 630 bins at 256 threads -- and whether rows of at least
+// 256 cells take four cells per lane.
+struct BinTable { int planes, bins256, bins128; bool cells4; };
+template <typename P> constexpr BinTable bin_table();
+template <> constexpr BinTable bin_table<PowerParams>() { return {BinSums<PowerParams>::N + 1, 512, 1024, false}; }      // (1024 = every count accepted: never 64 threads)
+template <> constexpr BinTable bin_table<MultipoleParams>() { return {BinSums<MultipoleParams>::N + 1, 384, 736, true}; }
+// cells: consecutive cells of a row per lane
+struct BinLaunch { int tx = 1, ty = 1; unsigned grid = 1; size_t lds = 0; int cells = 1; };
+BinLaunch bin_launch_shape(const BinTable& t, int nx, int ny, int nz, int nbins);
+// partials: t.planes planes of plane_words 8-byte words each (the count and the sums per workgroup and bin: plane_words >= grid * nbins
+// of bin_launch_shape, else hipErrorInvalidValue); out: [count nbins][sum_k nbins][sum_p nbins] or
+// [count nbins][sum_k nbins][m0 nbins][m2 nbins][m4 nbins], 8-byte words
+hipError_t launch_bins(int f64, const void* S, const PowerParams& g, const double* e2_dev, unsigned long long* partials, long long plane_words,
+                       unsigned long long* out, hipStream_t s);
+hipError_t launch_bins(int f64, const void* S, const MultipoleParams& g, const double* e2_dev, unsigned long long* partials, long long plane_words,
+                       unsigned long long* out, hipStream_t s);
 
 // on-GPU replay of RandomState(seed).normal (rf_k_mt.hip)
 // one stage of the jump tree: states[i + m * dist] = states[i] advanced by m * dist segments, i < nsrc, m = 1 .. nmult

@@ -10,10 +10,10 @@ test_gpu_power_measure.py, test_gpu_particles.py) stay below every cap in this t
     cic_convert_kernel, cic_paint_global_kernel          4096 x 256 threads (rf_k_particles.hip sweep_grid) > 1 048 576 cells / particles
     lpt2_accumulate_kernel, particles_accumulate_kernel  4096 x 256 threads of 16 bytes                    > 4 194 304 cells (float32, 4 per
                                                          (grid_for, sweep_grid)                            lane), > 2 097 152 (float64, 2)
-    power_sweep_kernel                                   2048 workgroups up to 128 bins, else 1024         nx ny > cap ty
-                                                         (rf_k_power.hip power_launch_shape)
+    bin_sweep_kernel (rf_measure_power)                  2048 workgroups up to 128 bins, else 1024         nx ny > cap ty
+                                                         (rf_k_power.hip bin_launch_shape)
 
-    the kz loop inside a row of derivative_kernel and power_sweep_kernel takes a second step when nz/2 + 1 > tx.
+    the kz loop inside a row of derivative_kernel and bin_sweep_kernel takes a second step when nz/2 + 1 > tx.
     float32 plans with nz >= 512 keep the potential in rows of nz/2 + 64 cells (rf_capi.hip rf_plan_create), below that nz/2 + 2.
 
 Every test opens with a regime guard: a plain assert, from the shape and the literal cap, that the launch it is named for strides --
@@ -179,7 +179,7 @@ def test_potential_gradient_hessian_lpt2(hip, shape, dtype):
 
 # ---- B2: the power spectrum ----
 def power_guard(shape, nbins, nstrides, kz_steps=None):
-    """the mirror of power_launch_shape: more rows than cap * ty, in exactly `nstrides` strides"""
+    """the mirror of bin_launch_shape with rf_measure_power's table: more rows than cap * ty, in exactly `nstrides` strides"""
     nx, ny, nz = shape
     tx, ty = row_block(nz, 256 if nbins <= 512 else 128)
     cap = 2048 if nbins <= 128 else 1024

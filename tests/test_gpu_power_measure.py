@@ -1,4 +1,4 @@
-"""The binned power spectrum on the device (rf_measure_power; rf_k_power.hip power_sweep_kernel / power_reduce_kernel) and
+"""The binned power spectrum on the device (rf_measure_power; rf_k_power.hip bin_sweep_kernel / bin_reduce_kernel) and
 Generator.measure_power_spectrum on the hip backend -- run with -m gpu on an MI355X.
 
 Oracle: tests/power_oracle.py, float64 numpy on the array the device itself was given.  Counts must be exact; sum_k and sum_p within
@@ -10,7 +10,9 @@ Shapes: tiled plans (16, 16, 16) both dtypes and (16, 32, 64); generic plans one
 (40, 60, 80), a ragged last workgroup (30, 14, 22), (154, 28, 44) complex128, and rows longer than a workgroup (4, 6, 1200).  Rows of
 at least 33 cells -- (16, 32, 64), (40, 60, 80), (4, 6, 1200) -- take the run-based reduction of the sweep, shorter ones the loop over bins.
 Tiled (16, 16, 512): rows of 257 cells, a second kz step that holds the Nyquist plane alone, which the packed FROM_FIELD sweep untangles
-from slot kz = 0 of two rows.  More rows than the sweep's workgroups take in one stride: tests/test_gpu_at_scale.py.
+from slot kz = 0 of two rows.  More rows than the sweep's workgroups take in one stride: tests/test_gpu_at_scale.py.  The launch shape
+is mirrored here (power_shape) and the mirror is asserted against the block shapes written out, at bin counts on both sides of its
+thresholds 128 (workgroup cap) and 512 (waves per workgroup).
 
 Generator, complex64, measure_power_spectrum(field) against the oracle on np.fft.rfftn(field): the float32 FFT's rounding is relative to
 the largest amplitude, not to each bin's, so no bound follows from the formats.  Measured once on an MI355X: largest relative bin
@@ -108,6 +110,42 @@ def test_from_field_equals_r2c_then_from_kspace(hip, shape, dtype):
         assert all(np.array_equal(a, b) for a, b in zip(got, again)), "two calls differ"
         one.close()
     two.close()
+
+
+def power_shape(shape, nbins):
+    """the mirror of bin_launch_shape with rf_measure_power's table (rf_k_power.hip): (tx, ty, workgroups, LDS bytes, workgroup cap)"""
+    nx, ny, nz = shape
+    nthreads = 256 if nbins <= 512 else 128
+    tx = 1
+    while tx < nthreads and tx < nz // 2 + 1:
+        tx *= 2
+    ty = nthreads // tx
+    cap = 2048 if nbins <= 128 else 1024
+    grid = min(max(-(-(nx * ny) // ty), 1), cap)
+    lds = ((nbins + 1) + 3 * (nthreads // 64) * nbins) * 8
+    assert lds <= 65536
+    return tx, ty, grid, lds, cap
+
+
+@pytest.mark.parametrize("nbins,block", [(128, 256), (129, 256), (512, 256), (513, 128), (1024, 128)])
+def test_bin_count_classes(hip, nbins, block):
+    """bin counts on both sides of the thresholds of rf_measure_power's launch shape: 128 (workgroup cap) and 512 (four waves per
+    workgroup, then two: three and five kz steps on the 601-cell rows), and 1024"""
+    shape, dtype = (4, 6, 1200), C64
+    tx, ty, grid, lds, cap = power_shape(shape, nbins)
+    assert (tx, ty, grid) == (block, 1, 24) and cap == (2048 if nbins <= 128 else 1024)
+    assert -(-601 // tx) == {256: 3, 128: 5}[block]          # kz steps of a row of 601 cells
+    from randomfield_amd import powertools
+    edges = powertools.default_k_edges(shape, SPACING, nbins)
+    plan = make_plan(hip, shape, dtype)
+    src = po.spectrum(shape, dtype)
+    plan.upload_k(src)
+    got = plan.measure_power(edges, hip.RF_POWER_FROM_KSPACE)
+    po.assert_sums(got, po.oracle(src, shape, SPACING, edges), "%d bins" % nbins)
+    again = plan.measure_power(edges, hip.RF_POWER_FROM_KSPACE)
+    assert all(np.array_equal(a, b) for a, b in zip(got, again)), "two calls differ"
+    assert np.array_equal(plan.download_k(), src)
+    plan.close()
 
 
 def test_tiled_from_field_leaves_an_existing_k_buffer_alone(hip):

@@ -1,5 +1,5 @@
-"""The power spectrum multipoles on the device (rf_measure_multipoles; rf_k_multipole.hip multipole_sweep_kernel /
-multipole_reduce_kernel), Generator.measure_power_multipoles and the redshift-space displacements on the hip backend -- run with -m gpu
+"""The power spectrum multipoles on the device (rf_measure_multipoles; rf_k_power.hip bin_sweep_kernel / bin_sweep_cells_kernel /
+bin_reduce_kernel), Generator.measure_power_multipoles and the redshift-space displacements on the hip backend -- run with -m gpu
 on an MI355X.
 
 Oracle: tests/multipole_oracle.py, float64 numpy on the array the device itself was given.  Counts must be exact; sum_k, m0, m2, m4
@@ -48,7 +48,7 @@ def hip():
 
 
 def multipole_shape(shape, nbins):
-    """the mirror of multipole_launch_shape (rf_k_multipole.hip): (tx, ty, workgroups, LDS bytes, workgroup cap, cells per lane)"""
+    """the mirror of bin_launch_shape with rf_measure_multipoles' table (rf_k_power.hip): (tx, ty, workgroups, LDS bytes, workgroup cap, cells per lane)"""
     nx, ny, nz = shape
     nthreads = 256 if nbins <= 384 else (128 if nbins <= 736 else 64)
     nzh = nz // 2 + 1
