@@ -45,6 +45,12 @@ int rf_merged_yz_ms(rf_plan* plan, float* sum_ms, int* launches);
  * No reference counterpart: the reference's FFT is one library call (transform.py:303-315). */
 int rf_yz_slabs(rf_plan* plan, int* nslab, int* planes);
 
+/* Which generation kernel a native-noise rf_realise of this plan runs right now (read-only): *fast = 1 the fast float32 pass (per-bin
+ * sigma records in LDS), 0 the exact chain -- because RF_FLAG_EXACT_GENERATION is set, or because the library declined the records for
+ * this table / k grid / shape (knots too dense for 512 bins, the edge margin not guaranteed, an irregular k grid, float64 with
+ * nx = 2048, a generic shape).  No reference counterpart: the reference has one sigma lookup (powertools.py:155-163). */
+int rf_diag_generation_path(rf_plan* plan, int* fast);
+
 /* ---- internal buffers ------------------------------------------------------ */
 /* copy deviates [first, first+count) of the device noise buffer to the host (tests) */
 int rf_download_noise(rf_plan* plan, double* host, unsigned long long first, unsigned long long count);

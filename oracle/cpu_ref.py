@@ -40,7 +40,7 @@ import numpy as np
 
 __all__ = [
     "expanded_shape", "packed_shape", "k_bounds", "ksq_axes", "fill_log10k",
-    "sigma_table", "interp_sigma", "tabulate_sigmas", "legacy_normals",
+    "sigma_table", "EDGE_TOL", "interp_sigma", "tabulate_sigmas", "legacy_normals",
     "randomize", "symmetrize_packed", "is_hermitian_packed", "c2r", "r2c",
     "generate_kspace", "generate_delta_field", "lognormal", "scale_z",
     "potential_kspace", "philox4x32", "philox4x32_10", "NATIVE_PHILOX_ROUNDS", "philox_normals", "native_noise_index",
@@ -139,7 +139,13 @@ def sigma_table(power_k, power_Pk, nx, ny, nz, spacing):
     return np.log10(k), N3 * np.sqrt(Pk / (2 * Vbox))
 
 
-def interp_sigma(x, xt, st):
+# The HIP path's edge rule (csrc/rf_core.h RF_EDGE_TOL): a cell whose log10|k| lies outside the
+# table by no more than this many dex takes the edge row's sigma -- the reference leaves such a cell to the last bit
+# of its float32 log10 (a table that ends exactly on the grid's k_min / k_max passes powertools.py:147-150).
+EDGE_TOL = 2e-6
+
+
+def interp_sigma(x, xt, st, edge_tol=0.0):
     """Piecewise-linear sigma(x) in float64, 0 outside [xt[0], xt[-1]].
 
     Restates scipy's ``interp1d(kind='linear', bounds_error=False,
@@ -147,6 +153,10 @@ def interp_sigma(x, xt, st):
     xt[j+1] the value is ``slope*(x - xt[j]) + st[j]`` with
     ``slope = (st[j+1]-st[j])/(xt[j+1]-xt[j])``; x == xt[-1] gives st[-1];
     anything else (including -inf and NaN) gives 0.
+
+    ``edge_tol`` = 0 is the reference bit for bit (what the golden fixtures pin); ``edge_tol=EDGE_TOL`` is the HIP
+    path's edge rule: x outside the table by no more than edge_tol gives the edge row's sigma.  Where no x lies
+    that close to an edge the two are the same array.
     """
     x = np.asarray(x, np.float64)
     n = len(xt)
@@ -157,14 +167,18 @@ def interp_sigma(x, xt, st):
     y = slope * (np.where(inside, x, xt[0]) - xt[j]) + st[j]
     # np.interp returns fp[j] exactly on a knot and fp[-1] on the last one
     y = np.where(x == xt[-1], st[-1], y)
-    return np.where(inside, y, 0.0)
+    y = np.where(inside, y, 0.0)
+    if edge_tol > 0:
+        y = np.where((x < xt[0]) & (x >= xt[0] - edge_tol), st[0], y)
+        y = np.where((x > xt[-1]) & (x <= xt[-1] + edge_tol), st[-1], y)
+    return y
 
 
-def tabulate_sigmas(data, power_k, power_Pk, spacing):
-    """Replace log10|k| in data.real by sigma -- powertools.py:125-164."""
+def tabulate_sigmas(data, power_k, power_Pk, spacing, edge_tol=0.0):
+    """Replace log10|k| in data.real by sigma -- powertools.py:125-164 (edge_tol: see interp_sigma)."""
     nx, ny, nz = expanded_shape(data.shape)
     xt, st = sigma_table(power_k, power_Pk, nx, ny, nz, spacing)
-    data.real = interp_sigma(data.real, xt, st)      # f64 result rounded to array dtype (:163)
+    data.real = interp_sigma(data.real, xt, st, edge_tol)      # f64 result rounded to array dtype (:163)
     return data
 
 
@@ -336,21 +350,21 @@ def r2c(field):
 # --------------------------------------------------------------------------
 
 def generate_kspace(nx, ny, nz, spacing, power_k, power_Pk, seed=None, noise=None,
-                    dtype=np.complex64):
-    """Steps 1-5 of generate.py:191-199 -> symmetrised k-space array."""
+                    dtype=np.complex64, edge_tol=0.0):
+    """Steps 1-5 of generate.py:191-199 -> symmetrised k-space array (edge_tol: see interp_sigma)."""
     data = fill_log10k(nx, ny, nz, spacing, dtype)
-    tabulate_sigmas(data, power_k, power_Pk, spacing)
+    tabulate_sigmas(data, power_k, power_Pk, spacing, edge_tol)
     randomize(data, seed=seed, noise=noise)
     symmetrize_packed(data)
     return data
 
 
 def generate_delta_field(nx, ny, nz, spacing, power_k, power_Pk, seed=None, noise=None,
-                         dtype=np.complex64, double_fft=False):
-    """generate.py:191-199,218-219 with save_potential=False.
+                         dtype=np.complex64, double_fft=False, edge_tol=0.0):
+    """generate.py:191-199,218-219 with save_potential=False (edge_tol: see interp_sigma).
 
     Returns (delta, rms) with rms = np.std(delta) (population std, array dtype)."""
-    data = generate_kspace(nx, ny, nz, spacing, power_k, power_Pk, seed, noise, dtype)
+    data = generate_kspace(nx, ny, nz, spacing, power_k, power_Pk, seed, noise, dtype, edge_tol)
     delta = c2r(data, double_fft=double_fft)
     return delta, np.std(delta.reshape(-1))
 

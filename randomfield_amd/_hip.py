@@ -123,6 +123,7 @@ DIAG_SIGNATURES = {
     "rf_mt_share_exchange_local": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
     "rf_download_noise": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_ulonglong, ctypes.c_ulonglong]),
     "rf_diag_live_resources": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "rf_diag_generation_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "rf_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     "rf_particles_download_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_particles_set_paint_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -314,6 +315,13 @@ class DevicePlan(object):
     def set_exact_generation(self, on=True):
         """Native-noise float32 realisations with the reference's exact float64 chain (slower)."""
         check(self._lib.rf_plan_set_flag(self._h, 1, int(bool(on))), "rf_plan_set_flag")
+
+    def generation_path(self):
+        """Diagnostics: ``"fast"`` or ``"exact"`` -- the kernel a native-noise ``realise`` of this plan runs right now
+        (rf_diag_generation_path: exact when ``set_exact_generation`` is on or the library declined the fast records)."""
+        fast = ctypes.c_int(0)
+        check(self._lib.rf_diag_generation_path(self._h, ctypes.byref(fast)), "rf_diag_generation_path")
+        return "fast" if fast.value else "exact"
 
     def set_replicated_generation(self, on=True):
         """Multi-rank plans: no all-to-all; every rank generates all of k space and keeps its x slab (native rng)."""

@@ -409,6 +409,7 @@ int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, d
   FastGenParams& f = io.gp;
   double x0, dx;
   if (!build_fast_records(h.tab, xlo, xhi, rec, x0, dx)) return -3;
+  if ((int)rec.size() > FAST_LDS_BINS) return -3;          // as build_fast (rf_capi.hip): such a plan runs the exact kernel
   f.nx = nx; f.ny = ny; f.nz = nz; f.dkx = (float)dkx; f.dky = (float)std::sqrt(h.gp.ky2[1]); f.dkz = (float)std::sqrt(h.gp.kz2[1]);
   f.rec = rec.data(); f.nbins = (int)rec.size();
   f.u_scale = (float)(0.5 * std::log10(2.0) / dx); f.u_off = (float)(-x0 / dx);

@@ -1164,6 +1164,12 @@ int rf_diag_live_resources(size_t* device_bytes, int* events, int* streams) {
   return 0;
 }
 
+int rf_diag_generation_path(rf_plan* p, int* fast) {
+  RF_REQUIRE(p && fast, "null argument");
+  *fast = (p->have_fast && !p->exact_gen) ? 1 : 0;
+  return 0;
+}
+
 int rf_plan_set_flag(rf_plan* p, int flag, int value) {
   RF_REQUIRE(p, "null plan");
   if (flag == RF_FLAG_FUSED_GENERIC_GENERATION) {  // the x pass generates the half spectrum it transforms (rf_generic.h generic_c2r_from_seq)

@@ -295,11 +295,27 @@ RF_HD double sum_of_squares(double a, double b) {
 #endif
 }
 
-// Row T: piecewise-linear sigma(log10 k), 0 outside the table (powertools.py:155-157,163).
+// The edge rule of row T.  The reference zeroes sigma outside the table (interp1d fill_value = 0, powertools.py:155-157) and asks
+// the table to cover every grid mode (powertools.py:147-150).  A table that ends exactly on the grid's own k_min or k_max
+// passes that check with the fundamental or corner modes ON its edge, and the last bit of log10|k| -- numpy's loop, libm, OCML
+// and v_log_f32 all round differently -- would decide whether those modes exist.  So: a non-DC cell whose log10|k| lies outside
+// the table by no more than RF_EDGE_TOL takes the edge row's sigma; anything further outside stays 0.
+// RF_EDGE_TOL is twice what the float32 chains can lose on x = log10|k| for |x| < 4 (k > 1e-4):
+//   exact chain (sigma_cell<float>): two roundings of |k|^2, 2 * 2^-24 relative = 0.5 log10(e) * 1.2e-7 = 2.6e-8 dex; log10f of
+//     |k|^2 (|.| < 8: one ulp is 4.8e-7) times 0.5 (exact) = 2.4e-7 dex per ulp of the implementation, 1 - 2 ulp:     <= 5e-7 dex
+//   fast chain (fast_sigma): u = log2|k|^2 * u_scale + u_off locates x - x0 = u dx; the roundings of u_scale, u_off and of the
+//     product cost 2^-24 |x| each, v_log_f32 (1 ulp) 2^-23 |x|, the sum 2^-24 (x - x0): 6e-8 (5 |x| + span) = 1e-6 dex at |x| = 2.6
+//     over 3 decades (the 3e-5 of a bin >= 4e-3 dex wide that the float32 u resolves is the smallest term)              ~ 1e-6 dex
+// (float64 plans round x to 1e-16; the same rule holds there).  build_fast_records (rf_host.h) evaluates the fast chain's bound
+// for the table at hand and declines when it exceeds RF_EDGE_TOL.
+constexpr double RF_EDGE_TOL = 2e-6;
+
+// Row T: piecewise-linear sigma(log10 k), 0 outside the table (powertools.py:155-157,163) but for the edge rule above.
 RF_HD double sigma_lookup(const GenParams& g, double x) {
   const int n = g.nt;
-  if (!(x >= g.xt[0] && x <= g.xt[n - 1])) return 0.0;  // also -inf (DC cell) and NaN
-  if (x == g.xt[n - 1]) return g.st[n - 1];
+  if (!(x >= g.xt[0] - RF_EDGE_TOL && x <= g.xt[n - 1] + RF_EDGE_TOL)) return 0.0;  // also -inf (DC cell) and NaN
+  if (x >= g.xt[n - 1]) return g.st[n - 1];
+  if (x < g.xt[0]) return g.st[0];
   int b = (int)((x - g.x0) * g.inv_dx);
   b = b < 0 ? 0 : (b >= g.nbins ? g.nbins - 1 : b);
   int j = g.bin[b];

@@ -36,18 +36,28 @@ inline void build_sigma_table(const double* log10k, const double* sigma, int n, 
 
 // Per-bin records of the fast float32 sigma lookup over [xlo, xhi] (the grid's own log10 k range,
 // padded).  Tries the smallest power-of-two bin count >= 128 with at most one knot per bin (so that
-// the records fit LDS when possible); false if even 65536 bins do not separate the knots -- the
-// caller then uses the exact kernel.
+// the records fit LDS when possible); false if even 65536 bins do not separate the knots, or if the
+// edge rule (rf_core.h RF_EDGE_TOL) cannot be guaranteed -- the caller then uses the exact kernel.
 inline bool build_fast_records(const SigmaTableHost& t, double xlo, double xhi, std::vector<FastRec>& rec,
                                double& x0, double& dx) {
-  const int n = (int)t.xt.size();
-  // cells outside the table get sigma = 0 (powertools.py:155-157): when the requested range reaches a
-  // table edge, one all-zero guard bin is put beyond it (x below / above clamps into it)
-  const bool guard_lo = xlo <= t.xt[0], guard_hi = xhi >= t.xt[n - 1];
-  xlo = std::max(xlo, t.xt[0]);
-  xhi = std::min(xhi, t.xt[n - 1]);
+  const int nt = (int)t.xt.size();
+  if (nt < 2) return false;
+  // The edge rule: the first and last pieces continue as constants over a margin of RF_EDGE_TOL beyond the table -- two more
+  // knots (slope 0 outside), which the one-knot-per-bin format takes like any other.  A range that ends inside the table never
+  // sees them: its records are what they were without the margin.
+  std::vector<double> xt(nt + 2), st(nt + 2), sl(nt + 1);
+  xt[0] = t.xt[0] - RF_EDGE_TOL; st[0] = t.st[0]; sl[0] = 0.0;
+  for (int j = 0; j < nt; ++j) { xt[j + 1] = t.xt[j]; st[j + 1] = t.st[j]; }
+  for (int j = 0; j + 1 < nt; ++j) sl[j + 1] = t.sl[j];
+  xt[nt + 1] = t.xt[nt - 1] + RF_EDGE_TOL; st[nt + 1] = t.st[nt - 1]; sl[nt] = 0.0;
+  const int n = nt + 2;
+  // cells further outside get sigma = 0 (powertools.py:155-157): when the requested range reaches beyond a
+  // margin, one all-zero guard bin is put there (x below / above clamps into it)
+  const bool guard_lo = xlo <= xt[0], guard_hi = xhi >= xt[n - 1];
+  xlo = std::max(xlo, xt[0]);
+  xhi = std::min(xhi, xt[n - 1]);
   if (!(xhi > xlo)) return false;
-  auto sigma_at = [&](double x, int j) { return t.sl[j] * (x - t.xt[j]) + t.st[j]; };
+  auto sigma_at = [&](double x, int j) { return sl[j] * (x - xt[j]) + st[j]; };
   for (int nbins = 126; nbins <= 65536; nbins = (nbins + 2) * 2 - 2) {   // +2 guard bins stay within 2^k
     dx = (xhi - xlo) / nbins;
     rec.assign(nbins, FastRec());
@@ -55,22 +65,29 @@ inline bool build_fast_records(const SigmaTableHost& t, double xlo, double xhi, 
     int j = 0;
     for (int b = 0; b < nbins && ok; ++b) {
       const double e0 = xlo + b * dx, e1 = xlo + (b + 1) * dx;
-      while (j + 1 < n - 1 && t.xt[j + 1] <= e0) ++j;          // interval containing e0
+      while (j + 1 < n - 1 && xt[j + 1] <= e0) ++j;            // interval containing e0
       FastRec& r = rec[b];
       r.v0 = (float)sigma_at(e0, j);
-      r.sa = (float)(t.sl[j] * dx);
+      r.sa = (float)(sl[j] * dx);
       r.fs = 2.0f;
       r.ds = 0.0f;
-      if (j + 1 < n - 1 && t.xt[j + 1] < e1) {                   // a knot inside the bin
-        r.fs = (float)((t.xt[j + 1] - e0) / dx);
-        r.ds = (float)((t.sl[j + 1] - t.sl[j]) * dx);
-        if (j + 2 < n - 1 && t.xt[j + 2] < e1) ok = false;       // a second one: need finer bins
+      if (j + 1 < n - 1 && xt[j + 1] < e1) {                     // a knot inside the bin
+        r.fs = (float)((xt[j + 1] - e0) / dx);
+        r.ds = (float)((sl[j + 1] - sl[j]) * dx);
+        if (j + 2 < n - 1 && xt[j + 2] < e1) ok = false;         // a second one: need finer bins
       }
     }
     if (ok) {
       x0 = xlo;
       if (guard_lo) { rec.insert(rec.begin(), FastRec{0.0f, 0.0f, 2.0f, 0.0f}); x0 -= dx; }
       if (guard_hi) rec.push_back(FastRec{0.0f, 0.0f, 2.0f, 0.0f});
+      if (guard_lo || guard_hi) {
+        // a cell ON the table's edge must land inside the margin, not in the guard bin: the float32 chain's worst error on x
+        // (derivation at RF_EDGE_TOL) has to stay below the margin's width
+        const double top = x0 + rec.size() * dx, span = top - x0;
+        const double err = std::ldexp(1.0, -24) * (5.0 * std::max(std::fabs(x0), std::fabs(top)) + span);
+        if (err > RF_EDGE_TOL) return false;
+      }
       return true;
     }
   }
