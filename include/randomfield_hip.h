@@ -47,7 +47,9 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * And for the particle calls -- the resident displacement buffer and the cloud-in-cell paint, rf_particles_accumulate, rf_particles_upload,
  * rf_particles_download, rf_particles_paint: rf_abi_features() & RF_FEATURE_PARTICLES, the version stays 5.5.
  * And for rf_measure_multipoles, the redshift-space multipole moments of the binned power spectrum with an optional window compensation:
- * rf_abi_features() & RF_FEATURE_POWER_MULTIPOLES, the version stays 5.5. */
+ * rf_abi_features() & RF_FEATURE_POWER_MULTIPOLES, the version stays 5.5.
+ * And for the cloud-in-cell gather of a field at the particles and the shift by it -- rf_particles_gather, rf_particles_gather_download,
+ * rf_particles_shift: rf_abi_features() & RF_FEATURE_PARTICLES_GATHER, the version stays 5.5. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -77,7 +79,9 @@ enum {
                                               the second-order Lagrangian displacement */
   RF_FEATURE_PARTICLES = 1 << 17,          /* rf_particles_accumulate, rf_particles_upload, rf_particles_download, rf_particles_paint: the three
                                               displacement components resident on the device, painted back onto the grid (cloud in cell) */
-  RF_FEATURE_POWER_MULTIPOLES = 1 << 18    /* rf_measure_multipoles: the moments of mu^2 behind P0, P2, P4 along a grid axis, window compensation */
+  RF_FEATURE_POWER_MULTIPOLES = 1 << 18,   /* rf_measure_multipoles: the moments of mu^2 behind P0, P2, P4 along a grid axis, window compensation */
+  RF_FEATURE_PARTICLES_GATHER = 1 << 19    /* rf_particles_gather, rf_particles_gather_download, rf_particles_shift: the current real field
+                                              interpolated at the particles (cloud in cell, the paint's adjoint), and the particles moved by it */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -340,6 +344,33 @@ int rf_particles_download(rf_plan* plan, int axis, void* host);
  * LIMIT: fewer than 65536 (2^64 / 2^48) particles' worth of mass may land in one cell; beyond it A wraps around, undetected.  Gaussian
  * initial conditions stay orders of magnitude below.  Blocks until *dropped is on the host. */
 int rf_particles_paint(rf_plan* plan, const double* inv_h, unsigned long long* dropped);
+
+/* ---- particles: a field gathered at the particles, and the shift by it (rf_abi_features() & RF_FEATURE_PARTICLES_GATHER) -- */
+/* The paint's adjoint: the current real field W (dense [nx][ny][nz], the plan's real type T) interpolated with cloud-in-cell weights at
+ * the displaced particles.  The values live in a buffer G[3][nx][ny][nz] of T indexed by the particle's LATTICE cell, as Q is -- three
+ * slots, so the three components of a vector field can be gathered at the same positions before any of them moves the particles.  G is
+ * allocated (and zeroed) by the first rf_particles_gather, counted by rf_plan_nbytes and freed with the plan.  Same plans as above; c2c
+ * plans and nranks > 1 are refused, nothing queued.
+ *
+ * For the particle of cell q the indices j0 / j1 and the integer weights w0 / w1 (w0 + w1 = 65536) per axis are exactly those of
+ * rf_particles_paint.  Everything that follows is float64, every product and every sum rounded on its own (nothing fused):
+ *   v(cx,cy,cz) = (double) W[jx_cx][jy_cy][jz_cz]
+ *   a(cx,cy)    = (double)wz0 * v(cx,cy,0) + (double)wz1 * v(cx,cy,1)
+ *   b(cx)       = (double)wy0 * a(cx,0)    + (double)wy1 * a(cx,1)
+ *   g           = ((double)wx0 * b(0) + (double)wx1 * b(1)) * 2^-48
+ *   G_slot[q]   = first ? (T)(coeff * g) : (T)((double)G_slot[q] + coeff * g)          one rounding to T
+ * No atomics: the same bits on every call, whichever kernel form runs.  Zero weights are NOT skipped: a non-finite value of W reaches
+ * every particle whose eight cells contain it, also where its weight is zero.  A particle whose u is not finite on some axis gathers
+ * g = 0 -- `first` writes 0, otherwise G_slot[q] stays -- and *dropped is the number of such particles.  For an integer-valued W the sum
+ * of g 2^48 over the particles equals the sum over the cells of A W, A the paint's grid of the same displacements, exactly.
+ * Reads the current real field (what rf_particles_accumulate reads) and changes nothing but G_slot: the field, Q, the paint's grid, the
+ * k buffer, both potentials and the moments stay bit for bit.  Blocks until *dropped is on the host. */
+int rf_particles_gather(rf_plan* plan, const double* inv_h, int slot, double coeff, int first, unsigned long long* dropped);
+/* one slot, a dense [nx][ny][nz] array of the plan's real type, to the host (blocking); refused before the first gather */
+int rf_particles_gather_download(rf_plan* plan, int slot, void* host);
+/* Q_axis = fma(coeff, G_slot, Q_axis): the sweep of rf_particles_accumulate(first = 0) with the gathered values in the field's place --
+ * coeff rounded once to T, one fused multiply-add per particle.  Refused without displacements or before the first gather. */
+int rf_particles_shift(rf_plan* plan, int axis, int slot, double coeff);
 
 /* ---- binned power spectrum (rf_abi_features() & RF_FEATURE_POWER_MEASURE) -- */
 /* The estimator that closes P(k) -> delta(x) -> P^(k): one sweep of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform

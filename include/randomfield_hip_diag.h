@@ -31,7 +31,7 @@ extern "C" {
  *       rf_execute_gradient_c2r: the elementwise gradient kernel of a plan whose x axis is in the four-step form, else 0
  * so that [4] + [0] is everything in front of the y pass.
  * After rf_particles_paint (any plan): [0] clearing the accumulator grid, [1] the scatter kernel, [2] the conversion into the field,
- * [3] = [4] = 0. */
+ * [3] = [4] = 0.  After rf_particles_gather (any plan): [0] the gather kernel, [1] = ... = [4] = 0. */
 int rf_kernel_ms(rf_plan* plan, float* ms5);
 /* The z pass of slab s and the y pass of slab s + 1 in ONE launch (the next slab's tiles fill the compute units the draining pass leaves
  * idle; float32 plans whose y pass is the 1024-point one and whose rows hold 512 complex: the 1024^3 pipeline).  mode 0: never;
@@ -62,6 +62,9 @@ int rf_particles_download_counts(rf_plan* plan, unsigned long long* host);
 int rf_particles_set_paint_form(rf_plan* plan, int form);
 /* the tiled kernel's brick (lattice cells per axis, brick3[3]) and halo (cells on every side): the tile is brick + 2 halo per axis */
 int rf_particles_paint_geometry(rf_plan* plan, int* brick3, int* halo);
+/* which kernel rf_particles_gather runs: 0 = the library's choice, 1 = global (one lane per particle, eight loads of the field from
+ * memory), 2 = tiled (the paint's brick + halo tile of the field staged in LDS, particles that leave it read memory).  Same bits. */
+int rf_particles_set_gather_form(rf_plan* plan, int form);
 
 /* What the plans of this process hold right now: bytes of device memory, HIP events, HIP streams (every allocation a plan makes is an
  * owning member of it, csrc/rf_owned.h).  Back at their earlier values once the plans made in between are destroyed: "freed with the plan",

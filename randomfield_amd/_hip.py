@@ -34,7 +34,8 @@ ABI_MAJOR, ABI_MINOR = 5, 5
 FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3, "potential": 1 << 4, "lensing": 1 << 5,
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
-            "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17, "power_multipoles": 1 << 18}
+            "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17, "power_multipoles": 1 << 18,
+            "particles_gather": 1 << 19}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -92,6 +93,9 @@ SIGNATURES = {
     "rf_particles_upload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rf_particles_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rf_particles_paint": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_particles_gather": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_particles_gather_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rf_particles_shift": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
     "rf_measure_multipoles": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp,
                                             ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp, _c_dp, _c_dp]),
@@ -128,6 +132,7 @@ DIAG_SIGNATURES = {
     "rf_particles_download_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_particles_set_paint_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rf_particles_paint_geometry": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "rf_particles_set_gather_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rf_set_merged_yz": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rf_merged_yz_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]),
     "rf_yz_slabs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -737,6 +742,33 @@ class DevicePlan(object):
         brick, halo = (ctypes.c_int * 3)(), ctypes.c_int()
         check(self._lib.rf_particles_paint_geometry(self._h, brick, ctypes.byref(halo)), "rf_particles_paint_geometry")
         return tuple(brick), halo.value
+
+    # -- particles: the field gathered at the particles, and the shift by it ----
+    def particles_gather(self, inv_h, slot, coeff=1.0, first=True):
+        """Cloud-in-cell interpolation of the current real field at the displaced lattice particles (rf_particles_gather), the
+        paint's adjoint: G_slot = coeff * g (``first``) or G_slot + coeff * g, indexed by the particle's lattice cell; nothing else
+        changes.  Returns the number of particles dropped for a non-finite displacement (they gather 0)."""
+        h = _f64(np.asarray(inv_h, np.float64).reshape(3))
+        dropped = ctypes.c_ulonglong(0)
+        check(self._lib.rf_particles_gather(self._h, _dp(h), int(slot), float(coeff), 1 if first else 0, ctypes.byref(dropped)), "rf_particles_gather")
+        return int(dropped.value)
+
+    def particles_gather_download(self, slot, out=None):
+        """slot ``slot`` of the gathered values, a dense (nx, ny, nz) array of the plan's real type (rf_particles_gather_download)"""
+        if out is None:
+            out = np.empty((self.nx, self.ny, self.nz), self.real_dtype)
+        if out.shape != (self.nx, self.ny, self.nz) or out.dtype != self.real_dtype or not out.flags.c_contiguous:
+            raise ValueError("particles_gather_download: out has the wrong shape, dtype or layout")
+        check(self._lib.rf_particles_gather_download(self._h, int(slot), out.ctypes.data_as(ctypes.c_void_p)), "rf_particles_gather_download")
+        return out
+
+    def particles_shift(self, axis, slot, coeff):
+        """Q_axis = fma(coeff, G_slot, Q_axis): the particles move along ``axis`` by the gathered values (rf_particles_shift)"""
+        check(self._lib.rf_particles_shift(self._h, int(axis), int(slot), float(coeff)), "rf_particles_shift")
+
+    def set_gather_form(self, form=0):
+        """diagnostic: the kernel of :meth:`particles_gather` -- 0 the library's choice, 1 loads from memory, 2 LDS tiles"""
+        check(self._lib.rf_particles_set_gather_form(self._h, int(form)), "rf_particles_set_gather_form")
 
     def measure_power(self, edges, source=RF_POWER_FROM_KSPACE):
         """Per-bin sums of the binned power spectrum (rf_measure_power): ``edges`` are ``nbins + 1`` increasing edges in k; returns

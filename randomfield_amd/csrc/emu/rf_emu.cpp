@@ -823,6 +823,68 @@ int particles_tile_stats_impl(int nx, int ny, int nz, const T* sx, const T* sy, 
   return 0;
 }
 
+// the gather as rf_k_particles.hip runs it: every particle writes its own element of G, so the threads share nothing but the tile image
+// (filled before a barrier, read-only after it) and the drop counter
+template <typename T>
+int particles_gather_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, const T* W, T* G, double coeff, int first,
+                          int form, int bx, int by, int bz, int halo, int nth, unsigned long long* dropped) {
+  const long long n = (long long)nx * ny * nz;
+  *dropped = 0;
+  if (form == 1) {                                   // cic_gather_global_kernel: one "lane" per particle
+    run_threads(nth, [&](int tid, auto sync) {
+      unsigned long long nd = 0;
+      for (long long i = tid; i < n; i += nth) {
+        const long long row = i / nz;
+        const int iz = (int)(i - row * nz), ix = (int)(row / ny), iy = (int)(row - (long long)ix * ny);
+        CicAxis x, y, z;
+        if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) {
+          ++nd;
+          if (first) G[i] = (T)0;
+          continue;
+        }
+        const double v = cic_gather_global(x, y, z, ny, nz, [&](long long cell) { return (double)W[cell]; });
+        G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
+      }
+      if (nd) atomic_add_u64(dropped, nd);
+    });
+    return 0;
+  }
+  // cic_gather_tiled_kernel: bricks one after the other, the threads of a brick stage its tile of W, meet at the kernel's barrier and read it
+  CicTile t;
+  t.bx = bx; t.by = by; t.bz = bz; t.h = halo; t.x0 = t.y0 = t.z0 = 0;
+  std::vector<T> tile((size_t)t.cells());
+  const int nbx = (nx + bx - 1) / bx, nby = (ny + by - 1) / by, nbz = (nz + bz - 1) / bz;
+  run_threads(nth, [&](int tid, auto sync) {
+    unsigned long long nd = 0;
+    for (int b = 0; b < nbx * nby * nbz; ++b) {
+      CicTile tb = t;
+      tb.z0 = (b % nbz) * bz; tb.y0 = ((b / nbz) % nby) * by; tb.x0 = (b / nbz / nby) * bx;
+      for (int s = tid; s < tb.cells(); s += nth) tile[s] = W[cic_tile_cell(tb, s, nx, ny, nz)];
+      sync();
+      for (int row = tid; row < bx * by; row += nth) {
+        const int lx = row / by, ly = row - lx * by, ix = tb.x0 + lx, iy = tb.y0 + ly;
+        for (int lz = 0; lz < bz; ++lz) {
+          const int iz = tb.z0 + lz;
+          if (ix >= nx || iy >= ny || iz >= nz) continue;
+          const long long i = ((long long)ix * ny + iy) * nz + iz;
+          CicAxis x, y, z;
+          if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) {
+            ++nd;
+            if (first) G[i] = (T)0;
+            continue;
+          }
+          const double v = cic_gather_tiled(x, y, z, lx, ly, lz, tb, ny, nz, [&](int slot) { return (double)tile[slot]; },
+                                            [&](long long cell) { return (double)W[cell]; });
+          G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
+        }
+      }
+      sync();                                        // (the next brick overwrites the tile)
+    }
+    if (nd) atomic_add_u64(dropped, nd);
+  });
+  return 0;
+}
+
 template <typename T>
 int particles_accumulate_impl(int first, double coeff, const T* W, T* Q, long long n) {
   const T c = (T)coeff;
@@ -1032,6 +1094,20 @@ int emu_particles_tile_stats(int f64, int nx, int ny, int nz, const void* sx, co
   if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && out4) || bx < 1 || by < 1 || bz < 1 || halo < 1) return -1;
   return f64 ? particles_tile_stats_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, bx, by, bz, halo, out4)
              : particles_tile_stats_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, bx, by, bz, halo, out4);
+}
+// The cloud-in-cell gather of the dense real field W at the lattice particles displaced by (sx, sy, sz) into G[nx][ny][nz], indexed by
+// the particle's lattice cell (rf_core.h cic_gather_value, the functions rf_k_particles.hip calls): G = (T)(coeff g) (first) or
+// (T)((double)G + coeff g).  form 1: every particle loads its eight cells from W; form 2: bricks of bx x by x bz cells whose tile of W
+// (brick + halo) is really staged in an array and read there.  nth real host threads.  *dropped: particles with a non-finite
+// displacement (they gather 0).
+int emu_particles_gather(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, const void* W, void* G,
+                         double coeff, int first, int form, int bx, int by, int bz, int halo, int nth, unsigned long long* dropped) {
+  if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && W && G && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
+  if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
+  return f64 ? particles_gather_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, (const double*)W, (double*)G, coeff,
+                                             first, form, bx, by, bz, halo, nth, dropped)
+             : particles_gather_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, (const float*)W, (float*)G, coeff,
+                                            first, form, bx, by, bz, halo, nth, dropped);
 }
 // Q = coeff W (first) or Q + coeff W over n elements (rf_core.h particles_axpy, the function the kernel calls per element)
 int emu_particles_accumulate(int f64, int first, double coeff, const void* W, void* Q, long long n) {

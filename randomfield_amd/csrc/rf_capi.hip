@@ -971,7 +971,7 @@ unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
          RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE | RF_FEATURE_LPT2 |
-         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES;
+         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES | RF_FEATURE_PARTICLES_GATHER;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1153,7 +1153,7 @@ int rf_plan_destroy(rf_plan* p) {
 
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
-  *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes +
+  *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes + p->PG.bytes +
             p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes;      // (+ resident deviates and the replay's scratch runs)
   return 0;
 }
@@ -1842,6 +1842,13 @@ int ensure_a(rf_plan* p) {
   RF_HIP(p->A.reserve(particle_cells(p) * 8));
   return 0;
 }
+int ensure_pg(rf_plan* p) {
+  RF_HIP(p->pa_drop.reserve(8));
+  if (p->PG) return 0;
+  RF_HIP(p->PG.reserve(3 * p->w_bytes));
+  RF_HIP(hipMemsetAsync(p->PG.ptr, 0, 3 * p->w_bytes, p->stream));
+  return 0;
+}
 }  // namespace rfc
 extern "C" {
 
@@ -2011,6 +2018,65 @@ int rf_particles_set_paint_form(rf_plan* p, int form) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(form >= 0 && form <= 2, "form is 0 (auto), 1 (global) or 2 (tiled)");
   p->paint_form = form;
+  return 0;
+}
+
+// G_slot <- the current real field at the particles (rf_core.h cic_gather_value).  rf_kernel_ms afterwards: [0] the gather, the others 0
+int rf_particles_gather(rf_plan* p, const double* inv_h, int slot, double coeff, int first, unsigned long long* dropped) {
+  if (int rc = particles_check(p, "the cloud-in-cell gather runs on single-rank plans")) return rc;
+  RF_REQUIRE(inv_h && dropped, "null argument");
+  RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
+  for (int a = 0; a < 3; ++a) RF_REQUIRE(inv_h[a] > 0 && inv_h[a] <= 1.7976931348623157e308, "inv_h must be positive and finite");
+  RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
+  RF_REQUIRE(p->real_valid && p->cur, "no real-space field on the device");
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_pg(p)) return rc;
+  // auto: the tiled form.  At 1024^3 / 1000^3 it takes 13.7 / 13.1 ms against the global form's 28.7 / 39.5 ms on displacements of rms 2
+  // cells and 11.2 / 11.1 against 10.1 / 10.1 ms on rms 0.1: it loses 1.1 ms where it loses and wins 15 to 26 ms where it wins, and the
+  // displacements' scale is not known without a sweep of its own (profiles/gather_bench.log)
+  const int form = p->gather_form ? p->gather_form : 2;
+  p->slab_timed = 0;
+  p->slab_merged = 0;
+  p->repair_timed = false;
+  RF_HIP(hipMemsetAsync(p->pa_drop.ptr, 0, 8, p->stream));
+  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  RF_HIP(launch_cic_gather(p->f64, form, p->Q.ptr, p->cur, (char*)p->PG.ptr + (size_t)slot * p->w_bytes, coeff, first, (unsigned long long*)p->pa_drop.ptr,
+                           p->nx, p->ny, p->nz, inv_h, p->stream));
+  for (int i = 1; i <= 4; ++i) RF_HIP(hipEventRecord(p->ev[i], p->stream));
+  p->timed = true;
+  RF_HIP(hipMemcpyAsync(dropped, p->pa_drop.ptr, 8, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+int rf_particles_gather_download(rf_plan* p, int slot, void* host) {
+  if (int rc = particles_check(p, "the cloud-in-cell gather runs on single-rank plans")) return rc;
+  RF_REQUIRE(host, "null argument");
+  RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
+  RF_REQUIRE(p->PG.ptr, "no gathered values: call rf_particles_gather first");
+  RF_HIP(hipSetDevice(p->device));
+  RF_HIP(hipMemcpyAsync(host, (char*)p->PG.ptr + (size_t)slot * p->w_bytes, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+// Q_axis = fma(coeff, G_slot, Q_axis): the accumulate sweep with the gathered values in the field's place
+int rf_particles_shift(rf_plan* p, int axis, int slot, double coeff) {
+  if (int rc = particles_check(p, "the particle displacements live on single-rank plans")) return rc;
+  RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
+  RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
+  RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
+  RF_REQUIRE(p->PG.ptr, "no gathered values: call rf_particles_gather first");
+  RF_HIP(hipSetDevice(p->device));
+  RF_HIP(launch_particles_accumulate(p->f64, (const char*)p->PG.ptr + (size_t)slot * p->w_bytes, (char*)p->Q.ptr + (size_t)axis * p->w_bytes, coeff, 0,
+                                     (long long)particle_cells(p), p->stream));
+  return 0;
+}
+
+int rf_particles_set_gather_form(rf_plan* p, int form) {
+  if (int rc = particles_check(p, "the cloud-in-cell gather runs on single-rank plans")) return rc;
+  RF_REQUIRE(form >= 0 && form <= 2, "form is 0 (auto), 1 (global) or 2 (tiled)");
+  p->gather_form = form;
   return 0;
 }
 

@@ -710,6 +710,70 @@ template <typename T> RF_HD T cic_delta(uint64_t a) { return (T)((double)a * (1.
 // Q = coeff W (first) or Q + coeff W: coeff already rounded to T, one explicit fma in T (lpt2_fma), so host and device round alike
 template <typename T> RF_HD T particles_axpy(bool first, T coeff, T w, T q) { return first ? coeff * w : lpt2_fma(coeff, w, q); }
 
+// ------------------------------------------ particles: cloud-in-cell gather --
+// The adjoint of the paint: the value of a real field W[nx][ny][nz] (type T) at the particle of lattice cell q, with the indices and
+// weights cic_particle gives for it.  All in float64, EVERY product and EVERY sum rounded on its own (never contracted: pragma /
+// volatile as mul_then_add), so numpy repeats it bit for bit; c = 0 stands for j0 / w0, c = 1 for j1 / w1:
+//   v(cx,cy,cz) = (double) W[jx_cx][jy_cy][jz_cz]
+//   a(cx,cy)    = (double)wz0 * v(cx,cy,0) + (double)wz1 * v(cx,cy,1)          z first: the contiguous axis
+//   b(cx)       = (double)wy0 * a(cx,0)    + (double)wy1 * a(cx,1)
+//   g           = ((double)wx0 * b(0) + (double)wx1 * b(1)) * 2^-48
+//   out         = first ? (T)(coeff * g) : (T)((double)G[q] + coeff * g)       one rounding to T
+// Zero weights are NOT skipped (0 * v is formed): a non-finite field value reaches every particle whose eight cells contain it, also
+// through a weight of zero.  For integer-valued W of modest size every step is exact and g 2^48 = sum of w_x w_y w_z W over the eight
+// cells: summed over the particles that is sum over the cells of A W, A the paint's grid of the same displacements -- the adjoint
+// identity, exact in integers.  A particle that cic_particle drops gathers g = 0: `first` writes 0, otherwise G[q] stays; it is counted.
+RF_HD double cic_lerp(uint32_t w0, uint32_t w1, double v0, double v1) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const double p0 = (double)w0 * v0, p1 = (double)w1 * v1;
+  return p0 + p1;
+#else
+  volatile double p0 = (double)w0 * v0, p1 = (double)w1 * v1;
+  return p0 + p1;
+#endif
+}
+// g of the eight values v[4 cx + 2 cy + cz]
+RF_HD double cic_gather_value(const CicAxis& x, const CicAxis& y, const CicAxis& z, const double (&v)[8]) {
+  const double a00 = cic_lerp(z.w0, z.w1, v[0], v[1]), a01 = cic_lerp(z.w0, z.w1, v[2], v[3]);
+  const double a10 = cic_lerp(z.w0, z.w1, v[4], v[5]), a11 = cic_lerp(z.w0, z.w1, v[6], v[7]);
+  const double b0 = cic_lerp(y.w0, y.w1, a00, a01), b1 = cic_lerp(y.w0, y.w1, a10, a11);
+  return cic_lerp(x.w0, x.w1, b0, b1) * (1.0 / 281474976710656.0);
+}
+// the value G[q] takes (old: what it holds, read only when first is false)
+template <typename T> RF_HD T cic_gather_out(bool first, double coeff, double g, T old) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const double p = coeff * g;
+#else
+  volatile double pv = coeff * g;
+  const double p = pv;
+#endif
+  return first ? (T)p : (T)((double)old + p);
+}
+// the eight loads of one particle straight from W: load(cell index) -> double
+template <class Load>
+RF_HD double cic_gather_global(const CicAxis& x, const CicAxis& y, const CicAxis& z, int ny, int nz, Load&& load) {
+  double v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = load(((long long)((k & 4) ? x.j1 : x.j0) * ny + ((k & 2) ? y.j1 : y.j0)) * nz + ((k & 1) ? z.j1 : z.j0));
+  return cic_gather_value(x, y, z, v);
+}
+// The tiled form over the scatter's tile rule (CicTile, cic_tile_slot): the tile image holds W at the cells cic_tile_cell names, and a
+// particle whose eight cells all fall inside the tile reads them there, load_tile(slot) -> double; any other reads W as
+// cic_gather_global does.  Same values, same operations in the same order: the same bits either way.
+template <class LoadTile, class LoadGlobal>
+RF_HD double cic_gather_tiled(const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const CicTile& t, int ny, int nz,
+                              LoadTile&& load_tile, LoadGlobal&& load_global) {
+  const int sx = cic_tile_slot(x, lx, t.bx, t.h), sy = cic_tile_slot(y, ly, t.by, t.h), sz = cic_tile_slot(z, lz, t.bz, t.h);
+  if (sx < 0 || sy < 0 || sz < 0) return cic_gather_global(x, y, z, ny, nz, load_global);
+  const int py = t.tz(), px = t.ty() * py, base = sx * px + sy * py + sz;
+  double v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = load_tile(base + ((k & 4) ? px : 0) + ((k & 2) ? py : 0) + (k & 1));
+  return cic_gather_value(x, y, z, v);
+}
+
 // ------------------------------------------------- fast native generation --
 // float32 plans with the native RNG do rows K,T,R,S entirely in float32: the
 // values are this repo's own definition (checked against the oracle's

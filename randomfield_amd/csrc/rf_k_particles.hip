@@ -1,6 +1,7 @@
 // particles (rf_core.h cic_axis ... cic_delta): the resident displacement buffer's fma sweep and the cloud-in-cell paint of the displaced
 // lattice particles into an unsigned 64-bit accumulator grid.  Integer atomics only -- vector (global) and LDS ones: integer addition is
 // associative, so the accumulator holds the same bits for every launch shape, either form and every run.  No floating-point atomics.
+// And the scatter's adjoint (rf_core.h cic_gather_value): the field gathered at the particles, no atomics but the drop counter's.
 #include "rf_kernels.h"
 #include "rf_launch.h"
 
@@ -81,6 +82,68 @@ __global__ __launch_bounds__(CIC_NT) void cic_paint_tiled_kernel(const T* __rest
   cic_count_dropped(ndrop, dropped);
 }
 
+// ---- the gather (rf_core.h cic_gather_value): the field W at the particles into G, the adjoint of the scatter above.  No atomics but
+// the drop counter's: every particle writes its own element of G.
+// Form 1, global: one lane per particle, lanes along z, eight plain loads of W through the caches; G read (unless first) and written
+// at the particle's own index, coalesced.  blockDim.x is a multiple of 64.
+template <typename T>
+__global__ __launch_bounds__(256) void cic_gather_global_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
+                                                                const T* __restrict__ W, T* __restrict__ G, u64* __restrict__ dropped,
+                                                                CicGrid g, double coeff, int first, long long n) {
+  int ndrop = 0;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  for (long long i0 = (long long)blockIdx.x * blockDim.x; i0 < n; i0 += step) {
+    const long long i = i0 + threadIdx.x;
+    if (i >= n) continue;
+    const long long row = i / g.nz;
+    const int iz = (int)(i - row * g.nz), ix = (int)(row / g.ny), iy = (int)(row - (long long)ix * g.ny);
+    CicAxis x, y, z;
+    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) {
+      ++ndrop;
+      if (first) G[i] = (T)0;
+      continue;
+    }
+    const double v = cic_gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; });
+    G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
+  }
+  cic_count_dropped(ndrop, dropped);
+}
+
+// Form 2, tiled: the paint's brick and halo.  The workgroup stages W at the tile's cells (cic_tile_cell: periodic wrap, partial bricks
+// and grids smaller than the tile are all in that map) into LDS with coalesced loads; a particle whose eight cells lie inside the tile
+// reads them there (a wave's lanes on consecutive addresses), any other reads W as form 1 does.
+extern __shared__ __attribute__((aligned(16))) unsigned char cic_gather_lds[];
+template <typename T>
+__global__ __launch_bounds__(CIC_NT) void cic_gather_tiled_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
+                                                                  const T* __restrict__ W, T* __restrict__ G, u64* __restrict__ dropped,
+                                                                  CicGrid g, double coeff, int first, int nby, int nbz) {
+  T* tile = reinterpret_cast<T*>(cic_gather_lds);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned b = blockIdx.x, bz = b % (unsigned)nbz, bxy = b / (unsigned)nbz, by = bxy % (unsigned)nby, bx = bxy / (unsigned)nby;
+  CicTile t;
+  t.bx = CIC_BX; t.by = CIC_BY; t.bz = CIC_BZ; t.h = CIC_H;
+  t.x0 = (int)bx * CIC_BX; t.y0 = (int)by * CIC_BY; t.z0 = (int)bz * CIC_BZ;
+  for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) tile[s] = W[cic_tile_cell(t, s, g.nx, g.ny, g.nz)];
+  __syncthreads();
+  int ndrop = 0;
+  const int iz = t.z0 + lane;
+  for (int row = wave; row < CIC_BX * CIC_BY; row += CIC_NT / 64) {
+    const int lx = row / CIC_BY, ly = row - lx * CIC_BY, ix = t.x0 + lx, iy = t.y0 + ly;
+    if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
+    const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
+    CicAxis x, y, z;
+    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) {
+      ++ndrop;
+      if (first) G[i] = (T)0;
+      continue;
+    }
+    const double v = cic_gather_tiled(x, y, z, lx, ly, lane, t, g.ny, g.nz, [&](int slot) { return (double)tile[slot]; },
+                                      [&](long long cell) { return (double)W[cell]; });
+    G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
+  }
+  cic_count_dropped(ndrop, dropped);
+}
+
 // W = (double)A 2^-48 - 1 rounded once to T (rf_core.h cic_delta)
 template <typename T>
 __global__ __launch_bounds__(256) void cic_convert_kernel(const u64* __restrict__ A, T* __restrict__ W, long long n) {
@@ -140,7 +203,37 @@ hipError_t cic_paint_t(int form, const T* Q, u64* A, u64* dropped, int nx, int n
   return hipGetLastError();
 }
 
+template <typename T>
+hipError_t cic_gather_t(int form, const T* Q, const T* W, T* G, double coeff, int first, u64* dropped, int nx, int ny, int nz, const double* inv_h,
+                        hipStream_t s) {
+  const long long n = (long long)nx * ny * nz;
+  CicGrid g;
+  g.nx = nx; g.ny = ny; g.nz = nz;
+  for (int a = 0; a < 3; ++a) g.inv_h[a] = inv_h[a];
+  const T *Qx = Q, *Qy = Q + n, *Qz = Q + 2 * n;
+  if (form == 1) {
+    hipLaunchKernelGGL(cic_gather_global_kernel<T>, dim3(sweep_grid(n, 256)), dim3(256), 0, s, Qx, Qy, Qz, W, G, dropped, g, coeff, first, n);
+    return hipGetLastError();
+  }
+  const long long nbx = (nx + CIC_BX - 1) / CIC_BX, nby = (ny + CIC_BY - 1) / CIC_BY, nbz = (nz + CIC_BZ - 1) / CIC_BZ;
+  const long long nb = nbx * nby * nbz;
+  if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
+  static LdsAttrLatch latch;
+  const int lds = CIC_TILE_CELLS * (int)sizeof(T);            // 39 168 bytes float32, 78 336 float64: two workgroups per compute unit
+  if (hipError_t e = latch.ensure(reinterpret_cast<const void*>(&cic_gather_tiled_kernel<T>), lds)) return e;
+  hipLaunchKernelGGL(cic_gather_tiled_kernel<T>, dim3((unsigned)nb), dim3(CIC_NT), lds, s, Qx, Qy, Qz, W, G, dropped, g, coeff, first, (int)nby,
+                     (int)nbz);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_cic_gather(int f64, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
+                             int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
+  if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
+  return f64 ? cic_gather_t<double>(form, (const double*)Q, (const double*)W, (double*)G_slot, coeff, first, dropped, nx, ny, nz, inv_h, s)
+             : cic_gather_t<float>(form, (const float*)Q, (const float*)W, (float*)G_slot, coeff, first, dropped, nx, ny, nz, inv_h, s);
+}
 
 hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double coeff, int first, long long n, hipStream_t s) {
   return f64 ? particles_accumulate_t<double, 2>((const double*)W, (double*)Q, coeff, first, n, s)

@@ -158,6 +158,13 @@ hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long
                             const double* inv_h, hipStream_t s);
 // the brick (cells per axis) and the halo of form 2's tile
 void cic_paint_geometry(int* brick3, int* halo);
+// the cloud-in-cell gather, the scatter's adjoint (rf_core.h cic_gather_value): the dense real field W at the lattice particles displaced
+// by Q[3][nx][ny][nz] into G_slot[nx][ny][nz], indexed by the particle's lattice cell: G = (T)(coeff g) (first != 0) or
+// (T)((double)G + coeff g).  form 1 = eight loads per particle from memory, form 2 = the paint's tile of W staged in LDS; the same bits
+// from both.  *dropped (cleared by the caller) counts the particles with a non-finite displacement: they gather 0.  W and G_slot must
+// not overlap.
+hipError_t launch_cic_gather(int f64, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
+                             int nx, int ny, int nz, const double* inv_h, hipStream_t s);
 // W = (double)A 2^-48 - 1, rounded once to the real type (rf_core.h cic_delta)
 hipError_t launch_cic_convert(int f64, const unsigned long long* A, void* W, long long n, hipStream_t s);
 // the binned sums of a half spectrum (rf_k_power.hip): the power spectrum (rf_core.h power_cell; P = PowerParams) or its multipoles

@@ -159,6 +159,10 @@ struct rf_plan {
   rfc::DevBuf<> Q, A, pa_drop;
   bool pa_valid = false;
   int paint_form = 0;
+  // lazy, rf_particles_gather: the gathered values PG[3][nx][ny][nz] of the plan's real type (3 x w_bytes, zeroed once), indexed by the
+  // particle's lattice cell as Q is and counted by rf_plan_nbytes; the drop counter is pa_drop.  gather_form: 0 auto, 1 global, 2 tiled.
+  rfc::DevBuf<> PG;
+  int gather_form = 0;
   rfc::DevBuf<> tw_x, tw_y, tw_z;
   rfc::DevBuf<double> kx2, ky2, kz2;
   rfc::DevBuf<double> xt, st, sl;

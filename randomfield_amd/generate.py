@@ -182,6 +182,7 @@ class Generator(object):
         self.potential = None
         self._lpt2 = None                   # second-order potential of the current field: the array (numpy) / its potential object (hip)
         self._particles = None              # particle displacements: the (3, nx, ny, nz) array (numpy) / True once the device buffer is filled (hip)
+        self._gathered = None               # gathered values: the (3, nx, ny, nz) array (numpy) / True once a gather has run (hip)
         self.particles_dropped = 0
 
         if nz % num_plot_sections != 0:
@@ -263,6 +264,7 @@ class Generator(object):
         self.smoothed_power = powertools.filter_power(self.power, smoothing_length_Mpc_h)
         self._lpt2 = None
         self._particles = None               # (displacements belong to the field they were made for or set beside)
+        self._gathered = None                # (... and so do the values gathered at them)
 
         if self.backend == "numpy":
             data = self.plan_c2r.data_in
@@ -397,6 +399,7 @@ class Generator(object):
         self.potential = None
         self._lpt2 = None
         self._particles = None               # (displacements belong to the field they were made for or set beside)
+        self._gathered = None                # (... and so do the values gathered at them)
         self.delta_field_rms = self.plan_c2r.data_out.dtype.type(rms)
         self._field_on_host = False
         if self.verbose:
@@ -492,14 +495,19 @@ class Generator(object):
         if nbins is not None and len(k_edges) != int(nbins) + 1:
             raise ValueError("k_edges must have nbins + 1 entries.")
         if field is not None:
-            field = np.asarray(field)
-            if field.shape != shape:
-                raise ValueError("field must have the shape {0}.".format(shape))
-            self.plan_c2r.data_out[...] = field
-            self._field_on_host = True
-            if self.backend == "hip":
-                self.plan_c2r.device.upload_real(self.plan_c2r.data_out_padded, padded=True)
+            self._make_current(field)
         return shape, k_edges
+
+    def _make_current(self, field):
+        """``field`` copied into the plan's host buffer and (hip backend) uploaded: it becomes the current field"""
+        shape = tuple(self.plan_c2r.shape)
+        field = np.asarray(field)
+        if field.shape != shape:
+            raise ValueError("field must have the shape {0}.".format(shape))
+        self.plan_c2r.data_out[...] = field
+        self._field_on_host = True
+        if self.backend == "hip":
+            self.plan_c2r.device.upload_real(self.plan_c2r.data_out_padded, padded=True)
 
     def _need_table(self, name):
         value = getattr(self, name)
@@ -868,6 +876,60 @@ class Generator(object):
         self.particles_dropped = self.plan_c2r.device.particles_paint(inv_h)
         self._field_on_host = False
         return self.download_field() if download else None
+
+    def interpolate_at_particles(self, field=None, *, slot=0, coeff=1.0, first=True, download=True):
+        """
+        Cloud-in-cell interpolation of a field at the displaced particles, the adjoint of :meth:`paint_particles` over the same
+        cells and integer weights: what carries a grid field -- a force component, a reconstruction displacement, the density --
+        back to the particles.  ``field=None`` gathers the current field (the one on the device, hip backend; ``plan_c2r.data_out``,
+        numpy backend); an ``(nx, ny, nz)`` array is uploaded first and becomes the current field, as in
+        :meth:`measure_power_spectrum`.  The field is left as it is.
+
+        The values go to one of three slots (``slot`` 0, 1, 2: the components of a vector field can be gathered at the same
+        positions before :meth:`shift_particles` moves anything): ``G[slot] = coeff * g`` with ``first=True``, otherwise
+        ``G[slot] + coeff * g``, g formed in float64 and the sum rounded once to the plan's real type -- the same bits on both
+        backends and on every call (hip backend: ``rf_particles_gather``, no atomics).  A particle with a non-finite displacement
+        gathers 0 and is counted in ``self.particles_dropped``.  The gathered values are kept until the next field is generated, as
+        the displacements are.  Returns a new ``(nx, ny, nz)`` array indexed by the particle's lattice cell, or None with
+        ``download=False``.
+        """
+        if self.distributed:
+            raise NotImplementedError("particles live on single-GPU plans (distributed=False).")
+        if slot not in (0, 1, 2):
+            raise ValueError("Invalid slot: {0!r} (expected 0, 1 or 2).".format(slot))
+        if self._particles is None:
+            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+        if field is not None:
+            self._make_current(field)                            # (as measure_power_spectrum(field=...) does)
+        inv_h = [1.0 / float(self.grid_spacing_Mpc_h)] * 3
+        if self.backend == "numpy":
+            from . import particles
+            if self._gathered is None:
+                self._gathered = np.zeros((3,) + tuple(self.plan_c2r.shape), self.plan_c2r.data_out.dtype)
+            _, self.particles_dropped = particles.gather(self._particles, inv_h, self.plan_c2r.data_out, coeff, first, self._gathered[slot])
+            return self._gathered[slot].copy() if download else None
+        dev = self.plan_c2r.device
+        self.particles_dropped = dev.particles_gather(inv_h, slot, coeff, first)
+        self._gathered = True
+        return dev.particles_gather_download(slot) if download else None
+
+    def shift_particles(self, axis, slot=None, coeff=1.0):
+        """Move the particles along ``axis`` by the gathered values: ``s[axis] += coeff * G[slot]`` (``slot=None``: the slot of the
+        same number as the axis), one fused multiply-add in the plan's real type (hip backend: ``rf_particles_shift``)."""
+        if axis not in (0, 1, 2):
+            raise ValueError("Invalid axis: {0!r} (expected 0, 1 or 2).".format(axis))
+        slot = axis if slot is None else slot
+        if slot not in (0, 1, 2):
+            raise ValueError("Invalid slot: {0!r} (expected 0, 1 or 2).".format(slot))
+        if self._particles is None:
+            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+        if self._gathered is None:
+            raise RuntimeError("No gathered values: call interpolate_at_particles() first.")
+        if self.backend == "numpy":
+            rtype = self.plan_c2r.data_out.dtype.type
+            self._particles[axis] += rtype(coeff) * self._gathered[slot]
+            return
+        self.plan_c2r.device.particles_shift(axis, slot, coeff)
 
     def calculate_lensing_potential(self, i_min=None, show_plot=False, save_plot_name=None):
         """

@@ -42,6 +42,40 @@ def paint_counts(displacements, inv_h):
     return A.reshape(shape), int(ok.size - np.count_nonzero(ok))
 
 
+def gather(displacements, inv_h, field, coeff=1.0, first=True, out=None):
+    """``(out, dropped)``: the cloud-in-cell interpolation of ``field`` (nx, ny, nz) at the particles displaced by ``displacements``
+    (3, nx, ny, nz), the adjoint of :func:`paint_counts` over the same indices and integer weights.  In float64, every product and
+    sum rounded on its own: along z first, a = wz0 v0 + wz1 v1, then y, then x, the result scaled by 2**-48;
+    ``out[q] = coeff * g`` (``first``) or ``out[q] + coeff * g``, rounded once to the field's type.  Zero weights are not skipped
+    (a non-finite field value reaches every particle whose eight cells contain it); a dropped particle gathers 0: ``first`` writes
+    0, otherwise ``out[q]`` stays."""
+    s = np.asarray(displacements)
+    field = np.asarray(field)
+    shape = s.shape[1:]
+    terms = [_axis(s[a], inv_h[a], a) for a in range(3)]
+    ok = terms[0][0] & terms[1][0] & terms[2][0]
+    (jx, jy, jz), (wx, wy, wz) = [t[1] for t in terms], [[w.astype(np.float64) for w in t[2]] for t in terms]
+    flat = field.ravel()
+    with np.errstate(invalid="ignore", over="ignore"):
+        b = []
+        for cx in (0, 1):
+            a = []
+            for cy in (0, 1):
+                row = (jx[cx] * shape[1] + jy[cy]) * shape[2]
+                v0, v1 = flat[row + jz[0]].astype(np.float64), flat[row + jz[1]].astype(np.float64)
+                a.append(wz[0] * v0 + wz[1] * v1)
+            b.append(wy[0] * a[0] + wy[1] * a[1])
+        g = (wx[0] * b[0] + wx[1] * b[1]) * 2.0 ** -48
+        term = np.float64(coeff) * g
+        if out is None:
+            out = np.zeros(shape, field.dtype)
+        if first:
+            out[...] = np.where(ok, term, 0.0).astype(field.dtype)
+        else:
+            out[...] = np.where(ok, (out.astype(np.float64) + term).astype(field.dtype), out)
+    return out, int(ok.size - np.count_nonzero(ok))
+
+
 def counts_to_delta(A, dtype):
     """delta = A * 2**-48 - 1 in float64, rounded once to ``dtype``"""
     return (A.astype(np.float64) * (1.0 / WEIGHT_ONE) - 1.0).astype(dtype)
