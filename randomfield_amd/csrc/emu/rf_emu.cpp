@@ -737,151 +737,129 @@ template <class Body> void run_threads(int nth, Body body) {
 }
 inline void atomic_add_u64(unsigned long long* p, uint64_t w) { __atomic_fetch_add(p, (unsigned long long)w, __ATOMIC_RELAXED); }
 
-template <typename T>
-int particles_paint_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, int form, int bx, int by, int bz, int halo,
-                         int nth, unsigned long long* A, unsigned long long* dropped) {
-  const long long n = (long long)nx * ny * nz;
-  memset(A, 0, (size_t)n * 8);
+// The two walks of rf_k_particles.hip over an operation Op -- what it does before a brick's particles (prologue), with one particle's
+// eight cells, with a dropped particle and after the brick (epilogue), over a tile of Op::Cell.  cic_global_kernel: one "lane" per particle.
+template <typename T, class Op>
+void cic_walk_global(const CicGrid& g, const T* sx, const T* sy, const T* sz, int nth, Op& op, unsigned long long* dropped) {
+  const long long n = (long long)g.nx * g.ny * g.nz;
   *dropped = 0;
-  if (form == 1) {                                   // cic_paint_global_kernel: one "lane" per particle
-    run_threads(nth, [&](int tid, auto sync) {
-      unsigned long long nd = 0;
-      for (long long i = tid; i < n; i += nth) {
-        const long long row = i / nz;
-        const int iz = (int)(i - row * nz), ix = (int)(row / ny), iy = (int)(row - (long long)ix * ny);
-        CicAxis x, y, z;
-        if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) { ++nd; continue; }
-        cic_scatter_global(x, y, z, ny, nz, [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
-      }
-      if (nd) atomic_add_u64(dropped, nd);
-    });
-    return 0;
-  }
-  // cic_paint_tiled_kernel: bricks one after the other, the threads of a brick share its tile image and meet at the kernel's barriers
-  CicTile t;
-  t.bx = bx; t.by = by; t.bz = bz; t.h = halo; t.x0 = t.y0 = t.z0 = 0;
-  std::vector<unsigned long long> tile((size_t)t.cells());
-  const int nbx = (nx + bx - 1) / bx, nby = (ny + by - 1) / by, nbz = (nz + bz - 1) / bz;
+  run_threads(nth, [&](int tid, auto sync) {
+    unsigned long long nd = 0;
+    for (long long i = tid; i < n; i += nth) {
+      int ix, iy, iz;
+      cic_lattice(i, g.ny, g.nz, ix, iy, iz);
+      CicAxis x, y, z;
+      if (!cic_particle<T>(sx[i], sy[i], sz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++nd; op.dropped(i); continue; }
+      op.particle(i, x, y, z, g);
+    }
+    if (nd) atomic_add_u64(dropped, nd);
+  });
+}
+// cic_tiled_kernel: bricks one after the other, the threads of a brick share its tile image and meet at the kernel's barriers (and
+// once more before the next brick takes the tile)
+template <typename T, class Op>
+void cic_walk_bricks(const CicGrid& g, const T* sx, const T* sy, const T* sz, int bx, int by, int bz, int halo, int nth, Op& op, unsigned long long* dropped) {
+  std::vector<typename Op::Cell> image((size_t)cic_brick_tile(0, 1, 1, bx, by, bz, halo).cells());
+  typename Op::Cell* tile = image.data();
+  const int nbx = (g.nx + bx - 1) / bx, nby = (g.ny + by - 1) / by, nbz = (g.nz + bz - 1) / bz;
+  *dropped = 0;
   run_threads(nth, [&](int tid, auto sync) {
     unsigned long long nd = 0;
     for (int b = 0; b < nbx * nby * nbz; ++b) {
-      CicTile tb = t;
-      tb.z0 = (b % nbz) * bz; tb.y0 = ((b / nbz) % nby) * by; tb.x0 = (b / nbz / nby) * bx;
-      for (int s = tid; s < tb.cells(); s += nth) tile[s] = 0ull;
+      const CicTile t = cic_brick_tile((unsigned)b, nby, nbz, bx, by, bz, halo);
+      op.prologue(tile, t, g, tid, nth);
       sync();
       for (int row = tid; row < bx * by; row += nth) {
-        const int lx = row / by, ly = row - lx * by, ix = tb.x0 + lx, iy = tb.y0 + ly;
+        const int lx = row / by, ly = row - lx * by, ix = t.x0 + lx, iy = t.y0 + ly;
         for (int lz = 0; lz < bz; ++lz) {
-          const int iz = tb.z0 + lz;
-          if (ix >= nx || iy >= ny || iz >= nz) continue;
-          const long long i = ((long long)ix * ny + iy) * nz + iz;
+          const int iz = t.z0 + lz;
+          if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
+          const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
           CicAxis x, y, z;
-          if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) { ++nd; continue; }
-          cic_scatter_tiled(x, y, z, lx, ly, lz, tb, ny, nz,
-                            [&](int slot, uint64_t w) { atomic_add_u64(&tile[slot], w); },
-                            [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+          if (!cic_particle<T>(sx[i], sy[i], sz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++nd; op.dropped(i); continue; }
+          op.particle(i, x, y, z, lx, ly, lz, tile, t, g);
         }
       }
       sync();
-      for (int s = tid; s < tb.cells(); s += nth)
-        if (tile[s]) atomic_add_u64(A + cic_tile_cell(tb, s, nx, ny, nz), tile[s]);
+      op.epilogue(tile, t, g, tid, nth);
       sync();
     }
     if (nd) atomic_add_u64(dropped, nd);
   });
-  return 0;
 }
 
-// what the tiled form does with these particles, counted with the kernel's own rule (cic_scatter_tiled): particles that leave their
-// brick's tile, their adds straight into A, and the non-zero tile cells the bricks flush
+// PaintOp: the threads add with __atomic operations to the shared accumulator grid and to the brick's shared tile image
+struct EmuPaintOp {
+  typedef unsigned long long Cell;
+  unsigned long long* A;
+  void prologue(Cell* tile, const CicTile& t, const CicGrid&, int tid, int nth) const {
+    for (int s = tid; s < t.cells(); s += nth) tile[s] = 0ull;
+  }
+  void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, const CicGrid& g) const {
+    cic_scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+  }
+  void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, Cell* tile, const CicTile& t, const CicGrid& g) const {
+    cic_scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { atomic_add_u64(&tile[slot], w); },
+                      [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+  }
+  void dropped(long long) const {}
+  void epilogue(Cell* tile, const CicTile& t, const CicGrid& g, int tid, int nth) const {
+    for (int s = tid; s < t.cells(); s += nth)
+      if (tile[s]) atomic_add_u64(A + cic_tile_cell(t, s, g.nx, g.ny, g.nz), tile[s]);
+  }
+};
+// GatherOp: every particle writes its own element of G, so the threads share nothing but the tile image (filled before a barrier,
+// read-only after it) and the drop counter
+template <typename T>
+struct EmuGatherOp {
+  typedef T Cell;
+  const T* W;
+  T* G;
+  double coeff;
+  int first;
+  void prologue(Cell* tile, const CicTile& t, const CicGrid& g, int tid, int nth) const {
+    for (int s = tid; s < t.cells(); s += nth) tile[s] = W[cic_tile_cell(t, s, g.nx, g.ny, g.nz)];
+  }
+  void out(long long i, double v) const { G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]); }
+  void particle(long long i, const CicAxis& x, const CicAxis& y, const CicAxis& z, const CicGrid& g) const {
+    out(i, cic_gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; }));
+  }
+  void particle(long long i, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const Cell* tile, const CicTile& t,
+                const CicGrid& g) const {
+    out(i, cic_gather_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot) { return (double)tile[slot]; }, [&](long long cell) { return (double)W[cell]; }));
+  }
+  void dropped(long long i) const { if (first) G[i] = (T)0; }
+  void epilogue(Cell*, const CicTile&, const CicGrid&, int, int) const {}
+};
+// what the tiled paint does with these particles, counted with the kernel's own rule (cic_scatter_tiled) by one thread: particles that
+// leave their brick's tile, their adds straight into A, and the non-zero tile cells the bricks flush
+struct EmuTileStatsOp {
+  typedef unsigned long long Cell;
+  unsigned long long fallback = 0, fallback_adds = 0, flushed = 0;
+  void prologue(Cell* tile, const CicTile& t, const CicGrid&, int, int) { std::fill(tile, tile + t.cells(), 0ull); }
+  void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, Cell* tile, const CicTile& t, const CicGrid& g) {
+    const unsigned long long before = fallback_adds;
+    cic_scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { tile[slot] += w; }, [&](long long, uint64_t) { ++fallback_adds; });
+    if (fallback_adds != before) ++fallback;
+  }
+  void dropped(long long) {}
+  void epilogue(Cell* tile, const CicTile& t, const CicGrid&, int, int) { flushed += t.cells() - std::count(tile, tile + t.cells(), 0ull); }
+};
+
+template <typename T, class Op>
+int particles_walk(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, int form, int bx, int by, int bz, int halo, int nth,
+                   Op op, unsigned long long* dropped) {
+  const CicGrid g = {nx, ny, nz, {inv_h[0], inv_h[1], inv_h[2]}};
+  if (form == 1) cic_walk_global(g, sx, sy, sz, nth, op, dropped);
+  else cic_walk_bricks(g, sx, sy, sz, bx, by, bz, halo, nth, op, dropped);
+  return 0;
+}
 template <typename T>
 int particles_tile_stats_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, int bx, int by, int bz, int halo,
                               unsigned long long* out4) {
-  CicTile t;
-  t.bx = bx; t.by = by; t.bz = bz; t.h = halo; t.x0 = t.y0 = t.z0 = 0;
-  std::vector<unsigned long long> tile((size_t)t.cells());
-  unsigned long long fallback = 0, fallback_adds = 0, flushed = 0, dropped = 0;
-  for (int x0 = 0; x0 < nx; x0 += bx)
-    for (int y0 = 0; y0 < ny; y0 += by)
-      for (int z0 = 0; z0 < nz; z0 += bz) {
-        t.x0 = x0; t.y0 = y0; t.z0 = z0;
-        std::fill(tile.begin(), tile.end(), 0ull);
-        for (int lx = 0; lx < bx && x0 + lx < nx; ++lx)
-          for (int ly = 0; ly < by && y0 + ly < ny; ++ly)
-            for (int lz = 0; lz < bz && z0 + lz < nz; ++lz) {
-              const long long i = ((long long)(x0 + lx) * ny + (y0 + ly)) * nz + (z0 + lz);
-              CicAxis x, y, z;
-              if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, x0 + lx, y0 + ly, z0 + lz, nx, ny, nz, x, y, z)) { ++dropped; continue; }
-              const unsigned long long before = fallback_adds;
-              cic_scatter_tiled(x, y, z, lx, ly, lz, t, ny, nz, [&](int slot, uint64_t w) { tile[slot] += w; },
-                                [&](long long, uint64_t) { ++fallback_adds; });
-              if (fallback_adds != before) ++fallback;
-            }
-        for (unsigned long long v : tile) flushed += v != 0;
-      }
-  out4[0] = fallback; out4[1] = fallback_adds; out4[2] = flushed; out4[3] = dropped;
-  return 0;
-}
-
-// the gather as rf_k_particles.hip runs it: every particle writes its own element of G, so the threads share nothing but the tile image
-// (filled before a barrier, read-only after it) and the drop counter
-template <typename T>
-int particles_gather_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, const T* W, T* G, double coeff, int first,
-                          int form, int bx, int by, int bz, int halo, int nth, unsigned long long* dropped) {
-  const long long n = (long long)nx * ny * nz;
-  *dropped = 0;
-  if (form == 1) {                                   // cic_gather_global_kernel: one "lane" per particle
-    run_threads(nth, [&](int tid, auto sync) {
-      unsigned long long nd = 0;
-      for (long long i = tid; i < n; i += nth) {
-        const long long row = i / nz;
-        const int iz = (int)(i - row * nz), ix = (int)(row / ny), iy = (int)(row - (long long)ix * ny);
-        CicAxis x, y, z;
-        if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) {
-          ++nd;
-          if (first) G[i] = (T)0;
-          continue;
-        }
-        const double v = cic_gather_global(x, y, z, ny, nz, [&](long long cell) { return (double)W[cell]; });
-        G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
-      }
-      if (nd) atomic_add_u64(dropped, nd);
-    });
-    return 0;
-  }
-  // cic_gather_tiled_kernel: bricks one after the other, the threads of a brick stage its tile of W, meet at the kernel's barrier and read it
-  CicTile t;
-  t.bx = bx; t.by = by; t.bz = bz; t.h = halo; t.x0 = t.y0 = t.z0 = 0;
-  std::vector<T> tile((size_t)t.cells());
-  const int nbx = (nx + bx - 1) / bx, nby = (ny + by - 1) / by, nbz = (nz + bz - 1) / bz;
-  run_threads(nth, [&](int tid, auto sync) {
-    unsigned long long nd = 0;
-    for (int b = 0; b < nbx * nby * nbz; ++b) {
-      CicTile tb = t;
-      tb.z0 = (b % nbz) * bz; tb.y0 = ((b / nbz) % nby) * by; tb.x0 = (b / nbz / nby) * bx;
-      for (int s = tid; s < tb.cells(); s += nth) tile[s] = W[cic_tile_cell(tb, s, nx, ny, nz)];
-      sync();
-      for (int row = tid; row < bx * by; row += nth) {
-        const int lx = row / by, ly = row - lx * by, ix = tb.x0 + lx, iy = tb.y0 + ly;
-        for (int lz = 0; lz < bz; ++lz) {
-          const int iz = tb.z0 + lz;
-          if (ix >= nx || iy >= ny || iz >= nz) continue;
-          const long long i = ((long long)ix * ny + iy) * nz + iz;
-          CicAxis x, y, z;
-          if (!cic_particle<T>(sx[i], sy[i], sz[i], inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) {
-            ++nd;
-            if (first) G[i] = (T)0;
-            continue;
-          }
-          const double v = cic_gather_tiled(x, y, z, lx, ly, lz, tb, ny, nz, [&](int slot) { return (double)tile[slot]; },
-                                            [&](long long cell) { return (double)W[cell]; });
-          G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
-        }
-      }
-      sync();                                        // (the next brick overwrites the tile)
-    }
-    if (nd) atomic_add_u64(dropped, nd);
-  });
+  EmuTileStatsOp op;
+  cic_walk_bricks(CicGrid{nx, ny, nz, {inv_h[0], inv_h[1], inv_h[2]}}, sx, sy, sz, bx, by, bz, halo, 1, op, &out4[3]);
+  out4[0] = op.fallback; out4[1] = op.fallback_adds; out4[2] = op.flushed;
   return 0;
 }
 
@@ -1084,8 +1062,9 @@ int emu_particles_paint(int f64, int nx, int ny, int nz, const void* sx, const v
                         int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped) {
   if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && A && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
   if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
-  return f64 ? particles_paint_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth, A, dropped)
-             : particles_paint_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
+  memset(A, 0, (size_t)nx * ny * nz * 8);
+  return f64 ? particles_walk(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth, EmuPaintOp{A}, dropped)
+             : particles_walk(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth, EmuPaintOp{A}, dropped);
 }
 // the tiled form's traffic for these particles, by the kernel's own rule: out4 = {particles that leave their brick's tile, their adds
 // straight into A, non-zero tile cells flushed, dropped particles}
@@ -1104,10 +1083,10 @@ int emu_particles_gather(int f64, int nx, int ny, int nz, const void* sx, const 
                          double coeff, int first, int form, int bx, int by, int bz, int halo, int nth, unsigned long long* dropped) {
   if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && W && G && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
   if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
-  return f64 ? particles_gather_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, (const double*)W, (double*)G, coeff,
-                                             first, form, bx, by, bz, halo, nth, dropped)
-             : particles_gather_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, (const float*)W, (float*)G, coeff,
-                                            first, form, bx, by, bz, halo, nth, dropped);
+  return f64 ? particles_walk(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth,
+                              EmuGatherOp<double>{(const double*)W, (double*)G, coeff, first}, dropped)
+             : particles_walk(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth,
+                              EmuGatherOp<float>{(const float*)W, (float*)G, coeff, first}, dropped);
 }
 // Q = coeff W (first) or Q + coeff W over n elements (rf_core.h particles_axpy, the function the kernel calls per element)
 int emu_particles_accumulate(int f64, int first, double coeff, const void* W, void* Q, long long n) {

@@ -1930,6 +1930,25 @@ static int particles_check(rf_plan* p, const char* multi) {
   RF_REQUIRE(p->nranks == 1, multi);
   return 0;
 }
+static int inv_h_check(const double* inv_h) {
+  for (int a = 0; a < 3; ++a) RF_REQUIRE(inv_h[a] > 0 && inv_h[a] <= 1.7976931348623157e308, "inv_h must be positive and finite");
+  return 0;
+}
+// component `axis` of the displacements Q, slot `slot` of the gathered values PG
+static char* q_component(rf_plan* p, int axis) { return (char*)p->Q.ptr + (size_t)axis * p->w_bytes; }
+static char* pg_slot(rf_plan* p, int slot) { return (char*)p->PG.ptr + (size_t)slot * p->w_bytes; }
+// one real array between the host and the device, complete on return
+static int particles_copy(rf_plan* p, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  RF_HIP(hipSetDevice(p->device));
+  RF_HIP(hipMemcpyAsync(dst, src, bytes, kind, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  return 0;
+}
+// (rf_kernel_ms: this call's events apply, not an earlier call's slabs or repair launch)
+static void particles_reset_timing(rf_plan* p) { p->slab_timed = p->slab_merged = 0; p->repair_timed = false; }
+// the drop counter around a sweep: cleared on the stream before it; copied out after it, the stream drained
+static hipError_t drop_clear(rf_plan* p) { return hipMemsetAsync(p->pa_drop.ptr, 0, 8, p->stream); }
+static int drop_read(rf_plan* p, unsigned long long* dropped) { return particles_copy(p, dropped, p->pa_drop.ptr, 8, hipMemcpyDeviceToHost); }
 
 int rf_particles_accumulate(rf_plan* p, int axis, double coeff, int first) {
   if (int rc = particles_check(p, "the particle displacements live on single-rank plans")) return rc;
@@ -1937,7 +1956,7 @@ int rf_particles_accumulate(rf_plan* p, int axis, double coeff, int first) {
   RF_REQUIRE(p->real_valid && p->cur, "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_q(p)) return rc;
-  RF_HIP(launch_particles_accumulate(p->f64, p->cur, (char*)p->Q.ptr + (size_t)axis * p->w_bytes, coeff, first, (long long)particle_cells(p), p->stream));
+  RF_HIP(launch_particles_accumulate(p->f64, p->cur, q_component(p, axis), coeff, first, (long long)particle_cells(p), p->stream));
   return 0;
 }
 
@@ -1947,9 +1966,7 @@ int rf_particles_upload(rf_plan* p, int axis, const void* host) {
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_q(p)) return rc;
-  RF_HIP(hipMemcpyAsync((char*)p->Q.ptr + (size_t)axis * p->w_bytes, host, p->w_bytes, hipMemcpyHostToDevice, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  return 0;
+  return particles_copy(p, q_component(p, axis), host, p->w_bytes, hipMemcpyHostToDevice);
 }
 
 int rf_particles_download(rf_plan* p, int axis, void* host) {
@@ -1957,10 +1974,7 @@ int rf_particles_download(rf_plan* p, int axis, void* host) {
   RF_REQUIRE(host, "null argument");
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
-  RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, (char*)p->Q.ptr + (size_t)axis * p->w_bytes, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  return 0;
+  return particles_copy(p, host, q_component(p, axis), p->w_bytes, hipMemcpyDeviceToHost);
 }
 
 // A <- 0, the scatter, W <- (double)A 2^-48 - 1.  rf_kernel_ms afterwards: [0] clearing A, [1] the scatter, [2] the conversion, [3] = [4] = 0
@@ -1968,7 +1982,7 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(inv_h && dropped, "null argument");
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
-  for (int a = 0; a < 3; ++a) RF_REQUIRE(inv_h[a] > 0 && inv_h[a] <= 1.7976931348623157e308, "inv_h must be positive and finite");
+  if (int rc = inv_h_check(inv_h)) return rc;
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_a(p)) return rc;
   const size_t n = particle_cells(p);
@@ -1976,12 +1990,10 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
   // 64 against 357 ms of scatter; profiles/paint_bench.log)
   const int form = p->paint_form ? p->paint_form : 2;
   p->pa_valid = false;
-  p->slab_timed = 0;
-  p->slab_merged = 0;
-  p->repair_timed = false;
+  particles_reset_timing(p);
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
   RF_HIP(hipMemsetAsync(p->A.ptr, 0, n * 8, p->stream));
-  RF_HIP(hipMemsetAsync(p->pa_drop.ptr, 0, 8, p->stream));
+  RF_HIP(drop_clear(p));
   RF_HIP(hipEventRecord(p->ev[1], p->stream));
   RF_HIP(launch_cic_paint(p->f64, form, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
   RF_HIP(hipEventRecord(p->ev[2], p->stream));
@@ -1993,19 +2005,14 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
   p->real_valid = true;
   p->stats_valid = false;
   p->pa_valid = true;
-  RF_HIP(hipMemcpyAsync(dropped, p->pa_drop.ptr, 8, hipMemcpyDeviceToHost, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  return 0;
+  return drop_read(p, dropped);
 }
 
 int rf_particles_download_counts(rf_plan* p, unsigned long long* host) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(host, "null argument");
   RF_REQUIRE(p->A.ptr && p->pa_valid, "no painted counts: call rf_particles_paint first");
-  RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, p->A.ptr, particle_cells(p) * 8, hipMemcpyDeviceToHost, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  return 0;
+  return particles_copy(p, host, p->A.ptr, particle_cells(p) * 8, hipMemcpyDeviceToHost);
 }
 
 int rf_particles_paint_geometry(rf_plan* p, int* brick3, int* halo) {
@@ -2026,7 +2033,7 @@ int rf_particles_gather(rf_plan* p, const double* inv_h, int slot, double coeff,
   if (int rc = particles_check(p, "the cloud-in-cell gather runs on single-rank plans")) return rc;
   RF_REQUIRE(inv_h && dropped, "null argument");
   RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
-  for (int a = 0; a < 3; ++a) RF_REQUIRE(inv_h[a] > 0 && inv_h[a] <= 1.7976931348623157e308, "inv_h must be positive and finite");
+  if (int rc = inv_h_check(inv_h)) return rc;
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
   RF_REQUIRE(p->real_valid && p->cur, "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
@@ -2035,18 +2042,14 @@ int rf_particles_gather(rf_plan* p, const double* inv_h, int slot, double coeff,
   // cells and 11.2 / 11.1 against 10.1 / 10.1 ms on rms 0.1: it loses 1.1 ms where it loses and wins 15 to 26 ms where it wins, and the
   // displacements' scale is not known without a sweep of its own (profiles/gather_bench.log)
   const int form = p->gather_form ? p->gather_form : 2;
-  p->slab_timed = 0;
-  p->slab_merged = 0;
-  p->repair_timed = false;
-  RF_HIP(hipMemsetAsync(p->pa_drop.ptr, 0, 8, p->stream));
+  particles_reset_timing(p);
+  RF_HIP(drop_clear(p));
   RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  RF_HIP(launch_cic_gather(p->f64, form, p->Q.ptr, p->cur, (char*)p->PG.ptr + (size_t)slot * p->w_bytes, coeff, first, (unsigned long long*)p->pa_drop.ptr,
-                           p->nx, p->ny, p->nz, inv_h, p->stream));
+  RF_HIP(launch_cic_gather(p->f64, form, p->Q.ptr, p->cur, pg_slot(p, slot), coeff, first, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h,
+                           p->stream));
   for (int i = 1; i <= 4; ++i) RF_HIP(hipEventRecord(p->ev[i], p->stream));
   p->timed = true;
-  RF_HIP(hipMemcpyAsync(dropped, p->pa_drop.ptr, 8, hipMemcpyDeviceToHost, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  return 0;
+  return drop_read(p, dropped);
 }
 
 int rf_particles_gather_download(rf_plan* p, int slot, void* host) {
@@ -2054,10 +2057,7 @@ int rf_particles_gather_download(rf_plan* p, int slot, void* host) {
   RF_REQUIRE(host, "null argument");
   RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
   RF_REQUIRE(p->PG.ptr, "no gathered values: call rf_particles_gather first");
-  RF_HIP(hipSetDevice(p->device));
-  RF_HIP(hipMemcpyAsync(host, (char*)p->PG.ptr + (size_t)slot * p->w_bytes, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
-  RF_HIP(hipStreamSynchronize(p->stream));
-  return 0;
+  return particles_copy(p, host, pg_slot(p, slot), p->w_bytes, hipMemcpyDeviceToHost);
 }
 
 // Q_axis = fma(coeff, G_slot, Q_axis): the accumulate sweep with the gathered values in the field's place
@@ -2068,8 +2068,7 @@ int rf_particles_shift(rf_plan* p, int axis, int slot, double coeff) {
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
   RF_REQUIRE(p->PG.ptr, "no gathered values: call rf_particles_gather first");
   RF_HIP(hipSetDevice(p->device));
-  RF_HIP(launch_particles_accumulate(p->f64, (const char*)p->PG.ptr + (size_t)slot * p->w_bytes, (char*)p->Q.ptr + (size_t)axis * p->w_bytes, coeff, 0,
-                                     (long long)particle_cells(p), p->stream));
+  RF_HIP(launch_particles_accumulate(p->f64, pg_slot(p, slot), q_component(p, axis), coeff, 0, (long long)particle_cells(p), p->stream));
   return 0;
 }
 

@@ -659,14 +659,29 @@ RF_HD bool cic_particle(T sx, T sy, T sz, const double* inv_h, int ix, int iy, i
 RF_HD uint64_t cic_weight(const CicAxis& x, const CicAxis& y, const CicAxis& z, int k) {
   return (uint64_t)((k & 4) ? x.w1 : x.w0) * (uint64_t)((k & 2) ? y.w1 : y.w0) * (uint64_t)((k & 1) ? z.w1 : z.w0);
 }
+// the grid and its spacing as the particle kernels and the emulator's walks carry them
+struct CicGrid {
+  int nx, ny, nz;
+  double inv_h[3];
+};
+// the lattice cell of particle i
+RF_HD void cic_lattice(long long i, int ny, int nz, int& ix, int& iy, int& iz) {
+  const long long row = i / nz;
+  iz = (int)(i - row * nz); ix = (int)(row / ny); iy = (int)(row - (long long)ix * ny);
+}
+// the eight cells of one particle straight in memory: f(k, cell index), k = 4 cx + 2 cy + cz with c = 0 for j0 / w0 and c = 1 for j1 / w1
+template <class F>
+RF_HD void cic_corners_global(const CicAxis& x, const CicAxis& y, const CicAxis& z, int ny, int nz, F&& f) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) f(k, ((long long)((k & 4) ? x.j1 : x.j0) * ny + ((k & 2) ? y.j1 : y.j0)) * nz + ((k & 1) ? z.j1 : z.j0));
+}
 // the eight adds of one particle straight into A: add(cell index, weight); zero weights add nothing and are skipped
 template <class Add>
 RF_HD void cic_scatter_global(const CicAxis& x, const CicAxis& y, const CicAxis& z, int ny, int nz, Add&& add) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
+  cic_corners_global(x, y, z, ny, nz, [&](int k, long long cell) {
     const uint64_t w = cic_weight(x, y, z, k);
-    if (w) add(((long long)((k & 4) ? x.j1 : x.j0) * ny + ((k & 2) ? y.j1 : y.j0)) * nz + ((k & 1) ? z.j1 : z.j0), w);
-  }
+    if (w) add(cell, w);
+  });
 }
 // The tiled form: a workgroup owns the brick of lattice cells [x0, x0 + bx) x [y0, y0 + by) x [z0, z0 + bz) and a tile image of
 // brick + halo h on every side, tile[tx][ty][tz] with t = b + 2 h, tile slot 0 standing for cell x0 - h (UNWRAPPED: periodic wrapping
@@ -685,6 +700,14 @@ struct CicTile {
 RF_HD int cic_tile_slot(const CicAxis& a, int li, int b, int h) {
   const double lo = (double)li + a.c;                          // (compared in float64: c may be far outside the int range)
   return (lo >= (double)-h && lo <= (double)(b + h - 2)) ? (int)lo + h : -1;
+}
+// the tile of brick number b, bricks numbered with z fastest among nbx x nby x nbz of them
+RF_HD CicTile cic_brick_tile(unsigned b, int nby, int nbz, int bx, int by, int bz, int h) {
+  const unsigned kz = b % (unsigned)nbz, kxy = b / (unsigned)nbz, ky = kxy % (unsigned)nby, kx = kxy / (unsigned)nby;
+  CicTile t;
+  t.bx = bx; t.by = by; t.bz = bz; t.h = h;
+  t.x0 = (int)kx * bx; t.y0 = (int)ky * by; t.z0 = (int)kz * bz;
+  return t;
 }
 template <class AddTile, class AddGlobal>
 RF_HD void cic_scatter_tiled(const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const CicTile& t, int ny, int nz,
@@ -755,13 +778,15 @@ template <typename T> RF_HD T cic_gather_out(bool first, double coeff, double g,
 template <class Load>
 RF_HD double cic_gather_global(const CicAxis& x, const CicAxis& y, const CicAxis& z, int ny, int nz, Load&& load) {
   double v[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = load(((long long)((k & 4) ? x.j1 : x.j0) * ny + ((k & 2) ? y.j1 : y.j0)) * nz + ((k & 1) ? z.j1 : z.j0));
+  cic_corners_global(x, y, z, ny, nz, [&](int k, long long cell) { v[k] = load(cell); });
   return cic_gather_value(x, y, z, v);
 }
 // The tiled form over the scatter's tile rule (CicTile, cic_tile_slot): the tile image holds W at the cells cic_tile_cell names, and a
 // particle whose eight cells all fall inside the tile reads them there, load_tile(slot) -> double; any other reads W as
 // cic_gather_global does.  Same values, same operations in the same order: the same bits either way.
+// (The rule is written out here as in cic_scatter_tiled, not shared: with both paths filling one v[] behind a common visitor all eight
+// values are live where the paths meet, and the float64 tiled kernel takes 84 VGPRs for 82; with the three tests in a function of
+// their own it takes 92.  As written each path feeds cic_gather_value by itself.)
 template <class LoadTile, class LoadGlobal>
 RF_HD double cic_gather_tiled(const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const CicTile& t, int ny, int nz,
                               LoadTile&& load_tile, LoadGlobal&& load_global) {

@@ -1,7 +1,11 @@
-// particles (rf_core.h cic_axis ... cic_delta): the resident displacement buffer's fma sweep and the cloud-in-cell paint of the displaced
-// lattice particles into an unsigned 64-bit accumulator grid.  Integer atomics only -- vector (global) and LDS ones: integer addition is
-// associative, so the accumulator holds the same bits for every launch shape, either form and every run.  No floating-point atomics.
-// And the scatter's adjoint (rf_core.h cic_gather_value): the field gathered at the particles, no atomics but the drop counter's.
+// particles (rf_core.h cic_axis ... cic_delta): the resident displacement buffer's fma sweep and the two cloud-in-cell operations over the
+// displaced lattice particles.  One walk per launch form (cic_global_kernel, cic_tiled_kernel) and one launcher (cic_launch) serve both; an
+// operation is a policy struct that says what happens before the particles of a brick, with one particle's eight cells, with a dropped
+// particle, and after the brick:
+//   PaintOp   the scatter into an unsigned 64-bit accumulator grid.  Integer atomics only -- vector (global) and LDS ones: integer
+//             addition is associative, so the accumulator holds the same bits for every launch shape, either form and every run.  No
+//             floating-point atomics.
+//   GatherOp  the scatter's adjoint (rf_core.h cic_gather_value): the field gathered at the particles, no atomics but the drop counter's.
 #include "rf_kernels.h"
 #include "rf_launch.h"
 
@@ -10,9 +14,73 @@ namespace {
 
 typedef unsigned long long u64;
 
-struct CicGrid {
-  int nx, ny, nz;
-  double inv_h[3];
+// Form 2's geometry: a workgroup owns a brick of BX x BY x BZ lattice cells (BZ = 64: a wave takes one z row of the brick, so its lanes
+// hit consecutive LDS and memory addresses) and a tile image of brick + halo H in LDS, CIC_TILE_CELLS elements of the operation's type.
+constexpr int CIC_BX = 8, CIC_BY = 8, CIC_BZ = 64, CIC_H = 2, CIC_NT = 512;
+constexpr int CIC_TILE_CELLS = (CIC_BX + 2 * CIC_H) * (CIC_BY + 2 * CIC_H) * (CIC_BZ + 2 * CIC_H);      // 12 x 12 x 68 = 9792 cells, 78336 bytes of 8
+static_assert(2 * CIC_TILE_CELLS * 8 <= 163840, "two workgroups per compute unit");
+// (one array for both operations, in the paint's element type: the paint indexes it as it stands -- through a pointer its LDS
+// addresses cost an instruction more per access -- and the gather views it as T)
+extern __shared__ __attribute__((aligned(16))) u64 cic_lds[];
+
+// The paint.  Global: eight no-return 64-bit integer atomics straight into A (a wave's adds to one of the eight corners are 512
+// contiguous bytes wherever the displacement varies slowly).  Tiled: LDS 64-bit integer atomics into the cleared tile; particles whose
+// eight cells do not all fall inside the tile add straight into A as the global form does.  The tile is flushed with one global atomic
+// per non-zero tile cell, indices wrapped periodically there: neighbouring bricks' halos overlap, bricks at the grid's edge are partial,
+// and on a grid smaller than the tile several tile cells alias one cell of A -- the atomic flush covers all three.
+template <typename T>
+struct PaintOp {
+  typedef u64 Cell;
+  u64* __restrict__ A;
+  __device__ void prologue(const CicTile&, const CicGrid&, int tid) const {
+    for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) cic_lds[s] = 0ull;
+  }
+  __device__ void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, const CicGrid& g) const {
+    cic_scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+  }
+  __device__ void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const CicTile& t,
+                           const CicGrid& g) const {
+    cic_scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { atomicAdd(&cic_lds[slot], (u64)w); },
+                      [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+  }
+  __device__ void dropped(long long) const {}
+  __device__ void epilogue(const CicTile& t, const CicGrid& g, int tid) const {
+    __syncthreads();                                   // (every wave's adds are in the tile)
+    __builtin_assume(tid >= 0 && tid < CIC_NT);        // (cic_tile_cell divides s: 16-bit arithmetic, as with threadIdx.x in its place)
+    for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) {
+      const u64 v = cic_lds[s];
+      if (v) atomicAdd(A + cic_tile_cell(t, s, g.nx, g.ny, g.nz), v);
+    }
+  }
+};
+
+// The gather: the field W at the particles into G, every particle writing its own element of G (read first unless `first`), coalesced.
+// Global: eight plain loads of W through the caches.  Tiled: the workgroup stages W at the tile's cells (cic_tile_cell: periodic wrap,
+// partial bricks and grids smaller than the tile are all in that map) into LDS with coalesced loads; a particle whose eight cells lie
+// inside the tile reads them there (a wave's lanes on consecutive addresses), any other reads W as the global form does.
+template <typename T>
+struct GatherOp {
+  typedef T Cell;
+  const T* __restrict__ W;
+  T* __restrict__ G;
+  double coeff;
+  int first;
+  static __device__ T* tile() { return reinterpret_cast<T*>(cic_lds); }
+  __device__ void prologue(const CicTile& t, const CicGrid& g, int tid) const {
+    __builtin_assume(tid >= 0 && tid < CIC_NT);        // (as in PaintOp::epilogue)
+    for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) tile()[s] = W[cic_tile_cell(t, s, g.nx, g.ny, g.nz)];
+  }
+  __device__ void out(long long i, double v) const { G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]); }
+  __device__ void particle(long long i, const CicAxis& x, const CicAxis& y, const CicAxis& z, const CicGrid& g) const {
+    out(i, cic_gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; }));
+  }
+  __device__ void particle(long long i, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const CicTile& t,
+                           const CicGrid& g) const {
+    out(i, cic_gather_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot) { return (double)tile()[slot]; },
+                            [&](long long cell) { return (double)W[cell]; }));
+  }
+  __device__ void dropped(long long i) const { if (first) G[i] = (T)0; }
+  __device__ void epilogue(const CicTile&, const CicGrid&, int) const {}
 };
 
 // the wave's dropped particles -> one integer atomic (nothing when the wave dropped none)
@@ -22,45 +90,33 @@ __device__ __forceinline__ void cic_count_dropped(int mine, u64* dropped) {
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(dropped, (u64)mine);
 }
 
-// Form 1, global: one lane per particle, lanes along z (a wave's adds to one of the eight corners are 512 contiguous bytes wherever the
-// displacement varies slowly), eight no-return 64-bit integer atomics straight into A.  blockDim.x is a multiple of 64.
-template <typename T>
-__global__ __launch_bounds__(256) void cic_paint_global_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
-                                                               u64* __restrict__ A, u64* __restrict__ dropped, CicGrid g, long long n) {
+// Form 1, global: one lane per particle, lanes along z, the operation's eight cells straight in memory.  blockDim.x is a multiple of 64.
+template <typename T, class Op>
+__global__ __launch_bounds__(256) void cic_global_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz, Op op,
+                                                         u64* __restrict__ dropped, CicGrid g, long long n) {
   int ndrop = 0;
   const long long step = (long long)gridDim.x * blockDim.x;
   // (every lane of a wave runs the same number of steps: the shuffles below see whole waves)
   for (long long i0 = (long long)blockIdx.x * blockDim.x; i0 < n; i0 += step) {
     const long long i = i0 + threadIdx.x;
     if (i >= n) continue;
-    const long long row = i / g.nz;
-    const int iz = (int)(i - row * g.nz), ix = (int)(row / g.ny), iy = (int)(row - (long long)ix * g.ny);
+    int ix, iy, iz;
+    cic_lattice(i, g.ny, g.nz, ix, iy, iz);
     CicAxis x, y, z;
-    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; continue; }
-    cic_scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; op.dropped(i); continue; }
+    op.particle(i, x, y, z, g);
   }
   cic_count_dropped(ndrop, dropped);
 }
 
-// Form 2, tiled: a workgroup owns a brick of BX x BY x BZ lattice cells (BZ = 64: a wave takes one z row of the brick, so its lanes hit
-// consecutive LDS and memory addresses) and accumulates with LDS 64-bit integer atomics into a tile of brick + halo H.  Particles whose
-// eight cells do not all fall inside the tile add straight into A as form 1 does.  The tile is flushed with one global atomic per
-// non-zero tile cell, indices wrapped periodically there: neighbouring bricks' halos overlap, bricks at the grid's edge are partial, and
-// on a grid smaller than the tile several tile cells alias one cell of A -- the atomic flush covers all three.
-constexpr int CIC_BX = 8, CIC_BY = 8, CIC_BZ = 64, CIC_H = 2, CIC_NT = 512;
-constexpr int CIC_TILE_CELLS = (CIC_BX + 2 * CIC_H) * (CIC_BY + 2 * CIC_H) * (CIC_BZ + 2 * CIC_H);      // 12 x 12 x 68 = 9792 cells, 78336 bytes
-static_assert(2 * CIC_TILE_CELLS * 8 <= 163840, "two workgroups per compute unit");
-
-template <typename T>
-__global__ __launch_bounds__(CIC_NT) void cic_paint_tiled_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
-                                                                 u64* __restrict__ A, u64* __restrict__ dropped, CicGrid g, int nby, int nbz) {
-  extern __shared__ __attribute__((aligned(16))) u64 cic_lds[];
+// Form 2, tiled: the workgroup of brick blockIdx.x; a wave takes one z row of the brick at a time (the trip count is the same for
+// every lane of a wave: the shuffles of cic_count_dropped see whole waves)
+template <typename T, class Op>
+__global__ __launch_bounds__(CIC_NT) void cic_tiled_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz, Op op,
+                                                           u64* __restrict__ dropped, CicGrid g, int nby, int nbz) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned b = blockIdx.x, bz = b % (unsigned)nbz, bxy = b / (unsigned)nbz, by = bxy % (unsigned)nby, bx = bxy / (unsigned)nby;
-  CicTile t;
-  t.bx = CIC_BX; t.by = CIC_BY; t.bz = CIC_BZ; t.h = CIC_H;
-  t.x0 = (int)bx * CIC_BX; t.y0 = (int)by * CIC_BY; t.z0 = (int)bz * CIC_BZ;
-  for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) cic_lds[s] = 0ull;
+  const CicTile t = cic_brick_tile(blockIdx.x, nby, nbz, CIC_BX, CIC_BY, CIC_BZ, CIC_H);
+  op.prologue(t, g, tid);
   __syncthreads();
   int ndrop = 0;
   const int iz = t.z0 + lane;
@@ -69,78 +125,10 @@ __global__ __launch_bounds__(CIC_NT) void cic_paint_tiled_kernel(const T* __rest
     if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
     const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
     CicAxis x, y, z;
-    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; continue; }
-    cic_scatter_tiled(x, y, z, lx, ly, lane, t, g.ny, g.nz,
-                      [&](int slot, uint64_t w) { atomicAdd(&cic_lds[slot], (u64)w); },
-                      [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; op.dropped(i); continue; }
+    op.particle(i, x, y, z, lx, ly, lane, t, g);
   }
-  __syncthreads();
-  for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) {
-    const u64 v = cic_lds[s];
-    if (v) atomicAdd(A + cic_tile_cell(t, s, g.nx, g.ny, g.nz), v);
-  }
-  cic_count_dropped(ndrop, dropped);
-}
-
-// ---- the gather (rf_core.h cic_gather_value): the field W at the particles into G, the adjoint of the scatter above.  No atomics but
-// the drop counter's: every particle writes its own element of G.
-// Form 1, global: one lane per particle, lanes along z, eight plain loads of W through the caches; G read (unless first) and written
-// at the particle's own index, coalesced.  blockDim.x is a multiple of 64.
-template <typename T>
-__global__ __launch_bounds__(256) void cic_gather_global_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
-                                                                const T* __restrict__ W, T* __restrict__ G, u64* __restrict__ dropped,
-                                                                CicGrid g, double coeff, int first, long long n) {
-  int ndrop = 0;
-  const long long step = (long long)gridDim.x * blockDim.x;
-  for (long long i0 = (long long)blockIdx.x * blockDim.x; i0 < n; i0 += step) {
-    const long long i = i0 + threadIdx.x;
-    if (i >= n) continue;
-    const long long row = i / g.nz;
-    const int iz = (int)(i - row * g.nz), ix = (int)(row / g.ny), iy = (int)(row - (long long)ix * g.ny);
-    CicAxis x, y, z;
-    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) {
-      ++ndrop;
-      if (first) G[i] = (T)0;
-      continue;
-    }
-    const double v = cic_gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; });
-    G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
-  }
-  cic_count_dropped(ndrop, dropped);
-}
-
-// Form 2, tiled: the paint's brick and halo.  The workgroup stages W at the tile's cells (cic_tile_cell: periodic wrap, partial bricks
-// and grids smaller than the tile are all in that map) into LDS with coalesced loads; a particle whose eight cells lie inside the tile
-// reads them there (a wave's lanes on consecutive addresses), any other reads W as form 1 does.
-extern __shared__ __attribute__((aligned(16))) unsigned char cic_gather_lds[];
-template <typename T>
-__global__ __launch_bounds__(CIC_NT) void cic_gather_tiled_kernel(const T* __restrict__ Qx, const T* __restrict__ Qy, const T* __restrict__ Qz,
-                                                                  const T* __restrict__ W, T* __restrict__ G, u64* __restrict__ dropped,
-                                                                  CicGrid g, double coeff, int first, int nby, int nbz) {
-  T* tile = reinterpret_cast<T*>(cic_gather_lds);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned b = blockIdx.x, bz = b % (unsigned)nbz, bxy = b / (unsigned)nbz, by = bxy % (unsigned)nby, bx = bxy / (unsigned)nby;
-  CicTile t;
-  t.bx = CIC_BX; t.by = CIC_BY; t.bz = CIC_BZ; t.h = CIC_H;
-  t.x0 = (int)bx * CIC_BX; t.y0 = (int)by * CIC_BY; t.z0 = (int)bz * CIC_BZ;
-  for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) tile[s] = W[cic_tile_cell(t, s, g.nx, g.ny, g.nz)];
-  __syncthreads();
-  int ndrop = 0;
-  const int iz = t.z0 + lane;
-  for (int row = wave; row < CIC_BX * CIC_BY; row += CIC_NT / 64) {
-    const int lx = row / CIC_BY, ly = row - lx * CIC_BY, ix = t.x0 + lx, iy = t.y0 + ly;
-    if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
-    const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
-    CicAxis x, y, z;
-    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) {
-      ++ndrop;
-      if (first) G[i] = (T)0;
-      continue;
-    }
-    const double v = cic_gather_tiled(x, y, z, lx, ly, lane, t, g.ny, g.nz, [&](int slot) { return (double)tile[slot]; },
-                                      [&](long long cell) { return (double)W[cell]; });
-    G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]);
-  }
+  op.epilogue(t, g, tid);
   cic_count_dropped(ndrop, dropped);
 }
 
@@ -182,47 +170,23 @@ hipError_t particles_accumulate_t(const T* W, T* Q, double coeff, int first, lon
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t cic_paint_t(int form, const T* Q, u64* A, u64* dropped, int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
+// both forms of one operation over the particles displaced by Q[3][nx][ny][nz]
+template <typename T, class Op>
+hipError_t cic_launch(int form, const T* Q, const Op& op, u64* dropped, int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
   const long long n = (long long)nx * ny * nz;
-  CicGrid g;
-  g.nx = nx; g.ny = ny; g.nz = nz;
-  for (int a = 0; a < 3; ++a) g.inv_h[a] = inv_h[a];
+  const CicGrid g = {nx, ny, nz, {inv_h[0], inv_h[1], inv_h[2]}};
   const T *Qx = Q, *Qy = Q + n, *Qz = Q + 2 * n;
   if (form == 1) {
-    hipLaunchKernelGGL(cic_paint_global_kernel<T>, dim3(sweep_grid(n, 256)), dim3(256), 0, s, Qx, Qy, Qz, A, dropped, g, n);
+    hipLaunchKernelGGL((cic_global_kernel<T, Op>), dim3(sweep_grid(n, 256)), dim3(256), 0, s, Qx, Qy, Qz, op, dropped, g, n);
     return hipGetLastError();
   }
   const long long nbx = (nx + CIC_BX - 1) / CIC_BX, nby = (ny + CIC_BY - 1) / CIC_BY, nbz = (nz + CIC_BZ - 1) / CIC_BZ;
   const long long nb = nbx * nby * nbz;
   if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
   static LdsAttrLatch latch;
-  const int lds = CIC_TILE_CELLS * 8;
-  if (hipError_t e = latch.ensure(reinterpret_cast<const void*>(&cic_paint_tiled_kernel<T>), lds)) return e;
-  hipLaunchKernelGGL(cic_paint_tiled_kernel<T>, dim3((unsigned)nb), dim3(CIC_NT), lds, s, Qx, Qy, Qz, A, dropped, g, (int)nby, (int)nbz);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t cic_gather_t(int form, const T* Q, const T* W, T* G, double coeff, int first, u64* dropped, int nx, int ny, int nz, const double* inv_h,
-                        hipStream_t s) {
-  const long long n = (long long)nx * ny * nz;
-  CicGrid g;
-  g.nx = nx; g.ny = ny; g.nz = nz;
-  for (int a = 0; a < 3; ++a) g.inv_h[a] = inv_h[a];
-  const T *Qx = Q, *Qy = Q + n, *Qz = Q + 2 * n;
-  if (form == 1) {
-    hipLaunchKernelGGL(cic_gather_global_kernel<T>, dim3(sweep_grid(n, 256)), dim3(256), 0, s, Qx, Qy, Qz, W, G, dropped, g, coeff, first, n);
-    return hipGetLastError();
-  }
-  const long long nbx = (nx + CIC_BX - 1) / CIC_BX, nby = (ny + CIC_BY - 1) / CIC_BY, nbz = (nz + CIC_BZ - 1) / CIC_BZ;
-  const long long nb = nbx * nby * nbz;
-  if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
-  static LdsAttrLatch latch;
-  const int lds = CIC_TILE_CELLS * (int)sizeof(T);            // 39 168 bytes float32, 78 336 float64: two workgroups per compute unit
-  if (hipError_t e = latch.ensure(reinterpret_cast<const void*>(&cic_gather_tiled_kernel<T>), lds)) return e;
-  hipLaunchKernelGGL(cic_gather_tiled_kernel<T>, dim3((unsigned)nb), dim3(CIC_NT), lds, s, Qx, Qy, Qz, W, G, dropped, g, coeff, first, (int)nby,
-                     (int)nbz);
+  const int lds = CIC_TILE_CELLS * (int)sizeof(typename Op::Cell);      // 78 336 bytes, the float32 gather 39 168: two workgroups per compute unit
+  if (hipError_t e = latch.ensure(reinterpret_cast<const void*>(&cic_tiled_kernel<T, Op>), lds)) return e;
+  hipLaunchKernelGGL((cic_tiled_kernel<T, Op>), dim3((unsigned)nb), dim3(CIC_NT), lds, s, Qx, Qy, Qz, op, dropped, g, (int)nby, (int)nbz);
   return hipGetLastError();
 }
 
@@ -231,8 +195,8 @@ hipError_t cic_gather_t(int form, const T* Q, const T* W, T* G, double coeff, in
 hipError_t launch_cic_gather(int f64, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
                              int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
   if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
-  return f64 ? cic_gather_t<double>(form, (const double*)Q, (const double*)W, (double*)G_slot, coeff, first, dropped, nx, ny, nz, inv_h, s)
-             : cic_gather_t<float>(form, (const float*)Q, (const float*)W, (float*)G_slot, coeff, first, dropped, nx, ny, nz, inv_h, s);
+  return f64 ? cic_launch(form, (const double*)Q, GatherOp<double>{(const double*)W, (double*)G_slot, coeff, first}, dropped, nx, ny, nz, inv_h, s)
+             : cic_launch(form, (const float*)Q, GatherOp<float>{(const float*)W, (float*)G_slot, coeff, first}, dropped, nx, ny, nz, inv_h, s);
 }
 
 hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double coeff, int first, long long n, hipStream_t s) {
@@ -243,8 +207,8 @@ hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double c
 hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
                             const double* inv_h, hipStream_t s) {
   if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
-  return f64 ? cic_paint_t<double>(form, (const double*)Q, A, dropped, nx, ny, nz, inv_h, s)
-             : cic_paint_t<float>(form, (const float*)Q, A, dropped, nx, ny, nz, inv_h, s);
+  return f64 ? cic_launch(form, (const double*)Q, PaintOp<double>{A}, dropped, nx, ny, nz, inv_h, s)
+             : cic_launch(form, (const float*)Q, PaintOp<float>{A}, dropped, nx, ny, nz, inv_h, s);
 }
 
 void cic_paint_geometry(int* brick3, int* halo) {
