@@ -247,7 +247,7 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   else if (fast_noise) fgp.noise = gp.noise;
   if (fast)
     RF_HIP(launch_col_fastgen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, fgp,
-                              kz0, (int)nzl, p->tw_x.ptr, sx, false, timed ? p->ev[5] : nullptr,
+                              kz0, (int)nzl, p->tw_x.ptr, sx, timed ? p->ev[5] : nullptr,
                               rep ? p->rank * p->nxl : 0, rep ? (p->rank + 1) * p->nxl : 1 << 30, cd.pot_target, p->fixbuf.ptr));
   else
     RF_HIP(launch_col_gen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, gp, kspace, kz0, (int)nzl, p->tw_x.ptr, sx));
@@ -1031,29 +1031,9 @@ int rf_plan_create(rf_plan** out, int nx, int ny, int nz, int dtype, int device,
   p->npartials = generic ? (gd.lz.split() ? 1024 : generic_row_blocks(dtype, gd.az, (long long)nx * ny))      // (long rows: the moments are a pass of their own, 1024 blocks)
                : nranks > 1 ? row_c2r_tiles(dtype, p->nzc, (long long)p->nxl * ny) : row_c2r_tiles(dtype, p->nzc, (long long)nx * ny);
   if (int rc = create_common(p, true)) return cleanup(rc);
-  if (!generic) {  // function attributes (dynamic LDS above 64 KB) are set here, never inside a graph capture
-    GenParams gp0; memset(&gp0, 0, sizeof(gp0)); gp0.nx = nx; gp0.ny = ny; gp0.nz = nz;
-    const long long nzc = p->nzc, nzl = p->nzl;
-    const ColGeom gx{(long long)ny * nzl, 0, (long long)ny * nzl}, gy{nzl, (long long)ny * nzl, nzl};
-    FastGenParams fp0; memset(&fp0, 0, sizeof(fp0)); fp0.nx = nx; fp0.ny = ny; fp0.nz = nz;
-    if ((e = launch_col_gen(dtype, nx, p->W.ptr, gx, (long long)ny * nzl, gp0, nullptr, 0, (int)nzl, p->tw_x.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_fastgen(dtype, nx, p->W.ptr, gx, (long long)ny * nzl, fp0, 0, (int)nzl, p->tw_x.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, ny, +1, p->W.ptr, gy, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_xpose(dtype, ny, p->W.ptr, gy, p->W.ptr, gy, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_direct(dtype, ny, p->W.ptr, gy, nullptr, 0, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain_acc(dtype, ny, p->W.ptr, gy, (long long)nx * nzl, 0, (int)nzl, nullptr, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_row_c2r_lognormal(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, 1.0, nullptr, nullptr, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
-        (yz_merged_supported(dtype, ny, (int)nzc) && (e = launch_yz_merged(dtype, ny, (int)nzc, p->W.ptr, 8, 1.0, p->tw_z.ptr, p->partials.get(), p->W.ptr, ColGeom{p->nzl, (long long)ny * p->nzl, p->nzl}, 8, p->tw_y.ptr, p->stream, true)) != hipSuccess) ||
-        (e = launch_row_c2r(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, 1.0, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
-        (e = launch_row_c2r_zscale(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, 1.0, nullptr, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
-        (e = launch_row_c2r_xgather(dtype, (int)nzc, p->W.ptr, p->W.ptr, (long long)p->nxl * ny, 1.0, 8, 8, ny, p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess ||
-        (e = launch_row_r2c(dtype, (int)nzc, p->W.ptr, (long long)p->nxl * ny, p->tw_z.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, ny, -1, p->W.ptr, gy, (long long)nx * nzl, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, nx, -1, p->W.ptr, gx, (long long)ny * nzl, p->tw_x.ptr, p->stream, true)) != hipSuccess ||
-        ((e = launch_row_c2r_gather(dtype, (int)nzc, p->W.ptr, p->W.ptr, (long long)p->nxl * ny, 1.0, (int)nzl, (long long)p->nxl * ny * nzl,
-                                                  p->tw_z.ptr, p->partials.get(), p->stream, true)) != hipSuccess))
-      return cleanup(fail(2, std::string("kernel preparation: ") + hipGetErrorString(e)));
-  }
+  // function attributes (dynamic LDS above 64 KB) are set here, never inside a graph capture
+  if (!generic && (e = prepare_packed_kernels(dtype, nx, ny, (int)p->nzc)) != hipSuccess)
+    return cleanup(fail(2, std::string("kernel preparation: ") + hipGetErrorString(e)));
   *out = p;
   return 0;
 }
@@ -1088,9 +1068,7 @@ int rf_plan_create_c2c(rf_plan** out, int nx, int ny, int nz, int dtype, int dev
     return cleanup(fail(1, "unsupported shape for a c2c plan: an axis shorter than 1024 with rows more than 4 GiB apart "
                            "(32-bit lane offsets); make that axis >= 1024 or the others smaller"));
   for (int dir = -1; dir <= 1 && !generic; dir += 2)
-    if ((e = launch_row_c2c(dtype, nz, dir, p->W.ptr, (long long)nx * ny, 1.0, p->tw_z.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, ny, dir, p->W.ptr, gy, (long long)nx * nz, p->tw_y.ptr, p->stream, true)) != hipSuccess ||
-        (e = launch_col_plain(dtype, nx, dir, p->W.ptr, gx, (long long)ny * nz, p->tw_x.ptr, p->stream, true)) != hipSuccess)
+    if ((e = prepare_c2c_kernels(dtype, nx, ny, nz, dir)) != hipSuccess)
       return cleanup(fail(2, std::string("kernel preparation: ") + hipGetErrorString(e)));
   *out = p;
   return 0;

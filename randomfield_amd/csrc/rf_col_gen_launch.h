@@ -2,12 +2,12 @@
 // compiled with the max-ILP scheduling strategy; rf_k_col_gen64.hip: float64, default strategy -- measured on MI355X: the float32
 // whole-column kernels gain 7 % from it, the float64 half-transform kernels lose 8 %)
 #pragma once
-#include "rf_kernels.h"
-#include "rf_launch.h"
+#include "rf_tile_launch.h"
 
 // (Launch structure of the kz = 0 repair, settled by measurement -- DESIGN_HISTORY.md: the tiles that hold slot kz = 0 run as a launch of
 // their own in FRONT of the lean kernel's launch over all other tiles.  One launch of the repairing kernel over all tiles, the lean
 // kernel over all tiles followed by the kz = 0 tiles again, and both kinds of tile in one grid were each measured and are gone.)
+// Which variant: rf_select.h fastgen_variant; which launches: fastgen_sequence.  This file turns both into kernels.
 
 namespace rf {
 namespace {
@@ -15,163 +15,145 @@ template <class IO, class = void> struct io_noise_src { static constexpr int val
 template <class IO> struct io_noise_src<IO, typename std::enable_if<(IO::NOISE_SRC >= 0)>::type> { static constexpr int value = IO::NOISE_SRC; };
 // runs tiles  b * tile_mul + tile_add,  b in [0, ntiles)
 template <class C, class IO>
-hipError_t launch_one(const IO& io_in, long long ncols, const cplx<typename C::T>* tw, hipStream_t s, bool prepare_only,
-                      long long ntiles_sub = -1, long long tile_mul = 1, long long tile_add = 0, int skip_period = 0) {
-  if (ncols % C::TC || io_in.g.inner <= 0 || (io_in.g.inner & (io_in.g.inner - 1))) return hipErrorInvalidValue;
-  if (!prepare_only && (!io_in.g.rows_ok(C::N / C::RL, C::NPASS) || (io_in.g.sub_shift > 0 && (1 << io_in.g.sub_shift) < C::TC))) return hipErrorInvalidValue;
-  const IO& io = io_in;
-  const long long ntiles = ntiles_sub >= 0 ? ntiles_sub : ncols / C::TC;
-  auto k = col_kernel<C, +1, IO>;
-  constexpr int lds_bytes = C::LDS_BYTES + IO::LDS_EXTRA;
-  static LdsAttrLatch latch;
-  if (hipError_t e = latch.ensure((const void*)k, lds_bytes); e != hipSuccess) return e;
-  if (prepare_only) return hipSuccess;
-  hipLaunchKernelGGL(k, dim3((unsigned)ntiles), dim3(C::NT), lds_bytes, s, io, tw, ntiles, tile_mul, tile_add, skip_period);
-  return hipGetLastError();
+hipError_t launch_col(const IO& io, long long ncols, const cplx<typename C::T>* tw, hipStream_t s, long long ntiles, long long tile_mul = 1,
+                      long long tile_add = 0, int skip_period = 0) {
+  if (ncols % C::TC || !pow2(io.g.inner)) return hipErrorInvalidValue;
+  if (!io.g.rows_ok(C::N / C::RL, C::NPASS) || (io.g.sub_shift > 0 && (1 << io.g.sub_shift) < C::TC)) return hipErrorInvalidValue;
+  return tile_launch<col_kernel<C, +1, IO>>(ntiles, C::NT, lds_of<C, IO>(), s, io, tw, ntiles, tile_mul, tile_add, skip_period);
 }
-
 // pairs of adjacent tiles, whole-line stores (rf_kernels.h colpair_kernel): runs pairs b * pair_mul + pair_add, b in [0, npairs)
 // (the float32 generation pass of length 1024 -- native generator or replayed deviates, whole grid or kz slab -- runs on tile pairs)
 template <class C, class IO>
-hipError_t launch_onepair(const IO& io_in, long long ncols, const cplx<typename C::T>* tw, hipStream_t s, bool prepare_only,
-                          long long npairs, long long pair_mul = 1, long long pair_add = 0, int skip_period = 0) {
-  if (ncols % (2 * C::TC) || io_in.g.inner <= 0 || (io_in.g.inner & (io_in.g.inner - 1))) return hipErrorInvalidValue;
-  if (!prepare_only && (!io_in.g.rows_ok(C::N / C::RL, C::NPASS) || io_in.g.sub_shift > 0 || io_in.g.inner % (2 * C::TC))) return hipErrorInvalidValue;
-  const IO& io = io_in;
-  auto k = colpair_kernel<C, +1, IO>;
-  constexpr int lds_bytes = C::LDS_BYTES + IO::LDS_EXTRA;
-  static LdsAttrLatch latch;
-  if (hipError_t e = latch.ensure((const void*)k, lds_bytes); e != hipSuccess) return e;
-  if (prepare_only) return hipSuccess;
-  if (npairs <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k, dim3((unsigned)npairs), dim3(C::NT), lds_bytes, s, io, tw, npairs, pair_mul, pair_add, skip_period);
-  return hipGetLastError();
+hipError_t launch_colpair(const IO& io, long long ncols, const cplx<typename C::T>* tw, hipStream_t s, long long npairs, long long pair_mul,
+                          long long pair_add, int skip_period) {
+  if (ncols % (2 * C::TC) || !pow2(io.g.inner)) return hipErrorInvalidValue;
+  if (!io.g.rows_ok(C::N / C::RL, C::NPASS) || io.g.sub_shift > 0 || io.g.inner % (2 * C::TC)) return hipErrorInvalidValue;
+  return tile_launch<colpair_kernel<C, +1, IO>>(npairs, C::NT, lds_of<C, IO>(), s, io, tw, npairs, pair_mul, pair_add, skip_period);
 }
-
 // the same through col2_kernel: a pass of length 2 C1::N as two C1 transforms per tile (rf_fft.h Col2); tw2 = the 2 C1::N-point table
 template <class C1, class IO>
-hipError_t launch_one2(const IO& io_in, long long ncols, const cplx<typename C1::T>* tw2, hipStream_t s, bool prepare_only,
-                       long long ntiles_sub = -1, long long tile_mul = 1, long long tile_add = 0, int skip_period = 0) {
-  if (ncols % C1::TC || io_in.g.inner <= 0 || (io_in.g.inner & (io_in.g.inner - 1))) return hipErrorInvalidValue;
-  const IO& io = io_in;
-  const long long ntiles = ntiles_sub >= 0 ? ntiles_sub : ncols / C1::TC;
-  auto k = col2_kernel<C1, +1, IO>;
-  constexpr int lds_bytes = C1::LDS_BYTES + IO::LDS_EXTRA;
-  static LdsAttrLatch latch;
-  if (hipError_t e = latch.ensure((const void*)k, lds_bytes); e != hipSuccess) return e;
-  if (prepare_only) return hipSuccess;
-  hipLaunchKernelGGL(k, dim3((unsigned)ntiles), dim3(C1::NT), lds_bytes, s, io, tw2, ntiles, tile_mul, tile_add, skip_period);
-  return hipGetLastError();
+hipError_t launch_col2(const IO& io, long long ncols, const cplx<typename C1::T>* tw2, hipStream_t s, long long ntiles, long long tile_mul,
+                       long long tile_add, int skip_period) {
+  if (ncols % C1::TC || !pow2(io.g.inner)) return hipErrorInvalidValue;
+  return tile_launch<col2_kernel<C1, +1, IO>>(ntiles, C1::NT, lds_of<C1, IO>(), s, io, tw2, ntiles, tile_mul, tile_add, skip_period);
 }
 
-// the side buffer of repaired kz = 0 slots for a FIX = 3 launch: out[iy * nx + ix], one thread per mode (rf_kernels.h fix_fill_kernel)
-template <class IOF, class CT>
-hipError_t launch_fix_fill(const IOF& iof, CT* out, hipStream_t s) {
-  const long long n = (long long)iof.gp.nx * iof.gp.ny;
-  hipLaunchKernelGGL((fix_fill_kernel<IOF, CT>), dim3((unsigned)((n + 255) / 256)), dim3(256), IOF::LDS_EXTRA, s, iof, out, iof.gp.nx, iof.gp.ny);
-  return hipGetLastError();
+// what a fast generation pass is called with ([x0, x1): the rows that are stored; fixbuf: the side buffer of repaired kz = 0 slots)
+template <typename T> struct FastArgs {
+  const FastGenParams& gp;
+  cplx<T>* W;
+  ColGeom g;
+  long long ncols;
+  int kz0, nzl;
+  const cplx<T>* tw;
+  hipStream_t s;
+  hipEvent_t after_repair;
+  int x0, x1;
+  cplx<T>*pot, *fixbuf;
+};
+template <class IO, typename T> IO make_io(const FastArgs<T>& a) {
+  IO io;
+  io.base = a.x0 > 0 ? a.W - (long long)a.x0 * a.g.row_stride : a.W;      // row x0 of the transform lands on row 0 of W
+  io.g = a.g; io.gp = a.gp; io.kz0 = a.kz0; io.nzl = a.nzl; io.rec = nullptr; io.x0 = a.x0; io.x1 = a.x1; io.pot = a.pot;
+  if constexpr (IO::FIX_MODE == 3) io.fixbuf = a.fixbuf;
+  return io;
 }
 
-// fast float32 generation + x pass of length 2 C1::N through Col2 (native generator, whole grid or kz slab; no potential store,
-// no resident deviates, no x-slab restriction: those keep the whole-column kernel)
-template <class C1, class IO0, class IO1>
-hipError_t launch_fast_one2(const FastGenParams& gp, cplx<typename C1::T>* W, ColGeom g, long long ncols, int kz0, int nzl,
-                            const cplx<typename C1::T>* tw2, hipStream_t s, bool po, hipEvent_t after_repair, cplx<typename C1::T>* fixbuf) {
-  if (nzl <= 0 || (nzl & (nzl - 1)) || ncols >= (1LL << 31) || g.needs_wide(C1::LMAX, C1::TC, (int)sizeof(cplx<typename C1::T>)) || !g.rows_ok(C1::N / C1::RL, C1::NPASS))
-    return hipErrorInvalidValue;
-  IO0 io0; io0.base = W; io0.g = g; io0.gp = gp; io0.kz0 = kz0; io0.nzl = nzl; io0.rec = nullptr; io0.pot = nullptr;
-  IO1 io1; io1.base = W; io1.g = g; io1.gp = gp; io1.kz0 = kz0; io1.nzl = nzl; io1.rec = nullptr; io1.pot = nullptr;
-  const bool split = nzl > C1::TC && nzl % C1::TC == 0;
-  const long long tiles_per_iy = nzl / C1::TC, ntiles = ncols / C1::TC;
-  // the split launch's repair kernel takes the repaired slots from the side buffer (FIX = 3, filled by fix_fill_kernel just before)
-  using IOC = typename IO1::template with_fix<3>;
-  using IOF = typename IO1::fill_io;
-  IOC ioc; ioc.base = W; ioc.g = g; ioc.gp = gp; ioc.kz0 = kz0; ioc.nzl = nzl; ioc.rec = nullptr; ioc.pot = nullptr; ioc.fixbuf = fixbuf;
-  if (po) {
-    hipError_t e = launch_one2<C1, IO0>(io0, ncols, tw2, s, true);
-    if (e == hipSuccess) e = launch_one2<C1, IOC>(ioc, ncols, tw2, s, true);
-    return e != hipSuccess ? e : launch_one2<C1, IO1>(io1, ncols, tw2, s, true);
-  }
-  if (!split) return launch_one2<C1, IO1>(io1, ncols, tw2, s, false);
-  if (kz0 != 0) return launch_one2<C1, IO0>(io0, ncols, tw2, s, false);
-  if (!fixbuf) return hipErrorInvalidValue;
-  IOF iof; iof.base = W; iof.g = g; iof.gp = gp; iof.kz0 = kz0; iof.nzl = nzl; iof.rec = nullptr; iof.pot = nullptr;
-  hipError_t e = launch_fix_fill(iof, fixbuf, s);
-  if (e == hipSuccess) e = launch_one2<C1, IOC>(ioc, ncols, tw2, s, false, ncols / nzl, tiles_per_iy, 0);
-  if (e != hipSuccess || tiles_per_iy >= (1LL << 30) || ntiles >= (1LL << 31)) return e != hipSuccess ? e : hipErrorInvalidValue;
-  if (after_repair && (e = hipEventRecord(after_repair, s)) != hipSuccess) return e;
-  return launch_one2<C1, IO0>(io0, ncols, tw2, s, false, ntiles - ntiles / tiles_per_iy, 1, 0, (int)tiles_per_iy);
-}
-
-// Fast float32 generation.  The tiles that contain the kz = 0 slot (one per iy when a tile is narrower than a
-// kz row) are run by the kernel WITH the Hermitian repair, which carries the extra register pressure only where
-// it is needed; every other tile by the kernel WITHOUT it (skip_period = tiles per iy).
-template <class C, class IO0, class IO1, class CT>
-hipError_t launch_fast_one(const FastGenParams& gp, CT* W, ColGeom g, long long ncols, int kz0, int nzl,
-                           const CT* tw, hipStream_t s, bool po, hipEvent_t after_repair, int x0, int x1, CT* fixbuf, CT* pot = nullptr) {
-  // the slab-restricted instantiations test the workgroup-uniform row offset m * L of the last pass: the slab
-  // boundaries must be multiples of L = N / (radix of the last pass)
-  if (nzl <= 0 || (nzl & (nzl - 1)) || ncols >= (1LL << 31) || g.needs_wide(C::LMAX, C::TC, (int)sizeof(CT))) return hipErrorInvalidValue;   // the IO splits a column index by shift and mask
-  if ((x0 > 0 || x1 < C::N) && (C::NPASS < 2 || x0 % (C::N / C::RL) || x1 % (C::N / C::RL))) return hipErrorInvalidValue;
-  CT* base = x0 > 0 ? W - (long long)x0 * g.row_stride : W;      // row x0 of the transform lands on row 0 of W
-  IO0 io0; io0.base = base; io0.g = g; io0.gp = gp; io0.kz0 = kz0; io0.nzl = nzl; io0.rec = nullptr; io0.x0 = x0; io0.x1 = x1;
-  io0.pot = pot;
-  IO1 io1; io1.base = base; io1.g = g; io1.gp = gp; io1.kz0 = kz0; io1.nzl = nzl; io1.rec = nullptr; io1.x0 = x0; io1.x1 = x1; io1.pot = pot;
-  const bool split = nzl > C::TC && nzl % C::TC == 0;
-  const long long tiles_per_iy = nzl / C::TC, ntiles = ncols / C::TC;
-  // the split launch's repair kernel of the long passes takes the repaired slots from the side buffer (FIX = 3); the short passes
-  // (a few tiles, one pass) keep the owning lane's own repair
-  constexpr bool side = C::N >= 512 && C::NPASS >= 2;
+// The kernels of one variant on configuration C (HALVES: C is the half-length configuration of a Col2 pass) and its launches.
+// IOT<FIX>: the variant's IO with that repair mode -- 0 none (lean), 1 the owning lane's own, 3 from the side buffer.
+template <class C, template <int> class IOT, bool HALVES>
+struct FastPassOf {
+  using T = typename C::T;
+  using IO0 = IOT<0>;
+  using IO1 = IOT<1>;
+  static constexpr FastPass pass = fast_pass_of<C>(HALVES, io_noise_src<IO0>::value);
+  static constexpr bool side = pass.side, pairs = pass.pairs;
+  // the kz = 0 launch: the repaired slots from the side buffer (FIX = 3, filled by fix_fill_kernel just before) or the owning lane's own
   using IOC = typename IO1::template with_fix<side ? 3 : 1>;
   using IOF = typename IO1::fill_io;
-  IOC ioc; ioc.base = base; ioc.g = g; ioc.gp = gp; ioc.kz0 = kz0; ioc.nzl = nzl; ioc.rec = nullptr; ioc.x0 = x0; ioc.x1 = x1; ioc.pot = pot;
-  if constexpr (side) ioc.fixbuf = fixbuf;
-  // tile pairs with whole-line stores (ColPair): the 1024-point float32 pass, every tile of a kz row in a pair of its own row
-  constexpr bool pairs = side && C::N == 1024 && sizeof(CT) == 8 && C::NPASS == 3 && (io_noise_src<IO0>::value == 0 || io_noise_src<IO0>::value == 2);
-  const bool use_pairs = pairs && split && x0 <= 0 && x1 >= C::N && tiles_per_iy % 2 == 0 && g.inner % (2 * C::TC) == 0 && g.sub_shift == 0;
-  if (po) {
-    hipError_t e = launch_one<C, IO0>(io0, ncols, tw, s, true);
-    if constexpr (pairs) {
-      if (e == hipSuccess) e = launch_onepair<C, IO0>(io0, ncols, tw, s, true, 0);
-      if (e == hipSuccess) e = launch_onepair<C, IOC>(ioc, ncols, tw, s, true, 0);
-    }
-    if (e == hipSuccess && side) e = launch_one<C, IOC>(ioc, ncols, tw, s, true);
-    return e != hipSuccess ? e : launch_one<C, IO1>(io1, ncols, tw, s, true);
+
+  template <class IO> static hipError_t one(const FastArgs<T>& a, const FastStep& st) {
+    if constexpr (HALVES) return launch_col2<C>(make_io<IO>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+    else return launch_col<C>(make_io<IO>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
   }
-  if (!split) return launch_one<C, IO1>(io1, ncols, tw, s, false);
-  if (kz0 != 0) {                                                       // only the slab that owns kz = 0 needs the repair
-    if constexpr (pairs)
-      if (use_pairs && ntiles / 2 < (1LL << 31)) return launch_onepair<C, IO0>(io0, ncols, tw, s, false, ntiles / 2);
-    return launch_one<C, IO0>(io0, ncols, tw, s, false);
-  }
-  // first the (few) tiles that hold slot kz = 0, with the repair; then every other tile without it
-  hipError_t e = hipSuccess;
-  if constexpr (side) {
-    if (!fixbuf) return hipErrorInvalidValue;
-    IOF iof; iof.base = base; iof.g = g; iof.gp = gp; iof.kz0 = kz0; iof.nzl = nzl; iof.rec = nullptr; iof.x0 = x0; iof.x1 = x1; iof.pot = pot;
-    e = launch_fix_fill(iof, fixbuf, s);
-  }
-  if constexpr (pairs) {
-    if (use_pairs) {
-      // the pair that holds the kz = 0 tile of every ky row (repair from the side buffer: only that tile's owning lanes take it), then all others
-      const long long ppi = tiles_per_iy / 2, npairs = ntiles / 2;
-      if (ppi >= (1LL << 30) || npairs >= (1LL << 31)) return hipErrorInvalidValue;
-      if (e == hipSuccess) e = launch_onepair<C, IOC>(ioc, ncols, tw, s, false, ncols / nzl, ppi, 0);
-      if (e != hipSuccess) return e;
-      if (after_repair && (e = hipEventRecord(after_repair, s)) != hipSuccess) return e;
-      if (ppi < 2) return hipSuccess;                    // (two tiles per ky row: the repair launch has covered everything)
-      return launch_onepair<C, IO0>(io0, ncols, tw, s, false, npairs - npairs / ppi, 1, 0, (int)ppi);
+  static hipError_t step(const FastArgs<T>& a, const FastStep& st) {
+    switch (st.kind) {
+      case FAST_FIX_FILL:     // one thread per mode (rf_kernels.h fix_fill_kernel): out[iy * nx + ix]
+        if constexpr (side) {
+          const long long n = (long long)a.gp.nx * a.gp.ny;
+          return tile_launch<fix_fill_kernel<IOF, cplx<T>>>((n + 255) / 256, 256, IOF::LDS_EXTRA, a.s, make_io<IOF>(a), a.fixbuf, a.gp.nx, a.gp.ny);
+        }
+        return hipErrorInvalidValue;
+      case FAST_COLPAIR:
+        if constexpr (pairs) {
+          if (st.io == FAST_IO_LEAN) return launch_colpair<C>(make_io<IO0>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+          if (st.io == FAST_IO_FIRST) return launch_colpair<C>(make_io<IOC>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+        }
+        return hipErrorInvalidValue;
+      default:
+        return st.io == FAST_IO_LEAN ? one<IO0>(a, st) : st.io == FAST_IO_REPAIR ? one<IO1>(a, st) : one<IOC>(a, st);
     }
   }
-  if (e == hipSuccess) e = launch_one<C, IOC>(ioc, ncols, tw, s, false, ncols / nzl, tiles_per_iy, 0);
-  if (e != hipSuccess || tiles_per_iy >= (1LL << 30) || ntiles >= (1LL << 31)) return e != hipSuccess ? e : hipErrorInvalidValue;
-  if (after_repair && (e = hipEventRecord(after_repair, s)) != hipSuccess) return e;
-  return launch_one<C, IO0>(io0, ncols, tw, s, false, ntiles - ntiles / tiles_per_iy, 1, 0, (int)tiles_per_iy);
-}
+  static hipError_t launch(const FastArgs<T>& a) {
+    if (!pow2(a.nzl) || a.ncols >= (1LL << 31) || a.g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) return hipErrorInvalidValue;   // the IO splits a column index by shift and mask
+    if (HALVES && !a.g.rows_ok(C::N / C::RL, C::NPASS)) return hipErrorInvalidValue;
+    // the slab-restricted instantiations test the workgroup-uniform row offset m * L of the last pass: the slab boundaries must be
+    // multiples of L = N / (radix of the last pass)
+    const bool full_rows = a.x0 <= 0 && a.x1 >= (HALVES ? 2 : 1) * C::N;
+    if (!full_rows && (HALVES || C::NPASS < 2 || a.x0 % (C::N / C::RL) || a.x1 % (C::N / C::RL))) return hipErrorInvalidValue;
+    const FastSequence q = fastgen_sequence(pass, a.nzl, a.ncols, a.kz0, full_rows, a.g, a.fixbuf != nullptr);
+    if (!q.valid) return hipErrorInvalidValue;
+    for (int i = 0; i < q.n; ++i) {
+      if (hipError_t e = step(a, q.step[i]); e != hipSuccess) return e;
+      if (q.step[i].record_after && a.after_repair)
+        if (hipError_t e = hipEventRecord(a.after_repair, a.s); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  static void prepare(Prepare& p) {
+    if constexpr (HALVES) {
+      p.kernel<col2_kernel<C, +1, IO0>>(lds_of<C, IO0>());
+      p.kernel<col2_kernel<C, +1, IOC>>(lds_of<C, IOC>());
+      p.kernel<col2_kernel<C, +1, IO1>>(lds_of<C, IO1>());
+    } else {
+      p.kernel<col_kernel<C, +1, IO0>>(lds_of<C, IO0>());
+      if constexpr (pairs) {
+        p.kernel<colpair_kernel<C, +1, IO0>>(lds_of<C, IO0>());
+        p.kernel<colpair_kernel<C, +1, IOC>>(lds_of<C, IOC>());
+      }
+      p.kernel<col_kernel<C, +1, IOC>>(lds_of<C, IOC>());
+      p.kernel<col_kernel<C, +1, IO1>>(lds_of<C, IO1>());
+    }
+  }
+};
+
+// One dtype's fast generation pass: IOV<V, FIX> = the IO type of list entry V (rf_select.h FastListOf<T>).  `launch` indexes the list by
+// the variant chosen, `prepare` walks it.
+template <typename T, template <class, int> class IOV>
+struct FastGen {
+  static constexpr int NH = fastgen_halves_length(sizeof(T) == 8);      // the halves form: Col2 on the configuration of half that length
+  using CHalf = typename GenSel<T, NH / 2>::type;
+  template <class V> struct Bind { template <int FIX> using IO = typename IOV<V, FIX>::type; };
+  // f(the FastPassOf of entry V at length N); `otherwise` where V has no kernel at N
+  template <class V, class R, class F> static R at(int N, R otherwise, F&& f) {
+    if constexpr (V::halves) return N == NH ? f(Cfg<FastPassOf<CHalf, Bind<V>::template IO, true>>{}) : otherwise;
+    else return for_col_size(N, otherwise, [&](auto n) { return f(Cfg<FastPassOf<typename GenSel<T, decltype(n)::value>::type, Bind<V>::template IO, false>>{}); });
+  }
+  static hipError_t launch(int N, const FastVariant& v, const FastArgs<T>& a) {
+    return with_fast_variant(FastListOf<T>{}, v, hipErrorInvalidValue, [&](auto e) {
+      return at<decltype(e)>(N, hipErrorInvalidValue, [&](auto k) { return decltype(k)::type::launch(a); });
+    });
+  }
+  static hipError_t prepare(int N) {
+    Prepare p;
+    for_each_fast_variant(FastListOf<T>{}, 0, [&](auto e) { return at<decltype(e)>(N, 0, [&](auto k) { decltype(k)::type::prepare(p); return 0; }); });
+    return p.e;
+  }
+};
 
 }  // namespace
 
-// the float64 branches of launch_col_fastgen (rf_k_col_gen64.hip)
-hipError_t launch_col_fastgen64(int N, void* W, ColGeom g, long long ncols, const FastGenParams& gp, int kz0, int nzl,
-                                const void* tw, hipStream_t s, bool po, hipEvent_t after_repair, int x0, int x1, void* pot, void* fixbuf);
+// the float64 half of launch_col_fastgen (rf_k_col_gen64.hip)
+hipError_t launch_col_fastgen64(int N, const FastVariant& v, void* W, ColGeom g, long long ncols, const FastGenParams& gp, int kz0, int nzl, const void* tw,
+                                hipStream_t s, hipEvent_t after_repair, int x0, int x1, void* pot, void* fixbuf);
 }  // namespace rf

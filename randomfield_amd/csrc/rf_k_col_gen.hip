@@ -4,165 +4,86 @@
 
 namespace rf {
 namespace {
-template <typename T>
-hipError_t launch_t(int N, cplx<T>* W, ColGeom g, long long ncols, const GenParams& gp, const cplx<T>* kspace,
-                    int kz0, int nzl, const cplx<T>* tw, hipStream_t s, bool po) {
-  GenColIO<T> io; io.base = W; io.g = g; io.gp = gp; io.kspace = kspace; io.kz0 = kz0; io.nzl = nzl;
-  switch (N) {
-#define X(NN)                                                                                                    \
-  case NN: {                                                                                                     \
-    using C = typename GenSel<T, NN>::type;                                                                      \
-    if constexpr (NN == 2048 && sizeof(T) == 8) {               /* 64-bit lane offsets: float64, length 2048 */ \
-      if (po || g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) {                                            \
-        GenColIO<T, true> iow; iow.base = W; iow.g = g; iow.gp = gp; iow.kspace = kspace; iow.kz0 = kz0; iow.nzl = nzl; \
-        hipError_t e = launch_one<C, GenColIO<T, true>>(iow, ncols, tw, s, po);                                  \
-        if (!po || e != hipSuccess) return e;                                                                    \
-      }                                                                                                          \
-    } else if (g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) {                                             \
-      return hipErrorInvalidValue;                                                                               \
-    }                                                                                                            \
-    return launch_one<C, GenColIO<T>>(io, ncols, tw, s, po);                                                     \
-  }
-    RF_COL_SIZES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+template <class V, int FIX> struct FastIo32 { using type = FastGenColIOT<FIX, V::slab, V::pot, V::src, V::halves ? 2 : 1>; };
+using Fast32 = FastGen<float, FastIo32>;
+
+template <typename T, bool WIDE> GenColIO<T, WIDE> gen_io(cplx<T>* W, ColGeom g, const GenParams& gp, const cplx<T>* kspace, int kz0, int nzl) {
+  GenColIO<T, WIDE> io; io.base = W; io.g = g; io.gp = gp; io.kspace = kspace; io.kz0 = kz0; io.nzl = nzl;
+  return io;
 }
+// the exact pass has 64-bit lane offsets where a packed plan can need them: float64, length 2048
+template <typename T, int NN> constexpr bool gen_has_wide = NN == 2048 && sizeof(T) == 8;
 }  // namespace
 
+// x pass fused with the fast native generation: the variant by rf_select.h fastgen_variant, float32 here and float64 in rf_k_col_gen64.hip
 hipError_t launch_col_fastgen(int f64, int N, void* W, ColGeom g, long long ncols, const FastGenParams& gp, int kz0, int nzl,
-                              const void* tw, hipStream_t s, bool po, hipEvent_t after_repair, int x0, int x1, void* pot, void* fixbuf) {
-  if (!col_fastgen_supported(f64, N)) return po ? hipSuccess : hipErrorInvalidValue;    // the caller keeps the exact kernel
-  if (f64) return launch_col_fastgen64(N, W, g, ncols, gp, kz0, nzl, tw, s, po, after_repair, x0, x1, pot, fixbuf);
-  const bool slab = x0 > 0 || x1 < N;          // replicated-generation mode: the SLAB instantiations guard their stores
-  if (gp.emit_potential || po) {               // POT = 2: the pass transforms pscale * delta(k) / k^2 (rf_realise_scaled_potential)
-    if (gp.emit_potential && (slab || pot || gp.noise)) return hipErrorInvalidValue;
-    if (gp.noise32 || po)                      // ... of the replayed deviates (float32 pairs in the replay's runs)
-      switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0, 2, 2>, FastGenColIOT<1, 0, 2, 2>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf); if (!po || e != hipSuccess) return e; break; }
-        RF_COL_SIZES(X)
-#undef X
-        default: return hipErrorInvalidValue;
-      }
-    if (RF_COL2_2048 && N == 2048) {
-      using C1 = GenSel<float, 1024>::type;
-      hipError_t e = launch_fast_one2<C1, FastGenColIOT<0, 0, 2, 0, 2>, FastGenColIOT<1, 0, 2, 0, 2>>(
-          gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, (cplx<float>*)fixbuf);
-      if (!po || e != hipSuccess) return e;
-    }
-    switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0, 2>, FastGenColIOT<1, 0, 2>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf); if (!po || e != hipSuccess) return e; break; }
-      RF_COL_SIZES(X)
-#undef X
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (gp.noise || po) {                        // resident float64 deviates (rng='reference') through the fast float32 sigma path
-    if (gp.noise && (slab || pot)) return hipErrorInvalidValue;
-    switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0, 0, 1>, FastGenColIOT<1, 0, 0, 1>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf); if (!po || e != hipSuccess) return e; break; }
-      RF_COL_SIZES(X)
-#undef X
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (gp.noise32 || po) {                      // resident float32 deviates, without / with the potential store
-    if (gp.noise32 && slab) return hipErrorInvalidValue;
-    // (the same pass as two 512-point transforms per tile, as the in-place y pass runs: measured 2.69 against 2.47 ms per 1024^3, not kept)
-    if (!pot || po)
-      switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0, 0, 2>, FastGenColIOT<1, 0, 0, 2>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf); if (!po || e != hipSuccess) return e; break; }
-        RF_COL_SIZES(X)
-#undef X
-        default: return hipErrorInvalidValue;
-      }
-    if (pot || po)
-      switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0, 1, 2>, FastGenColIOT<1, 0, 1, 2>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf, (cplx<float>*)pot); if (!po || e != hipSuccess) return e; break; }
-        RF_COL_SIZES(X)
-#undef X
-        default: return hipErrorInvalidValue;
-      }
-  }
-  if (pot || po) {                             // generation + potential store (save_potential=True), whole grid
-    if (slab && pot) return hipErrorInvalidValue;
-    switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0, 1>, FastGenColIOT<1, 0, 1>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf, (cplx<float>*)pot); if (!po || e != hipSuccess) return e; break; }
-      RF_COL_SIZES(X)
-#undef X
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (slab || po) {
-    switch (N) {
-#define X(NN) case NN: { hipError_t e = launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 1>, FastGenColIOT<1, 1>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf); if (!po || e != hipSuccess) return e; break; }
-      RF_COL_SIZES(X)
-#undef X
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (RF_COL2_2048 && N == 2048 && (!slab || po)) {
-    using C1 = GenSel<float, 1024>::type;
-    hipError_t e = launch_fast_one2<C1, FastGenColIOT<0, 0, 0, 0, 2>, FastGenColIOT<1, 0, 0, 0, 2>>(
-        gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, (cplx<float>*)fixbuf);
-    if (!po || e != hipSuccess) return e;
-  }
-  switch (N) {
-#define X(NN) case NN: return launch_fast_one<typename GenSel<float, NN>::type, FastGenColIOT<0, 0>, FastGenColIOT<1, 0>, cplx<float>>(gp, (cplx<float>*)W, g, ncols, kz0, nzl, (const cplx<float>*)tw, s, po, after_repair, x0, x1, (cplx<float>*)fixbuf);
-    RF_COL_SIZES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+                              const void* tw, hipStream_t s, hipEvent_t after_repair, int x0, int x1, void* pot, void* fixbuf) {
+  const bool slab = x0 > 0 || x1 < N;          // replicated-generation mode
+  const FastVariant v = fastgen_variant(f64, N, gp.emit_potential != 0, gp.noise != nullptr, gp.noise32 != nullptr, pot != nullptr, slab);
+  if (!v.valid) return hipErrorInvalidValue;
+  if (f64) return launch_col_fastgen64(N, v, W, g, ncols, gp, kz0, nzl, tw, s, after_repair, x0, x1, pot, fixbuf);
+  using R = Real<float>;
+  return Fast32::launch(N, v, FastArgs<float>{gp, R::p(W), g, ncols, kz0, nzl, R::p(tw), s, after_repair, x0, x1, R::p(pot), R::p(fixbuf)});
 }
 
 int col_gen_tile_cols(int f64, int N) {
-  switch (N) {
-#define X(NN) case NN: return f64 ? GenSel<double, NN>::type::TC : GenSel<float, NN>::type::TC;
-    RF_COL_SIZES(X)
-#undef X
-    default: return 0;
-  }
+  return with_real(f64, [&](auto r) {
+    return for_col_size(N, 0, [&](auto n) { return (int)GenSel<typename decltype(r)::type, decltype(n)::value>::type::TC; });
+  });
 }
 
 // rows of x per block of the transposed intermediate (rf_fft.h xpose_store_geom): `want` if the last pass's uniform row
 // offsets (multiples of N / RL) are whole blocks, else N (no blocking)
 int col_gen_row_block(int f64, int N, int want) {
   if (want <= 0 || want >= N || (want & (want - 1))) return N;
-  switch (N) {
-#define X(NN) case NN: { using C = GenSel<float, NN>::type; using D = GenSel<double, NN>::type;                              \
-    const int np = f64 ? D::NPASS : C::NPASS, L = f64 ? NN / D::RL : NN / C::RL; return (np >= 2 && L % want == 0) ? want : N; }
-    RF_COL_SIZES(X)
-#undef X
-    default: return N;
-  }
+  return with_real(f64, [&](auto r) {
+    return for_col_size(N, N, [&](auto n) {
+      using C = typename GenSel<typename decltype(r)::type, decltype(n)::value>::type;
+      return (C::NPASS >= 2 && (C::N / C::RL) % want == 0) ? want : N;
+    });
+  });
 }
 
 // does the fast-generation x pass of this length fit a CU's LDS (tile + twiddles + the generation tables)?
-bool col_fastgen_supported(int f64, int N) {
-  switch (N) {
-#define X(NN) case NN: return f64 ? GenSel<double, NN>::type::LDS_BYTES + FastGenColIO64<1, 0>::LDS_EXTRA <= 160 * 1024 \
-                                  : GenSel<float, NN>::type::LDS_BYTES + FastGenColIOT<1, 0>::LDS_EXTRA <= 160 * 1024;
-    RF_COL_SIZES(X)
-#undef X
-    default: return false;
-  }
-}
+bool col_fastgen_supported(int f64, int N) { return fastgen_supported(f64, N); }
 
 // replicated-generation mode stores rows [rank N/P, (rank+1) N/P) only and tests the row offset m * L of the last pass:
 // available when the x pass has an LDS stage and N/P is a multiple of L = N / (radix of the last pass)
 bool col_replicate_supported(int f64, int N, int nranks) {
   if (!col_fastgen_supported(f64, N) || nranks < 1 || N % nranks) return false;
-  switch (N) {
-#define X(NN) case NN: { using C = GenSel<float, NN>::type; return C::NPASS >= 2 && (NN / nranks) % (NN / C::RL) == 0; }
-    RF_COL_SIZES(X)
-#undef X
-    default: return false;
-  }
+  return for_col_size(N, false, [&](auto n) { using C = typename GenSel<float, decltype(n)::value>::type; return C::NPASS >= 2 && (C::N / nranks) % (C::N / C::RL) == 0; });
 }
 
+// x pass of c2r fused with generation (kspace == nullptr) or reading an API-layout k array: the exact dtype chain
 hipError_t launch_col_gen(int f64, int N, void* W, ColGeom g, long long ncols, const GenParams& gp,
-                          const void* kspace, int kz0, int nzl, const void* tw, hipStream_t s, bool po) {
-  if (f64) return launch_t<double>(N, (cplx<double>*)W, g, ncols, gp, (const cplx<double>*)kspace, kz0, nzl, (const cplx<double>*)tw, s, po);
-  return launch_t<float>(N, (cplx<float>*)W, g, ncols, gp, (const cplx<float>*)kspace, kz0, nzl, (const cplx<float>*)tw, s, po);
+                          const void* kspace, int kz0, int nzl, const void* tw, hipStream_t s) {
+  return with_real(f64, [&](auto r) {
+    using R = decltype(r); using T = typename R::type;
+    return for_col_size(N, hipErrorInvalidValue, [&](auto n) {
+      constexpr int NN = decltype(n)::value;
+      using C = typename GenSel<T, NN>::type;
+      if (g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) {
+        if constexpr (gen_has_wide<T, NN>) return launch_col<C>(gen_io<T, true>(R::p(W), g, gp, R::p(kspace), kz0, nzl), ncols, R::p(tw), s, ncols / C::TC);
+        return hipErrorInvalidValue;
+      }
+      return launch_col<C>(gen_io<T, false>(R::p(W), g, gp, R::p(kspace), kz0, nzl), ncols, R::p(tw), s, ncols / C::TC);
+    });
+  });
+}
+
+hipError_t prepare_col_gen(int f64, int N) {
+  Prepare p;
+  with_real(f64, [&](auto r) {
+    using T = typename decltype(r)::type;
+    return for_col_size(N, 0, [&](auto n) {
+      constexpr int NN = decltype(n)::value;
+      using C = typename GenSel<T, NN>::type;
+      if constexpr (gen_has_wide<T, NN>) p.kernel<col_kernel<C, +1, GenColIO<T, true>>>(lds_of<C, GenColIO<T, true>>());
+      p.kernel<col_kernel<C, +1, GenColIO<T>>>(lds_of<C, GenColIO<T>>());
+      return 0;
+    });
+  });
+  if (p.e != hipSuccess || !fastgen_supported(f64, N)) return p.e;
+  return f64 ? prepare_col_fastgen64(N) : Fast32::prepare(N);
 }
 }  // namespace rf

@@ -7,8 +7,7 @@
 // on neither.  So the tiles of both go into one grid, the z tiles first: the hardware hands out workgroups in order, and the y tiles of
 // the next slab start on the CUs the draining z pass leaves free.  No flags, no spinning: the two halves are independent.
 // Both bodies are the product kernels' own (rf_kernels.h row_c2r_body / col2_body): same arithmetic, same field bit for bit.
-#include "rf_kernels.h"
-#include "rf_launch.h"
+#include "rf_tile_launch.h"
 
 namespace rf {
 namespace {
@@ -16,9 +15,9 @@ namespace {
 // the y half's tile body: the in-place pass as two half-length transforms per tile (Col2)
 template <class C1> struct YHalves {
   using IO = Pair2ColIO<float>;
-  static constexpr int NT = C1::NT, TC = C1::TC, LMAX = C1::LMAX, LDS = C1::LDS_BYTES + IO::LDS_EXTRA;
+  static constexpr int NT = C1::NT, TC = C1::TC, LDS = C1::LDS_BYTES + IO::LDS_EXTRA;
   static IO make(void* W, ColGeom g) { IO io; io.base = (cplx<float>*)W; io.g = g; io.gin = g; io.gin.row_stride = 2 * g.row_stride; io.par_off = g.row_stride; return io; }
-  static bool addressable(ColGeom g) { ColGeom gin = g; gin.row_stride = 2 * g.row_stride; return !gin.needs_wide(LMAX, TC, 8) && !g.needs_wide(LMAX, TC, 8); }
+  static bool fits(ColGeom g) { return halves_fit<C1>(g); }       // (the in-place pass's own test: rf_select.h)
   __device__ static void run(IO& io, const cplx<float>* tw, long long tile, char* smem) { col2_body<C1, +1, IO>(io, tw, tile, smem); }
 };
 
@@ -44,28 +43,27 @@ __global__ __launch_bounds__((CR::NT > YB::NT ? CR::NT : YB::NT)) void yz_merged
 
 template <class CR, class YB>
 bool fits(ColGeom gy, long long nrows, long long ncols) {
-  if (!YB::addressable(gy) || gy.row_shift < 30 || gy.hi_shift < 62 || gy.sub_shift != 0) return false;
+  if (!YB::fits(gy)) return false;
   const long long nz_tiles = (nrows + CR::NRT - 1) / CR::NRT;
-  return ncols % YB::TC == 0 && nz_tiles % 8 == 0 && nz_tiles + ncols / YB::TC <= 0x7fffffffLL && gy.inner > 0 && (gy.inner & (gy.inner - 1)) == 0;
+  return ncols % YB::TC == 0 && nz_tiles % 8 == 0 && nz_tiles + ncols / YB::TC <= 0x7fffffffLL && pow2(gy.inner);
 }
 
-template <class CR, class YB>
-hipError_t launch_merged(void* Wz, long long nrows, double scale, const void* twz, double* partials, void* Wy, ColGeom gy, long long ncols,
-                         const void* twy, hipStream_t s, bool po) {
+template <class CR, class YB> struct Merged {
   using T = typename CR::T;
   using RIO = PlainRowIO<T>;
+  static constexpr auto kernel = yz_merged_kernel<CR, RIO, YB>;
+  static constexpr int lds = CR::LDS_BYTES > YB::LDS ? CR::LDS_BYTES : YB::LDS, nt = CR::NT > YB::NT ? CR::NT : YB::NT;
+};
+template <class CR, class YB>
+hipError_t launch_merged(void* Wz, long long nrows, double scale, const void* twz, double* partials, void* Wy, ColGeom gy, long long ncols,
+                         const void* twy, hipStream_t s) {
+  using K = Merged<CR, YB>;
+  using T = typename K::T;
   const long long nz_tiles = (nrows + CR::NRT - 1) / CR::NRT, ny_tiles = ncols / YB::TC;
-  if (!po && !fits<CR, YB>(gy, nrows, ncols)) return hipErrorInvalidValue;
-  RIO rio; rio.base = (cplx<T>*)Wz; rio.scale = (T)scale; rio.M_of = CR::M;
-  typename YB::IO cio = YB::make(Wy, gy);
-  auto k = yz_merged_kernel<CR, RIO, YB>;
-  constexpr int lds_z = CR::LDS_BYTES, lds = lds_z > YB::LDS ? lds_z : YB::LDS, nt = CR::NT > YB::NT ? CR::NT : YB::NT;
-  static LdsAttrLatch latch;
-  if (hipError_t e = latch.ensure((const void*)k, lds); e != hipSuccess) return e;
-  if (po) return hipSuccess;
-  hipLaunchKernelGGL(k, dim3((unsigned)(nz_tiles + ny_tiles)), dim3(nt), lds, s, rio, (const cplx<T>*)twz, nrows, partials, (unsigned)nz_tiles,
-                     cio, (const cplx<T>*)twy, ny_tiles);
-  return hipGetLastError();
+  if (!fits<CR, YB>(gy, nrows, ncols)) return hipErrorInvalidValue;
+  typename K::RIO rio; rio.base = (cplx<T>*)Wz; rio.scale = (T)scale; rio.M_of = CR::M;
+  return tile_launch<K::kernel>(nz_tiles + ny_tiles, K::nt, K::lds, s, rio, (const cplx<T>*)twz, nrows, partials, (unsigned)nz_tiles, YB::make(Wy, gy),
+                                (const cplx<T>*)twy, ny_tiles);
 }
 
 // the (ny, nz / 2) pairs that are served, float32: the y pass's product kernel for that length next to the z pass's
@@ -83,7 +81,7 @@ using Y1024 = YHalves<PairSel1024::type>;
 // which (ny, nz / 2) the merged launch serves: float32, the in-place y pass of length 1024 as two 512-point halves (256 threads) next to
 // the 256-thread z pass of rows of 512 complex -- the 1024^3 pipeline
 bool yz_merged_supported(int f64, int ny, int M) {
-  if (f64 || !RF_Y_COL2_1024 || !RF_COL2_2048) return false;
+  if (col_halves(f64, ny) != HALVES_OF_1024 || !RF_COL2_2048) return false;      // (the y half IS the in-place pass's halves form)
 #define X(NY, MM, YB) if (ny == NY && M == MM) return true;
   RF_YZ_PAIRS(X)
 #undef X
@@ -101,11 +99,40 @@ bool yz_merged_fits(int f64, int ny, int M, ColGeom gy, long long nrows, long lo
 }
 
 hipError_t launch_yz_merged(int f64, int ny, int M, void* Wz, long long nrows, double scale, const void* twz, double* partials, void* Wy, ColGeom gy,
-                            long long ncols, const void* twy, hipStream_t s, bool po) {
+                            long long ncols, const void* twy, hipStream_t s) {
   if (!yz_merged_supported(f64, ny, M)) return hipErrorInvalidValue;
-#define X(NY, MM, YB) if (ny == NY && M == MM) return launch_merged<ZRows<MM>, YB>(Wz, nrows, scale, twz, partials, Wy, gy, ncols, twy, s, po);
+#define X(NY, MM, YB) if (ny == NY && M == MM) return launch_merged<ZRows<MM>, YB>(Wz, nrows, scale, twz, partials, Wy, gy, ncols, twy, s);
   RF_YZ_PAIRS(X)
 #undef X
   return hipErrorInvalidValue;
+}
+
+hipError_t prepare_yz_merged(int f64, int ny, int M) {
+  if (!yz_merged_supported(f64, ny, M)) return hipSuccess;
+#define X(NY, MM, YB) if (ny == NY && M == MM) return tile_prepare<Merged<ZRows<MM>, YB>::kernel>(Merged<ZRows<MM>, YB>::lds);
+  RF_YZ_PAIRS(X)
+#undef X
+  return hipSuccess;
+}
+
+// Plan creation: the function attribute of every tiled kernel a plan of this dtype and these axis lengths can launch, family by family.
+// A packed plan: the generating x pass; the y pass in place (both directions), out of place, accumulating and direct; every z pass;
+// the forward x pass.
+hipError_t prepare_packed_kernels(int f64, int nx, int ny, int nzc) {
+  hipError_t e;
+  if ((e = prepare_col_gen(f64, nx)) != hipSuccess || (e = prepare_col_plain(f64, ny, +1, true)) != hipSuccess ||
+      (e = prepare_col_direct(f64, ny)) != hipSuccess || (e = prepare_yz_merged(f64, ny, nzc)) != hipSuccess ||
+      (e = prepare_rows(f64, nzc)) != hipSuccess || (e = prepare_col_plain(f64, ny, -1, false)) != hipSuccess ||
+      (e = prepare_col_plain(f64, nx, -1, false)) != hipSuccess)
+    return e;
+  return hipSuccess;
+}
+// An unpacked c2c plan of one direction: its three in-place passes.
+hipError_t prepare_c2c_kernels(int f64, int nx, int ny, int nz, int dir) {
+  hipError_t e;
+  if ((e = prepare_row_c2c(f64, nz, dir)) != hipSuccess || (e = prepare_col_plain(f64, ny, dir, false)) != hipSuccess ||
+      (e = prepare_col_plain(f64, nx, dir, false)) != hipSuccess)
+    return e;
+  return hipSuccess;
 }
 }  // namespace rf

@@ -37,27 +37,29 @@ inline int device_cu_count() {
   return v;
 }
 
+// Function attributes (dynamic LDS above 64 KB) of every tiled kernel a plan can launch: called at plan creation, never inside a graph
+// capture.  A packed plan of axis lengths (nx, ny, nz/2 = nzc); an unpacked c2c plan in direction dir (rf_k_yz.hip).
+hipError_t prepare_packed_kernels(int f64, int nx, int ny, int nzc);
+hipError_t prepare_c2c_kernels(int f64, int nx, int ny, int nz, int dir);
 // strided FFT pass in place (y pass of c2r; x/y passes of r2c). dir = +1 inverse, -1 forward.
-// prepare_only = true sets the kernel's function attributes (dynamic LDS > 64 KB) without launching
 hipError_t launch_col_plain(int f64, int N, int dir, void* base, ColGeom g, long long ncols, const void* tw,
-                            hipStream_t s, bool prepare_only = false);
+                            hipStream_t s);
 // inverse strided pass out of place: reads src through geometry gs, writes dst through gd (the y pass of the c2r transform
 // when the x pass left a transposed intermediate: DESIGN.md section 3.8)
 hipError_t launch_col_xpose(int f64, int N, const void* src, ColGeom gs, void* dst, ColGeom gd, long long ncols, const void* tw,
-                            hipStream_t s, bool prepare_only = false);
+                            hipStream_t s);
 // the inverse pass out of place with every output tile stored through tab[ix >> dest_shift] instead of `src`'s own base (device table of
 // per-destination base pointers; ix = the tile's index of the slow column axis: rf_fft.h DirectColIO) -- the y pass of a kz-slab rank
 // writing straight into the receive buffers of the exchange
 bool col_direct_supported(int f64, int N, long long inner);
 hipError_t launch_col_direct(int f64, int N, const void* src, ColGeom g, void* const* tab, int dest_shift, long long ncols, const void* tw,
-                             hipStream_t s, bool prepare_only = false);
+                             hipStream_t s);
 int col_gen_tile_cols(int f64, int N);   // tile width of the generation-fused x pass of length N
 int col_gen_row_block(int f64, int N, int want);   // x rows per block of the transposed intermediate: `want`, or N when the pass cannot block
 // x pass of c2r fused with generation (kspace == nullptr) or reading an API-layout k array
 // [kz0, kz0+nzl) is the slab of packed kz planes this rank owns (0, nz/2 on one GPU)
 hipError_t launch_col_gen(int f64, int N, void* W, ColGeom g, long long ncols, const GenParams& gp,
-                          const void* kspace, int kz0, int nzl, const void* tw, hipStream_t s,
-                          bool prepare_only = false);
+                          const void* kspace, int kz0, int nzl, const void* tw, hipStream_t s);
 // x pass fused with the fast native generation (float32 arithmetic; float64 plans widen the result)
 // (when the kz = 0 tiles run as a separate repairing launch first, `after_repair` is recorded between the two)
 bool col_fastgen_supported(int f64, int N);   // false when tile + twiddles + generation tables exceed a CU's LDS (float64, N = 2048)
@@ -65,7 +67,7 @@ bool col_replicate_supported(int f64, int N, int nranks);   // can the x pass of
 // [x0, x1): rows that are stored (replicated-generation mode: W is then the local x slab, row x0 at its start);
 // the default keeps every row.
 hipError_t launch_col_fastgen(int f64, int N, void* W, ColGeom g, long long ncols, const FastGenParams& gp, int kz0, int nzl,
-                              const void* tw, hipStream_t s, bool prepare_only = false, hipEvent_t after_repair = nullptr,
+                              const void* tw, hipStream_t s, hipEvent_t after_repair = nullptr,
                               int x0 = 0, int x1 = 1 << 30, void* pot = nullptr, void* fixbuf = nullptr);
 // (fixbuf: nx * ny complex of the plan's dtype -- the side buffer of repaired kz = 0 slots the pass fills and reads when it runs the
 // kz = 0 tiles as a launch of their own: rf_kernels.h fix_fill_kernel; required for N >= 512 on the rank that owns kz = 0)
@@ -77,39 +79,36 @@ int col_tile_cols(int f64, int N);   // tile width (columns) of the strided pass
 bool yz_merged_supported(int f64, int ny, int M);
 bool yz_merged_fits(int f64, int ny, int M, ColGeom gy, long long nrows, long long ncols);
 hipError_t launch_yz_merged(int f64, int ny, int M, void* Wz, long long nrows, double scale, const void* twz, double* partials, void* Wy, ColGeom gy,
-                            long long ncols, const void* twy, hipStream_t s, bool prepare_only = false);
+                            long long ncols, const void* twy, hipStream_t s);
 hipError_t launch_row_c2r(int f64, int M, void* W, long long nrows, double scale, const void* tw,
-                          double* partials, hipStream_t s, bool prepare_only = false);
+                          double* partials, hipStream_t s);
 // z pass of a slab-decomposed plan: rows gathered from P received blocks of nzl kz planes each
 hipError_t launch_row_c2r_gather(int f64, int M, const void* src, void* dst, long long nrows, double scale, int nzl,
-                                 long long seg_stride, const void* tw, double* partials, hipStream_t s,
-                                 bool prepare_only = false);
+                                 long long seg_stride, const void* tw, double* partials, hipStream_t s);
 // z pass reading the blocked intermediate X [x block][kz tile][ny][rb][tc] (rf_fft.h xblock_*_geom) of the slab at `src` and writing
 // the dense rows of W at `dst`; nrows = (x planes of the slab) * ny, in the order (x block, iy, row of the block)
 hipError_t launch_row_c2r_xgather(int f64, int M, const void* src, void* dst, long long nrows, double scale, int tc, int rb, int ny,
-                                  const void* tw, double* partials, hipStream_t s, bool prepare_only = false);
+                                  const void* tw, double* partials, hipStream_t s);
 bool row_c2r_xgather_ok(int f64, int M, int tc, int rb);
 // y pass (inverse, in place) that also leaves the Parseval partials of its output, one per tile (rf_fft.h AccColIO): columns
 // C = hi * nzl + (kz - kz0)
 hipError_t launch_col_plain_acc(int f64, int N, void* base, ColGeom g, long long ncols, int kz0, int nzl, double* partials, const void* tw,
-                                hipStream_t s, bool prepare_only = false);
+                                hipStream_t s);
 // sig[0] = sigma = sqrt(norm * sum of the n partials) (rounded to float32 first when sigma_as_float), Ap[z] = sqrt(log t) / sigma,
 // Bp[z] = density[z] / sqrt(t) (density may be null: 1), t = 1 + (sigma growth[z])^2
 hipError_t launch_lognormal_tables(const double* partials, long long n, double norm, const double* growth, const double* density, int nz,
                                    int sigma_as_float, double ap_unit, double* sig, double* Ap, double* Bp, hipStream_t s);
 // z pass with rho = exp(delta Ap_z) Bp_z in its epilogue (rf_fft.h LognormalRowIO)
 hipError_t launch_row_c2r_lognormal(int f64, int M, void* W, long long nrows, double scale, const double* Ap, const double* Bp,
-                                    const void* tw, double* partials, hipStream_t s, bool prepare_only = false);
+                                    const void* tw, double* partials, hipStream_t s);
 // the z pass with a per-z factor applied in its store (ScaleZRowIO)
 hipError_t launch_row_c2r_zscale(int f64, int M, void* W, long long nrows, double scale, const double* Sz, const void* tw, double* partials,
-                                 hipStream_t s, bool po = false);
+                                 hipStream_t s);
 // forward z pass (r2c rows, in place: nz reals -> nz/2 complex with (X[0], X[nz/2]) packed in element 0)
-hipError_t launch_row_r2c(int f64, int M, void* W, long long nrows, const void* tw, hipStream_t s,
-                          bool prepare_only = false);
+hipError_t launch_row_r2c(int f64, int M, void* W, long long nrows, const void* tw, hipStream_t s);
 // contiguous-axis pass of an unpacked c2c plan: rows of M = nz complex, in place; dir = +1 inverse (scaled), -1 forward;
 // tw = exp(2 pi i q / M), q in [0, M)
-hipError_t launch_row_c2c(int f64, int M, int dir, void* W, long long nrows, double scale, const void* tw, hipStream_t s,
-                          bool prepare_only = false);
+hipError_t launch_row_c2c(int f64, int M, int dir, void* W, long long nrows, double scale, const void* tw, hipStream_t s);
 // packed device array [nx][ny][nz/2] -> API layout [nx][ny][nz/2+1] (separates the kz = 0 and nz/2 planes)
 hipError_t launch_unpack_kspace(int f64, const void* W, void* K, int nx, int ny, int nzl, int kz0, hipStream_t s);
 long long row_c2r_tiles(int f64, int M, long long nrows);
