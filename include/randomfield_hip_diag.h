@@ -20,6 +20,12 @@ extern "C" {
 /* ---- timing and launch structure ----------------------------------------- */
 /* GPU time of each kernel of the last rf_realise, 5 floats: x pass (main kernel), y pass, z pass, reduce,
  * and the small x-pass launch that repairs the kz = 0 tiles (0 when the x pass is a single launch).
+ * The five entries are the parts of one timeline: the call records its start, a mark behind each launch (or group of launches) that
+ * says which entry the time since the previous mark belongs to, and its end; an entry is the sum of its intervals and exactly 0 when
+ * the call had none for it, the time from the last mark to the end is [3], and the five add up to rf_elapsed_ms.  A call that
+ * exchanges in sub-slabs (RF_FLAG_EXCHANGE_CHUNKS) charges its whole forward half to [0]; multi-rank calls count the exchange, the
+ * gathering z pass and its moments as [2] and the all-reduce as [3].  rf_kernel_ms, rf_merged_yz_ms and rf_elapsed_ms refuse before
+ * the plan's first call and after a call that failed half way.
  * Plans on the generic kernels (shapes that are not powers of two), after rf_realise, rf_execute_c2r or rf_execute_gradient_c2r, from
  * events around the launches:
  *   [0] the x pass -- with the generation inside it under RF_FLAG_FUSED_GENERIC_GENERATION, with the factor i k_a inside it after

@@ -57,6 +57,15 @@ void drop_graphs(rf_plan* p) {
 
 int ensure_k(rf_plan* p) { RF_HIP(p->K.reserve(p->k_bytes)); return 0; }
 
+// is the stream inside a graph capture?  (no allocation and no host wait there)
+bool capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+
+// numpy's normalisation of an inverse transform of the plan's grid
+double inv_cells(const rf_plan* p) { return 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz); }
+
 // The saved potential is written by a second store stream of the generation pass, row for row next to the field's.  The time of
 // that pass is bimodal -- 5.2 or 5.75 ms for the whole default call at 1024^3 -- and tools/pot_offset.py shows what decides it:
 // NOT the virtual addresses (45 plans at identical virtual addresses of both arrays and 15 offsets of the potential inside its
@@ -220,7 +229,8 @@ int slab_chunks(const rf_plan* p) {
 size_t chunk_bytes(const rf_plan* p) { return p->w_bytes / (size_t)slab_chunks(p); }
 
 // (kz0c, nzlc >= 0: a sub-slab of this rank's planes instead of all of them -- W then points at the sub-slab's own region)
-int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, bool timed, int kz0c, int nzlc) {
+// (tl: the fast generation's kz = 0 tiles are rf_kernel_ms's entry 4; the caller marks the end of the pass)
+int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, Timeline* tl, int kz0c, int nzlc) {
   // resident deviates (the numpy stream replayed by rf_noise_mt19937) take the fast float32 sigma path too; host-supplied
   // deviates (RF_NOISE_EXTERNAL, the parity mode) keep the exact reference dtype chain
   // (float32 copies of the deviates exist for this path only, and it can store the potential too; float64 ones cannot)
@@ -238,7 +248,8 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   const ColGeom gx = (W == p->X.ptr && W != nullptr)
                          ? xblock_x_geom(p->nx, p->ny, nzl, col_gen_tile_cols(p->f64, p->nx), xpose_row_block(p))
                          : ColGeom{(long long)p->ny * nzl, 0, (long long)p->ny * nzl};
-  if (timed) { RF_HIP(hipEventRecord(p->ev[5], sx)); p->repair_timed = fast; }   // overwritten by the launcher if it splits
+  hipEvent_t after_repair = nullptr;
+  if (fast) RF_HIP(mark(tl, rft::EXTRA, sx, &after_repair));       // in front of the pass; recorded again by the launcher if it splits
   FastGenParams fgp = make_fast(p, cd, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
   if (fast_noise && p->noise32_resident) {
     fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch.ptr);      // (a later float64 replay reuses the scratch: it clears noise32_resident)
@@ -247,7 +258,7 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   else if (fast_noise) fgp.noise = gp.noise;
   if (fast)
     RF_HIP(launch_col_fastgen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, fgp,
-                              kz0, (int)nzl, p->tw_x.ptr, sx, timed ? p->ev[5] : nullptr,
+                              kz0, (int)nzl, p->tw_x.ptr, sx, after_repair,
                               rep ? p->rank * p->nxl : 0, rep ? (p->rank + 1) * p->nxl : 1 << 30, cd.pot_target, p->fixbuf.ptr));
   else
     RF_HIP(launch_col_gen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, gp, kspace, kz0, (int)nzl, p->tw_x.ptr, sx));
@@ -306,52 +317,51 @@ int queue_y_direct(rf_plan* p, const void* W, int rbuf, hipStream_t s, int c) {
 
 // The forward half of a plan in direct mode: sub-slab by sub-slab the x pass on stream A and the storing y pass on stream Y (Y == A: one
 // stream; Y != A: the stores of sub-slab c -- link-bound on a real job -- run beside the x pass of sub-slab c + 1).  The caller has
-// put the barrier that frees the receive buffers in front of it on Y.  `timed` (Y == A only): ev[5] / ev[1] / ev[2] as queue_xy.
-int direct_forward(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, int rbuf, hipStream_t A, hipStream_t Y, bool timed) {
+// put the barrier that frees the receive buffers in front of it on Y.  tl (Y == A or sub-slabs): the marks of queue_xy; in sub-slabs the
+// whole forward half is the x entry (Y != A: the stores are still running on Y -- the x passes' end stands for both, as in the chunked rccl path).
+int direct_forward(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, int rbuf, hipStream_t A, hipStream_t Y, Timeline* tl) {
   const int C = slab_chunks(p);
   const long long nzc_ = p->nzl / C;
   if (Y != A) RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
   for (int c = 0; c < C; ++c) {
-    if (C == 1) { if (int rc = queue_x(p, cd, gp, kspace, W, A, timed)) return rc; }
-    else if (int rc = queue_x(p, cd, gp, kspace, (char*)W + (size_t)c * chunk_bytes(p), A, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
-    if (timed && C == 1) RF_HIP(hipEventRecord(p->ev[1], A));
-    if (Y != A) { RF_HIP(hipEventRecord(p->chunk_ev[c], A)); RF_HIP(hipStreamWaitEvent(Y, p->chunk_ev[c], 0)); }
+    if (C == 1) { if (int rc = queue_x(p, cd, gp, kspace, W, A, tl)) return rc; }
+    else if (int rc = queue_x(p, cd, gp, kspace, (char*)W + (size_t)c * chunk_bytes(p), A, nullptr, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
+    if (C == 1) RF_HIP(mark(tl, rft::X, A));
+    if (Y != A) RF_HIP(hop(p->chunk_ev[c], A, Y));
     if (int rc = queue_y_direct(p, W, rbuf, Y, c)) return rc;
   }
-  if (timed && C > 1) { RF_HIP(hipEventRecord(p->ev[5], A)); p->repair_timed = false; RF_HIP(hipEventRecord(p->ev[1], A)); }
-  if (timed) RF_HIP(hipEventRecord(p->ev[2], A));          // (Y != A: the stores are still running on Y -- the x passes' end stands for both, as in the chunked rccl path)
+  RF_HIP(mark(tl, C == 1 ? rft::Y : rft::X, A));
   return 0;
 }
 
-// x pass (generation or API k-space fused into its load) + y pass of buffer W on stream s.
-// Records ev[1] (after x) and ev[2] (after y) when `timed`.
+// x pass (generation or API k-space fused into its load) + y pass of buffer W on stream s, with a mark behind either.
 // the forward half of ONE sub-slab c of a plan that exchanges in chunks: x pass + y pass on its nzl / xchunks planes (region c of W)
 int queue_xy_chunk(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, int c) {
   const int C = slab_chunks(p);
   const long long nzc_ = p->nzl / C;
   char* Wc = (char*)W + (size_t)c * chunk_bytes(p);
-  if (int rc = queue_x(p, cd, gp, kspace, Wc, s, false, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
+  if (int rc = queue_x(p, cd, gp, kspace, Wc, s, nullptr, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
   const ColGeom gy{nzc_, (long long)p->ny * nzc_, nzc_};
   RF_HIP(launch_col_plain(p->f64, p->ny, +1, Wc, gy, (long long)p->nx * nzc_, p->tw_y.ptr, s));
   return 0;
 }
 
 // (a plan in direct mode: the y pass stores into the peers' receive buffers `rbuf`, and what follows is the z pass, not an exchange)
-int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, bool timed, int rbuf) {
-  if (direct_active(p)) return direct_forward(p, cd, gp, kspace, W, rbuf, s, s, timed);
+int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, Timeline* tl, int rbuf) {
+  if (direct_active(p)) return direct_forward(p, cd, gp, kspace, W, rbuf, s, s, tl);
   if (slab_chunks(p) > 1) {
     for (int c = 0; c < slab_chunks(p); ++c)
       if (int rc = queue_xy_chunk(p, cd, gp, kspace, W, s, c)) return rc;
-    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = false; RF_HIP(hipEventRecord(p->ev[1], s)); RF_HIP(hipEventRecord(p->ev[2], s)); }
+    RF_HIP(mark(tl, rft::X, s));             // (sub-slabs: the whole forward half is the x entry)
     return 0;
   }
   const bool rep = p->replicate && p->nranks > 1;
   const long long nzl = rep ? p->nzc : p->nzl, nxp = rep ? p->nxl : p->nx;      // the local array is [nxp][ny][nzl]
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
-  if (int rc = queue_x(p, cd, gp, kspace, W, s, timed)) return rc;
-  if (timed) RF_HIP(hipEventRecord(p->ev[1], s));
+  if (int rc = queue_x(p, cd, gp, kspace, W, s, tl)) return rc;
+  RF_HIP(mark(tl, rft::X, s));
   RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, nxp * nzl, p->tw_y.ptr, s));
-  if (timed) RF_HIP(hipEventRecord(p->ev[2], s));
+  RF_HIP(mark(tl, rft::Y, s));
   return 0;
 }
 
@@ -359,12 +369,21 @@ int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ks
 // (dense real [nxl][ny][nz]) into W, then the local (sum, sumsq)
 int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStream_t s) {
   const long long nrows = (long long)p->nxl * p->ny;
-  const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
   const long long nzseg = p->nzl / slab_chunks(p);            // planes per received segment: nranks * chunks of them make a row
-  RF_HIP(launch_row_c2r_gather(p->f64, p->nzc, R, W, nrows, scale, (int)nzseg, nrows * nzseg, p->tw_z.ptr, p->partials.get(), s));
+  RF_HIP(launch_row_c2r_gather(p->f64, p->nzc, R, W, nrows, inv_cells(p), (int)nzseg, nrows * nzseg, p->tw_z.ptr, p->partials.get(), s));
   RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
   p->cur = W;
   p->real_valid = true;
+  return 0;
+}
+
+// replicated generation, behind queue_xy: the local array already is this rank's x slab [nxl][ny][nz/2] -- the z pass on it and its
+// (sum, sumsq) into pair `slot` (the z entry of a timed call), then, allreduce > 0, the global sums of the first so many pairs
+int replicated_z(rf_plan* p, int slot, int allreduce, Timeline* tl) {
+  RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nxl * p->ny, inv_cells(p), p->tw_z.ptr, p->partials.get(), p->stream));
+  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get() + 2 * slot, p->partials.get() + 2 * p->npartials, p->stream));
+  RF_HIP(mark(tl, rft::Z, p->stream));
+  if (allreduce > 0 && p->comm) RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)allreduce, ncclFloat64, ncclSum, p->comm, p->stream));
   return 0;
 }
 
@@ -422,6 +441,20 @@ int ensure_batch_buffers(rf_plan* p) {
   return 0;
 }
 
+// The plan holds the real-space field of its last call in W, and that field's (sum, sumsq) in pair `slot` of `stats`
+void field_ready(rf_plan* p, int slot) {
+  p->cur = p->W.ptr;
+  p->stats_slot = slot;
+  p->real_valid = true;
+  p->stats_valid = true;
+}
+// ... of a pipelined batch of n: the last field lies in the buffer of its turn, `cur`; real: it is a field (no stand-in exchange)
+void batch_ready(rf_plan* p, int n, void* cur, bool real) {
+  field_ready(p, n - 1);
+  p->cur = cur;
+  p->real_valid = real;
+}
+
 // Pipelined batch of a plan in direct mode.  The y pass of realisation i stores into the PEERS' receive buffers i % 2 -- it is the
 // exchange, and on a real job it runs at the speed of the links -- so it goes to the exchange stream Y, where it runs beside the z pass of
 // realisation i - 1 and the x pass of realisation i + 1 on the compute stream A; B(i), a tiny all-reduce on Y, tells every rank that
@@ -439,14 +472,14 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
   const hipEvent_t *ev_fwd = p->pev.ev.data(), *ev_bar = ev_fwd + 2, *ev_z = ev_fwd + 4;
   const bool two = p->direct_overlap != 0;
   hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
-  RF_HIP(hipEventRecord(p->ev[0], A));
-  if (two) { RF_HIP(hipEventRecord(ev_z[1], A)); RF_HIP(hipStreamWaitEvent(Y, ev_z[1], 0)); }     // whatever the plan's stream did before
+  RF_HIP(p->tl.begin(A, false));
+  if (two) RF_HIP(hop(ev_z[1], A, Y));                            // whatever the plan's stream did before
   if (int rc = direct_barrier(p, Y)) return rc;                   // B(-1): nobody is still reading (or sending from) a receive buffer
   for (int i = 0; i <= n; ++i) {
     const int b = i & 1, pb = (i - 1) & 1;
     if (i < n) {
       // (sub-slab by sub-slab when the plan chunks: x(c) on A, the stores of sub-slab c on Y behind an event)
-      if (int rc = direct_forward(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, A, Y, false)) return rc;
+      if (int rc = direct_forward(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, A, Y, nullptr)) return rc;
       (void)ev_fwd;
     }
     if (i >= 1) {
@@ -464,23 +497,11 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
     const int lb = (n - 1) & 1;
     if (two) RF_HIP(hipStreamWaitEvent(Y, ev_z[lb], 0));
     RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, Y));
-    if (two) { RF_HIP(hipEventRecord(ev_bar[lb], Y)); RF_HIP(hipStreamWaitEvent(A, ev_bar[lb], 0)); }
+    if (two) RF_HIP(hop(ev_bar[lb], Y, A));
   }
-  RF_HIP(hipEventRecord(p->ev[4], A));
-  p->cur = Wb[(n - 1) & 1];
-  p->stats_slot = n - 1;
-  p->timed = false;
-  p->real_valid = !p->direct_standin;
-  p->stats_valid = true;
+  RF_HIP(p->tl.end(A));
+  batch_ready(p, n, Wb[(n - 1) & 1], !p->direct_standin);
   return 0;
-}
-
-// The plan holds the real-space field of its last call in W, and that field's (sum, sumsq) in pair `slot` of `stats`
-void field_ready(rf_plan* p, int slot) {
-  p->cur = p->W.ptr;
-  p->stats_slot = slot;
-  p->real_valid = true;
-  p->stats_valid = true;
 }
 
 // room for the (sum, sumsq) pairs of n realisations (captured batch graphs carry the array's address: they go)
@@ -501,16 +522,12 @@ int ensure_stats(rf_plan* p, int n) {
 int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
   if (int rc = ensure_stats(p, n)) return rc;
   if (p->replicate && p->nranks > 1) {          // no exchange to overlap: realisations back to back, one all-reduce at the end
-    const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-    RF_HIP(hipEventRecord(p->ev[0], p->stream));
+    RF_HIP(p->tl.begin(p->stream, false));
     for (int i = 0; i < n; ++i) {
-      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W.ptr, p->stream, false)) return rc;
-      RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nxl * p->ny, scale, p->tw_z.ptr, p->partials.get(), p->stream));
-      RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get() + 2 * i, p->partials.get() + 2 * p->npartials, p->stream));
+      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W.ptr, p->stream, nullptr)) return rc;
+      if (int rc = replicated_z(p, i, i + 1 == n ? n : 0, nullptr)) return rc;
     }
-    if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, p->stream));
-    RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->timed = false;
+    RF_HIP(p->tl.end(p->stream));
     field_ready(p, n - 1);
     return 0;
   }
@@ -520,13 +537,12 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
   void* Rb[2] = {p->R.ptr, p->R2.ptr};
   const hipEvent_t *ev_fwd = p->pev.ev.data(), *ev_exch = ev_fwd + 2, *ev_z = ev_fwd + 4;
   hipStream_t A = p->stream, C = p->comm_stream;
-  RF_HIP(hipEventRecord(p->ev[0], A));
+  RF_HIP(p->tl.begin(A, false));
   for (int i = 0; i <= n; ++i) {
     if (i < n) {
       const int b = i & 1;
-      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], A, false)) return rc;
-      RF_HIP(hipEventRecord(ev_fwd[b], A));
-      RF_HIP(hipStreamWaitEvent(C, ev_fwd[b], 0));
+      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], A, nullptr)) return rc;
+      RF_HIP(hop(ev_fwd[b], A, C));
       if (i >= 2) RF_HIP(hipStreamWaitEvent(C, ev_z[b], 0));          // R[b] still being read by z(i-2)?
       if (int rc = queue_exchange_rccl(p, Wb[b], Rb[b], C)) return rc;
       RF_HIP(hipEventRecord(ev_exch[b], C));
@@ -544,15 +560,10 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
     const int lb = (n - 1) & 1;
     RF_HIP(hipStreamWaitEvent(C, ev_z[lb], 0));
     RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, C));
-    RF_HIP(hipEventRecord(ev_exch[lb], C));
-    RF_HIP(hipStreamWaitEvent(A, ev_exch[lb], 0));
+    RF_HIP(hop(ev_exch[lb], C, A));
   }
-  RF_HIP(hipEventRecord(p->ev[4], A));
-  p->cur = Wb[(n - 1) & 1];
-  p->stats_slot = n - 1;
-  p->timed = false;
-  p->real_valid = !(p->nranks > 1 && !p->comm);        // (a stand-in exchange leaves this rank's own data in the segments: not a field)
-  p->stats_valid = true;
+  RF_HIP(p->tl.end(A));
+  batch_ready(p, n, Wb[(n - 1) & 1], !(p->nranks > 1 && !p->comm));        // (a stand-in exchange leaves this rank's own data in the segments: not a field)
   return 0;
 }
 
@@ -606,89 +617,51 @@ int sink_finish(rf_plan* p) {
   return 0;
 }
 
-int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, bool timed) {
+// tl: a mark behind every launch (rf_kernel_ms: [1], [2] = the sums over the slabs' y and z launches; a merged launch counts as y) and,
+// the call's last pass being queued here, its end -- in front of the last slab's copy to a host sink, which waits on the host.
+int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, Timeline* tl) {
   const long long nzl = p->nzl;
-  bool sink = p->sink_host != nullptr && !cd.zscale;
-  if (sink) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    sink = cap == hipStreamCaptureStatusNone;      // (a captured batch keeps its fields on the device)
-  }
-  const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
+  const bool sink = p->sink_host != nullptr && !cd.zscale && !capturing(s);      // (a captured batch keeps its fields on the device)
+  const double scale = inv_cells(p);
   const bool xp = p->X.ptr && xpose_ok(p);
   const long long rb = xpose_row_block(p), tc = col_tile_cols(p->f64, p->ny);
   const ColGeom gy = xp ? xblock_y_geom(p->nx, p->ny, nzl, tc, rb) : ColGeom{nzl, (long long)p->ny * nzl, nzl};
-  long long B = yz_slab_planes(p);
-  if (xp && B > 0 && (B % rb || (B & (B - 1)) || p->nx % B)) B = 0;      // a slab of X is whole x blocks, a power of two of them
-  if (B <= 0) B = p->nx;
-  const int nslab = (int)((p->nx + B - 1) / B);
-  const long long plane = (long long)p->ny * nzl * (long long)p->csize, tiles_per_plane = p->npartials / p->nx;
-  if (timed) {
-    RF_HIP(p->slab_ev.ensure(2 * nslab, hipEventDefault));
-    p->slab_timed = nslab;
-  }
+  const YzSlabs sl = yz_slabs(p->nx, yz_slab_planes(p), xp, (int)rb);
+  const long long B = sl.planes, plane = (long long)p->ny * nzl * (long long)p->csize, tiles_per_plane = p->npartials / p->nx;
   // untimed single-rank float32 realisations at the sizes rf_k_yz.hip serves: the z pass of slab i and the y pass of slab i + 1 share a
   // launch (the next slab's y tiles fill the CUs the draining z pass leaves idle); timed calls keep one launch per pass and slab, so
   // that rf_kernel_ms still means what it says
-  // (rf_set_merged_yz(2) merges timed calls too, with an event behind every launch: rf_merged_yz_ms)
+  // (rf_set_merged_yz(2) merges timed calls too, with a mark behind every launch: rf_merged_yz_ms)
   // (the last slab may be smaller -- a slab size that does not divide nx: RF_FLAG_YZ_SLAB_PLANES -- as long as both sizes fit the kernel)
-  const long long Blast = p->nx - (long long)(nslab - 1) * B;
-  if ((timed ? p->yz_merge >= 2 : p->yz_merge >= 1) && !xp && !cd.zscale && nslab > 1 &&
-      yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, B * nzl) &&
-      (Blast == B || yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, Blast * nzl))) {
-    if (timed) {
-      RF_HIP(p->slab_ev.ensure(nslab + 1, hipEventDefault));
-      p->slab_merged = nslab;
-      p->slab_timed = 0;       // (rf_kernel_ms: the merged form's events apply, the per-pass pairs of slab_ev were not recorded by this call)
-    }
-    RF_HIP(launch_col_plain(p->f64, p->ny, +1, W, gy, B * nzl, p->tw_y.ptr, s));
-    if (timed) RF_HIP(hipEventRecord(p->slab_ev[0], s));
-    for (int i = 0; i < nslab; ++i) {
-      char* Ws = (char*)W + (long long)i * B * plane;
-      double* part = p->partials.get() + 2 * (long long)i * B * tiles_per_plane;
-      const long long nb = i + 1 < nslab ? B : Blast, nb_next = i + 2 < nslab ? B : Blast;       // planes of slab i / of slab i + 1
-      if (i + 1 < nslab)
-        RF_HIP(launch_yz_merged(p->f64, p->ny, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, Ws + B * plane, gy, nb_next * nzl, p->tw_y.ptr, s));
-      else
-        RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, s));
-      if (timed) RF_HIP(hipEventRecord(p->slab_ev[i + 1], s));
-      if (sink) {
-        if (int rc = sink_mark(p, i, s)) return rc;
-        if (i > 0) if (int rc = sink_copy(p, W, (long long)(i - 1) * B, B, i - 1)) return rc;       // (slab i - 1, while the GPU runs slab i)
-      }
-    }
-    if (timed) { RF_HIP(hipEventRecord(p->ev[2], s)); RF_HIP(hipEventRecord(p->ev[3], s)); }
-    RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
-    if (timed) RF_HIP(hipEventRecord(p->ev[4], s));
-    if (sink) {
-      if (int rc = sink_copy(p, W, (long long)(nslab - 1) * B, Blast, nslab - 1)) return rc;
-      return sink_finish(p);
-    }
-    return 0;
-  }
-  for (int i = 0; i < nslab; ++i) {
-    const long long x0 = (long long)i * B, nb = x0 + B <= p->nx ? B : p->nx - x0;      // planes [x0, x0 + nb)
+  const bool merge = p->yz_merge >= ((tl && tl->detailed) ? 2 : 1) && !xp && !cd.zscale && sl.count > 1 &&
+                     yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, B * nzl) &&
+                     (sl.last == B || yz_merged_fits(p->f64, p->ny, (int)p->nzc, gy, B * p->ny, sl.last * nzl));
+  auto planes_of = [&](int i) { return i + 1 < sl.count ? B : (long long)sl.last; };
+  for (int i = 0; i < sl.count; ++i) {
+    const long long x0 = (long long)i * B, nb = planes_of(i);      // planes [x0, x0 + nb)
     char* Ws = (char*)W + x0 * plane;
     char* Xs = xp ? (char*)p->X.ptr + x0 * plane : nullptr;        // (x blocks are contiguous and as large as their planes)
-    if (xp) RF_HIP(launch_col_xpose(p->f64, p->ny, Xs, gy, Xs, gy, nb * nzl, p->tw_y.ptr, s));
-    else RF_HIP(launch_col_plain(p->f64, p->ny, +1, Ws, gy, nb * nzl, p->tw_y.ptr, s));
-    if (timed) RF_HIP(hipEventRecord(p->slab_ev[2 * i], s));
     double* part = p->partials.get() + 2 * x0 * tiles_per_plane;
-    if (xp) RF_HIP(launch_row_c2r_xgather(p->f64, (int)p->nzc, Xs, Ws, nb * p->ny, scale, (int)tc, (int)rb, p->ny, p->tw_z.ptr, part, s));
+    if (!merge || i == 0) {                                        // (merged: the launch of slab i - 1 has run this slab's y pass)
+      if (xp) RF_HIP(launch_col_xpose(p->f64, p->ny, Xs, gy, Xs, gy, nb * nzl, p->tw_y.ptr, s));
+      else RF_HIP(launch_col_plain(p->f64, p->ny, +1, Ws, gy, nb * nzl, p->tw_y.ptr, s));
+      RF_HIP(mark(tl, rft::Y, s));
+    }
+    const bool with_next = merge && i + 1 < sl.count;              // this slab's z pass and the next slab's y pass in one launch
+    if (with_next) RF_HIP(launch_yz_merged(p->f64, p->ny, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, Ws + B * plane, gy, planes_of(i + 1) * nzl, p->tw_y.ptr, s));
+    else if (xp) RF_HIP(launch_row_c2r_xgather(p->f64, (int)p->nzc, Xs, Ws, nb * p->ny, scale, (int)tc, (int)rb, p->ny, p->tw_z.ptr, part, s));
     else if (cd.zscale) RF_HIP(launch_row_c2r_zscale(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, cd.zscale, p->tw_z.ptr, part, s));
     else RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, Ws, nb * p->ny, scale, p->tw_z.ptr, part, s));
-    if (timed) RF_HIP(hipEventRecord(p->slab_ev[2 * i + 1], s));
+    RF_HIP(mark(tl, with_next ? rft::Y : rft::Z, s, nullptr, with_next));
     if (sink) {
       if (int rc = sink_mark(p, i, s)) return rc;
       if (i > 0) if (int rc = sink_copy(p, W, x0 - B, B, i - 1)) return rc;                          // (slab i - 1, while the GPU runs slab i)
     }
   }
-  if (timed) { RF_HIP(hipEventRecord(p->ev[2], s)); RF_HIP(hipEventRecord(p->ev[3], s)); }   // (rf_kernel_ms sums the slab events)
   RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
-  if (timed) RF_HIP(hipEventRecord(p->ev[4], s));
+  if (tl) RF_HIP(tl->end(s));
   if (sink) {
-    const long long xl = (long long)(nslab - 1) * B;
-    if (int rc = sink_copy(p, W, xl, p->nx - xl, nslab - 1)) return rc;
+    if (int rc = sink_copy(p, W, (long long)(sl.count - 1) * B, sl.last, sl.count - 1)) return rc;
     return sink_finish(p);
   }
   return 0;
@@ -696,27 +669,25 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
 
 // the whole single-rank pipeline: x pass (generation or API k-space fused into its load; into the transposed intermediate
 // when the plan uses it), then queue_yz
-int queue_xyz(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, double* stats_out, bool timed) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  if (cap == hipStreamCaptureStatusNone)           // (no allocation inside a graph capture: batch_prepare() has done it)
+int queue_xyz(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, double* stats_out, Timeline* tl) {
+  if (!capturing(s))                               // (no allocation inside a graph capture: batch_prepare() has done it)
     if (int rc = ensure_x(p)) return rc;
   const bool xp = p->X.ptr && xpose_ok(p);
-  if (int rc = queue_x(p, cd, gp, kspace, xp ? p->X.ptr : W, s, timed)) return rc;
-  if (timed) RF_HIP(hipEventRecord(p->ev[1], s));
-  return queue_yz(p, cd, W, s, stats_out, timed);
+  if (int rc = queue_x(p, cd, gp, kspace, xp ? p->X.ptr : W, s, tl)) return rc;
+  RF_HIP(mark(tl, rft::X, s));
+  return queue_yz(p, cd, W, s, stats_out, tl);
 }
 
 // the launches behind the sequences of rf_generic.h (generic_c2r_seq / generic_r2c_seq / generic_c2c_seq) on the plan's stream
 struct HipGenericOps {
   rf_plan* p;
   hipStream_t s;
-  // per-kernel times of a realisation (rf_kernel_ms): the inverse sequence launches on the x, y and z root tables in that order, so
-  // ev[1] goes in front of the first launch of the y pass and ev[2] in front of the first of the contiguous pass
-  bool timed = false;
+  // per-kernel times of a realisation (rf_kernel_ms): the inverse sequence launches on the x, y and z root tables in that order; when
+  // the phase changes, what was queued until now belongs to the part that just ended
+  Timeline* tl = nullptr;
   int phase = 0;
   int enter(int ph) {
-    if (timed) while (phase < ph) RF_HIP(hipEventRecord(p->ev[++phase], s));
+    if (ph > phase) { RF_HIP(mark(tl, Part(phase), s)); phase = ph; }
     return 0;
   }
   const void* root(int which) const { return which == 0 ? p->tw_x.ptr : (which == 1 ? p->tw_y.ptr : p->tw_z.ptr); }
@@ -737,18 +708,16 @@ struct HipGenericOps {
     return 0;
   }
   // ... and, for a plan whose x axis is split, the same cells by a launch of its own into a scratch array (rf_kernel_ms: entry 4)
-  int materialised() {
-    if (timed) { RF_HIP(hipEventRecord(p->ev[5], s)); p->repair_timed = true; }
-    return 0;
-  }
   int materialise(const GenParams& gp, const void*, void* K) {
     RF_HIP(launch_gen_kspace(p->f64, K, gp, s));
-    return materialised();
+    RF_HIP(mark(tl, rft::EXTRA, s));
+    return 0;
   }
   template <class P>
   int materialise(const P& dp, const void* S, void* K) {
     RF_HIP(launch_derivative(p->f64, S, K, dp, s));
-    return materialised();
+    RF_HIP(mark(tl, rft::EXTRA, s));
+    return 0;
   }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
     if (int rc = enter(which)) return rc;
@@ -780,13 +749,13 @@ int ensure_g2(rf_plan* p) {
 // generic_c2r_seq: axes too long for one line of the LDS take the four-step form through the scratch arrays), (sum, sumsq) into stats_out.
 // from != null: the x pass takes its cells from that descriptor instead of loading K (generic_c2r_from_seq) -- GenParams: it generates
 // the half spectrum (RF_FLAG_FUSED_GENERIC_GENERATION; K is ignored); GradParams / HessParams: K is the array whose gradient / Hessian
-// component is transformed, and is only read.  timed: events ev[1] .. ev[3] behind the x pass, the y pass and the contiguous pass.
+// component is transformed, and is only read.  tl: marks behind the x pass, the y pass and the contiguous pass.
 template <class From>
-int generic_c2r(rf_plan* p, const void* K, double* stats_out, bool timed, const From* from) {
+int generic_c2r(rf_plan* p, const void* K, double* stats_out, Timeline* tl, const From* from) {
   if (int rc = ensure_g(p)) return rc;
   if (int rc = ensure_g2(p)) return rc;
-  HipGenericOps ops{p, p->stream, timed};
-  const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
+  HipGenericOps ops{p, p->stream, tl};
+  const double scale = inv_cells(p);
   if (from) { if (int rc = generic_c2r_from_seq(ops, p->gdims, *from, K, p->G.ptr, p->G2.ptr, p->W.ptr, scale)) return rc; }
   else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G.ptr, p->G2.ptr, p->W.ptr, scale)) return rc;
   if (int rc = ops.enter(3)) return rc;
@@ -802,48 +771,44 @@ void kspace_ready(rf_plan* p) {
 
 // What the exchanging branches of queue_c2r end with, the receive buffer being complete for stream A: the gathering z pass on A, then
 // the all-reduce of the moments on S, the stream that drives the communicator in this call (S != A: behind an event hop each way)
-int gather_and_reduce(rf_plan* p, hipStream_t A, hipStream_t S) {
-  hipEvent_t hop = S != A ? p->chunk_ev[slab_chunks(p)] : nullptr;
+// (the timeline: the exchange, the z pass and its moments are the z entry, the all-reduce what is left until the call's end)
+int gather_and_reduce(rf_plan* p, hipStream_t A, hipStream_t S, Timeline* tl) {
+  hipEvent_t ev = S != A ? p->chunk_ev[slab_chunks(p)] : nullptr;
   if (int rc = queue_z_slab(p, p->R.ptr, p->W.ptr, p->stats.get(), A)) return rc;
-  if (p->timed) RF_HIP(hipEventRecord(p->ev[3], A));
+  RF_HIP(mark(tl, rft::Z, A));
   if (p->nranks > 1 && p->comm) {       // global (sum, sumsq): one 2-double all-reduce
-    if (hop) { RF_HIP(hipEventRecord(hop, A)); RF_HIP(hipStreamWaitEvent(S, hop, 0)); }
+    if (ev) RF_HIP(hop(ev, A, S));
     RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2, ncclFloat64, ncclSum, p->comm, S));
-    if (hop) { RF_HIP(hipEventRecord(hop, S)); RF_HIP(hipStreamWaitEvent(A, hop, 0)); }
+    if (ev) RF_HIP(hop(ev, S, A));
   }
-  if (p->timed) RF_HIP(hipEventRecord(p->ev[4], A));
+  RF_HIP(tl->end(A));
   p->stats_slot = 0;
   p->stats_valid = true;
   return 0;
 }
 
-// one realisation / transform on the plan's stream into the primary buffer
+// one realisation / transform on the plan's stream into the primary buffer; a timed call: every branch marks its passes and ends the timeline
 int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace) {
+  Timeline* tl = &p->tl;
+  RF_HIP(tl->begin(p->stream, true));
   if (p->generic) {
-    // per-kernel times (rf_kernel_ms): ev[0] | generation launch | ev[5] | x | ev[1] | y | ev[2] | contiguous | ev[3] | reduce | ev[4]
-    p->slab_timed = 0;
-    p->slab_merged = 0;
-    p->repair_timed = false;                        // (here: "the generation was a launch of its own", entry 4)
-    RF_HIP(hipEventRecord(p->ev[0], p->stream));
+    // per-kernel times (rf_kernel_ms): start | generation launch | EXTRA | x | X | y | Y | contiguous | Z | reduce | end
     if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->noise_resident, "no float64 deviates resident on the device");
     const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and k_valid stay as they are
     if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
       if (int rc = ensure_k(p)) return rc;
       RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
-      if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], p->stream)); p->repair_timed = true; }
+      RF_HIP(mark(tl, rft::EXTRA, p->stream));
       kspace_ready(p);
       kspace = p->K.ptr;
     }
-    if (int rc = generic_c2r(p, kspace, p->stats.get(), p->timed, fused ? &gp : nullptr)) return rc;
-    RF_HIP(hipEventRecord(p->ev[4], p->stream));
+    if (int rc = generic_c2r(p, kspace, p->stats.get(), tl, fused ? &gp : nullptr)) return rc;
+    RF_HIP(tl->end(p->stream));
     field_ready(p, 0);
     return 0;
   }
-  p->slab_timed = 0;                            // (set again by queue_yz when this call runs the y / z passes slab by slab, timed)
-  p->slab_merged = 0;
-  if (p->timed) RF_HIP(hipEventRecord(p->ev[0], p->stream));
   if (p->nranks == 1 && !p->force_slab) {       // one GPU: x pass, then the y / z passes (slab by slab on large grids)
-    if (int rc = queue_xyz(p, cd, gp, kspace, p->W.ptr, p->stream, p->stats.get(), p->timed)) return rc;
+    if (int rc = queue_xyz(p, cd, gp, kspace, p->W.ptr, p->stream, p->stats.get(), tl)) return rc;
     field_ready(p, 0);
     return 0;
   }
@@ -858,12 +823,12 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
     RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
     hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
-    if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], A)); RF_HIP(hipStreamWaitEvent(Y, p->chunk_ev[C], 0)); }
+    if (two) RF_HIP(hop(p->chunk_ev[C], A, Y));
     if (int rc = direct_barrier(p, Y)) return rc;
-    if (int rc = direct_forward(p, cd, gp, kspace, p->W.ptr, 0, A, Y, p->timed)) return rc;
+    if (int rc = direct_forward(p, cd, gp, kspace, p->W.ptr, 0, A, Y, tl)) return rc;
     if (int rc = direct_barrier(p, Y)) return rc;
-    if (two) { RF_HIP(hipEventRecord(p->chunk_ev[C], Y)); RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0)); }
-    if (int rc = gather_and_reduce(p, A, Y)) return rc;
+    if (two) RF_HIP(hop(p->chunk_ev[C], Y, A));
+    if (int rc = gather_and_reduce(p, A, Y, tl)) return rc;
     if (p->direct_standin) p->real_valid = false;       // (the stores went to this rank's own buffers: no field came out)
     return 0;
   }
@@ -876,35 +841,28 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
     RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
     hipStream_t A = p->stream, X = p->comm_stream;
-    RF_HIP(hipEventRecord(p->chunk_ev[C], A));                 // (whatever used R / the communicator before on the plan's stream)
-    RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[C], 0));
+    RF_HIP(hop(p->chunk_ev[C], A, X));                         // (whatever used R / the communicator before on the plan's stream)
     for (int c = 0; c < C; ++c) {
       if (int rc = queue_xy_chunk(p, cd, gp, kspace, p->W.ptr, A, c)) return rc;
-      RF_HIP(hipEventRecord(p->chunk_ev[c], A));
-      RF_HIP(hipStreamWaitEvent(X, p->chunk_ev[c], 0));
+      RF_HIP(hop(p->chunk_ev[c], A, X));
       if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, X, c)) return rc;
     }
-    if (p->timed) { RF_HIP(hipEventRecord(p->ev[5], A)); p->repair_timed = false; RF_HIP(hipEventRecord(p->ev[1], A)); RF_HIP(hipEventRecord(p->ev[2], A)); }
-    RF_HIP(hipEventRecord(p->chunk_ev[C], X));
-    RF_HIP(hipStreamWaitEvent(A, p->chunk_ev[C], 0));
-    if (int rc = gather_and_reduce(p, A, X)) return rc;
+    RF_HIP(mark(tl, rft::X, A));                               // (the whole forward half is the x entry)
+    RF_HIP(hop(p->chunk_ev[C], X, A));
+    if (int rc = gather_and_reduce(p, A, X, tl)) return rc;
     if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
     return 0;
   }
-  if (int rc = queue_xy(p, cd, gp, kspace, p->W.ptr, p->stream, p->timed)) return rc;
-  if (p->replicate && p->nranks > 1) {          // the local array already is this rank's x slab [nxl][ny][nz/2]
-    const double scale = 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz);
-    RF_HIP(launch_row_c2r(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nxl * p->ny, scale, p->tw_z.ptr, p->partials.get(), p->stream));
-    RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get(), p->partials.get() + 2 * p->npartials, p->stream));
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[3], p->stream));
-    if (p->comm) RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2, ncclFloat64, ncclSum, p->comm, p->stream));
-    if (p->timed) RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  if (int rc = queue_xy(p, cd, gp, kspace, p->W.ptr, p->stream, tl)) return rc;
+  if (p->replicate && p->nranks > 1) {
+    if (int rc = replicated_z(p, 0, 1, tl)) return rc;
+    RF_HIP(tl->end(p->stream));
     field_ready(p, 0);
     return 0;
   }
   if (p->nranks > 1 || p->force_slab) {
     if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, p->stream)) return rc;
-    if (int rc = gather_and_reduce(p, p->stream, p->stream)) return rc;
+    if (int rc = gather_and_reduce(p, p->stream, p->stream, tl)) return rc;
     if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
     return 0;
   }
@@ -941,7 +899,7 @@ int create_common(rf_plan* p, bool packed) {
        (e = p->kz2.reserve((p->nzc + 1) * sizeof(double))) != hipSuccess ||
        (e = p->ztab.reserve(2 * p->nz * sizeof(double))) != hipSuccess))
     return fail(2, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-  if ((e = p->ev.ensure(6, hipEventDefault)) != hipSuccess) return fail(2, std::string("hipEventCreate: ") + hipGetErrorString(e));
+  if ((e = p->tl.ev.ensure(6, hipEventDefault)) != hipSuccess) return fail(2, std::string("hipEventCreate: ") + hipGetErrorString(e));      // (start, end and a whole-grid call's four marks; more on demand)
   return 0;
 }
 
@@ -1100,8 +1058,8 @@ int rf_execute_c2c(rf_plan* p, int direction) {
   RF_HIP(hipSetDevice(p->device));
   const long long nz = p->nz;
   const ColGeom gx{(long long)p->ny * nz, 0, (long long)p->ny * nz}, gy{nz, (long long)p->ny * nz, nz};
-  const double scale = direction > 0 ? 1.0 / ((double)p->nx * (double)p->ny * (double)p->nz) : 1.0;
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  const double scale = direction > 0 ? inv_cells(p) : 1.0;
+  RF_HIP(p->tl.begin(p->stream, false));
   if (p->generic) {
     if (generic_any_long(p)) RF_HIP(p->G.reserve(p->w_bytes));        // scratch of the four-step form
     HipGenericOps ops{p, p->stream};
@@ -1111,8 +1069,7 @@ int rf_execute_c2c(rf_plan* p, int direction) {
     RF_HIP(launch_col_plain(p->f64, p->ny, direction, p->W.ptr, gy, (long long)p->nx * nz, p->tw_y.ptr, p->stream));
     RF_HIP(launch_row_c2c(p->f64, (int)nz, direction, p->W.ptr, (long long)p->nx * p->ny, scale, p->tw_z.ptr, p->stream));
   }
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->timed = false;
+  RF_HIP(p->tl.end(p->stream));
   return 0;
 }
 
@@ -1277,7 +1234,6 @@ int rf_execute_c2r(rf_plan* p) {
   RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
   RF_REQUIRE(!(p->replicate && p->nranks > 1), "replicated-generation plans have no distributed k-space buffer");
   RF_HIP(hipSetDevice(p->device));
-  p->timed = true;
   return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr);
 }
 
@@ -1345,18 +1301,16 @@ int rf_execute_r2c(rf_plan* p) {
     // transform.py:278-301 on x-slab / kz-slab ranks: rows, the all-to-all in the other direction (block g of R -> rank g,
     // arriving as block h of W: the same grouped send / receive with the buffers swapped), columns
     RF_REQUIRE(!p->generic && !p->replicate, "the multi-rank forward transform runs on the tiled kernels of exchange-mode plans");
-    RF_HIP(hipEventRecord(p->ev[0], p->stream));
+    RF_HIP(p->tl.begin(p->stream, false));
     if (int rc = queue_r2c_slab_rows(p, p->stream)) return rc;
     if (int rc = queue_exchange_rccl(p, p->R.ptr, p->W.ptr, p->stream, -1, true)) return rc;
     if (int rc = queue_r2c_slab_cols(p, p->stream)) return rc;
-    RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->timed = false;
+    RF_HIP(p->tl.end(p->stream));
     return 0;
   }
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  RF_HIP(p->tl.begin(p->stream, false));
   if (int rc = queue_r2c_single(p, true)) return rc;
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->timed = false;
+  RF_HIP(p->tl.end(p->stream));
   return 0;
 }
 
@@ -1367,7 +1321,6 @@ int rf_realise(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   RF_REQUIRE(mode == RF_NOISE_NATIVE || mode == RF_NOISE_EXTERNAL || mode == RF_NOISE_RESIDENT, "invalid noise mode");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  p->timed = true;
   CallDesc cd;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
@@ -1395,7 +1348,6 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   RF_REQUIRE(rf_can_regenerate_potential(p, mode), "this plan / noise mode stores its potential (rf_realise_potential): nothing to regenerate from");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, nullptr)) return rc;
-  p->timed = true;
   CallDesc cd;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   cd.emit_potential = true;
@@ -1454,16 +1406,15 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
     if (int rc = rf_generate(p, seed, mode, noise_host)) return rc;
     if (int rc = rf_save_potential(p)) return rc;
     if (whole) return rf_execute_c2r(p);
-    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, false);
+    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, nullptr);
   }
   if (int rc = ensure_p(p)) return rc;
   p->p2_valid = false;                               // (P is rewritten: a second-order potential made from the old one is stale)
-  p->timed = whole;
   CallDesc cd;
   cd.pot_target = p->P.ptr;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
   const GenParams gp = make_gen(p, seed, mode, false);
-  return whole ? queue_c2r(p, cd, gp, nullptr) : queue_xy(p, cd, gp, nullptr, p->W.ptr, p->stream, false);
+  return whole ? queue_c2r(p, cd, gp, nullptr) : queue_xy(p, cd, gp, nullptr, p->W.ptr, p->stream, nullptr);
 }
 }  // namespace rfc
 extern "C" {
@@ -1479,7 +1430,7 @@ static int batch_issue(rf_plan* p, int n) {
   for (int i = 0; i < n; ++i) {
     GenParams gp = make_gen(p, 0, RF_NOISE_NATIVE, true);
     gp.seed_dev = p->seeds_dev.get() + i;
-    if (int rc = queue_xyz(p, CallDesc(), gp, nullptr, p->W.ptr, p->stream, p->stats.get() + 2 * i, false)) return rc;
+    if (int rc = queue_xyz(p, CallDesc(), gp, nullptr, p->W.ptr, p->stream, p->stats.get() + 2 * i, nullptr)) return rc;
   }
   return 0;
 }
@@ -1539,14 +1490,13 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     if (int rc = ensure_stats(p, n)) return rc;
     const bool fused = p->fused_generic;        // generation inside the x pass: no K, k_valid as it was (queue_c2r)
     if (!fused) { if (int rc = ensure_k(p)) return rc; }
-    RF_HIP(hipEventRecord(p->ev[0], p->stream));
+    RF_HIP(p->tl.begin(p->stream, false));
     for (int i = 0; i < n; ++i) {
       const GenParams gp = make_gen(p, seeds[i], RF_NOISE_NATIVE, false);
       if (!fused) RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
-      if (int rc = generic_c2r(p, p->K.ptr, p->stats.get() + 2 * i, false, fused ? &gp : nullptr)) return rc;
+      if (int rc = generic_c2r(p, p->K.ptr, p->stats.get() + 2 * i, nullptr, fused ? &gp : nullptr)) return rc;
     }
-    RF_HIP(hipEventRecord(p->ev[4], p->stream));
-    p->timed = false;
+    RF_HIP(p->tl.end(p->stream));
     field_ready(p, n - 1);
     if (!fused) kspace_ready(p);
     return rms_out ? rms_from_stats(p, n, rms_out) : 0;
@@ -1563,10 +1513,9 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
   std::memcpy(p->seeds_pin[slot].get(), seeds, n * sizeof(uint64_t));
   RF_HIP(hipMemcpyAsync(p->seeds_dev.get(), p->seeds_pin[slot].get(), n * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipEventRecord(p->seeds_ev[slot], p->stream));
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  RF_HIP(p->tl.begin(p->stream, false));
   RF_HIP(hipGraphLaunch(p->graphs[n].exec, p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->timed = false;
+  RF_HIP(p->tl.end(p->stream));
   field_ready(p, n - 1);
   return rms_out ? rms_from_stats(p, n, rms_out) : 0;
 }
@@ -1631,25 +1580,23 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   hipStream_t s = p->stream;
   const GenParams gp = make_gen(p, seed, mode, false);
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
-  const double n3 = (double)p->nx * (double)p->ny * (double)p->nz, scale = 1.0 / n3;
+  const double n3 = (double)p->nx * (double)p->ny * (double)p->nz, scale = inv_cells(p);
   double *growth = p->lntab.get(), *dens = p->lntab.get() + p->nz, *A = p->lntab.get() + 2 * p->nz, *B = p->lntab.get() + 3 * p->nz, *sig = p->lntab.get() + 4 * p->nz;
-  RF_HIP(hipEventRecord(p->ev[0], s));
-  p->slab_timed = 0;
-  p->slab_merged = 0;
+  Timeline* tl = &p->tl;
+  RF_HIP(tl->begin(s, true));
   // into W, the plain layout whatever RF_FLAG_TRANSPOSED_INTERMEDIATE says: the accumulating y pass runs in place on W
   // (timed: rf_kernel_ms reports x, y + tables, z + map, reduce of this call too)
-  if (int rc = queue_x(p, cd, gp, nullptr, p->W.ptr, s, true)) return rc;
-  RF_HIP(hipEventRecord(p->ev[1], s));
+  if (int rc = queue_x(p, cd, gp, nullptr, p->W.ptr, s, tl)) return rc;
+  RF_HIP(mark(tl, rft::X, s));
   RF_HIP(launch_col_plain_acc(p->f64, p->ny, p->W.ptr, gy, (long long)p->nx * nzl, p->kz0, (int)nzl, p->ypart.get(), p->tw_y.ptr, s));
   // rms = sqrt(S / (nx ny)) / N3  (rf_fft.h AccColIO)
   RF_HIP(launch_lognormal_tables(p->ypart.get(), ntiles, 1.0 / ((double)p->nx * (double)p->ny * n3 * n3), growth, p->ln_density ? dens : nullptr, p->nz,
                                  p->f64 ? 0 : 1, p->f64 ? lognormal_ap_unit<double>(scale) : 1.0, sig, A, B, s));
-  RF_HIP(hipEventRecord(p->ev[2], s));
+  RF_HIP(mark(tl, rft::Y, s));
   RF_HIP(launch_row_c2r_lognormal(p->f64, (int)p->nzc, p->W.ptr, (long long)p->nx * p->ny, scale, A, B, p->tw_z.ptr, p->partials.get(), s));
-  RF_HIP(hipEventRecord(p->ev[3], s));
+  RF_HIP(mark(tl, rft::Z, s));
   RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get(), p->partials.get() + 2 * p->npartials, s));
-  RF_HIP(hipEventRecord(p->ev[4], s));
-  p->timed = true;
+  RF_HIP(tl->end(s));
   field_ready(p, 0);                                 // (the moments of the DENSITY field now)
   p->k_valid = false;
   if (sigma_out) {
@@ -1794,13 +1741,9 @@ int execute_derivative_c2r(rf_plan* p, const P& g, const void* S, int source) {
     return rc;
   }
   // generic plans: the factor is applied by the x pass to the cells it loads (rf_generic.h generic_c2r_from_seq); K, P are only read
-  p->slab_timed = 0;
-  p->slab_merged = 0;
-  p->repair_timed = false;
-  p->timed = true;                                  // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
-  if (int rc = generic_c2r(p, S, p->stats.get(), true, &g)) return rc;
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  RF_HIP(p->tl.begin(p->stream, true));             // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
+  if (int rc = generic_c2r(p, S, p->stats.get(), &p->tl, &g)) return rc;
+  RF_HIP(p->tl.end(p->stream));
   field_ready(p, 0);
   if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
   return 0;
@@ -1876,8 +1819,8 @@ int rf_lpt2_source(rf_plan* p, const double* dk) {
     if (int rc = rf_execute_hessian_c2r(p, c[0], c[1], 1.0, dk[c[0]], dk[c[1]], RF_GRAD_FROM_POTENTIAL)) return rc;
     RF_HIP(launch_lpt2_accumulate(p->f64, c[2], p->W.ptr, T, S, n, p->stream));
   }
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));       // (rf_elapsed_ms: the last component's transform and the last step)
-  p->timed = false;
+  RF_HIP(p->tl.end(p->stream));                      // (rf_elapsed_ms: the last component's transform and the last step ...
+  p->tl.detailed = false;                            // ... which no entry of rf_kernel_ms describes: refused, as it always was)
   p->cur = p->W.ptr;
   p->real_valid = true;
   p->stats_valid = false;
@@ -1896,7 +1839,7 @@ int rf_lpt2_potential(rf_plan* p, const double* dk) {
   if (int rc = rf_lpt2_source(p, dk)) return rc;
   if (int rc = rf_execute_r2c(p)) return rc;
   RF_HIP(launch_save_potential(p->f64, p->K.ptr, p->L.ptr, p->nx, p->ny, p->nz, p->kx2.get(), p->ky2.get(), p->kz2.get(), p->nzl + 1, p->kz0, p->ppitch, p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
+  RF_HIP(p->tl.end(p->stream));
   p->p2_valid = true;
   return 0;
 }
@@ -1922,8 +1865,6 @@ static int particles_copy(rf_plan* p, void* dst, const void* src, size_t bytes, 
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
-// (rf_kernel_ms: this call's events apply, not an earlier call's slabs or repair launch)
-static void particles_reset_timing(rf_plan* p) { p->slab_timed = p->slab_merged = 0; p->repair_timed = false; }
 // the drop counter around a sweep: cleared on the stream before it; copied out after it, the stream drained
 static hipError_t drop_clear(rf_plan* p) { return hipMemsetAsync(p->pa_drop.ptr, 0, 8, p->stream); }
 static int drop_read(rf_plan* p, unsigned long long* dropped) { return particles_copy(p, dropped, p->pa_drop.ptr, 8, hipMemcpyDeviceToHost); }
@@ -1968,17 +1909,15 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
   // 64 against 357 ms of scatter; profiles/paint_bench.log)
   const int form = p->paint_form ? p->paint_form : 2;
   p->pa_valid = false;
-  particles_reset_timing(p);
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  RF_HIP(p->tl.begin(p->stream, true));
   RF_HIP(hipMemsetAsync(p->A.ptr, 0, n * 8, p->stream));
   RF_HIP(drop_clear(p));
-  RF_HIP(hipEventRecord(p->ev[1], p->stream));
+  RF_HIP(p->tl.mark(rft::X, p->stream));
   RF_HIP(launch_cic_paint(p->f64, form, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
-  RF_HIP(hipEventRecord(p->ev[2], p->stream));
+  RF_HIP(p->tl.mark(rft::Y, p->stream));
   RF_HIP(launch_cic_convert(p->f64, (const unsigned long long*)p->A.ptr, p->W.ptr, (long long)n, p->stream));
-  RF_HIP(hipEventRecord(p->ev[3], p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->timed = true;
+  RF_HIP(p->tl.mark(rft::Z, p->stream));
+  RF_HIP(p->tl.end(p->stream));
   p->cur = p->W.ptr;
   p->real_valid = true;
   p->stats_valid = false;
@@ -2020,13 +1959,12 @@ int rf_particles_gather(rf_plan* p, const double* inv_h, int slot, double coeff,
   // cells and 11.2 / 11.1 against 10.1 / 10.1 ms on rms 0.1: it loses 1.1 ms where it loses and wins 15 to 26 ms where it wins, and the
   // displacements' scale is not known without a sweep of its own (profiles/gather_bench.log)
   const int form = p->gather_form ? p->gather_form : 2;
-  particles_reset_timing(p);
   RF_HIP(drop_clear(p));
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  RF_HIP(p->tl.begin(p->stream, true));
   RF_HIP(launch_cic_gather(p->f64, form, p->Q.ptr, p->cur, pg_slot(p, slot), coeff, first, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h,
                            p->stream));
-  for (int i = 1; i <= 4; ++i) RF_HIP(hipEventRecord(p->ev[i], p->stream));
-  p->timed = true;
+  RF_HIP(p->tl.mark(rft::X, p->stream));
+  RF_HIP(p->tl.end(p->stream));
   return drop_read(p, dropped);
 }
 
@@ -2111,7 +2049,7 @@ int measure_bins(rf_plan* p, int source, const double* k_edges, int nbins, DevBu
     }
     tab_dev += clen[a];
   }
-  RF_HIP(hipEventRecord(p->ev[0], p->stream));
+  RF_HIP(p->tl.begin(p->stream, false));
   if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false)) return rc; }     // tiled plans: W packed, no K
   PowerParams& gp = bin_geom(g);
   gp.nx = p->nx; gp.ny = p->ny; gp.nz = p->nz;
@@ -2121,8 +2059,7 @@ int measure_bins(rf_plan* p, int source, const double* k_edges, int nbins, DevBu
   for (size_t i = 1; i < p->h_kz2.size(); ++i) if (!(p->h_kz2[i - 1] <= p->h_kz2[i])) gp.kz_sorted = 0;
   gp.kx2 = p->kx2.get(); gp.ky2 = p->ky2.get(); gp.kz2 = p->kz2.get();
   RF_HIP(launch_bins(p->f64, gp.packed ? p->W.ptr : p->K.ptr, g, e2_dev, part_dev, plane_words, out_dev, p->stream));
-  RF_HIP(hipEventRecord(p->ev[4], p->stream));
-  p->timed = false;
+  RF_HIP(p->tl.end(p->stream));
   std::vector<unsigned long long> out(T.planes * (size_t)nbins);
   RF_HIP(hipMemcpyAsync(out.data(), out_dev, out.size() * 8, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
@@ -2258,49 +2195,21 @@ int rf_sync(rf_plan* p) {
   return 0;
 }
 
+// (the three read-outs refuse before any call and after a call that failed half way: rf_timing.h)
 int rf_elapsed_ms(rf_plan* p, float* ms) {
   RF_REQUIRE(p && ms, "null argument");
-  RF_HIP(hipEventSynchronize(p->ev[4]));
-  RF_HIP(hipEventElapsedTime(ms, p->ev[0], p->ev[4]));
+  RF_REQUIRE(p->tl.complete, "no call of this plan has run to its end: nothing was timed");
+  RF_HIP(p->tl.elapsed(ms));
   return 0;
 }
 
+// ([4]: the x pass of the fast generation is two launches, the few tiles that hold slot kz = 0 -- with the Hermitian repair -- first; they are
+// reported separately so that [0] is the main kernel alone)
 int rf_kernel_ms(rf_plan* p, float* ms5) {
   RF_REQUIRE(p && ms5, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->timed, "per-kernel times are recorded by rf_realise / rf_execute_c2r only");
-  RF_HIP(hipEventSynchronize(p->ev[4]));
-  for (int i = 0; i < 4; ++i) RF_HIP(hipEventElapsedTime(&ms5[i], p->ev[i], p->ev[i + 1]));
-  if (p->slab_merged == 0 && p->slab_timed > 0) {   // y / z passes ran slab by slab, one launch per pass: [1], [2] = the sums over their launches
-    float ys = 0, zs = 0, t = 0;
-    for (int i = 0; i < p->slab_timed; ++i) {
-      RF_HIP(hipEventElapsedTime(&t, i == 0 ? p->ev[1] : p->slab_ev[2 * i - 1], p->slab_ev[2 * i]));
-      ys += t;
-      RF_HIP(hipEventElapsedTime(&t, p->slab_ev[2 * i], p->slab_ev[2 * i + 1]));
-      zs += t;
-    }
-    ms5[1] = ys;
-    ms5[2] = zs;
-    RF_HIP(hipEventElapsedTime(&ms5[3], p->slab_ev[2 * p->slab_timed - 1], p->ev[4]));
-  }
-  if (p->slab_merged > 0) {                // merged launches (rf_set_merged_yz(2)): [1] = the first y launch + every merged launch, [2] = the last z launch
-    float t = 0, ys = 0;
-    RF_HIP(hipEventElapsedTime(&ys, p->ev[1], p->slab_ev[0]));
-    for (int i = 1; i < p->slab_merged; ++i) {
-      RF_HIP(hipEventElapsedTime(&t, p->slab_ev[i - 1], p->slab_ev[i]));
-      ys += t;
-    }
-    ms5[1] = ys;
-    RF_HIP(hipEventElapsedTime(&ms5[2], p->slab_ev[p->slab_merged - 1], p->slab_ev[p->slab_merged]));
-    RF_HIP(hipEventElapsedTime(&ms5[3], p->slab_ev[p->slab_merged], p->ev[4]));
-  }
-  // the x pass of the fast generation is two launches: the few tiles that hold slot kz = 0 (with the Hermitian
-  // repair), then all the others; report them separately so that [0] is the main kernel alone
-  ms5[4] = 0.0f;
-  if (p->repair_timed) {
-    RF_HIP(hipEventElapsedTime(&ms5[4], p->ev[0], p->ev[5]));
-    RF_HIP(hipEventElapsedTime(&ms5[0], p->ev[5], p->ev[1]));
-  }
+  RF_REQUIRE(p->tl.complete && p->tl.detailed, "per-kernel times are recorded by rf_realise / rf_execute_c2r only");
+  RF_HIP(p->tl.report(ms5));
   return 0;
 }
 
@@ -2321,25 +2230,21 @@ int rf_set_merged_yz(rf_plan* p, int mode) {
 // the merged launches of the last timed call under rf_set_merged_yz(2): their summed duration (HIP events on the plan's stream) and number
 int rf_merged_yz_ms(rf_plan* p, float* sum_ms, int* launches) {
   RF_REQUIRE(p && sum_ms && launches, "null argument");
-  RF_REQUIRE(p->timed && p->slab_merged > 1, "the last call was not a timed call with merged y / z launches (rf_set_merged_yz(2), a shape rf_k_yz.hip serves)");
-  RF_HIP(hipEventSynchronize(p->ev[4]));
-  float t = 0, sum = 0;
-  for (int i = 1; i < p->slab_merged; ++i) {
-    RF_HIP(hipEventElapsedTime(&t, p->slab_ev[i - 1], p->slab_ev[i]));
-    sum += t;
-  }
+  float sum = 0;
+  int n = 0;
+  if (p->tl.complete && p->tl.detailed) RF_HIP(p->tl.merged(&sum, &n));
+  RF_REQUIRE(n > 0, "the last call was not a timed call with merged y / z launches (rf_set_merged_yz(2), a shape rf_k_yz.hip serves)");
   *sum_ms = sum;
-  *launches = p->slab_merged - 1;
+  *launches = n;
   return 0;
 }
 
 int rf_yz_slabs(rf_plan* p, int* nslab, int* planes) {
   RF_REQUIRE(p && nslab && planes, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  long long B = yz_slab_planes(p);
-  if (p->X.ptr && xpose_ok(p) && B > 0 && (B % xpose_row_block(p) || (B & (B - 1)) || p->nx % B)) B = 0;
-  *planes = B > 0 ? (int)B : p->nxl;
-  *nslab = B > 0 ? (int)((p->nx + B - 1) / B) : 1;
+  const YzSlabs sl = yz_slabs(p->nx, yz_slab_planes(p), p->X.ptr && xpose_ok(p), xpose_row_block(p));
+  *planes = sl.count > 1 ? sl.planes : p->nxl;
+  *nslab = sl.count;
   return 0;
 }
 

@@ -450,23 +450,22 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   CallDesc cd;
   cd.resident_fast = true;
   auto issue = [&]() -> int {
-    RF_HIP(hipEventRecord(p->ev[0], S));
-    RF_HIP(hipEventRecord(p->bev[1], S));
-    RF_HIP(hipStreamWaitEvent(R, p->bev[1], 0));          // (whatever ran on the main stream before the batch has finished with the runs)
+    RF_HIP(p->tl.begin(S, false));
+    RF_HIP(hop(p->bev[1], S, R));                         // (whatever ran on the main stream before the batch has finished with the runs)
     if (int rc = replay(0)) return rc;
     for (int i = 0; i < n; ++i) {
       RF_HIP(hipStreamWaitEvent(S, p->bev[0], 0));        // the runs of seed i are complete
       p->noise32_resident = true;                         // (queue_x selects the float32-pair kernel by it; cleared again on failure)
       const bool xp = p->X.ptr && xpose_ok(p);
-      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X.ptr : p->W.ptr, S, false)) return rc;
+      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X.ptr : p->W.ptr, S, nullptr)) return rc;
       RF_HIP(hipEventRecord(p->bev[1], S));               // the generation pass of seed i has read the runs
       if (i + 1 < n) {
         RF_HIP(hipStreamWaitEvent(R, p->bev[1], 0));
         if (int rc2 = replay(i + 1)) return rc2;
       }
-      if (int rc3 = queue_yz(p, cd, p->W.ptr, S, p->stats.get() + 2 * i, false)) return rc3;
+      if (int rc3 = queue_yz(p, cd, p->W.ptr, S, p->stats.get() + 2 * i, nullptr)) return rc3;
     }
-    RF_HIP(hipEventRecord(p->ev[4], S));
+    RF_HIP(p->tl.end(S));
     return 0;
   };
   std::vector<unsigned long long> totals((size_t)n);
@@ -493,7 +492,6 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     return drain(rc);
   }
   p->noise32_resident = true;                             // the last seed's deviates, as float32 pairs in the runs
-  p->timed = false;
   field_ready(p, n - 1);
   p->k_valid = false;
   if (rms_out) memcpy(rms_out, rms.data(), (size_t)n * sizeof(double));

@@ -18,6 +18,8 @@
 #include "rf_host.h"
 #include "rf_launch.h"
 #include "rf_owned.h"
+#include "rf_select.h"
+#include "rf_timing.h"
 
 namespace rfc {
 using namespace rf;
@@ -76,6 +78,10 @@ struct HipApi {
   static Error free(void* q) { return hipFree(q); }
   static Error event_create(Event* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
   static Error event_destroy(Event e) { return hipEventDestroy(e); }
+  static constexpr Error not_ready = hipErrorNotReady;      // (rf_timing.h: a read-out before a call has finished)
+  static Error event_record(Event e, Stream s) { return hipEventRecord(e, s); }
+  static Error event_sync(Event e) { return hipEventSynchronize(e); }
+  static Error event_elapsed(float* ms, Event from, Event to) { return hipEventElapsedTime(ms, from, to); }
   static Error stream_create(Stream* s, unsigned flags) { return hipStreamCreateWithFlags(s, flags); }
   static Error stream_destroy(Stream s) { return hipStreamDestroy(s); }
 };
@@ -87,6 +93,18 @@ struct HipPinned : HipApi {
 template <class T = void> using DevBuf = rfo::Buffer<HipApi, T>;
 using Events = rfo::EventList<HipApi>;
 using OwnedStream = rfo::Stream<HipApi>;
+using Timeline = rft::Timeline<HipApi>;
+using rft::Part;
+
+// a mark of the call's timeline where a schedule has one (tl == nullptr: the call is not timed; rf_timing.h)
+inline hipError_t mark(Timeline* tl, Part part, hipStream_t s, hipEvent_t* out = nullptr, bool merged = false) {
+  return tl ? tl->mark(part, s, out, merged) : hipSuccess;
+}
+// stream `to` goes on once stream `from` has come this far
+inline hipError_t hop(hipEvent_t e, hipStream_t from, hipStream_t to) {
+  if (hipError_t r = hipEventRecord(e, from); r != hipSuccess) return r;
+  return hipStreamWaitEvent(to, e, 0);
+}
 
 }  // namespace rfc
 
@@ -141,10 +159,7 @@ struct rf_plan {
   bool sink_delivered = false;            // the last armed call has delivered
   rfc::Events sink_ev;
   rfc::Events bev;                        // rf_realise_batch_reference: replay finished / generation pass has read the runs
-  rfc::Events slab_ev;                    // timed runs: after y(i), after z(i)
-  int slab_timed = 0;                     // slabs of the last timed run (0: whole-grid passes, ev[2] / ev[3] apply)
-  int yz_merge = 1;                       // rf_set_merged_yz: 0 never, 1 untimed calls (default), 2 timed calls too (events per launch)
-  int slab_merged = 0;                    // slabs of the last timed run that used merged launches: slab_ev = after y(0), after every merged launch, after the last z
+  int yz_merge = 1;                       // rf_set_merged_yz: 0 never, 1 untimed calls (default), 2 timed calls too (a mark per launch)
   rfc::DevBuf<> P;                        // lazy: saved potential, API layout, at offset 0 of its allocation (ensure_p)
   size_t w_bytes = 0, k_bytes = 0, p_bytes = 0;      // field buffer, k-space side array, potential array (padded rows)
   int ppitch = 0;                         // cells per row of the potential array: nzl + 1, rounded up to even on float32 plans
@@ -220,8 +235,7 @@ struct rf_plan {
   // fused lognormal realisations (rf_realise_lognormal): [growth nz][density nz][A nz][B nz][sigma 8] and the y pass's Parseval partials
   rfc::DevBuf<double> lntab, ypart;
   bool ln_tables = false, ln_density = false;
-  rfc::Events ev;                      // start, after x, y, z, reduce; [5] = after the kz = 0 repair launch
-  bool repair_timed = false;
+  rfc::Timeline tl;                    // the last call's start, end and marks: rf_elapsed_ms, rf_kernel_ms, rf_merged_yz_ms
   bool aux_valid = false;              // the k buffer's memory currently holds an auxiliary REAL field (lensing potential)
   bool unpacked = false;               // c2c plan: W is the full [nx][ny][nz] complex array, only rf_*_c / rf_execute_c2c apply
   // non-power-of-two grid (rf_generic.h): the transforms run on API-layout arrays, K -> G -> W (generation fused into the x pass only
@@ -234,7 +248,6 @@ struct rf_plan {
   bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; k_valid untouched)
   rfc::DevBuf<> pw_buf;                 // lazy, rf_measure_power: squared edges, result, per-workgroup partials
   rfc::DevBuf<> mp_buf;                 // lazy, rf_measure_multipoles: squared edges, result, compensation tables, per-workgroup partials (counted by rf_plan_nbytes)
-  bool timed = false;
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations
   bool real_valid = false, k_valid = false, stats_valid = false;
@@ -262,12 +275,12 @@ bool xpose_ok(const rf_plan* p);
 int slab_chunks(const rf_plan* p);
 GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev);
 int upload_noise(rf_plan* p, int mode, const double* noise_host);
-int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, bool timed = false, int kz0c = -1, int nzlc = -1);
-int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, bool timed, int rbuf = 0);
+int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, Timeline* tl, int kz0c = -1, int nzlc = -1);
+int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, Timeline* tl, int rbuf = 0);
 int ensure_batch_buffers(rf_plan* p);
 int rebuild_peer_tab(rf_plan* p);
 int direct_barrier(rf_plan* p, hipStream_t s);
-int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, bool timed);
+int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, Timeline* tl);
 int ensure_stats(rf_plan* p, int n);
 int rms_from_stats(rf_plan* p, int n, double* rms_out);
 void field_ready(rf_plan* p, int slot);

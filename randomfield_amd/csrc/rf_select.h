@@ -72,6 +72,19 @@ template <class F> bool for_col_halves(int f64, int N, const ColGeom& g, F&& f) 
   return fit;
 }
 
+// ---- the y / z passes slab by slab: the partition of the nx planes ---------------------------------------------------------------
+// planes: x planes per slab as asked for (<= 0 or >= nx: whole-grid passes); blocked: the x pass left its output in the blocked
+// intermediate, whose slabs are whole x blocks of row_block rows, a power of two of them, dividing nx -- any other size: one slab.
+// The last slab may be smaller.
+struct YzSlabs { int planes, count, last; };      // planes per slab, number of slabs, planes of the last one
+inline YzSlabs yz_slabs(int nx, long long planes, bool blocked, int row_block) {
+  long long B = planes;
+  if (blocked && B > 0 && (B % row_block || (B & (B - 1)) || nx % B)) B = 0;
+  if (B <= 0 || B >= nx) B = nx;
+  const int count = (int)((nx + B - 1) / B);
+  return YzSlabs{(int)B, count, (int)(nx - (long long)(count - 1) * B)};
+}
+
 // ---- the fast generation pass: which kernel variant ------------------------------------------------------------------------------
 // does the pass of this length fit a CU's LDS (tile + twiddles + the generation tables)?  false: float64, N = 2048 (and any N not served)
 inline bool fastgen_supported(int f64, int N) {

@@ -180,12 +180,35 @@ void test_sequences() {
   CHECK(q3.valid && q3.n == 3 && q3.step[1].kind == FAST_COL);
 }
 
+// ---- yz_slabs: the partition of the nx planes for the y / z passes --------------------------------------------------------------------
+bool same(const YzSlabs& a, int planes, int count, int last) { return a.planes == planes && a.count == count && a.last == last; }
+void test_slabs() {
+  CHECK(same(yz_slabs(256, 64, false, 0), 64, 4, 64));          // a size that divides nx
+  CHECK(same(yz_slabs(8, 3, false, 0), 3, 3, 2));               // ... and one that does not: a smaller last slab
+  CHECK(same(yz_slabs(256, 48, false, 0), 48, 6, 16));
+  CHECK(same(yz_slabs(8, 8, false, 0), 8, 1, 8));               // a size >= nx: one slab
+  CHECK(same(yz_slabs(8, 100, false, 0), 8, 1, 8));
+  CHECK(same(yz_slabs(8, 0, false, 0), 8, 1, 8));               // whole-grid passes asked for, or automatic and nothing to gain
+  CHECK(same(yz_slabs(8, -1, false, 0), 8, 1, 8));
+  CHECK(same(yz_slabs(8, 1, false, 0), 1, 8, 1));
+  // the blocked intermediate: whole row blocks, a power of two of them, dividing nx -- else one slab
+  CHECK(same(yz_slabs(256, 64, true, 16), 64, 4, 64));
+  CHECK(same(yz_slabs(256, 16, true, 16), 16, 16, 16));
+  CHECK(same(yz_slabs(256, 24, true, 16), 256, 1, 256));        // not whole row blocks
+  CHECK(same(yz_slabs(256, 48, true, 16), 256, 1, 256));        // whole row blocks, not a power of two
+  CHECK(same(yz_slabs(192, 128, true, 16), 192, 1, 192));       // a power of two of row blocks that does not divide nx
+  CHECK(same(yz_slabs(192, 64, true, 16), 64, 3, 64));
+  CHECK(same(yz_slabs(256, 0, true, 16), 256, 1, 256));
+  CHECK(same(yz_slabs(192, 128, false, 16), 128, 2, 64));       // (the plain layout takes any size)
+}
+
 }  // namespace
 
 int main() {
   test_variants();
   test_halves();
   test_sequences();
+  test_slabs();
   if (g_failed) { std::printf("%d of %d checks FAILED\n", g_failed, g_checked); return 1; }
   std::printf("all checks passed (%d)\n", g_checked);
   return 0;
