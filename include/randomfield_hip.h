@@ -49,7 +49,9 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * And for rf_measure_multipoles, the redshift-space multipole moments of the binned power spectrum with an optional window compensation:
  * rf_abi_features() & RF_FEATURE_POWER_MULTIPOLES, the version stays 5.5.
  * And for the cloud-in-cell gather of a field at the particles and the shift by it -- rf_particles_gather, rf_particles_gather_download,
- * rf_particles_shift: rf_abi_features() & RF_FEATURE_PARTICLES_GATHER, the version stays 5.5. */
+ * rf_particles_shift: rf_abi_features() & RF_FEATURE_PARTICLES_GATHER, the version stays 5.5.
+ * And for the assignment scheme as an argument, with the triangular-shaped cloud as the second scheme -- rf_particles_paint_ex,
+ * rf_particles_gather_ex: rf_abi_features() & RF_FEATURE_PARTICLES_TSC, the version stays 5.5. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -80,8 +82,10 @@ enum {
   RF_FEATURE_PARTICLES = 1 << 17,          /* rf_particles_accumulate, rf_particles_upload, rf_particles_download, rf_particles_paint: the three
                                               displacement components resident on the device, painted back onto the grid (cloud in cell) */
   RF_FEATURE_POWER_MULTIPOLES = 1 << 18,   /* rf_measure_multipoles: the moments of mu^2 behind P0, P2, P4 along a grid axis, window compensation */
-  RF_FEATURE_PARTICLES_GATHER = 1 << 19    /* rf_particles_gather, rf_particles_gather_download, rf_particles_shift: the current real field
+  RF_FEATURE_PARTICLES_GATHER = 1 << 19,   /* rf_particles_gather, rf_particles_gather_download, rf_particles_shift: the current real field
                                               interpolated at the particles (cloud in cell, the paint's adjoint), and the particles moved by it */
+  RF_FEATURE_PARTICLES_TSC = 1 << 20       /* rf_particles_paint_ex, rf_particles_gather_ex: the paint and the gather with the assignment scheme
+                                              as an argument, RF_ASSIGN_CIC or RF_ASSIGN_TSC (triangular-shaped cloud, three cells per axis) */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -371,6 +375,28 @@ int rf_particles_gather_download(rf_plan* plan, int slot, void* host);
 /* Q_axis = fma(coeff, G_slot, Q_axis): the sweep of rf_particles_accumulate(first = 0) with the gathered values in the field's place --
  * coeff rounded once to T, one fused multiply-add per particle.  Refused without displacements or before the first gather. */
 int rf_particles_shift(rf_plan* plan, int axis, int slot, double coeff);
+
+/* ---- particles: the assignment scheme as an argument; triangular-shaped cloud (rf_abi_features() & RF_FEATURE_PARTICLES_TSC) -- */
+/* The scheme's value is its window order p: the power of sinc that rf_measure_multipoles' window compensation divides out of a field
+ * painted with it. */
+enum { RF_ASSIGN_CIC = 2, RF_ASSIGN_TSC = 3 };
+/* rf_particles_paint and rf_particles_gather with the scheme as an argument of the call (no plan state): RF_ASSIGN_CIC is those calls
+ * word for word; any scheme but these two is refused with nothing queued.  The kernel form chosen with the diagnostics' set-form calls
+ * applies to both schemes.  RF_ASSIGN_TSC, per axis: u, the drop rule, c = floor(u), t in [0, 65536] and j0 exactly as for cloud in cell;
+ * then, in integers,
+ *   up = t >= 32768,  tau = up ? t - 32768 : t + 32768 in [0, 65535]   (tau / 65536: the offset from the left edge of the nearest cell)
+ *   jc = up ? (j0 + 1) mod n : j0,  jm = (jc - 1) mod n,  jp = (jc + 1) mod n      (two coincide on an axis shorter than three cells)
+ *   Wm = (65536 - tau)^2 >> 17,  Wp = tau^2 >> 17,  W0 = 65536 - Wm - Wp            (64-bit arithmetic)
+ * -- (1 - s)^2 / 2, 1/2 + s - s^2, s^2 / 2 at s = tau / 65536 to within 1, 2 and 1 units of 2^-16; the three sum to 65536 and
+ * Wp - Wm = tau - 32768 exactly.  Paint: the 27 products W_x W_y W_z (exact, 2^48 per particle) are added to the same grid A with integer
+ * atomics, zero products skipped; delta, rf_particles_download_counts and the LIMIT of rf_particles_paint are unchanged, and the field
+ * is the same bit for bit on every call and kernel form.  Gather: float64, every product and sum rounded on its own,
+ *   lerp3(w, v) = ((double)w_m * v_m + (double)w_0 * v_0) + (double)w_p * v_p
+ * along z first, then y, then x, times 2^-48, then G_slot[q] exactly as rf_particles_gather forms it; zero weights are NOT skipped, a
+ * dropped particle gathers 0.  For an integer-valued W the adjoint identity of rf_particles_gather holds with the TSC paint's A.
+ * Pass window order 3 ('tsc') to the window compensation of a measurement of a TSC-painted field. */
+int rf_particles_paint_ex(rf_plan* plan, const double* inv_h, int scheme, unsigned long long* dropped);
+int rf_particles_gather_ex(rf_plan* plan, const double* inv_h, int scheme, int slot, double coeff, int first, unsigned long long* dropped);
 
 /* ---- binned power spectrum (rf_abi_features() & RF_FEATURE_POWER_MEASURE) -- */
 /* The estimator that closes P(k) -> delta(x) -> P^(k): one sweep of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform

@@ -35,7 +35,7 @@ FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
             "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17, "power_multipoles": 1 << 18,
-            "particles_gather": 1 << 19}
+            "particles_gather": 1 << 19, "particles_tsc": 1 << 20}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -94,6 +94,9 @@ SIGNATURES = {
     "rf_particles_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rf_particles_paint": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_particles_gather": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_particles_paint_ex": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_particles_gather_ex": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_particles_gather_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rf_particles_shift": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
@@ -719,12 +722,16 @@ class DevicePlan(object):
         check(self._lib.rf_particles_download(self._h, int(axis), out.ctypes.data_as(ctypes.c_void_p)), "rf_particles_download")
         return out
 
-    def particles_paint(self, inv_h):
+    def particles_paint(self, inv_h, scheme=2):
         """Cloud-in-cell mass assignment of the displaced lattice particles (rf_particles_paint): delta_cic becomes the current real
-        field; ``inv_h``: the three 1 / (grid spacing).  Returns the number of particles dropped for a non-finite displacement."""
+        field; ``inv_h``: the three 1 / (grid spacing).  ``scheme``: 2 cloud in cell, 3 triangular-shaped cloud
+        (rf_particles_paint_ex).  Returns the number of particles dropped for a non-finite displacement."""
         h = _f64(np.asarray(inv_h, np.float64).reshape(3))
         dropped = ctypes.c_ulonglong(0)
-        check(self._lib.rf_particles_paint(self._h, _dp(h), ctypes.byref(dropped)), "rf_particles_paint")
+        if scheme == 2:
+            check(self._lib.rf_particles_paint(self._h, _dp(h), ctypes.byref(dropped)), "rf_particles_paint")
+        else:
+            check(self._lib.rf_particles_paint_ex(self._h, _dp(h), int(scheme), ctypes.byref(dropped)), "rf_particles_paint_ex")
         return int(dropped.value)
 
     def particles_download_counts(self):
@@ -744,13 +751,18 @@ class DevicePlan(object):
         return tuple(brick), halo.value
 
     # -- particles: the field gathered at the particles, and the shift by it ----
-    def particles_gather(self, inv_h, slot, coeff=1.0, first=True):
+    def particles_gather(self, inv_h, slot, coeff=1.0, first=True, scheme=2):
         """Cloud-in-cell interpolation of the current real field at the displaced lattice particles (rf_particles_gather), the
         paint's adjoint: G_slot = coeff * g (``first``) or G_slot + coeff * g, indexed by the particle's lattice cell; nothing else
-        changes.  Returns the number of particles dropped for a non-finite displacement (they gather 0)."""
+        changes.  ``scheme``: 2 cloud in cell, 3 triangular-shaped cloud (rf_particles_gather_ex).  Returns the number of particles
+        dropped for a non-finite displacement (they gather 0)."""
         h = _f64(np.asarray(inv_h, np.float64).reshape(3))
         dropped = ctypes.c_ulonglong(0)
-        check(self._lib.rf_particles_gather(self._h, _dp(h), int(slot), float(coeff), 1 if first else 0, ctypes.byref(dropped)), "rf_particles_gather")
+        if scheme == 2:
+            check(self._lib.rf_particles_gather(self._h, _dp(h), int(slot), float(coeff), 1 if first else 0, ctypes.byref(dropped)), "rf_particles_gather")
+        else:
+            check(self._lib.rf_particles_gather_ex(self._h, _dp(h), int(scheme), int(slot), float(coeff), 1 if first else 0, ctypes.byref(dropped)),
+                  "rf_particles_gather_ex")
         return int(dropped.value)
 
     def particles_gather_download(self, slot, out=None):

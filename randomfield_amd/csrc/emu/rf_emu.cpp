@@ -737,6 +737,29 @@ template <class Body> void run_threads(int nth, Body body) {
 }
 inline void atomic_add_u64(unsigned long long* p, uint64_t w) { __atomic_fetch_add(p, (unsigned long long)w, __ATOMIC_RELAXED); }
 
+// The assignment scheme of an operation: the per-axis type, how a particle is located, and the rf_core.h functions that visit its cells
+// -- cloud in cell (cic_*, eight cells) or the triangular-shaped cloud (tsc_*, 27), the functions rf_k_particles.hip's policies call.
+struct EmuCic {
+  typedef CicAxis Axis;
+  template <typename T> static bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return cic_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
+  template <class... A> static void scatter_global(A&&... a) { cic_scatter_global(std::forward<A>(a)...); }
+  template <class... A> static void scatter_tiled(A&&... a) { cic_scatter_tiled(std::forward<A>(a)...); }
+  template <class... A> static double gather_global(A&&... a) { return cic_gather_global(std::forward<A>(a)...); }
+  template <class... A> static double gather_tiled(A&&... a) { return cic_gather_tiled(std::forward<A>(a)...); }
+};
+struct EmuTsc {
+  typedef TscAxis Axis;
+  template <typename T> static bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return tsc_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
+  template <class... A> static void scatter_global(A&&... a) { tsc_scatter_global(std::forward<A>(a)...); }
+  template <class... A> static void scatter_tiled(A&&... a) { tsc_scatter_tiled(std::forward<A>(a)...); }
+  template <class... A> static double gather_global(A&&... a) { return tsc_gather_global(std::forward<A>(a)...); }
+  template <class... A> static double gather_tiled(A&&... a) { return tsc_gather_tiled(std::forward<A>(a)...); }
+};
+
 // The two walks of rf_k_particles.hip over an operation Op -- what it does before a brick's particles (prologue), with one particle's
 // eight cells, with a dropped particle and after the brick (epilogue), over a tile of Op::Cell.  cic_global_kernel: one "lane" per particle.
 template <typename T, class Op>
@@ -748,8 +771,8 @@ void cic_walk_global(const CicGrid& g, const T* sx, const T* sy, const T* sz, in
     for (long long i = tid; i < n; i += nth) {
       int ix, iy, iz;
       cic_lattice(i, g.ny, g.nz, ix, iy, iz);
-      CicAxis x, y, z;
-      if (!cic_particle<T>(sx[i], sy[i], sz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++nd; op.dropped(i); continue; }
+      typename Op::Scheme::Axis x, y, z;
+      if (!Op::Scheme::template locate<T>(sx[i], sy[i], sz[i], g, ix, iy, iz, x, y, z)) { ++nd; op.dropped(i); continue; }
       op.particle(i, x, y, z, g);
     }
     if (nd) atomic_add_u64(dropped, nd);
@@ -775,8 +798,8 @@ void cic_walk_bricks(const CicGrid& g, const T* sx, const T* sy, const T* sz, in
           const int iz = t.z0 + lz;
           if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
           const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
-          CicAxis x, y, z;
-          if (!cic_particle<T>(sx[i], sy[i], sz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++nd; op.dropped(i); continue; }
+          typename Op::Scheme::Axis x, y, z;
+          if (!Op::Scheme::template locate<T>(sx[i], sy[i], sz[i], g, ix, iy, iz, x, y, z)) { ++nd; op.dropped(i); continue; }
           op.particle(i, x, y, z, lx, ly, lz, tile, t, g);
         }
       }
@@ -789,18 +812,21 @@ void cic_walk_bricks(const CicGrid& g, const T* sx, const T* sy, const T* sz, in
 }
 
 // PaintOp: the threads add with __atomic operations to the shared accumulator grid and to the brick's shared tile image
+template <class S>
 struct EmuPaintOp {
   typedef unsigned long long Cell;
+  typedef S Scheme;
+  typedef typename S::Axis Axis;
   unsigned long long* A;
   void prologue(Cell* tile, const CicTile& t, const CicGrid&, int tid, int nth) const {
     for (int s = tid; s < t.cells(); s += nth) tile[s] = 0ull;
   }
-  void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, const CicGrid& g) const {
-    cic_scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+  void particle(long long, const Axis& x, const Axis& y, const Axis& z, const CicGrid& g) const {
+    S::scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
   }
-  void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, Cell* tile, const CicTile& t, const CicGrid& g) const {
-    cic_scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { atomic_add_u64(&tile[slot], w); },
-                      [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
+  void particle(long long, const Axis& x, const Axis& y, const Axis& z, int lx, int ly, int lz, Cell* tile, const CicTile& t, const CicGrid& g) const {
+    S::scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { atomic_add_u64(&tile[slot], w); },
+                     [&](long long cell, uint64_t w) { atomic_add_u64(A + cell, w); });
   }
   void dropped(long long) const {}
   void epilogue(Cell* tile, const CicTile& t, const CicGrid& g, int tid, int nth) const {
@@ -810,9 +836,11 @@ struct EmuPaintOp {
 };
 // GatherOp: every particle writes its own element of G, so the threads share nothing but the tile image (filled before a barrier,
 // read-only after it) and the drop counter
-template <typename T>
+template <typename T, class S>
 struct EmuGatherOp {
   typedef T Cell;
+  typedef S Scheme;
+  typedef typename S::Axis Axis;
   const T* W;
   T* G;
   double coeff;
@@ -821,25 +849,28 @@ struct EmuGatherOp {
     for (int s = tid; s < t.cells(); s += nth) tile[s] = W[cic_tile_cell(t, s, g.nx, g.ny, g.nz)];
   }
   void out(long long i, double v) const { G[i] = cic_gather_out<T>(first != 0, coeff, v, first ? (T)0 : G[i]); }
-  void particle(long long i, const CicAxis& x, const CicAxis& y, const CicAxis& z, const CicGrid& g) const {
-    out(i, cic_gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; }));
+  void particle(long long i, const Axis& x, const Axis& y, const Axis& z, const CicGrid& g) const {
+    out(i, S::gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; }));
   }
-  void particle(long long i, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, const Cell* tile, const CicTile& t,
+  void particle(long long i, const Axis& x, const Axis& y, const Axis& z, int lx, int ly, int lz, const Cell* tile, const CicTile& t,
                 const CicGrid& g) const {
-    out(i, cic_gather_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot) { return (double)tile[slot]; }, [&](long long cell) { return (double)W[cell]; }));
+    out(i, S::gather_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot) { return (double)tile[slot]; }, [&](long long cell) { return (double)W[cell]; }));
   }
   void dropped(long long i) const { if (first) G[i] = (T)0; }
   void epilogue(Cell*, const CicTile&, const CicGrid&, int, int) const {}
 };
 // what the tiled paint does with these particles, counted with the kernel's own rule (cic_scatter_tiled) by one thread: particles that
 // leave their brick's tile, their adds straight into A, and the non-zero tile cells the bricks flush
+template <class S>
 struct EmuTileStatsOp {
   typedef unsigned long long Cell;
+  typedef S Scheme;
+  typedef typename S::Axis Axis;
   unsigned long long fallback = 0, fallback_adds = 0, flushed = 0;
   void prologue(Cell* tile, const CicTile& t, const CicGrid&, int, int) { std::fill(tile, tile + t.cells(), 0ull); }
-  void particle(long long, const CicAxis& x, const CicAxis& y, const CicAxis& z, int lx, int ly, int lz, Cell* tile, const CicTile& t, const CicGrid& g) {
+  void particle(long long, const Axis& x, const Axis& y, const Axis& z, int lx, int ly, int lz, Cell* tile, const CicTile& t, const CicGrid& g) {
     const unsigned long long before = fallback_adds;
-    cic_scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { tile[slot] += w; }, [&](long long, uint64_t) { ++fallback_adds; });
+    S::scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { tile[slot] += w; }, [&](long long, uint64_t) { ++fallback_adds; });
     if (fallback_adds != before) ++fallback;
   }
   void dropped(long long) {}
@@ -854,13 +885,35 @@ int particles_walk(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz
   else cic_walk_bricks(g, sx, sy, sz, bx, by, bz, halo, nth, op, dropped);
   return 0;
 }
-template <typename T>
+template <typename T, class S>
 int particles_tile_stats_impl(int nx, int ny, int nz, const T* sx, const T* sy, const T* sz, const double* inv_h, int bx, int by, int bz, int halo,
                               unsigned long long* out4) {
-  EmuTileStatsOp op;
+  EmuTileStatsOp<S> op;
   cic_walk_bricks(CicGrid{nx, ny, nz, {inv_h[0], inv_h[1], inv_h[2]}}, sx, sy, sz, bx, by, bz, halo, 1, op, &out4[3]);
   out4[0] = op.fallback; out4[1] = op.fallback_adds; out4[2] = op.flushed;
   return 0;
+}
+
+// the real type of the arrays chosen at run time, for the entry points with a scheme argument
+template <class S>
+int particles_paint_impl(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int form, int bx, int by,
+                         int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped) {
+  return f64 ? particles_walk(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth, EmuPaintOp<S>{A}, dropped)
+             : particles_walk(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth, EmuPaintOp<S>{A}, dropped);
+}
+template <class S>
+int particles_tile_stats_any(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int bx, int by, int bz,
+                             int halo, unsigned long long* out4) {
+  return f64 ? particles_tile_stats_impl<double, S>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, bx, by, bz, halo, out4)
+             : particles_tile_stats_impl<float, S>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, bx, by, bz, halo, out4);
+}
+template <class S>
+int particles_gather_impl(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, const void* W, void* G,
+                          double coeff, int first, int form, int bx, int by, int bz, int halo, int nth, unsigned long long* dropped) {
+  return f64 ? particles_walk(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth,
+                              EmuGatherOp<double, S>{(const double*)W, (double*)G, coeff, first}, dropped)
+             : particles_walk(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth,
+                              EmuGatherOp<float, S>{(const float*)W, (float*)G, coeff, first}, dropped);
 }
 
 template <typename T>
@@ -1058,35 +1111,59 @@ int emu_lpt2_accumulate(int f64, int step, void* H, void* T, void* S, long long 
 // 64-bit grid A[nx][ny][nz] (cleared here; rf_core.h cic_particle, the functions rf_k_particles.hip calls).  form 1: every particle adds
 // straight into A; form 2: bricks of bx x by x bz cells with a tile of brick + halo each, flushed with wrapped indices.  nth > 1: that many
 // real host threads share A and the tile through atomic adds.  *dropped: particles with a non-finite displacement.
+int emu_particles_paint_ex(int f64, int scheme, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int form,
+                           int bx, int by, int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped);
 int emu_particles_paint(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int form, int bx, int by,
                         int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped) {
+  return emu_particles_paint_ex(f64, 2, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
+}
+// the same with the assignment scheme: 2 cloud in cell, 3 triangular-shaped cloud (rf_core.h tsc_particle, 27 cells under the same walks)
+int emu_particles_paint_ex(int f64, int scheme, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int form,
+                           int bx, int by, int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped) {
+  if (scheme != 2 && scheme != 3) return -1;
   if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && A && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
   if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
   memset(A, 0, (size_t)nx * ny * nz * 8);
-  return f64 ? particles_walk(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth, EmuPaintOp{A}, dropped)
-             : particles_walk(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth, EmuPaintOp{A}, dropped);
+  return scheme == 3 ? particles_paint_impl<EmuTsc>(f64, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped)
+                     : particles_paint_impl<EmuCic>(f64, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
 }
 // the tiled form's traffic for these particles, by the kernel's own rule: out4 = {particles that leave their brick's tile, their adds
 // straight into A, non-zero tile cells flushed, dropped particles}
+int emu_particles_tile_stats_ex(int f64, int scheme, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int bx,
+                                int by, int bz, int halo, unsigned long long* out4);
 int emu_particles_tile_stats(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int bx, int by, int bz,
                              int halo, unsigned long long* out4) {
+  return emu_particles_tile_stats_ex(f64, 2, nx, ny, nz, sx, sy, sz, inv_h, bx, by, bz, halo, out4);
+}
+// the same with the assignment scheme (2, 3): the triangular-shaped cloud's 27 adds per particle and its tighter tile rule
+int emu_particles_tile_stats_ex(int f64, int scheme, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, int bx,
+                                int by, int bz, int halo, unsigned long long* out4) {
+  if (scheme != 2 && scheme != 3) return -1;
   if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && out4) || bx < 1 || by < 1 || bz < 1 || halo < 1) return -1;
-  return f64 ? particles_tile_stats_impl<double>(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, bx, by, bz, halo, out4)
-             : particles_tile_stats_impl<float>(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, bx, by, bz, halo, out4);
+  return scheme == 3 ? particles_tile_stats_any<EmuTsc>(f64, nx, ny, nz, sx, sy, sz, inv_h, bx, by, bz, halo, out4)
+                     : particles_tile_stats_any<EmuCic>(f64, nx, ny, nz, sx, sy, sz, inv_h, bx, by, bz, halo, out4);
 }
 // The cloud-in-cell gather of the dense real field W at the lattice particles displaced by (sx, sy, sz) into G[nx][ny][nz], indexed by
 // the particle's lattice cell (rf_core.h cic_gather_value, the functions rf_k_particles.hip calls): G = (T)(coeff g) (first) or
 // (T)((double)G + coeff g).  form 1: every particle loads its eight cells from W; form 2: bricks of bx x by x bz cells whose tile of W
 // (brick + halo) is really staged in an array and read there.  nth real host threads.  *dropped: particles with a non-finite
 // displacement (they gather 0).
+int emu_particles_gather_ex(int f64, int scheme, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h,
+                            const void* W, void* G, double coeff, int first, int form, int bx, int by, int bz, int halo, int nth,
+                            unsigned long long* dropped);
 int emu_particles_gather(int f64, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h, const void* W, void* G,
                          double coeff, int first, int form, int bx, int by, int bz, int halo, int nth, unsigned long long* dropped) {
+  return emu_particles_gather_ex(f64, 2, nx, ny, nz, sx, sy, sz, inv_h, W, G, coeff, first, form, bx, by, bz, halo, nth, dropped);
+}
+// the same with the assignment scheme (2, 3): rf_core.h tsc_gather_cells, 27 values per particle reduced three at a time
+int emu_particles_gather_ex(int f64, int scheme, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz, const double* inv_h,
+                            const void* W, void* G, double coeff, int first, int form, int bx, int by, int bz, int halo, int nth,
+                            unsigned long long* dropped) {
+  if (scheme != 2 && scheme != 3) return -1;
   if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && W && G && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
   if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
-  return f64 ? particles_walk(nx, ny, nz, (const double*)sx, (const double*)sy, (const double*)sz, inv_h, form, bx, by, bz, halo, nth,
-                              EmuGatherOp<double>{(const double*)W, (double*)G, coeff, first}, dropped)
-             : particles_walk(nx, ny, nz, (const float*)sx, (const float*)sy, (const float*)sz, inv_h, form, bx, by, bz, halo, nth,
-                              EmuGatherOp<float>{(const float*)W, (float*)G, coeff, first}, dropped);
+  return scheme == 3 ? particles_gather_impl<EmuTsc>(f64, nx, ny, nz, sx, sy, sz, inv_h, W, G, coeff, first, form, bx, by, bz, halo, nth, dropped)
+                     : particles_gather_impl<EmuCic>(f64, nx, ny, nz, sx, sy, sz, inv_h, W, G, coeff, first, form, bx, by, bz, halo, nth, dropped);
 }
 // Q = coeff W (first) or Q + coeff W over n elements (rf_core.h particles_axpy, the function the kernel calls per element)
 int emu_particles_accumulate(int f64, int first, double coeff, const void* W, void* Q, long long n) {

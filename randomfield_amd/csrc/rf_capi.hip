@@ -929,7 +929,7 @@ unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
          RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE | RF_FEATURE_LPT2 |
-         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES | RF_FEATURE_PARTICLES_GATHER;
+         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES | RF_FEATURE_PARTICLES_GATHER | RF_FEATURE_PARTICLES_TSC;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1897,9 +1897,13 @@ int rf_particles_download(rf_plan* p, int axis, void* host) {
 }
 
 // A <- 0, the scatter, W <- (double)A 2^-48 - 1.  rf_kernel_ms afterwards: [0] clearing A, [1] the scatter, [2] the conversion, [3] = [4] = 0
-int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* dropped) {
+int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* dropped) { return rf_particles_paint_ex(p, inv_h, RF_ASSIGN_CIC, dropped); }
+
+// the same with the assignment scheme as an argument of the call (RF_ASSIGN_CIC, RF_ASSIGN_TSC); any other is refused with nothing queued
+int rf_particles_paint_ex(rf_plan* p, const double* inv_h, int scheme, unsigned long long* dropped) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(inv_h && dropped, "null argument");
+  RF_REQUIRE(scheme == RF_ASSIGN_CIC || scheme == RF_ASSIGN_TSC, "scheme is RF_ASSIGN_CIC (2) or RF_ASSIGN_TSC (3)");
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
   if (int rc = inv_h_check(inv_h)) return rc;
   RF_HIP(hipSetDevice(p->device));
@@ -1907,13 +1911,15 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
   const size_t n = particle_cells(p);
   // auto: the tiled form, the faster one at 1024^3 and 1000^3 on both displacement scales measured (rms 0.1 and 2 cells: 13 against 208 ms and
   // 64 against 357 ms of scatter; profiles/paint_bench.log)
+  // The triangular-shaped cloud: the tiled form too, 16.3 against 185 ms and 254 against 1200 ms of scatter at 1024^3 (15.9 / 167 and
+  // 253 / 1108 ms at 1000^3), rms 0.1 and 2 cells, spread between rounds below 10 ms (profiles/tsc_bench.log)
   const int form = p->paint_form ? p->paint_form : 2;
   p->pa_valid = false;
   RF_HIP(p->tl.begin(p->stream, true));
   RF_HIP(hipMemsetAsync(p->A.ptr, 0, n * 8, p->stream));
   RF_HIP(drop_clear(p));
   RF_HIP(p->tl.mark(rft::X, p->stream));
-  RF_HIP(launch_cic_paint(p->f64, form, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
+  RF_HIP(launch_cic_paint(p->f64, scheme, form, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
   RF_HIP(p->tl.mark(rft::Y, p->stream));
   RF_HIP(launch_cic_convert(p->f64, (const unsigned long long*)p->A.ptr, p->W.ptr, (long long)n, p->stream));
   RF_HIP(p->tl.mark(rft::Z, p->stream));
@@ -1947,8 +1953,14 @@ int rf_particles_set_paint_form(rf_plan* p, int form) {
 
 // G_slot <- the current real field at the particles (rf_core.h cic_gather_value).  rf_kernel_ms afterwards: [0] the gather, the others 0
 int rf_particles_gather(rf_plan* p, const double* inv_h, int slot, double coeff, int first, unsigned long long* dropped) {
+  return rf_particles_gather_ex(p, inv_h, RF_ASSIGN_CIC, slot, coeff, first, dropped);
+}
+
+// the same with the assignment scheme as an argument of the call (rf_core.h tsc_gather_cells for RF_ASSIGN_TSC)
+int rf_particles_gather_ex(rf_plan* p, const double* inv_h, int scheme, int slot, double coeff, int first, unsigned long long* dropped) {
   if (int rc = particles_check(p, "the cloud-in-cell gather runs on single-rank plans")) return rc;
   RF_REQUIRE(inv_h && dropped, "null argument");
+  RF_REQUIRE(scheme == RF_ASSIGN_CIC || scheme == RF_ASSIGN_TSC, "scheme is RF_ASSIGN_CIC (2) or RF_ASSIGN_TSC (3)");
   RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
   if (int rc = inv_h_check(inv_h)) return rc;
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
@@ -1958,10 +1970,13 @@ int rf_particles_gather(rf_plan* p, const double* inv_h, int slot, double coeff,
   // auto: the tiled form.  At 1024^3 / 1000^3 it takes 13.7 / 13.1 ms against the global form's 28.7 / 39.5 ms on displacements of rms 2
   // cells and 11.2 / 11.1 against 10.1 / 10.1 ms on rms 0.1: it loses 1.1 ms where it loses and wins 15 to 26 ms where it wins, and the
   // displacements' scale is not known without a sweep of its own (profiles/gather_bench.log)
+  // The triangular-shaped cloud: the tiled form too.  At 1024^3 / 1000^3 it takes 22.4 / 20.2 ms against the global form's 67.5 / 69.7 ms
+  // on rms 2 cells and 14.6 / 14.4 against 12.4 / 12.4 ms on rms 0.1 (spread between rounds 0.3 ms there, 2.2 ms at rms 2): it loses
+  // 2.0 to 2.2 ms where it loses and wins 45 to 50 ms where it wins (profiles/tsc_bench.log)
   const int form = p->gather_form ? p->gather_form : 2;
   RF_HIP(drop_clear(p));
   RF_HIP(p->tl.begin(p->stream, true));
-  RF_HIP(launch_cic_gather(p->f64, form, p->Q.ptr, p->cur, pg_slot(p, slot), coeff, first, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h,
+  RF_HIP(launch_cic_gather(p->f64, scheme, form, p->Q.ptr, p->cur, pg_slot(p, slot), coeff, first, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h,
                            p->stream));
   RF_HIP(p->tl.mark(rft::X, p->stream));
   RF_HIP(p->tl.end(p->stream));

@@ -799,6 +799,134 @@ RF_HD double cic_gather_tiled(const CicAxis& x, const CicAxis& y, const CicAxis&
   return cic_gather_value(x, y, z, v);
 }
 
+// ------------------------------- particles: triangular-shaped-cloud (TSC) --
+// The second assignment scheme under the same walks, tile map and accumulator grid: three cells per axis where cloud in cell has two.
+// Per axis everything up to t is cic_axis as it stands (u, the drop rule, c, t in [0, 65536], j0); then, all in integers:
+//   up  = t >= 32768,   tau = up ? t - 32768 : t + 32768  in [0, 65535]    tau / 65536: the particle's offset from the LEFT EDGE of its
+//         nearest cell  (t = 65536, the -2^-54 <= u < 0 case: up = 1, tau = 32768 -- the particle's own cell, in its middle)
+//   jc  = up ? (j0 + 1) mod n : j0,   jm = (jc - 1) mod n,   jp = (jc + 1) mod n   (on an axis shorter than 3 cells two of them coincide;
+//         nothing is special-cased)
+//   Wm  = (65536 - tau)^2 >> 17,   Wp = tau^2 >> 17,   W0 = 65536 - Wm - Wp      (64-bit: the square reaches 2^32)
+// -- (1 - s)^2 / 2, 1/2 + s - s^2 and s^2 / 2 at s = tau / 65536 in units of 2^-16.  Over all t: every weight in [0, 49153], the three
+// sum to 65536 exactly, Wp - Wm = tau - 32768 exactly (the two floors drop the same fraction: the first moment is the quantised position).
+// PAINT: the 27 products W_x W_y W_z (exact in 64 bits, 2^48 per particle) go to the same grid A with the same integer atomics, zero
+// products skipped: cic_delta, the conversion and the 65536-particles-per-cell limit carry over.
+// GATHER: float64, every product and sum rounded on its own, lerp3(w, v) = ((double)wm vm + (double)w0 v0) + (double)wp vp along z first,
+// then y, then x, times 2^-48, then cic_gather_out.  Zero weights are NOT skipped.  Each z row of three values is reduced as soon as it is
+// loaded: at most three a and three b values are live, never 27.
+// TILE RULE: the brick, halo and tile of CicTile; with the lowest cell's offset c_lo = c + up - 1 a particle at local index l uses the tile
+// on an axis when -h <= l + c_lo <= b + h - 3 (float64 comparison, as cic_tile_slot); every particle with |u| < 1.5 stays for h = 2.
+// (Written beside the cloud-in-cell functions, not as one set templated on the cells per axis: those are left verbatim so that their
+// kernels keep their register counts, which the comment at cic_gather_tiled shows to hang on such details.)
+struct TscAxis {
+  double clo;                 // c + up - 1: the whole-cell offset of the lowest of the three cells
+  int j[3];                   // wrapped target indices jm, jc, jp
+  uint32_t w[3];              // their integer weights Wm, W0, Wp; they sum to 65536
+};
+// the three weights of t in [0, 65536]
+RF_HD void tsc_weights(uint32_t t, uint32_t (&w)[3]) {
+  const uint32_t tau = t >= 32768u ? t - 32768u : t + 32768u;
+  const uint64_t r = 65536u - tau;
+  w[0] = (uint32_t)((r * r) >> 17);
+  w[2] = (uint32_t)(((uint64_t)tau * tau) >> 17);
+  w[1] = 65536u - w[0] - w[2];
+}
+RF_HD bool tsc_axis(double s, double inv_h, int i, int n, TscAxis& o) {
+  CicAxis a;
+  if (!cic_axis(s, inv_h, i, n, a)) return false;
+  const bool up = a.w1 >= 32768u;
+  const int jc = up ? a.j1 : a.j0;
+  o.clo = a.c + (up ? 0.0 : -1.0);
+  o.j[0] = jc == 0 ? n - 1 : jc - 1;
+  o.j[1] = jc;
+  o.j[2] = jc + 1 == n ? 0 : jc + 1;
+  tsc_weights(a.w1, o.w);
+  return true;
+}
+// the three axes of one particle; false: dropped
+template <typename T>
+RF_HD bool tsc_particle(T sx, T sy, T sz, const double* inv_h, int ix, int iy, int iz, int nx, int ny, int nz, TscAxis& x, TscAxis& y, TscAxis& z) {
+  const bool okx = tsc_axis((double)sx, inv_h[0], ix, nx, x), oky = tsc_axis((double)sy, inv_h[1], iy, ny, y), okz = tsc_axis((double)sz, inv_h[2], iz, nz, z);
+  return okx && oky && okz;
+}
+// tile slot of the lowest cell along one axis for the particle at local index li (slot + 1 and slot + 2 are then inside too), or -1
+RF_HD int tsc_tile_slot(const TscAxis& a, int li, int b, int h) {
+  const double lo = (double)li + a.clo;
+  return (lo >= (double)-h && lo <= (double)(b + h - 3)) ? (int)lo + h : -1;
+}
+// the 27 cells of one particle: f(weight product, cell(cx, cy, cz)) with c = 0, 1, 2 for m, 0, p
+template <class Cell, class Add>
+RF_HD void tsc_scatter_cells(const TscAxis& x, const TscAxis& y, const TscAxis& z, Cell&& cell, Add&& add) {
+#pragma unroll
+  for (int cx = 0; cx < 3; ++cx) {
+#pragma unroll
+    for (int cy = 0; cy < 3; ++cy) {
+      const uint64_t wxy = (uint64_t)x.w[cx] * (uint64_t)y.w[cy];
+#pragma unroll
+      for (int cz = 0; cz < 3; ++cz) {
+        const uint64_t w = wxy * (uint64_t)z.w[cz];
+        if (w) add(cell(cx, cy, cz), w);
+      }
+    }
+  }
+}
+// the 27 adds of one particle straight into A: add(cell index, weight)
+template <class Add>
+RF_HD void tsc_scatter_global(const TscAxis& x, const TscAxis& y, const TscAxis& z, int ny, int nz, Add&& add) {
+  tsc_scatter_cells(x, y, z, [&](int cx, int cy, int cz) { return ((long long)x.j[cx] * ny + y.j[cy]) * nz + z.j[cz]; }, add);
+}
+// the tiled form: into the tile when all 27 cells fall inside it (add_tile(slot, weight)), otherwise as tsc_scatter_global
+template <class AddTile, class AddGlobal>
+RF_HD void tsc_scatter_tiled(const TscAxis& x, const TscAxis& y, const TscAxis& z, int lx, int ly, int lz, const CicTile& t, int ny, int nz,
+                             AddTile&& add_tile, AddGlobal&& add_global) {
+  const int sx = tsc_tile_slot(x, lx, t.bx, t.h), sy = tsc_tile_slot(y, ly, t.by, t.h), sz = tsc_tile_slot(z, lz, t.bz, t.h);
+  if (sx < 0 || sy < 0 || sz < 0) { tsc_scatter_global(x, y, z, ny, nz, add_global); return; }
+  const int py = t.tz(), px = t.ty() * py, base = sx * px + sy * py + sz;
+  tsc_scatter_cells(x, y, z, [&](int cx, int cy, int cz) { return base + cx * px + cy * py + cz; }, add_tile);
+}
+RF_HD double tsc_lerp3(const uint32_t (&w)[3], double vm, double v0, double vp) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const double pm = (double)w[0] * vm, p0 = (double)w[1] * v0, pp = (double)w[2] * vp;
+  const double s = pm + p0;
+  return s + pp;
+#else
+  volatile double pm = (double)w[0] * vm, p0 = (double)w[1] * v0, pp = (double)w[2] * vp;
+  volatile double s = pm + p0;
+  return s + pp;
+#endif
+}
+// g of the 27 values load(cx, cy, cz): a z row of three is reduced as it arrives, three rows make a b, three b make g
+template <class Load>
+RF_HD double tsc_gather_cells(const TscAxis& x, const TscAxis& y, const TscAxis& z, Load&& load) {
+  double b[3];
+#pragma unroll
+  for (int cx = 0; cx < 3; ++cx) {
+    double a[3];
+#pragma unroll
+    for (int cy = 0; cy < 3; ++cy) {
+      const double vm = load(cx, cy, 0), v0 = load(cx, cy, 1), vp = load(cx, cy, 2);
+      a[cy] = tsc_lerp3(z.w, vm, v0, vp);
+    }
+    b[cx] = tsc_lerp3(y.w, a[0], a[1], a[2]);
+  }
+  return tsc_lerp3(x.w, b[0], b[1], b[2]) * (1.0 / 281474976710656.0);
+}
+// the 27 loads of one particle straight from W: load(cell index) -> double
+template <class Load>
+RF_HD double tsc_gather_global(const TscAxis& x, const TscAxis& y, const TscAxis& z, int ny, int nz, Load&& load) {
+  return tsc_gather_cells(x, y, z, [&](int cx, int cy, int cz) { return load(((long long)x.j[cx] * ny + y.j[cy]) * nz + z.j[cz]); });
+}
+// the tiled form: from the tile image when all 27 cells fall inside it (load_tile(slot) -> double), otherwise as tsc_gather_global
+template <class LoadTile, class LoadGlobal>
+RF_HD double tsc_gather_tiled(const TscAxis& x, const TscAxis& y, const TscAxis& z, int lx, int ly, int lz, const CicTile& t, int ny, int nz,
+                              LoadTile&& load_tile, LoadGlobal&& load_global) {
+  const int sx = tsc_tile_slot(x, lx, t.bx, t.h), sy = tsc_tile_slot(y, ly, t.by, t.h), sz = tsc_tile_slot(z, lz, t.bz, t.h);
+  if (sx < 0 || sy < 0 || sz < 0) return tsc_gather_global(x, y, z, ny, nz, load_global);
+  const int py = t.tz(), px = t.ty() * py, base = sx * px + sy * py + sz;
+  return tsc_gather_cells(x, y, z, [&](int cx, int cy, int cz) { return load_tile(base + cx * px + cy * py + cz); });
+}
+
 // ------------------------------------------------- fast native generation --
 // float32 plans with the native RNG do rows K,T,R,S entirely in float32: the
 // values are this repo's own definition (checked against the oracle's

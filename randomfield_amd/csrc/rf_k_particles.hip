@@ -6,6 +6,8 @@
 //             addition is associative, so the accumulator holds the same bits for every launch shape, either form and every run.  No
 //             floating-point atomics.
 //   GatherOp  the scatter's adjoint (rf_core.h cic_gather_value): the field gathered at the particles, no atomics but the drop counter's.
+// The operation also names the assignment scheme -- its per-axis type (Op::Axis) and how a particle is located (Op::locate): cloud in
+// cell for these two, the triangular-shaped cloud (27 cells, rf_core.h tsc_*) for TscPaintOp / TscGatherOp, which inherit the rest.
 #include "rf_kernels.h"
 #include "rf_launch.h"
 
@@ -31,7 +33,11 @@ extern __shared__ __attribute__((aligned(16))) u64 cic_lds[];
 template <typename T>
 struct PaintOp {
   typedef u64 Cell;
+  typedef CicAxis Axis;
   u64* __restrict__ A;
+  static __device__ bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return cic_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
   __device__ void prologue(const CicTile&, const CicGrid&, int tid) const {
     for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) cic_lds[s] = 0ull;
   }
@@ -61,11 +67,15 @@ struct PaintOp {
 template <typename T>
 struct GatherOp {
   typedef T Cell;
+  typedef CicAxis Axis;
   const T* __restrict__ W;
   T* __restrict__ G;
   double coeff;
   int first;
   static __device__ T* tile() { return reinterpret_cast<T*>(cic_lds); }
+  static __device__ bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return cic_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
   __device__ void prologue(const CicTile& t, const CicGrid& g, int tid) const {
     __builtin_assume(tid >= 0 && tid < CIC_NT);        // (as in PaintOp::epilogue)
     for (int s = tid; s < CIC_TILE_CELLS; s += CIC_NT) tile()[s] = W[cic_tile_cell(t, s, g.nx, g.ny, g.nz)];
@@ -81,6 +91,42 @@ struct GatherOp {
   }
   __device__ void dropped(long long i) const { if (first) G[i] = (T)0; }
   __device__ void epilogue(const CicTile&, const CicGrid&, int) const {}
+};
+
+// The same two operations with the triangular-shaped cloud (rf_core.h tsc_axis ... tsc_gather_tiled): 27 cells per particle where cloud
+// in cell has eight.  The tile, its clearing, staging and flush are the cloud-in-cell operations' own; only what happens with one
+// particle differs.
+template <typename T>
+struct TscPaintOp : PaintOp<T> {
+  typedef TscAxis Axis;
+  static __device__ bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return tsc_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
+  __device__ void particle(long long, const Axis& x, const Axis& y, const Axis& z, const CicGrid& g) const {
+    u64* A = this->A;
+    tsc_scatter_global(x, y, z, g.ny, g.nz, [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+  }
+  __device__ void particle(long long, const Axis& x, const Axis& y, const Axis& z, int lx, int ly, int lz, const CicTile& t, const CicGrid& g) const {
+    u64* A = this->A;
+    tsc_scatter_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot, uint64_t w) { atomicAdd(&cic_lds[slot], (u64)w); },
+                      [&](long long cell, uint64_t w) { atomicAdd(A + cell, (u64)w); });
+  }
+};
+template <typename T>
+struct TscGatherOp : GatherOp<T> {
+  typedef TscAxis Axis;
+  static __device__ bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return tsc_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
+  __device__ void particle(long long i, const Axis& x, const Axis& y, const Axis& z, const CicGrid& g) const {
+    const T* W = this->W;
+    this->out(i, tsc_gather_global(x, y, z, g.ny, g.nz, [&](long long cell) { return (double)W[cell]; }));
+  }
+  __device__ void particle(long long i, const Axis& x, const Axis& y, const Axis& z, int lx, int ly, int lz, const CicTile& t, const CicGrid& g) const {
+    const T* W = this->W;
+    this->out(i, tsc_gather_tiled(x, y, z, lx, ly, lz, t, g.ny, g.nz, [&](int slot) { return (double)GatherOp<T>::tile()[slot]; },
+                                  [&](long long cell) { return (double)W[cell]; }));
+  }
 };
 
 // the wave's dropped particles -> one integer atomic (nothing when the wave dropped none)
@@ -102,8 +148,8 @@ __global__ __launch_bounds__(256) void cic_global_kernel(const T* __restrict__ Q
     if (i >= n) continue;
     int ix, iy, iz;
     cic_lattice(i, g.ny, g.nz, ix, iy, iz);
-    CicAxis x, y, z;
-    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; op.dropped(i); continue; }
+    typename Op::Axis x, y, z;
+    if (!Op::locate(Qx[i], Qy[i], Qz[i], g, ix, iy, iz, x, y, z)) { ++ndrop; op.dropped(i); continue; }
     op.particle(i, x, y, z, g);
   }
   cic_count_dropped(ndrop, dropped);
@@ -124,8 +170,8 @@ __global__ __launch_bounds__(CIC_NT) void cic_tiled_kernel(const T* __restrict__
     const int lx = row / CIC_BY, ly = row - lx * CIC_BY, ix = t.x0 + lx, iy = t.y0 + ly;
     if (ix >= g.nx || iy >= g.ny || iz >= g.nz) continue;
     const long long i = ((long long)ix * g.ny + iy) * g.nz + iz;
-    CicAxis x, y, z;
-    if (!cic_particle<T>(Qx[i], Qy[i], Qz[i], g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z)) { ++ndrop; op.dropped(i); continue; }
+    typename Op::Axis x, y, z;
+    if (!Op::locate(Qx[i], Qy[i], Qz[i], g, ix, iy, iz, x, y, z)) { ++ndrop; op.dropped(i); continue; }
     op.particle(i, x, y, z, lx, ly, lane, t, g);
   }
   op.epilogue(t, g, tid);
@@ -192,9 +238,14 @@ hipError_t cic_launch(int form, const T* Q, const Op& op, u64* dropped, int nx, 
 
 }  // namespace
 
-hipError_t launch_cic_gather(int f64, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
+hipError_t launch_cic_gather(int f64, int scheme, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
                              int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
   if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
+  if (scheme == 3) {
+    return f64 ? cic_launch(form, (const double*)Q, TscGatherOp<double>{{(const double*)W, (double*)G_slot, coeff, first}}, dropped, nx, ny, nz, inv_h, s)
+               : cic_launch(form, (const float*)Q, TscGatherOp<float>{{(const float*)W, (float*)G_slot, coeff, first}}, dropped, nx, ny, nz, inv_h, s);
+  }
+  if (scheme != 2) return hipErrorInvalidValue;
   return f64 ? cic_launch(form, (const double*)Q, GatherOp<double>{(const double*)W, (double*)G_slot, coeff, first}, dropped, nx, ny, nz, inv_h, s)
              : cic_launch(form, (const float*)Q, GatherOp<float>{(const float*)W, (float*)G_slot, coeff, first}, dropped, nx, ny, nz, inv_h, s);
 }
@@ -204,9 +255,14 @@ hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double c
              : particles_accumulate_t<float, 4>((const float*)W, (float*)Q, coeff, first, n, s);
 }
 
-hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
+hipError_t launch_cic_paint(int f64, int scheme, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
                             const double* inv_h, hipStream_t s) {
   if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
+  if (scheme == 3) {
+    return f64 ? cic_launch(form, (const double*)Q, TscPaintOp<double>{{A}}, dropped, nx, ny, nz, inv_h, s)
+               : cic_launch(form, (const float*)Q, TscPaintOp<float>{{A}}, dropped, nx, ny, nz, inv_h, s);
+  }
+  if (scheme != 2) return hipErrorInvalidValue;
   return f64 ? cic_launch(form, (const double*)Q, PaintOp<double>{A}, dropped, nx, ny, nz, inv_h, s)
              : cic_launch(form, (const float*)Q, PaintOp<float>{A}, dropped, nx, ny, nz, inv_h, s);
 }

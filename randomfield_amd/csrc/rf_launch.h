@@ -153,7 +153,8 @@ hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double c
 // the cloud-in-cell scatter of the lattice particles displaced by Q[3][nx][ny][nz] into the CLEARED 64-bit accumulator grid A
 // (rf_core.h cic_particle; PaintOp over cic_global_kernel / cic_tiled_kernel): form 1 = global atomics, form 2 = LDS tiles flushed with
 // global atomics; *dropped (cleared by the caller) counts the particles with a non-finite displacement.  Same A from both forms.
-hipError_t launch_cic_paint(int f64, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
+// scheme: 2 = cloud in cell, 3 = triangular-shaped cloud (rf_core.h tsc_particle; TscPaintOp over the same walks, tile and launcher).
+hipError_t launch_cic_paint(int f64, int scheme, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
                             const double* inv_h, hipStream_t s);
 // the brick (cells per axis) and the halo of form 2's tile
 void cic_paint_geometry(int* brick3, int* halo);
@@ -161,8 +162,8 @@ void cic_paint_geometry(int* brick3, int* halo);
 // by Q[3][nx][ny][nz] into G_slot[nx][ny][nz], indexed by the particle's lattice cell: G = (T)(coeff g) (first != 0) or
 // (T)((double)G + coeff g).  GatherOp over the paint's two walks: form 1 = eight loads per particle from memory, form 2 = the paint's
 // tile of W staged in LDS; the same bits from both.  *dropped (cleared by the caller) counts the particles with a non-finite displacement: they gather 0.  W and G_slot must
-// not overlap.
-hipError_t launch_cic_gather(int f64, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
+// not overlap.  scheme: 2 = cloud in cell, 3 = triangular-shaped cloud (rf_core.h tsc_gather_cells; TscGatherOp, 27 loads per particle).
+hipError_t launch_cic_gather(int f64, int scheme, int form, const void* Q, const void* W, void* G_slot, double coeff, int first, unsigned long long* dropped,
                              int nx, int ny, int nz, const double* inv_h, hipStream_t s);
 // W = (double)A 2^-48 - 1, rounded once to the real type (rf_core.h cic_delta)
 hipError_t launch_cic_convert(int f64, const unsigned long long* A, void* W, long long n, hipStream_t s);

@@ -30,6 +30,14 @@ from . import random as rf_random
 __all__ = ["Generator"]
 
 
+def _assignment_order(assignment):
+    """the cells per axis (the window order) of a mass-assignment scheme's name"""
+    orders = {"cic": 2, "tsc": 3}
+    if assignment not in orders:
+        raise ValueError("Invalid assignment: {0!r} (expected 'cic' or 'tsc').".format(assignment))
+    return orders[assignment]
+
+
 class _DevicePotential(object):
     """Marker for a saved delta(k)/k**2 field that lives in device memory."""
 
@@ -855,7 +863,7 @@ class Generator(object):
             out[axis] = np.mod(q * h + Q[axis].astype(np.float64), n * h)
         return out
 
-    def paint_particles(self, download=True):
+    def paint_particles(self, download=True, *, assignment="cic"):
         """
         Cloud-in-cell mass assignment of the displaced particles onto the grid: delta_cic = (mass per cell) - 1 becomes the current
         field, so ``measure_power_spectrum()`` with no argument measures the particles.  The weights are integers in units of
@@ -863,21 +871,27 @@ class Generator(object):
         ``rf_particles_paint``, integer atomics).  Particles with a non-finite displacement are dropped and counted in
         ``self.particles_dropped``.  Fewer than 65536 particles' worth of mass may land in one cell.  Returns the field, or None
         with ``download=False``.
+
+        ``assignment``: ``'cic'`` (two cells per axis) or ``'tsc'``, the triangular-shaped cloud over three cells per axis with
+        integer weights of the same unit (``particles.py``; hip backend: ``rf_particles_paint_ex``), bit for bit the same on both
+        backends.  Pass the same name as ``window=`` to :meth:`measure_power_spectrum` / :meth:`measure_power_multipoles` to divide
+        the assignment window out of the painted field: ``window='cic'`` after ``assignment='cic'``, ``window='tsc'`` after ``'tsc'``.
         """
+        order = _assignment_order(assignment)
         if self._particles is None:
             raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
         inv_h = [1.0 / float(self.grid_spacing_Mpc_h)] * 3
         if self.backend == "numpy":
             from . import particles
-            A, self.particles_dropped = particles.paint_counts(self._particles, inv_h)
+            A, self.particles_dropped = particles.paint_counts(self._particles, inv_h, order)
             self.plan_c2r.data_out[...] = particles.counts_to_delta(A, self.plan_c2r.data_out.dtype)
             self._field_on_host = True
             return self.plan_c2r.data_out if download else None
-        self.particles_dropped = self.plan_c2r.device.particles_paint(inv_h)
+        self.particles_dropped = self.plan_c2r.device.particles_paint(inv_h, order)
         self._field_on_host = False
         return self.download_field() if download else None
 
-    def interpolate_at_particles(self, field=None, *, slot=0, coeff=1.0, first=True, download=True):
+    def interpolate_at_particles(self, field=None, *, slot=0, coeff=1.0, first=True, download=True, assignment="cic"):
         """
         Cloud-in-cell interpolation of a field at the displaced particles, the adjoint of :meth:`paint_particles` over the same
         cells and integer weights: what carries a grid field -- a force component, a reconstruction displacement, the density --
@@ -892,7 +906,13 @@ class Generator(object):
         gathers 0 and is counted in ``self.particles_dropped``.  The gathered values are kept until the next field is generated, as
         the displacements are.  Returns a new ``(nx, ny, nz)`` array indexed by the particle's lattice cell, or None with
         ``download=False``.
+
+        ``assignment``: ``'cic'`` or ``'tsc'``, the kernel of :meth:`paint_particles` with the same name (hip backend:
+        ``rf_particles_gather_ex``).  Gathering with the kernel the density was painted with puts the same window on both legs (no
+        self-force); a field measured from that painted density takes ``window=`` of the same name in
+        :meth:`measure_power_spectrum` / :meth:`measure_power_multipoles`.
         """
+        order = _assignment_order(assignment)
         if self.distributed:
             raise NotImplementedError("particles live on single-GPU plans (distributed=False).")
         if slot not in (0, 1, 2):
@@ -906,10 +926,10 @@ class Generator(object):
             from . import particles
             if self._gathered is None:
                 self._gathered = np.zeros((3,) + tuple(self.plan_c2r.shape), self.plan_c2r.data_out.dtype)
-            _, self.particles_dropped = particles.gather(self._particles, inv_h, self.plan_c2r.data_out, coeff, first, self._gathered[slot])
+            _, self.particles_dropped = particles.gather(self._particles, inv_h, self.plan_c2r.data_out, coeff, first, self._gathered[slot], order)
             return self._gathered[slot].copy() if download else None
         dev = self.plan_c2r.device
-        self.particles_dropped = dev.particles_gather(inv_h, slot, coeff, first)
+        self.particles_dropped = dev.particles_gather(inv_h, slot, coeff, first, order)
         self._gathered = True
         return dev.particles_gather_download(slot) if download else None
 

@@ -13,7 +13,11 @@ xor-folded checksum of the downloaded slot is compared once per case.
 Algorithmic bytes of a gather: the three displacement components and the field read, the slot written = 5 arrays of the plan's real
 type (21.5 GB at 1024^3 complex64); printed per form as a rate and as a fraction of 8 TB/s.
 
-usage: gather_bench.py [--f64] [--rounds N] [--rms A,B] [edge | NXxNYxNZ ...]    (default: 1024 and 1000, complex64, rms 0.1 and 2, 7 rounds)"""
+--scheme cic|tsc|cic,tsc: the assignment scheme(s), rf_particles_gather_ex; with several, every round gathers under each scheme and form
+in turn, so the unchanged cloud-in-cell kernels are the yardstick of the same run (the paint that closes a round stays cloud in cell).
+
+usage: gather_bench.py [--f64] [--rounds N] [--rms A,B] [--scheme S[,S]] [edge | NXxNYxNZ ...]
+       (default: 1024 and 1000, complex64, rms 0.1 and 2, 7 rounds, cic)"""
 import os
 import sys
 
@@ -25,6 +29,7 @@ from randomfield_amd import _hip, powertools      # noqa: E402
 SPACING = 2.5
 INV_H = [1.0 / SPACING] * 3
 FORMS = ((1, "global"), (2, "tiled "))
+SCHEMES = {"cic": 2, "tsc": 3}                      # name -> RF_ASSIGN_*: the cells per axis
 PEAK_TBS = 8.0
 
 
@@ -42,51 +47,56 @@ def white_plan(shape, ct, rms_cells):
     return plan
 
 
-def run_case(shape, ct, rms, rounds):
+def run_case(shape, ct, rms, rounds, schemes):
     plan = white_plan(shape, ct, rms)
-    gather = {f: [] for f, name in FORMS}
+    gather = {(s, f): [] for s in schemes for f, name in FORMS}
     scatter = []
     dropped = 0
     for r in range(rounds + 1):                    # (the first round warms up: lazy allocations, LDS attributes)
-        for form, name in FORMS:
-            plan.set_gather_form(form)
-            dropped = plan.particles_gather(INV_H, 0, 1.0, True)
-            gather[form].append(plan.kernel_ms()[0])
+        for scheme in schemes:
+            for form, name in FORMS:
+                plan.set_gather_form(form)
+                dropped = plan.particles_gather(INV_H, 0, 1.0, True, SCHEMES[scheme])
+                gather[scheme, form].append(plan.kernel_ms()[0])
         plan.particles_paint(INV_H)
         scatter.append(plan.kernel_ms()[1])
-    head = "%-20s %-10s rms %-4g " % (shape, np.dtype(ct).name, rms)
+    head0 = "%-20s %-10s rms %-4g " % (shape, np.dtype(ct).name, rms)
     cells = float(np.prod(shape))
     nbytes = 5 * cells * (8 if ct == np.complex128 else 4)
     paint = scatter[1:]
-    print(head + "paint's scatter (its own choice of form)   %8.3f ms (min %.3f max %.3f, %d rounds)"
+    print(head0 + "paint's scatter (its own choice of form)   %8.3f ms (min %.3f max %.3f, %d rounds)"
           % (np.median(paint), min(paint), max(paint), len(paint)), flush=True)
     med = {}
-    for form, name in FORMS:
-        g = gather[form][1:]
-        med[form] = float(np.median(g))
-        rate = nbytes / max(med[form], 1e-9) / 1e9
-        print(head + "gather form %d %s                      %8.3f ms (min %.3f max %.3f, %d rounds) = %.3f x the scatter; "
-              "%.2f GB algorithmic = %.2f TB/s = %.1f %% of %g TB/s"
-              % (form, name, med[form], min(g), max(g), len(g), med[form] / np.median(paint), nbytes / 1e9, rate, 100 * rate / PEAK_TBS, PEAK_TBS),
-              flush=True)
-    spread = max(max(gather[f][1:]) - min(gather[f][1:]) for f, name in FORMS)
-    print(head + "tiled / global = %.3f; global - tiled = %.3f ms against a spread between rounds of %.3f ms; dropped %d; plan holds %.2f GB"
-          % (med[2] / med[1], med[1] - med[2], spread, dropped, plan.nbytes / 1e9), flush=True)
-    sums = []
-    for form, name in FORMS:
-        plan.set_gather_form(form)
-        plan.particles_gather(INV_H, 0, 1.0, True)
-        G = plan.particles_gather_download(0)
-        bits = G.view(np.uint64 if G.dtype == np.float64 else np.uint32).ravel()
-        sums.append((int(np.bitwise_xor.reduce(bits)), int(bits.sum(dtype=np.uint64))))
-        del G, bits
-    print(head + "gathered values of the two forms %s (xor %x)" % ("EQUAL" if sums[0] == sums[1] else "DIFFER", sums[0][0]), flush=True)
+    for scheme in schemes:
+        head = head0 + scheme + " "
+        for form, name in FORMS:
+            g = gather[scheme, form][1:]
+            med[scheme, form] = float(np.median(g))
+            rate = nbytes / max(med[scheme, form], 1e-9) / 1e9
+            print(head + "gather form %d %s                      %8.3f ms (min %.3f max %.3f, %d rounds) = %.3f x the scatter; "
+                  "%.2f GB algorithmic = %.2f TB/s = %.1f %% of %g TB/s"
+                  % (form, name, med[scheme, form], min(g), max(g), len(g), med[scheme, form] / np.median(paint), nbytes / 1e9, rate,
+                     100 * rate / PEAK_TBS, PEAK_TBS), flush=True)
+        spread = max(max(gather[scheme, f][1:]) - min(gather[scheme, f][1:]) for f, name in FORMS)
+        print(head + "tiled / global = %.3f; global - tiled = %.3f ms against a spread between rounds of %.3f ms; dropped %d; plan holds %.2f GB"
+              % (med[scheme, 2] / med[scheme, 1], med[scheme, 1] - med[scheme, 2], spread, dropped, plan.nbytes / 1e9), flush=True)
+        sums = []
+        for form, name in FORMS:
+            plan.set_gather_form(form)
+            plan.particles_gather(INV_H, 0, 1.0, True, SCHEMES[scheme])
+            G = plan.particles_gather_download(0)
+            bits = G.view(np.uint64 if G.dtype == np.float64 else np.uint32).ravel()
+            sums.append((int(np.bitwise_xor.reduce(bits)), int(bits.sum(dtype=np.uint64))))
+            del G, bits
+        print(head + "gathered values of the two forms %s (xor %x)" % ("EQUAL" if sums[0] == sums[1] else "DIFFER", sums[0][0]), flush=True)
+    if "cic" in schemes and "tsc" in schemes:
+        print(head0 + "tsc / cic gather: global %.3f, tiled %.3f" % (med["tsc", 1] / med["cic", 1], med["tsc", 2] / med["cic", 2]), flush=True)
     plan.close()
 
 
 def main(argv):
     ct = np.complex128 if "--f64" in argv else np.complex64
-    opts = {"--rounds": "7", "--rms": "0.1,2"}
+    opts = {"--rounds": "7", "--rms": "0.1,2", "--scheme": "cic"}
     skip = set()
     for name in opts:
         if name in argv:
@@ -97,9 +107,12 @@ def main(argv):
         if a.startswith("--") or i in skip:
             continue
         shapes.append(tuple(int(v) for v in a.split("x")) if "x" in a else (int(a),) * 3)
+    schemes = opts["--scheme"].split(",")
+    if not schemes or any(s not in SCHEMES for s in schemes):
+        sys.exit("--scheme takes cic, tsc or cic,tsc")
     for shape in shapes or [(1024,) * 3, (1000,) * 3]:
         for rms in [float(v) for v in opts["--rms"].split(",")]:
-            run_case(shape, ct, rms, int(opts["--rounds"]))
+            run_case(shape, ct, rms, int(opts["--rounds"]), schemes)
 
 
 if __name__ == "__main__":
