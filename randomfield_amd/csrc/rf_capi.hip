@@ -129,14 +129,14 @@ GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev) {
 
 int ensure_noise(rf_plan* p) {
   const size_t need = 2 * (size_t)p->nx * p->ny * (p->nzl + 1) * sizeof(double);       // this rank's planes + the Nyquist plane
-  if (p->noise.bytes < need) p->noise_resident = false;
+  if (p->noise.bytes < need) p->has.deviates64_dropped();
   RF_HIP(p->noise.reserve(need));
   return 0;
 }
 
 int upload_noise(rf_plan* p, int mode, const double* noise_host) {
   if (mode == RF_NOISE_RESIDENT) {
-    RF_REQUIRE(p->noise_resident || p->noise32_resident, "no deviates resident on the device: call rf_noise_mt19937 (or an external-noise run) first");
+    RF_REQUIRE(p->has.deviates(), "no deviates resident on the device: call rf_noise_mt19937 (or an external-noise run) first");
     return 0;
   }
   if (mode != RF_NOISE_EXTERNAL) return 0;
@@ -151,8 +151,7 @@ int upload_noise(rf_plan* p, int mode, const double* noise_host) {
     RF_HIP(hipMemcpy2DAsync(p->noise.get(), dp, (const char*)noise_host + (size_t)p->kz0 * cell, hp, (size_t)p->nzl * cell, rows, hipMemcpyHostToDevice, p->stream));
     RF_HIP(hipMemcpy2DAsync((char*)p->noise.get() + (size_t)p->nzl * cell, dp, (const char*)noise_host + (size_t)p->nzc * cell, hp, cell, rows, hipMemcpyHostToDevice, p->stream));
   }
-  p->noise_resident = true;
-  p->noise32_resident = false;
+  p->has.deviates64_ready();
   return 0;
 }
 
@@ -235,8 +234,8 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   // deviates (RF_NOISE_EXTERNAL, the parity mode) keep the exact reference dtype chain
   // (float32 copies of the deviates exist for this path only, and it can store the potential too; float64 ones cannot)
   const bool fast_noise = !kspace && gp.noise_mode == NOISE_EXTERNAL && cd.resident_fast && p->have_fast && !p->exact_gen &&
-                          !p->f64 && !(p->replicate && p->nranks > 1) && (p->noise32_resident || !cd.pot_target);
-  RF_REQUIRE(kspace || gp.noise_mode != NOISE_EXTERNAL || fast_noise || p->noise_resident,
+                          !p->f64 && !(p->replicate && p->nranks > 1) && (p->has.deviates32() || !cd.pot_target);
+  RF_REQUIRE(kspace || gp.noise_mode != NOISE_EXTERNAL || fast_noise || p->has.deviates64(),
              "only float32 copies of the deviates are resident: this path (exact chain / float64 plan) needs rf_noise_mt19937's float64 ones");
   const bool fast = (!kspace && gp.noise_mode == NOISE_PHILOX && p->have_fast && !p->exact_gen) || fast_noise;
   const bool rep = p->replicate && p->nranks > 1;
@@ -251,8 +250,8 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   hipEvent_t after_repair = nullptr;
   if (fast) RF_HIP(mark(tl, rft::EXTRA, sx, &after_repair));       // in front of the pass; recorded again by the launcher if it splits
   FastGenParams fgp = make_fast(p, cd, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
-  if (fast_noise && p->noise32_resident) {
-    fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch.ptr);      // (a later float64 replay reuses the scratch: it clears noise32_resident)
+  if (fast_noise && p->has.deviates32()) {
+    fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch.ptr);      // (a later float64 replay reuses the scratch: the float32 claim goes with it)
     fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt_rowtab.ptr); fgp.seg_cap = p->seg_cap;
   }
   else if (fast_noise) fgp.noise = gp.noise;
@@ -372,8 +371,7 @@ int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStrea
   const long long nzseg = p->nzl / slab_chunks(p);            // planes per received segment: nranks * chunks of them make a row
   RF_HIP(launch_row_c2r_gather(p->f64, p->nzc, R, W, nrows, inv_cells(p), (int)nzseg, nrows * nzseg, p->tw_z.ptr, p->partials.get(), s));
   RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
-  p->cur = W;
-  p->real_valid = true;
+  p->has.field_gathered(W);
   return 0;
 }
 
@@ -441,20 +439,6 @@ int ensure_batch_buffers(rf_plan* p) {
   return 0;
 }
 
-// The plan holds the real-space field of its last call in W, and that field's (sum, sumsq) in pair `slot` of `stats`
-void field_ready(rf_plan* p, int slot) {
-  p->cur = p->W.ptr;
-  p->stats_slot = slot;
-  p->real_valid = true;
-  p->stats_valid = true;
-}
-// ... of a pipelined batch of n: the last field lies in the buffer of its turn, `cur`; real: it is a field (no stand-in exchange)
-void batch_ready(rf_plan* p, int n, void* cur, bool real) {
-  field_ready(p, n - 1);
-  p->cur = cur;
-  p->real_valid = real;
-}
-
 // Pipelined batch of a plan in direct mode.  The y pass of realisation i stores into the PEERS' receive buffers i % 2 -- it is the
 // exchange, and on a real job it runs at the speed of the links -- so it goes to the exchange stream Y, where it runs beside the z pass of
 // realisation i - 1 and the x pass of realisation i + 1 on the compute stream A; B(i), a tiny all-reduce on Y, tells every rank that
@@ -500,7 +484,8 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
     if (two) RF_HIP(hop(ev_bar[lb], Y, A));
   }
   RF_HIP(p->tl.end(A));
-  batch_ready(p, n, Wb[(n - 1) & 1], !p->direct_standin);
+  p->has.field_ready(Wb[(n - 1) & 1], n - 1);                     // the last field lies in the buffer of its turn
+  if (p->direct_standin) p->has.not_a_field();                    // (the stores went to this rank's own buffers)
   return 0;
 }
 
@@ -528,7 +513,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
       if (int rc = replicated_z(p, i, i + 1 == n ? n : 0, nullptr)) return rc;
     }
     RF_HIP(p->tl.end(p->stream));
-    field_ready(p, n - 1);
+    p->has.field_ready(p->W.ptr, n - 1);
     return 0;
   }
   if (int rc = ensure_batch_buffers(p)) return rc;
@@ -563,7 +548,8 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
     RF_HIP(hop(ev_exch[lb], C, A));
   }
   RF_HIP(p->tl.end(A));
-  batch_ready(p, n, Wb[(n - 1) & 1], !(p->nranks > 1 && !p->comm));        // (a stand-in exchange leaves this rank's own data in the segments: not a field)
+  p->has.field_ready(Wb[(n - 1) & 1], n - 1);      // the last field lies in the buffer of its turn
+  if (p->nranks > 1 && !p->comm) p->has.not_a_field();      // (a stand-in exchange leaves this rank's own data in the segments)
   return 0;
 }
 
@@ -763,12 +749,6 @@ int generic_c2r(rf_plan* p, const void* K, double* stats_out, Timeline* tl, cons
   return 0;
 }
 
-// the k-space side array K holds a half spectrum (and no auxiliary real field any more)
-void kspace_ready(rf_plan* p) {
-  p->k_valid = true;
-  p->aux_valid = false;
-}
-
 // What the exchanging branches of queue_c2r end with, the receive buffer being complete for stream A: the gathering z pass on A, then
 // the all-reduce of the moments on S, the stream that drives the communicator in this call (S != A: behind an event hop each way)
 // (the timeline: the exchange, the z pass and its moments are the z entry, the all-reduce what is left until the call's end)
@@ -782,8 +762,7 @@ int gather_and_reduce(rf_plan* p, hipStream_t A, hipStream_t S, Timeline* tl) {
     if (ev) RF_HIP(hop(ev, S, A));
   }
   RF_HIP(tl->end(A));
-  p->stats_slot = 0;
-  p->stats_valid = true;
+  p->has.moments_ready(0);
   return 0;
 }
 
@@ -793,23 +772,23 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
   RF_HIP(tl->begin(p->stream, true));
   if (p->generic) {
     // per-kernel times (rf_kernel_ms): start | generation launch | EXTRA | x | X | y | Y | contiguous | Z | reduce | end
-    if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->noise_resident, "no float64 deviates resident on the device");
-    const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and k_valid stay as they are
+    if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->has.deviates64(), "no float64 deviates resident on the device");
+    const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and what it holds stay as they are
     if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
       if (int rc = ensure_k(p)) return rc;
       RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
       RF_HIP(mark(tl, rft::EXTRA, p->stream));
-      kspace_ready(p);
+      p->has.kspace_ready();
       kspace = p->K.ptr;
     }
     if (int rc = generic_c2r(p, kspace, p->stats.get(), tl, fused ? &gp : nullptr)) return rc;
     RF_HIP(tl->end(p->stream));
-    field_ready(p, 0);
+    p->has.field_ready(p->W.ptr, 0);
     return 0;
   }
   if (p->nranks == 1 && !p->force_slab) {       // one GPU: x pass, then the y / z passes (slab by slab on large grids)
     if (int rc = queue_xyz(p, cd, gp, kspace, p->W.ptr, p->stream, p->stats.get(), tl)) return rc;
-    field_ready(p, 0);
+    p->has.field_ready(p->W.ptr, 0);
     return 0;
   }
   if (direct_active(p)) {
@@ -829,7 +808,7 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     if (int rc = direct_barrier(p, Y)) return rc;
     if (two) RF_HIP(hop(p->chunk_ev[C], Y, A));
     if (int rc = gather_and_reduce(p, A, Y, tl)) return rc;
-    if (p->direct_standin) p->real_valid = false;       // (the stores went to this rank's own buffers: no field came out)
+    if (p->direct_standin) p->has.not_a_field();        // (the stores went to this rank's own buffers: no field came out)
     return 0;
   }
   if (slab_chunks(p) > 1) {
@@ -850,20 +829,20 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
     RF_HIP(mark(tl, rft::X, A));                               // (the whole forward half is the x entry)
     RF_HIP(hop(p->chunk_ev[C], X, A));
     if (int rc = gather_and_reduce(p, A, X, tl)) return rc;
-    if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
+    if (p->nranks > 1 && !p->comm) p->has.not_a_field();        // (stand-in exchange)
     return 0;
   }
   if (int rc = queue_xy(p, cd, gp, kspace, p->W.ptr, p->stream, tl)) return rc;
   if (p->replicate && p->nranks > 1) {
     if (int rc = replicated_z(p, 0, 1, tl)) return rc;
     RF_HIP(tl->end(p->stream));
-    field_ready(p, 0);
+    p->has.field_ready(p->W.ptr, 0);
     return 0;
   }
   if (p->nranks > 1 || p->force_slab) {
     if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, p->stream)) return rc;
     if (int rc = gather_and_reduce(p, p->stream, p->stream, tl)) return rc;
-    if (p->nranks > 1 && !p->comm) p->real_valid = false;       // (stand-in exchange: not a field)
+    if (p->nranks > 1 && !p->comm) p->has.not_a_field();        // (stand-in exchange)
     return 0;
   }
   return fail(1, "queue_c2r: unreachable");
@@ -1132,7 +1111,7 @@ int rf_plan_set_flag(rf_plan* p, int flag, int value) {
                "too many exchange chunks for the direct exchange: a y-pass tile would straddle two x planes");
     p->xchunks = C;
     drop_graphs(p);
-    p->real_valid = false;                       // (the buffers' layout between the passes changes; nothing resident survives it)
+    p->has.not_a_field();                        // (the buffers' layout between the passes changes; nothing resident survives it)
     if (p->direct) return rebuild_peer_tab(p);
     return 0;
   }
@@ -1221,17 +1200,17 @@ int rf_generate(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;        // a kz-slab rank holds (and generates) its own planes + the Nyquist plane
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  RF_REQUIRE(mode != RF_NOISE_RESIDENT || p->noise_resident, "rf_generate needs float64 deviates: only float32 copies are resident");
+  RF_REQUIRE(mode != RF_NOISE_RESIDENT || p->has.deviates64(), "rf_generate needs float64 deviates: only float32 copies are resident");
   RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, make_gen(p, seed, mode, false), p->stream));
   if (mode == RF_NOISE_EXTERNAL) RF_HIP(hipStreamSynchronize(p->stream));  // host noise buffer may be released by the caller
-  kspace_ready(p);
+  p->has.kspace_ready();
   return 0;
 }
 
 int rf_execute_c2r(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+  RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
   RF_REQUIRE(!(p->replicate && p->nranks > 1), "replicated-generation plans have no distributed k-space buffer");
   RF_HIP(hipSetDevice(p->device));
   return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr);
@@ -1257,14 +1236,13 @@ int queue_r2c_slab_cols(rf_plan* p, hipStream_t s) {
   RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W.ptr, gy, (long long)p->nx * nzl, p->tw_y.ptr, s));
   RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W.ptr, gx, (long long)p->ny * nzl, p->tw_x.ptr, s));
   RF_HIP(launch_unpack_kspace(p->f64, p->W.ptr, p->K.ptr, p->nx, p->ny, (int)nzl, p->kz0, s));
-  p->real_valid = false;      // the field buffer now holds packed k space
-  p->stats_valid = false;
-  kspace_ready(p);
+  p->has.field_consumed();    // the field buffer now holds packed k space
+  p->has.kspace_ready();
   return 0;
 }
 // single-rank forward transform of the field in W.  Generic plans: rows -> half spectrum in K, then the y and x forward passes
 // (rf_generic.h generic_r2c_seq); W is untouched.  Tiled plans: the three passes in place in W, then (unpack) the API-layout array K;
-// without it W is left packed (slot kz = 0 = A0 + i A_nyq), K and k_valid as they were (rf_measure_power reads W directly).
+// without it W is left packed (slot kz = 0 = A0 + i A_nyq), K and what it holds as they were (rf_measure_power reads W directly).
 int queue_r2c_single(rf_plan* p, bool unpack) {
   const long long nzc = p->nzc;
   const ColGeom gx{(long long)p->ny * nzc, 0, (long long)p->ny * nzc}, gy{nzc, (long long)p->ny * nzc, nzc};
@@ -1273,18 +1251,17 @@ int queue_r2c_single(rf_plan* p, bool unpack) {
     if (generic_any_long(p)) { if (int rc = ensure_g(p)) return rc; if (int rc = ensure_g2(p)) return rc; }
     HipGenericOps ops{p, p->stream};
     if (int rc = generic_r2c_seq(ops, p->gdims, p->W.ptr, p->K.ptr, p->G.ptr, p->G2.ptr)) return rc;
-    kspace_ready(p);            // the real field in W is untouched on this path
+    p->has.kspace_ready();            // the real field in W is untouched on this path
     return 0;
   }
   if (unpack) { if (int rc = ensure_k(p)) return rc; }
   RF_HIP(launch_row_r2c(p->f64, (int)nzc, p->W.ptr, (long long)p->nx * p->ny, p->tw_z.ptr, p->stream));     // z, in place
   RF_HIP(launch_col_plain(p->f64, p->ny, -1, p->W.ptr, gy, (long long)p->nx * nzc, p->tw_y.ptr, p->stream));   // y forward
   RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W.ptr, gx, (long long)p->ny * nzc, p->tw_x.ptr, p->stream));   // x forward
-  p->real_valid = false;      // the field buffer now holds packed k space
-  p->stats_valid = false;
+  p->has.field_consumed();    // the field buffer now holds packed k space
   if (unpack) {
     RF_HIP(launch_unpack_kspace(p->f64, p->W.ptr, p->K.ptr, p->nx, p->ny, (int)nzc, 0, p->stream));
-    kspace_ready(p);
+    p->has.kspace_ready();
   }
   return 0;
 }
@@ -1294,7 +1271,7 @@ extern "C" {
 int rf_execute_r2c(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  RF_REQUIRE(p->has.field_in(p->W.ptr), "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
   if (p->nranks > 1) {
@@ -1337,7 +1314,7 @@ int rf_realise(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
 int rf_can_regenerate_potential(rf_plan* p, int mode) {
   if (!p || p->unpacked || p->generic || !p->have_fast || p->exact_gen || (p->replicate && p->nranks > 1)) return 0;
   if (mode == RF_NOISE_NATIVE) return 1;
-  if (mode == RF_NOISE_RESIDENT) return (p->noise32_resident && !p->f64) ? 1 : 0;
+  if (mode == RF_NOISE_RESIDENT) return (p->has.deviates32() && !p->f64) ? 1 : 0;
   return 0;
 }
 
@@ -1362,8 +1339,8 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   cd.zscale = fuse_z ? p->ztab.get() : nullptr;
   if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
   if (factor_z && !fuse_z) {
-    RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, p->nz, p->ztab.get(), 0.0, p->stream));
-    p->stats_valid = false;
+    RF_HIP(launch_affine_z(p->f64, p->has.where(), (long long)p->nxl * p->ny, p->nz, p->ztab.get(), 0.0, p->stream));
+    p->has.field_modified();
   }
   if (factor_z) RF_HIP(hipStreamSynchronize(p->stream));     // (factor_z is the caller's memory)
   return 0;
@@ -1400,7 +1377,7 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
   RF_HIP(hipSetDevice(p->device));
   // fused: delta(k) / k^2 is a second store stream of the generation pass -- native generator (float32 and float64 plans)
   // or resident float32 deviates (float32 plans)
-  const bool fused = ((mode == RF_NOISE_NATIVE) || (mode == RF_NOISE_RESIDENT && p->noise32_resident && !p->f64)) && p->have_fast &&
+  const bool fused = ((mode == RF_NOISE_NATIVE) || (mode == RF_NOISE_RESIDENT && p->has.deviates32() && !p->f64)) && p->have_fast &&
                      !p->exact_gen && !p->generic;
   if (!fused) {
     if (int rc = rf_generate(p, seed, mode, noise_host)) return rc;
@@ -1409,7 +1386,7 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
     return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, nullptr);
   }
   if (int rc = ensure_p(p)) return rc;
-  p->p2_valid = false;                               // (P is rewritten: a second-order potential made from the old one is stale)
+  p->has.potential2_stale();                         // (P is rewritten: a second-order potential made from the old one is stale)
   CallDesc cd;
   cd.pot_target = p->P.ptr;
   cd.resident_fast = (mode == RF_NOISE_RESIDENT);
@@ -1488,7 +1465,7 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
     RF_HIP(hipSetDevice(p->device));
     if (int rc = ensure_stats(p, n)) return rc;
-    const bool fused = p->fused_generic;        // generation inside the x pass: no K, k_valid as it was (queue_c2r)
+    const bool fused = p->fused_generic;        // generation inside the x pass: no K, what it holds as it was (queue_c2r)
     if (!fused) { if (int rc = ensure_k(p)) return rc; }
     RF_HIP(p->tl.begin(p->stream, false));
     for (int i = 0; i < n; ++i) {
@@ -1497,8 +1474,8 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
       if (int rc = generic_c2r(p, p->K.ptr, p->stats.get() + 2 * i, nullptr, fused ? &gp : nullptr)) return rc;
     }
     RF_HIP(p->tl.end(p->stream));
-    field_ready(p, n - 1);
-    if (!fused) kspace_ready(p);
+    p->has.field_ready(p->W.ptr, n - 1);
+    if (!fused) p->has.kspace_ready();
     return rms_out ? rms_from_stats(p, n, rms_out) : 0;
   }
   if (int rc = batch_prepare(p, n)) return rc;
@@ -1516,17 +1493,17 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
   RF_HIP(p->tl.begin(p->stream, false));
   RF_HIP(hipGraphLaunch(p->graphs[n].exec, p->stream));
   RF_HIP(p->tl.end(p->stream));
-  field_ready(p, n - 1);
+  p->has.field_ready(p->W.ptr, n - 1);
   return rms_out ? rms_from_stats(p, n, rms_out) : 0;
 }
 
 int rf_moments(rf_plan* p, double* mean, double* std_out) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->stats_valid, "no realisation has been computed");
+  RF_REQUIRE(p->has.moments(), "no realisation has been computed");
   RF_HIP(hipSetDevice(p->device));
   double st[2];
-  RF_HIP(hipMemcpyAsync(st, p->stats.get() + 2 * p->stats_slot, sizeof(st), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipMemcpyAsync(st, p->stats.get() + 2 * p->has.moments_pair(), sizeof(st), hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   mean_std(p, st, mean, std_out);
   return 0;
@@ -1536,14 +1513,14 @@ int rf_lognormal(rf_plan* p, const double* a_z, const double* b_z, int nz, doubl
   RF_REQUIRE(p && a_z && b_z, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(nz == p->nz, "table length must equal nz");
-  RF_REQUIRE(p->real_valid, "no real-space field on the device");
+  RF_REQUIRE(p->has.field(), "no real-space field on the device");
   RF_REQUIRE(sigma > 0, "sigma must be positive");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipMemcpyAsync(p->ztab.get(), a_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipMemcpyAsync(p->ztab.get() + nz, b_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(launch_lognormal(p->f64, p->cur, (long long)p->nxl * p->ny, nz, p->ztab.get(), p->ztab.get() + nz, sigma, p->stream));
+  RF_HIP(launch_lognormal(p->f64, p->has.where(), (long long)p->nxl * p->ny, nz, p->ztab.get(), p->ztab.get() + nz, sigma, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));  // host tables may go away
-  p->stats_valid = false;
+  p->has.field_modified();
   return 0;
 }
 
@@ -1597,8 +1574,8 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   RF_HIP(mark(tl, rft::Z, s));
   RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, p->stats.get(), p->partials.get() + 2 * p->npartials, s));
   RF_HIP(tl->end(s));
-  field_ready(p, 0);                                 // (the moments of the DENSITY field now)
-  p->k_valid = false;
+  p->has.field_ready(p->W.ptr, 0);                                 // (the moments of the DENSITY field now)
+  p->has.kspace_consumed();
   if (sigma_out) {
     RF_HIP(hipMemcpyAsync(sigma_out, sig, sizeof(double), hipMemcpyDeviceToHost, s));
     RF_HIP(hipStreamSynchronize(s));
@@ -1610,12 +1587,12 @@ int rf_affine_z(rf_plan* p, const double* mul_z, int nz, double add) {
   RF_REQUIRE(p && mul_z, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(nz == p->nz, "table length must equal nz");
-  RF_REQUIRE(p->real_valid, "no real-space field on the device");
+  RF_REQUIRE(p->has.field(), "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipMemcpyAsync(p->ztab.get(), mul_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(launch_affine_z(p->f64, p->cur, (long long)p->nxl * p->ny, nz, p->ztab.get(), add, p->stream));
+  RF_HIP(launch_affine_z(p->f64, p->has.where(), (long long)p->nxl * p->ny, nz, p->ztab.get(), add, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  p->stats_valid = false;
+  p->has.field_modified();
   return 0;
 }
 
@@ -1629,14 +1606,13 @@ int rf_lensing_potential(rf_plan* p, const double* cot_z, int nz, double spacing
   RF_REQUIRE(nz == p->nz, "table length must equal nz");
   RF_REQUIRE(i_min >= 0 && i_min < nz, "invalid i_min");
   RF_REQUIRE(spacing > 0, "spacing must be positive");
-  RF_REQUIRE(p->real_valid, "no real-space field on the device");
+  RF_REQUIRE(p->has.field(), "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;            // (nx ny (nz/2+1)) complex >= (nx ny nz) real
   RF_HIP(hipMemcpyAsync(p->ztab.get(), cot_z, nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  RF_HIP(launch_lensing(p->f64, p->cur, p->K.ptr, (long long)p->nxl * p->ny, nz, p->ztab.get(), spacing, i_min, p->stream));   // rows are local: x slab
+  RF_HIP(launch_lensing(p->f64, p->has.where(), p->K.ptr, (long long)p->nxl * p->ny, nz, p->ztab.get(), spacing, i_min, p->stream));   // rows are local: x slab
   RF_HIP(hipStreamSynchronize(p->stream));
-  p->k_valid = false;
-  p->aux_valid = true;
+  p->has.aux_ready();
   return 0;
 }
 
@@ -1644,7 +1620,7 @@ int rf_lensing_potential(rf_plan* p, const double* cot_z, int nz, double spacing
 int rf_download_aux(rf_plan* p, void* host, int x0, int x1) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K.ptr && p->aux_valid, "no auxiliary field on the device");
+  RF_REQUIRE(p->K.ptr && p->has.aux(), "no auxiliary field on the device");
   RF_REQUIRE(0 <= x0 && x0 < x1 && x1 <= p->nxl, "invalid x range (multi-GPU plans hold nx/ranks local planes)");
   RF_HIP(hipSetDevice(p->device));
   const size_t plane = (size_t)p->ny * p->nz * (p->csize / 2);
@@ -1656,11 +1632,11 @@ int rf_download_aux(rf_plan* p, void* host, int x0, int x1) {
 int rf_save_potential(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data");
+  RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data");
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_p(p)) return rc;
-  p->p2_valid = false;
+  p->has.potential2_stale();
   RF_HIP(launch_save_potential(p->f64, p->K.ptr, p->P.ptr, p->nx, p->ny, p->nz, p->kx2.get(), p->ky2.get(), p->kz2.get(), p->nzl + 1, p->kz0, p->ppitch, p->stream));
   return 0;
 }
@@ -1672,7 +1648,7 @@ int rf_load_potential(rf_plan* p, double scale) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
   RF_HIP(launch_scale_copy(p->f64, p->P.ptr, p->K.ptr, (long long)p->nx * p->ny * (p->nzl + 1), (int)p->nzl + 1, p->ppitch, scale, p->stream));
-  kspace_ready(p);
+  p->has.kspace_ready();
   return 0;
 }
 
@@ -1684,9 +1660,9 @@ namespace rfc {
 template <class P>
 int derivative_source(rf_plan* p, int source, P& g, const void*& S) {
   if (source == RF_GRAD_FROM_POTENTIAL) RF_REQUIRE(p->P.ptr, "no saved potential");
-  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L.ptr && p->p2_valid, "no second-order potential: call rf_lpt2_potential first");
+  else if (source == RF_GRAD_FROM_POTENTIAL2) RF_REQUIRE(p->L.ptr && p->has.potential2(), "no second-order potential: call rf_lpt2_potential first");
   else {
-    RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
+    RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
     RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
   }
   g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
@@ -1726,7 +1702,7 @@ int load_derivative(rf_plan* p, const P& g, const void* S) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;
   RF_HIP(launch_derivative(p->f64, S, p->K.ptr, g, p->stream));
-  kspace_ready(p);
+  p->has.kspace_ready();
   return 0;
 }
 // the component as a real field (rf_execute_gradient_c2r / rf_execute_hessian_c2r).  RF_GRAD_FROM_KSPACE consumes K on either kind of
@@ -1737,15 +1713,15 @@ int execute_derivative_c2r(rf_plan* p, const P& g, const void* S, int source) {
   if (!p->generic) {    // the component as a sweep of its own, then the plan's inverse transform
     if (int rc = load_derivative(p, g, S)) return rc;
     const int rc = rf_execute_c2r(p);
-    if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
+    if (source == RF_GRAD_FROM_KSPACE) p->has.kspace_consumed();
     return rc;
   }
   // generic plans: the factor is applied by the x pass to the cells it loads (rf_generic.h generic_c2r_from_seq); K, P are only read
   RF_HIP(p->tl.begin(p->stream, true));             // (rf_kernel_ms: x with the factor, y, contiguous, reduce; [4] = the sweep of a plan whose x axis is split)
   if (int rc = generic_c2r(p, S, p->stats.get(), &p->tl, &g)) return rc;
   RF_HIP(p->tl.end(p->stream));
-  field_ready(p, 0);
-  if (source == RF_GRAD_FROM_KSPACE) p->k_valid = false;
+  p->has.field_ready(p->W.ptr, 0);
+  if (source == RF_GRAD_FROM_KSPACE) p->has.kspace_consumed();
   return 0;
 }
 // the accumulators of rf_lpt2_source, later the second-order potential
@@ -1810,7 +1786,7 @@ int rf_lpt2_source(rf_plan* p, const double* dk) {
   RF_REQUIRE(p->P.ptr, "no saved potential");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_l(p)) return rc;
-  p->p2_valid = false;                               // (the accumulators take the memory of the second-order potential)
+  p->has.potential2_stale();                         // (the accumulators take the memory of the second-order potential)
   static const int comp[6][3] = {{0, 0, LPT2_FIRST}, {1, 1, LPT2_DIAG2}, {2, 2, LPT2_DIAG3}, {0, 1, LPT2_OFF}, {0, 2, LPT2_OFF}, {1, 2, LPT2_LAST}};
   void* T = p->L.ptr;
   void* S = (char*)p->L.ptr + p->w_bytes;
@@ -1821,11 +1797,8 @@ int rf_lpt2_source(rf_plan* p, const double* dk) {
   }
   RF_HIP(p->tl.end(p->stream));                      // (rf_elapsed_ms: the last component's transform and the last step ...
   p->tl.detailed = false;                            // ... which no entry of rf_kernel_ms describes: refused, as it always was)
-  p->cur = p->W.ptr;
-  p->real_valid = true;
-  p->stats_valid = false;
-  p->k_valid = false;                                // (tiled plans left a Hessian component there: one contract)
-  p->aux_valid = false;
+  p->has.field_written(p->W.ptr);
+  p->has.kside_cleared();                            // (tiled plans left a Hessian component there: one contract)
   return 0;
 }
 
@@ -1840,7 +1813,7 @@ int rf_lpt2_potential(rf_plan* p, const double* dk) {
   if (int rc = rf_execute_r2c(p)) return rc;
   RF_HIP(launch_save_potential(p->f64, p->K.ptr, p->L.ptr, p->nx, p->ny, p->nz, p->kx2.get(), p->ky2.get(), p->kz2.get(), p->nzl + 1, p->kz0, p->ppitch, p->stream));
   RF_HIP(p->tl.end(p->stream));
-  p->p2_valid = true;
+  p->has.potential2_ready();
   return 0;
 }
 
@@ -1872,10 +1845,10 @@ static int drop_read(rf_plan* p, unsigned long long* dropped) { return particles
 int rf_particles_accumulate(rf_plan* p, int axis, double coeff, int first) {
   if (int rc = particles_check(p, "the particle displacements live on single-rank plans")) return rc;
   RF_REQUIRE(axis >= 0 && axis <= 2, "axis must be 0, 1 or 2");
-  RF_REQUIRE(p->real_valid && p->cur, "no real-space field on the device");
+  RF_REQUIRE(p->has.field(), "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_q(p)) return rc;
-  RF_HIP(launch_particles_accumulate(p->f64, p->cur, q_component(p, axis), coeff, first, (long long)particle_cells(p), p->stream));
+  RF_HIP(launch_particles_accumulate(p->f64, p->has.where(), q_component(p, axis), coeff, first, (long long)particle_cells(p), p->stream));
   return 0;
 }
 
@@ -1914,7 +1887,7 @@ int rf_particles_paint_ex(rf_plan* p, const double* inv_h, int scheme, unsigned 
   // The triangular-shaped cloud: the tiled form too, 16.3 against 185 ms and 254 against 1200 ms of scatter at 1024^3 (15.9 / 167 and
   // 253 / 1108 ms at 1000^3), rms 0.1 and 2 cells, spread between rounds below 10 ms (profiles/tsc_bench.log)
   const int form = p->paint_form ? p->paint_form : 2;
-  p->pa_valid = false;
+  p->has.counts_stale();
   RF_HIP(p->tl.begin(p->stream, true));
   RF_HIP(hipMemsetAsync(p->A.ptr, 0, n * 8, p->stream));
   RF_HIP(drop_clear(p));
@@ -1924,17 +1897,15 @@ int rf_particles_paint_ex(rf_plan* p, const double* inv_h, int scheme, unsigned 
   RF_HIP(launch_cic_convert(p->f64, (const unsigned long long*)p->A.ptr, p->W.ptr, (long long)n, p->stream));
   RF_HIP(p->tl.mark(rft::Z, p->stream));
   RF_HIP(p->tl.end(p->stream));
-  p->cur = p->W.ptr;
-  p->real_valid = true;
-  p->stats_valid = false;
-  p->pa_valid = true;
+  p->has.field_written(p->W.ptr);
+  p->has.counts_ready();
   return drop_read(p, dropped);
 }
 
 int rf_particles_download_counts(rf_plan* p, unsigned long long* host) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(host, "null argument");
-  RF_REQUIRE(p->A.ptr && p->pa_valid, "no painted counts: call rf_particles_paint first");
+  RF_REQUIRE(p->A.ptr && p->has.counts(), "no painted counts: call rf_particles_paint first");
   return particles_copy(p, host, p->A.ptr, particle_cells(p) * 8, hipMemcpyDeviceToHost);
 }
 
@@ -1964,7 +1935,7 @@ int rf_particles_gather_ex(rf_plan* p, const double* inv_h, int scheme, int slot
   RF_REQUIRE(slot >= 0 && slot <= 2, "slot must be 0, 1 or 2");
   if (int rc = inv_h_check(inv_h)) return rc;
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
-  RF_REQUIRE(p->real_valid && p->cur, "no real-space field on the device");
+  RF_REQUIRE(p->has.field(), "no real-space field on the device");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_pg(p)) return rc;
   // auto: the tiled form.  At 1024^3 / 1000^3 it takes 13.7 / 13.1 ms against the global form's 28.7 / 39.5 ms on displacements of rms 2
@@ -1976,7 +1947,7 @@ int rf_particles_gather_ex(rf_plan* p, const double* inv_h, int scheme, int slot
   const int form = p->gather_form ? p->gather_form : 2;
   RF_HIP(drop_clear(p));
   RF_HIP(p->tl.begin(p->stream, true));
-  RF_HIP(launch_cic_gather(p->f64, scheme, form, p->Q.ptr, p->cur, pg_slot(p, slot), coeff, first, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h,
+  RF_HIP(launch_cic_gather(p->f64, scheme, form, p->Q.ptr, p->has.where(), pg_slot(p, slot), coeff, first, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h,
                            p->stream));
   RF_HIP(p->tl.mark(rft::X, p->stream));
   RF_HIP(p->tl.end(p->stream));
@@ -2040,8 +2011,8 @@ int measure_bins(rf_plan* p, int source, const double* k_edges, int nbins, DevBu
                  unsigned long long* count, double* const (&sums)[BinSums<P>::N]) {
   constexpr BinTable T = bin_table<P>();
   RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
-  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate or rf_upload_k first");
-  else RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  if (source == RF_POWER_FROM_KSPACE) RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
+  else RF_REQUIRE(p->has.field_in(p->W.ptr), "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
   const BinLaunch L = bin_launch_shape(T, p->nx, p->ny, p->nz, nbins);
   const long long plane_words = (long long)L.grid * nbins;
@@ -2120,14 +2091,14 @@ int rf_upload_k(rf_plan* p, const void* host) {
   if (int rc = ensure_k(p)) return rc;
   RF_HIP(hipMemcpyAsync(p->K.ptr, host, p->k_bytes, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  kspace_ready(p);
+  p->has.kspace_ready();
   return 0;
 }
 
 int rf_download_k(rf_plan* p, void* host) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data");
+  RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipMemcpyAsync(host, p->K.ptr, p->k_bytes, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
@@ -2145,22 +2116,20 @@ int rf_upload_real(rf_plan* p, const void* host, int layout) {
   // (a multi-rank plan takes its own nx / ranks planes)
   RF_HIP(hipMemcpy2DAsync(p->W.ptr, width, host, hpitch, width, (size_t)p->nxl * p->ny, hipMemcpyHostToDevice, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  p->cur = p->W.ptr;
-  p->real_valid = true;
-  p->stats_valid = false;
+  p->has.field_written(p->W.ptr);
   return 0;
 }
 
 int rf_download_real(rf_plan* p, void* host, int layout, int x0, int x1) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->real_valid, "no real-space field on the device");
+  RF_REQUIRE(p->has.field(), "no real-space field on the device");
   RF_REQUIRE(0 <= x0 && x0 < x1 && x1 <= p->nxl, "invalid x range (multi-GPU plans hold nx/ranks local planes)");
   RF_HIP(hipSetDevice(p->device));
   const size_t rsize = p->csize / 2;
   const size_t width = (size_t)p->nz * rsize;
   const size_t hpitch = layout == RF_LAYOUT_PADDED ? (size_t)(p->nz + 2) * rsize : width;
-  const char* src = (const char*)p->cur + (size_t)x0 * p->ny * width;
+  const char* src = (const char*)p->has.where() + (size_t)x0 * p->ny * width;
   RF_HIP(hipMemcpy2DAsync(host, hpitch, src, width, width, (size_t)(x1 - x0) * p->ny, hipMemcpyDeviceToHost, p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
@@ -2198,7 +2167,7 @@ int rf_host_sink_delivered(rf_plan* p, int* delivered) {
 
 int rf_device_ptr(rf_plan* p, void** real_field, void** kspace) {
   RF_REQUIRE(p, "null plan");
-  if (real_field) *real_field = p->cur ? p->cur : p->W.ptr;
+  if (real_field) *real_field = p->has.where() ? p->has.where() : p->W.ptr;
   if (kspace) *kspace = p->K.ptr;
   return 0;
 }

@@ -146,8 +146,7 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
   const int nseg = g.nseg;
   unsigned long long total = 0;
   int flags = 0;
-  p->noise_resident = false;
-  p->noise32_resident = false;
+  p->has.deviates_none();
   RF_HIP(hipMemcpyAsync(&total, p->mt_offsets.get() + nseg, sizeof(total), hipMemcpyDeviceToHost, s));
   if (single) RF_HIP(hipMemcpyAsync(&flags, p->mt_flags.get(), sizeof(flags), hipMemcpyDeviceToHost, s));
   RF_HIP(hipStreamSynchronize(s));
@@ -156,9 +155,8 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
   if (accepted) *accepted = total;
   RF_REQUIRE(total >= g.ncells, "MT19937 replay: not enough accepted polar attempts (increase the margin)");
   RF_REQUIRE(!(flags & 1), "MT19937 replay: a segment holds fewer deviate pairs than a row of the grid has cells (segment length too short for the float32 form)");
-  p->noise_resident = !single;
-  p->noise32_resident = single != 0;
   if (!single) {
+    p->has.deviates64_ready();
     // the runs are dead once the compaction has moved them into p->noise (the stream is idle here).  They are 1.27x the noise
     // buffer -- 11 GB at 1024^3, the difference between fitting and not fitting a 2048^3 float64 plan with a saved potential
     // into 288 GB -- so they are given back when the device is getting full; otherwise they stay for the next seed (allocating
@@ -167,7 +165,7 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < total_b / 3) {
       RF_HIP(p->mt_scratch.release());
     }
-  }
+  } else p->has.deviates32_ready();
   return 0;
 }
 
@@ -246,8 +244,7 @@ int rf_mt_share_begin(rf_plan* p, const uint32_t* state624, int single, unsigned
   RF_HIP(hipMemcpyAsync(counts_out, p->mt_counts.get(), (size_t)nloc * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   RF_HIP(hipStreamSynchronize(s));
   p->sh_single = single; p->sh_first = first; p->sh_nloc = nloc;
-  p->noise_resident = false;                              // (p->noise is about to be overwritten)
-  p->noise32_resident = false;                            // (the runs in mt_scratch are this rank's share only)
+  p->has.deviates_none();                                 // (p->noise is about to be overwritten; the runs in mt_scratch are this rank's share only)
   p->sh_state = 1;
   return 0;
 }
@@ -387,8 +384,7 @@ int rf_mt_share_finish(rf_plan* p, unsigned long long* accepted) {
   if (p->sh_single)
     RF_HIP(launch_mt_share_widen(p->mt_recv.ptr, p->noise.get(), (long long)p->nx * p->ny * (p->nzl + 1), p->stream));
   RF_HIP(hipStreamSynchronize(p->stream));
-  p->noise_resident = true;
-  p->noise32_resident = false;
+  p->has.deviates64_ready();
   p->sh_state = 0;
   if (accepted) *accepted = p->sh_total;
   return 0;
@@ -431,10 +427,8 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   hipStream_t S = p->stream, R = p->aux_stream;
   // whatever deviates were resident are about to be overwritten; the plan claims the new ones (and a field) only once every
   // replay of the batch has been checked
-  p->noise_resident = false;
-  p->noise32_resident = false;
-  p->real_valid = false;
-  p->stats_valid = false;
+  p->has.deviates_none();
+  p->has.field_consumed();
   p->nseg = g.nseg;
   p->seg_cap = g.cap;
   // both streams are drained before any return from here on
@@ -455,7 +449,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     if (int rc = replay(0)) return rc;
     for (int i = 0; i < n; ++i) {
       RF_HIP(hipStreamWaitEvent(S, p->bev[0], 0));        // the runs of seed i are complete
-      p->noise32_resident = true;                         // (queue_x selects the float32-pair kernel by it; cleared again on failure)
+      p->has.deviates32_ready();                          // (queue_x selects the float32-pair kernel by it; cleared again on failure)
       const bool xp = p->X.ptr && xpose_ok(p);
       if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X.ptr : p->W.ptr, S, nullptr)) return rc;
       RF_HIP(hipEventRecord(p->bev[1], S));               // the generation pass of seed i has read the runs
@@ -488,12 +482,12 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
       else if (flags[i] & 1) rc = fail(1, "MT19937 replay: a segment holds fewer deviate pairs than a row of the grid has cells");
     }
   if (rc) {
-    p->noise32_resident = false;
+    p->has.deviates_none();
     return drain(rc);
   }
-  p->noise32_resident = true;                             // the last seed's deviates, as float32 pairs in the runs
-  field_ready(p, n - 1);
-  p->k_valid = false;
+  p->has.deviates32_ready();                              // the last seed's deviates, as float32 pairs in the runs
+  p->has.field_ready(p->W.ptr, n - 1);
+  p->has.kspace_consumed();
   if (rms_out) memcpy(rms_out, rms.data(), (size_t)n * sizeof(double));
   return 0;
 }
@@ -510,7 +504,7 @@ int rf_can_batch_reference(rf_plan* p) {
 int rf_download_noise(rf_plan* p, double* host, unsigned long long first, unsigned long long count) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(p->noise_resident, "no float64 deviates resident on the device");
+  RF_REQUIRE(p->has.deviates64(), "no float64 deviates resident on the device");
   RF_REQUIRE(first + count <= 2ull * p->nx * p->ny * (p->nzl + 1), "range outside the noise buffer");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipMemcpyAsync(host, p->noise.get() + first, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));

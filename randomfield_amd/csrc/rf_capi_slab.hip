@@ -89,7 +89,7 @@ int rf_slab_forward_ex(rf_plan* p, uint64_t seed, int mode, const double* noise_
   if (source == RF_SLAB_GENERATE_SAVE_POTENTIAL) {
     if (int rc = potential_forward(p, seed, mode, noise_host, false)) return rc;
   } else {
-    RF_REQUIRE(p->K.ptr && p->k_valid, "no k-space data: call rf_generate, rf_load_potential or rf_upload_k first");
+    RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate, rf_load_potential or rf_upload_k first");
     if (int rc = queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, nullptr)) return rc;
   }
   RF_HIP(hipStreamSynchronize(p->stream));
@@ -123,10 +123,10 @@ int rf_slab_r2c_rows(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked && !p->generic, "this call applies to packed plans on the tiled kernels");
   RF_REQUIRE(p->nranks > 1, "rf_slab_* are for multi-rank plans");
-  RF_REQUIRE(p->real_valid && p->cur == p->W.ptr, "no real-space field on the device: call rf_upload_real (or a c2r) first");
+  RF_REQUIRE(p->has.field_in(p->W.ptr), "no real-space field on the device: call rf_upload_real (or a c2r) first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = queue_r2c_slab_rows(p, p->stream)) return rc;
-  p->real_valid = false;
+  p->has.not_a_field();                  // (the rows lie cut into the send blocks of R)
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -399,7 +399,7 @@ int rf_slab_backward(rf_plan* p) {
   RF_REQUIRE(p->nranks > 1, "rf_slab_* are for multi-rank plans");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = queue_z_slab(p, p->R.ptr, p->W.ptr, p->stats.get(), p->stream)) return rc;
-  p->stats_slot = 0;
+  p->has.moments_moved(0);
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }

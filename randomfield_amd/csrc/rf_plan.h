@@ -1,6 +1,7 @@
 // rf_plan.h -- the plan object behind the C-ABI and the helpers its translation units share (rf_capi.hip: plans, inputs,
 // realisations, transforms, host <-> device; rf_capi_mt.hip: the MT19937 replay and its sharing between ranks; rf_capi_slab.hip: the
-// communicator and the slab pipeline in separate steps).  Internal: nothing here crosses the C-ABI.
+// communicator and the slab pipeline in separate steps).  What the plan's buffers HOLD belongs to none of the three: it is the member
+// `has` (rf_contents.h), asked and changed through its predicates and transitions only.  Internal: nothing here crosses the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -15,6 +16,7 @@
 
 #include "../../include/randomfield_hip.h"
 #include "../../include/randomfield_hip_diag.h"
+#include "rf_contents.h"
 #include "rf_host.h"
 #include "rf_launch.h"
 #include "rf_owned.h"
@@ -164,15 +166,13 @@ struct rf_plan {
   size_t w_bytes = 0, k_bytes = 0, p_bytes = 0;      // field buffer, k-space side array, potential array (padded rows)
   int ppitch = 0;                         // cells per row of the potential array: nzl + 1, rounded up to even on float32 plans
   // lazy, rf_lpt2_source: the accumulators T and S of the real-space sweep (2 x w_bytes); once the source exists they are dead and the
-  // same memory holds the second-order potential in P's padded layout (rf_lpt2_potential; p_bytes <= L.bytes).  p2_valid is cleared by
-  // everything that writes P or starts a new source.
+  // same memory holds the second-order potential in P's padded layout (rf_lpt2_potential; p_bytes <= L.bytes).  has.potential2() goes
+  // stale with everything that writes P or starts a new source.
   rfc::DevBuf<> L;
-  bool p2_valid = false;
   // lazy, rf_particles_*: the particle displacements Q[3][nx][ny][nz] of the plan's real type (3 x w_bytes) and the 64-bit accumulator
   // grid A[nx][ny][nz] of the cloud-in-cell paint (8 bytes per cell), both counted by rf_plan_nbytes; pa_drop: the paint's counter of
-  // dropped particles (8 bytes).  pa_valid: A holds the counts of a paint; paint_form: 0 auto, 1 global, 2 tiled.
+  // dropped particles (8 bytes).  has.counts(): A holds the counts of a paint; paint_form: 0 auto, 1 global, 2 tiled.
   rfc::DevBuf<> Q, A, pa_drop;
-  bool pa_valid = false;
   int paint_form = 0;
   // lazy, rf_particles_gather: the gathered values PG[3][nx][ny][nz] of the plan's real type (3 x w_bytes, zeroed once), indexed by the
   // particle's lattice cell as Q is and counted by rf_plan_nbytes; the drop counter is pa_drop.  gather_form: 0 auto, 1 global, 2 tiled.
@@ -192,12 +192,10 @@ struct rf_plan {
   bool have_fast = false, exact_gen = false;
   std::vector<double> h_kx2, h_ky2, h_kz2;   // host copies (k range of the grid for the fast records)
   rf::SigmaTableHost h_tab;
-  rfc::DevBuf<double> noise;
-  bool noise_resident = false;            // the device noise buffer holds a full set of deviates
+  rfc::DevBuf<double> noise;              // has.deviates64(): a full set of deviates
   // float32 deviates (rf_noise_mt19937_ex(single = 1)) stay where the one-pass replay writes them: mt_scratch, every
-  // segment's accepted pairs from slot seg * seg_cap, located through mt_offsets (FastGenParams::seg_*).  Only one of
-  // the two forms (float64 in cell order / float32 in segment order) is valid at a time.
-  bool noise32_resident = false;
+  // segment's accepted pairs from slot seg * seg_cap, located through mt_offsets (FastGenParams::seg_*): has.deviates32().  Only one
+  // of the two forms (float64 in cell order / float32 in segment order) is valid at a time.
   unsigned long long seg_cap = 0;
   int nseg = 0;
   rfc::DevBuf<> mt_rowtab;             // float32 form: where each row (ix, iy) of the stream starts in the runs (rf_core.h RowLoc, 8 B x nx ny)
@@ -236,7 +234,6 @@ struct rf_plan {
   rfc::DevBuf<double> lntab, ypart;
   bool ln_tables = false, ln_density = false;
   rfc::Timeline tl;                    // the last call's start, end and marks: rf_elapsed_ms, rf_kernel_ms, rf_merged_yz_ms
-  bool aux_valid = false;              // the k buffer's memory currently holds an auxiliary REAL field (lensing potential)
   bool unpacked = false;               // c2c plan: W is the full [nx][ny][nz] complex array, only rf_*_c / rf_execute_c2c apply
   // non-power-of-two grid (rf_generic.h): the transforms run on API-layout arrays, K -> G -> W (generation fused into the x pass only
   // with fused_generic), no graphs, one rank.  gax / gay factor nx / ny, gaz factors nz/2 (packed plans) or nz (c2c plans)
@@ -245,14 +242,12 @@ struct rf_plan {
   rfc::DevBuf<> G2;                    // lazy second scratch: only when an axis is too long for one line (four-step form, rf_generic.h)
   rf::GenericAxis gax, gay, gaz;
   rf::GenericDims gdims;               // the same + the split of the long axes, as the sequences of rf_generic.h take them
-  bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; k_valid untouched)
+  bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; has.kspace() untouched)
   rfc::DevBuf<> pw_buf;                 // lazy, rf_measure_power: squared edges, result, per-workgroup partials
   rfc::DevBuf<> mp_buf;                 // lazy, rf_measure_multipoles: squared edges, result, compensation tables, per-workgroup partials (counted by rf_plan_nbytes)
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations
-  bool real_valid = false, k_valid = false, stats_valid = false;
-  void* cur = nullptr;                    // buffer holding the current real-space field
-  int stats_slot = 0;                     // which (sum, sumsq) pair of `stats` belongs to the current field
+  rfc::Contents has;                      // what W / W2, stats, K, noise / mt_scratch, L and A hold right now
 };
 
 namespace rfc {
@@ -283,7 +278,6 @@ int direct_barrier(rf_plan* p, hipStream_t s);
 int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, Timeline* tl);
 int ensure_stats(rf_plan* p, int n);
 int rms_from_stats(rf_plan* p, int n, double* rms_out);
-void field_ready(rf_plan* p, int slot);
 int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStream_t s);
 int queue_r2c_slab_rows(rf_plan* p, hipStream_t s);
 int queue_r2c_slab_cols(rf_plan* p, hipStream_t s);
