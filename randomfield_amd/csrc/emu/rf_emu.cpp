@@ -4,8 +4,10 @@
 // kernels inline, one "thread" after another with a plain array standing in
 // for LDS and a loop boundary standing in for each workgroup barrier.  It
 // checks index math, twiddles, Hermitian packing and the generation rules
-// against the oracle without a GPU.  It is not a product path: nothing in
-// randomfield_amd/ loads it.
+// against the oracle without a GPU.  Which configuration a pass takes, which
+// launches it makes and how its IO object is filled come from the functions the
+// launchers call: rf_select.h and the builders next to each IO type.  It is
+// not a product path: nothing in randomfield_amd/ loads it.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -14,7 +16,7 @@
 #include <pthread.h>
 #include <thread>
 #include <vector>
-#include "../rf_configs.h"
+#include "../rf_select.h"
 #include "../rf_host.h"
 #include "../rf_generic.h"
 
@@ -22,17 +24,28 @@ using namespace rf;
 
 namespace {
 
-template <class C, int DIR, class IO>
-void run_col_pass(const IO& io_in, long long ncols, const cplx<typename C::T>* tw) {
+// The tiles (tile pairs) of one launch: b * mul + add for b in [0, count), less the skipped ones -- a FastStep (rf_select.h), walked with
+// fast_step_tile as the kernels walk it.  every(n): the launch over all n tiles.
+inline FastStep every(long long n) { return FastStep{FAST_COL, FAST_IO_REPAIR, n, 1, 0, 0, false}; }
+// what the last emulated fast generation pass ran (emu_fast_steps): its steps, and how often each tile of the pass was transformed
+std::vector<FastStep> g_fast_steps;
+std::vector<int> g_fast_visits;
+bool g_count_visits = false;
+inline void visit(long long tile) { if (g_count_visits && tile >= 0 && tile < (long long)g_fast_visits.size()) ++g_fast_visits[(size_t)tile]; }
+struct NoHook { template <class IO> void operator()(long long, const std::vector<IO>&) const {} };
+
+// hook(tile, ios): called after every tile with the threads' IO objects (what the kernel's epilogue reads: AccColIO's sums)
+template <class C, int DIR, class IO, class Hook = NoHook>
+void run_col_pass(const IO& io_in, const FastStep& run, const cplx<typename C::T>* tw, Hook hook = Hook()) {
   using F = ColFFT<C, DIR, IO>;
   using cx = cplx<typename C::T>;
   std::vector<cx> lds((size_t)(C::LDS_BYTES + IO::LDS_EXTRA) / sizeof(cx));   // exactly the kernel's dynamic LDS
   std::vector<typename F::Regs> regs(C::NT);
-  std::vector<IO> ios(C::NT, io_in);             // every "thread" has its own copy of the kernel argument
-  for (auto& io : ios) io.bind_seed();
-  const long long ntiles = ncols / C::TC;
-  for (long long t0 = 0; t0 < ntiles; ++t0) {
-    const long long tile = io_in.remap_tile(t0);
+  for (long long b = 0; b < run.count; ++b) {
+    std::vector<IO> ios(C::NT, io_in);           // every "thread" of a workgroup has its own copy of the kernel argument
+    for (auto& io : ios) io.bind_seed();
+    const long long tile = io_in.remap_tile(fast_step_tile(run, b));
+    visit(tile);
     const cx* ltw = tw;
     if (F::HAS_PROLOGUE) {
       for (int t = 0; t < C::NT; ++t) F::prologue(t, ios[t], tw, lds.data());
@@ -45,12 +58,13 @@ void run_col_pass(const IO& io_in, long long ncols, const cplx<typename C::T>* t
     }
     if (C::NPASS >= 2)
       for (int t = 0; t < C::NT; ++t) F::pass_last(t, tile, ios[t], ltw, lds.data());
+    hook(tile, ios);
   }
 }
 
 // a pass of length 2 C1::N through Col2 (col2_kernel's phases, a loop boundary for each of its barriers); tw2 = the 2 C1::N-point table
 template <class C1, int DIR, class IO>
-void run_col2_pass(const IO& io_in, long long ncols, const cplx<typename C1::T>* tw2) {
+void run_col2_pass(const IO& io_in, const FastStep& run, const cplx<typename C1::T>* tw2) {
   using X = Col2<C1, DIR, IO>;
   using F = typename X::F;
   using cx = cplx<typename C1::T>;
@@ -60,9 +74,9 @@ void run_col2_pass(const IO& io_in, long long ncols, const cplx<typename C1::T>*
   std::vector<typename X::Park> pk(C1::NT);
   std::vector<IO> ios(C1::NT, io_in);
   for (auto& io : ios) io.bind_seed();
-  const long long ntiles = ncols / C1::TC;
-  for (long long t0 = 0; t0 < ntiles; ++t0) {
-    const long long tile = io_in.remap_tile(t0);
+  for (long long b = 0; b < run.count; ++b) {
+    const long long tile = fast_step_tile(run, b);
+    visit(tile);
     if (IO::LDS_EXTRA > 0) for (int t = 0; t < C1::NT; ++t) ios[t].prologue(t, C1::NT, F::lds_io(lds.data()));
     for (int t = 0; t < C1::NT; ++t) X::tw_fetch(t, tw2, twr[t]);
     const cx* ltw = F::lds_tw(lds.data());
@@ -82,7 +96,7 @@ void run_col2_pass(const IO& io_in, long long ncols, const cplx<typename C1::T>*
 // tile pairs with whole-line stores (rf_kernels.h colpair_body, rf_fft_col.h ColPair): phase 0 transforms tile 2p and PARKS the last
 // pass's outputs, phase 1 transforms tile 2p + 1 (built without the kz = 0 repair: FIXOK = false) and stores both tiles row by row
 template <class C, int DIR, class IO>
-void run_colpair_pass(const IO& io_in, long long ncols, const cplx<typename C::T>* tw) {
+void run_colpair_pass(const IO& io_in, const FastStep& run, const cplx<typename C::T>* tw) {
   using X = ColPair<C, DIR, IO>;
   using F = typename X::F;
   using cx = cplx<typename C::T>;
@@ -93,13 +107,14 @@ void run_colpair_pass(const IO& io_in, long long ncols, const cplx<typename C::T
   std::vector<typename X::Park> pk(C::NT);
   std::vector<IO> ios(C::NT, io_in);
   for (auto& io : ios) io.bind_seed();
-  const long long npairs = ncols / (2 * C::TC);
-  for (long long pair = 0; pair < npairs; ++pair) {
+  for (long long b = 0; b < run.count; ++b) {
+    const long long pair = fast_step_tile(run, b);
     if (IO::LDS_EXTRA > 0) for (int t = 0; t < C::NT; ++t) ios[t].prologue(t, C::NT, F::lds_io(lds.data()));
     for (int t = 0; t < C::NT; ++t) F::tw_fetch(t, tw, twr[t]);
     const cx* ltw = F::lds_tw(lds.data());
     for (int phase = 0; phase < 2; ++phase) {
       const long long tile = 2 * pair + phase;
+      visit(tile);
       if (F::PRELOAD) for (int t = 0; t < C::NT; ++t) F::preload(t, tile, ios[t], pre[t]);
       for (int t = 0; t < C::NT; ++t) {
         if (phase == 0) F::template pass_first<true>(t, tile, ios[t], lds.data(), pre[t], F::PRELOAD);
@@ -115,73 +130,50 @@ void run_colpair_pass(const IO& io_in, long long ncols, const cplx<typename C::T
     }
   }
 }
-int g_pairs = 1;           // (the product's rule: the float32 generation pass of length 1024 runs on tile pairs)
 
-// the product's rule (rf_k_col_plain.hip / rf_k_col_gen.hip): float32 in-place passes of length 2048 -- and, since round 4, of length
-// 1024 -- run through Col2 (two half-length transforms per tile)
-template <typename T, int DIR>
-bool pair_pass_2048(int N, cplx<T>* base, ColGeom g, long long ncols) {
-  if ((N != 2048 && N != 1024) || sizeof(T) != 4 || ncols % 8) return false;
-  if constexpr (sizeof(T) == 4) {
-    auto tw2 = make_twiddles<float>(N);
-    Pair2ColIO<float> io; io.base = base; io.g = g; io.gin = g; io.gin.row_stride = 2 * g.row_stride; io.par_off = g.row_stride;
-    if (N == 2048) run_col2_pass<GenSel<float, 1024>::type, DIR, Pair2ColIO<float>>(io, ncols, tw2.data());
-    else run_col2_pass<PairSel1024::type, DIR, Pair2ColIO<float>>(io, ncols, tw2.data());
-  }
-  return true;
-}
-
-template <typename T, int DIR, class IO, template <typename, int> class SEL = ColSel>
-int dispatch_col(int N, const IO& io, long long ncols) {
+// one whole-column pass of length N over all its tiles, on the configuration SEL<T, N> (ColSel, or GenSel for the generating x pass)
+template <typename T, int DIR, class IO, template <typename, int> class SEL = ColSel, class Hook = NoHook>
+int dispatch_col(int N, const IO& io, long long ncols, Hook hook = Hook()) {
   auto tw = make_twiddles<T>(N);
-  switch (N) {
-#define X(NN)                                                                        \
-  case NN:                                                                           \
-    if (ncols % SEL<T, NN>::type::TC) return -2;                                     \
-    run_col_pass<typename SEL<T, NN>::type, DIR, IO>(io, ncols, tw.data());          \
+  return for_col_size(N, -1, [&](auto n) {
+    using C = typename SEL<T, decltype(n)::value>::type;
+    if (ncols % C::TC) return -2;
+    run_col_pass<C, DIR, IO>(io, every(ncols / C::TC), tw.data(), hook);
     return 0;
-    RF_COL_SIZES(X)
-#undef X
-    default: return -1;
-  }
+  });
 }
 
-// The product's hand-off of the x pass's output through the blocked intermediate X [x block][kz tile][ny][rb][tc] (rf_capi.hip
-// queue_xyz / queue_yz): y pass in place on X, z pass gathering X -> W.  g_xposed mirrors RF_FLAG_TRANSPOSED_INTERMEDIATE; the
-// rule for when it applies is the product's xpose_ok().
-int g_xposed = 0;          // (the product's default: RF_FLAG_TRANSPOSED_INTERMEDIATE is off)
+// The in-place strided pass as launch_col_plain (rf_k_col_plain.hip) runs it: two half-length transforms per tile where rf_select.h
+// for_col_halves says so and the geometry fits, else the whole column.  emu_set_col_halves(0) keeps the whole column everywhere.
+int g_col_halves = 1;
+template <typename T, int DIR>
+int plain_col_pass(int N, cplx<T>* base, const ColGeom& g, long long ncols) {
+  int rc = 0;
+  if (g_col_halves && for_col_halves(sizeof(T) == 8, N, g, [&](auto c) {
+        using C1 = typename decltype(c)::type;
+        if (ncols % C1::TC) { rc = -2; return; }
+        auto tw2 = make_twiddles<float>(N);
+        run_col2_pass<C1, DIR>(pair2_col_io<Pair2ColIO<float>>((cplx<float>*)base, g), every(ncols / C1::TC), tw2.data());
+      }))
+    return rc;
+  PlainColIO<T> io; io.base = base; io.g = g;
+  return dispatch_col<T, DIR>(N, io, ncols);
+}
+inline ColGeom x_geom(long long ny, long long nzl) { return ColGeom{ny * nzl, 0, ny * nzl}; }       // x pass: C = iy * nzl + kz, row = ix
+inline ColGeom y_geom(long long ny, long long nzl) { return ColGeom{nzl, ny * nzl, nzl}; }          // y pass: C = ix * nzl + kz, row = iy
+
+// The hand-off of the x pass's output through the blocked intermediate X [x block][kz tile][ny][rb][tc] (rf_capi.hip queue_xyz /
+// queue_yz): y pass in place on X, z pass gathering X -> W.  g_xposed mirrors RF_FLAG_TRANSPOSED_INTERMEDIATE, g_rowblock the rows of
+// x per block the plan asks for; whether the shape allows it: rf_select.h xpose_shape_ok.
+int g_xposed = 0;          // (RF_FLAG_TRANSPOSED_INTERMEDIATE is off by default)
 int g_rowblock = 64;
-template <typename T> int tile_cols(int N, bool gen) {
-  switch (N) {
-#define X(NN) case NN: return gen ? GenSel<T, NN>::type::TC : ColSel<T, NN>::type::TC;
-    RF_COL_SIZES(X)
-#undef X
-    default: return 0;
-  }
-}
-template <typename T> int row_block(int N) {          // the product's col_gen_row_block()
-  if (g_rowblock <= 0 || g_rowblock >= N || (g_rowblock & (g_rowblock - 1))) return N;
-  switch (N) {
-#define X(NN) case NN: { using C = typename GenSel<T, NN>::type; return (C::NPASS >= 2 && (NN / C::RL) % g_rowblock == 0) ? g_rowblock : N; }
-    RF_COL_SIZES(X)
-#undef X
-    default: return N;
-  }
-}
-template <typename T> bool xgather_ok(int M, int tc, int rb) {     // the product's row_c2r_xgather_ok()
-  switch (M) {
-#define X(MM) case MM: { using C = typename RowSel<T, MM>::type; return tc > 0 && rb > 0 && rb % C::NRT == 0 && M % tc == 0; }
-    RF_ROW_SIZES(X)
-#undef X
-    default: return false;
-  }
-}
-template <typename T> bool xpose_ok(int nx, int ny, long long nzl) {
-  const int tcx = tile_cols<T>(nx, true), tcy = tile_cols<T>(ny, false);
-  return g_xposed && tcx > 0 && tcx == tcy && nzl >= tcx && nzl % tcx == 0 && xgather_ok<T>((int)nzl, tcx, row_block<T>(nx));
+template <typename T> bool xposed(int nx, int ny, long long nzc) {
+  constexpr int f64 = sizeof(T) == 8;
+  return g_xposed && xpose_shape_ok(f64, nx, ny, nzc, nzc, col_gen_row_block(f64, nx, g_rowblock));
 }
 template <typename T> ColGeom xposed_x_geom(int nx, int ny, long long nzl) {
-  return xblock_x_geom(nx, ny, nzl, tile_cols<T>(nx, true), row_block<T>(nx));
+  constexpr int f64 = sizeof(T) == 8;
+  return xblock_x_geom(nx, ny, nzl, col_gen_tile_cols(f64, nx), col_gen_row_block(f64, nx, g_rowblock));
 }
 
 template <class C, class IO>
@@ -209,39 +201,35 @@ void run_row_c2r(const IO& io_in, long long nrows, const cplx<typename C::T>* tw
   }
   *s1 = a1; *s2 = a2;
 }
-
-template <typename T>
-int dispatch_row_c2r(int M, cplx<T>* base, long long nrows, double scale, double* s1, double* s2) {
+// the z pass of rows of M complex with the IO that make_io(Cfg<row configuration>) returns
+template <typename T, class MakeIO>
+int dispatch_row_c2r(int M, long long nrows, double* s1, double* s2, MakeIO make_io) {
   auto tw = make_twiddles<T>(2 * M);
-  PlainRowIO<T> io; io.base = base; io.scale = (T)scale; io.M_of = M;
-  switch (M) {
-#define X(MM) case MM: run_row_c2r<typename RowSel<T, MM>::type, PlainRowIO<T>>(io, nrows, tw.data(), s1, s2); return 0;
-    RF_ROW_SIZES(X)
-#undef X
-    default: return -1;
-  }
+  return for_row_size(M, -1, [&](auto m) {
+    using C = typename RowSel<T, decltype(m)::value>::type;
+    auto io = make_io(Cfg<C>{});
+    run_row_c2r<C, decltype(io)>(io, nrows, tw.data(), s1, s2);
+    return 0;
+  });
+}
+template <typename T>
+int plain_row_c2r(int M, cplx<T>* base, long long nrows, double scale, double* s1, double* s2) {
+  return dispatch_row_c2r<T>(M, nrows, s1, s2, [&](auto) { PlainRowIO<T> io; io.base = base; io.scale = (T)scale; io.M_of = M; return io; });
+}
+template <typename T>
+int xgather_row_c2r(int M, int nx, int ny, int tc, int rb, const cplx<T>* X, cplx<T>* W, double scale, double* s1, double* s2) {
+  return dispatch_row_c2r<T>(M, (long long)nx * ny, s1, s2, [&](auto) { return xgather_row_io(X, W, scale, M, tc, rb, ny); });
 }
 
-// y pass in place on X, then the gathering z pass X -> W (+ moments)
+// y pass in place on X (launch_col_xpose: whole columns), then the gathering z pass X -> W (+ moments)
 template <typename T>
 int xposed_yz(int nx, int ny, int nz, cplx<T>* X, cplx<T>* W, double* s1, double* s2) {
-  const long long nzc = nz / 2, tc = tile_cols<T>(ny, false), rb = row_block<T>(nx);
-  XposeColIO<T> io;
-  io.src = X; io.gs = xblock_y_geom(nx, ny, nzc, tc, rb);
-  io.base = X; io.g = io.gs;
-  set_xpose_order(io, nx, nzc / tc);
-  if (int rc = dispatch_col<T, +1>(ny, io, (long long)nx * nzc)) return rc;
-  auto tw = make_twiddles<T>(2 * (int)nzc);
-  XGatherRowIO<T> zio;
-  zio.src = X; zio.dst = W; zio.scale = (T)(1.0 / ((double)nx * ny * nz)); zio.M_of = (int)nzc;
-  zio.seg_shift = ilog2ll(tc); zio.rb_shift = ilog2ll(rb); zio.ny_shift = ilog2ll(ny);
-  zio.kt_stride = (long long)ny * rb * tc; zio.xb_stride = (nzc / tc) * zio.kt_stride;
-  switch ((int)nzc) {
-#define X(MM) case MM: run_row_c2r<typename RowSel<T, MM>::type, XGatherRowIO<T>>(zio, (long long)nx * ny, tw.data(), s1, s2); return 0;
-    RF_ROW_SIZES(X)
-#undef X
-    default: return -1;
-  }
+  constexpr int f64 = sizeof(T) == 8;
+  const long long nzc = nz / 2;
+  const int tc = col_tile_cols(f64, ny), rb = col_gen_row_block(f64, nx, g_rowblock);
+  const ColGeom gy = xblock_y_geom(nx, ny, nzc, tc, rb);
+  if (int rc = dispatch_col<T, +1>(ny, xpose_col_io<T>(X, gy, X, gy, (long long)nx * nzc, tc), (long long)nx * nzc)) return rc;
+  return xgather_row_c2r<T>((int)nzc, nx, ny, tc, rb, X, W, 1.0 / ((double)nx * ny * nz), s1, s2);
 }
 
 template <class C>
@@ -268,12 +256,7 @@ template <typename T>
 int dispatch_row_r2c(int M, cplx<T>* base, long long nrows) {
   auto tw = make_twiddles<T>(2 * M);
   PlainRowFwdIO<T> io; io.base = base; io.M_of = M;
-  switch (M) {
-#define X(MM) case MM: run_row_r2c<typename RowSel<T, MM>::type>(io, nrows, tw.data()); return 0;
-    RF_ROW_SIZES(X)
-#undef X
-    default: return -1;
-  }
+  return for_row_size(M, -1, [&](auto m) { run_row_r2c<typename RowSel<T, decltype(m)::value>::type>(io, nrows, tw.data()); return 0; });
 }
 
 template <typename T>
@@ -283,11 +266,9 @@ int r2c_impl(int nx, int ny, int nz, const T* field, cplx<T>* K) {
   memcpy(W.data(), field, W.size() * sizeof(cplx<T>));
   int rc = dispatch_row_r2c<T>((int)nzc, W.data(), (long long)nx * ny);
   if (rc) return rc;
-  PlainColIO<T> yio; yio.base = W.data(); yio.g = ColGeom{nzc, (long long)ny * nzc, nzc};
-  rc = dispatch_col<T, -1>(ny, yio, (long long)nx * nzc);
+  rc = plain_col_pass<T, -1>(ny, W.data(), y_geom(ny, nzc), (long long)nx * nzc);
   if (rc) return rc;
-  PlainColIO<T> xio; xio.base = W.data(); xio.g = ColGeom{(long long)ny * nzc, 0, (long long)ny * nzc};
-  rc = dispatch_col<T, -1>(nx, xio, (long long)ny * nzc);
+  rc = plain_col_pass<T, -1>(nx, W.data(), x_geom(ny, nzc), (long long)ny * nzc);
   if (rc) return rc;
   const int nzh = (int)nzc + 1;
   for (int ix = 0; ix < nx; ++ix)
@@ -325,22 +306,15 @@ template <typename T, int DIR>
 int dispatch_row_c2c(int M, cplx<T>* base, long long nrows, double scale) {
   auto tw = make_twiddles<T>(M);
   ScaledRowIO<T> io; io.base = base; io.M_of = M; io.scale = (T)scale;
-  switch (M) {
-#define X(MM) case MM: run_row_c2c<typename RowSel<T, MM>::type, DIR>(io, nrows, tw.data()); return 0;
-    RF_ROWC_SIZES(X)
-#undef X
-    default: return -1;
-  }
+  return for_rowc_size(M, -1, [&](auto m) { run_row_c2c<typename RowSel<T, decltype(m)::value>::type, DIR>(io, nrows, tw.data()); return 0; });
 }
 
 // unpacked c2c in place on data[nx][ny][nz] (same pass order as rf_execute_c2c)
 template <typename T, int DIR>
 int c2c_impl(int nx, int ny, int nz, cplx<T>* W) {
-  PlainColIO<T> xio; xio.base = W; xio.g = ColGeom{(long long)ny * nz, 0, (long long)ny * nz};
-  int rc = dispatch_col<T, DIR>(nx, xio, (long long)ny * nz);
+  int rc = plain_col_pass<T, DIR>(nx, W, x_geom(ny, nz), (long long)ny * nz);
   if (rc) return rc;
-  PlainColIO<T> yio; yio.base = W; yio.g = ColGeom{nz, (long long)ny * nz, nz};
-  rc = dispatch_col<T, DIR>(ny, yio, (long long)nx * nz);
+  rc = plain_col_pass<T, DIR>(ny, W, y_geom(ny, nz), (long long)nx * nz);
   if (rc) return rc;
   return dispatch_row_c2c<T, DIR>(nz, W, (long long)nx * ny, DIR > 0 ? 1.0 / ((double)nx * ny * nz) : 1.0);
 }
@@ -360,38 +334,39 @@ void fill_gen(GenHost& h, int nx, int ny, int nz, const double* kx2, const doubl
   g.noise_mode = noise_mode; g.seed = seed; g.seed_dev = nullptr; g.noise = noise;
   g.zpitch = nz / 2 + 1; g.zoff = 0;
 }
+// the parameters of an x pass that reads an API-layout k array instead of generating
+inline GenParams kspace_params(int nx, int ny, int nz) {
+  GenParams gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.nx = nx; gp.ny = ny; gp.nz = nz; gp.zpitch = nz / 2 + 1;
+  return gp;
+}
+
+// the y and z passes behind an x pass that wrote `Wx` (W itself, or the blocked intermediate)
+template <typename T>
+int yz_passes(int nx, int ny, int nz, cplx<T>* Wx, cplx<T>* W, double* s1, double* s2) {
+  const long long nzc = nz / 2;
+  if (Wx != W) return xposed_yz<T>(nx, ny, nz, Wx, W, s1, s2);
+  if (int rc = plain_col_pass<T, +1>(ny, W, y_geom(ny, nzc), (long long)nx * nzc)) return rc;
+  return plain_row_c2r<T>((int)nzc, W, (long long)nx * ny, 1.0 / ((double)nx * ny * nz), s1, s2);
+}
 
 template <typename T>
 int c2r_impl(int nx, int ny, int nz, const GenHost* gen, const cplx<T>* kspace, cplx<T>* W, double* s1, double* s2) {
   const long long nzc = nz / 2;
-  // x pass (generation or API-layout k-space fused into the load)
-  GenColIO<T> gio;
-  gio.base = W; gio.g = ColGeom{(long long)ny * nzc, 0, (long long)ny * nzc};
-  if (gen) gio.gp = gen->gp; else { memset(&gio.gp, 0, sizeof(gio.gp)); gio.gp.nx = nx; gio.gp.ny = ny; gio.gp.nz = nz; gio.gp.zpitch = nz / 2 + 1; }
-  gio.kspace = kspace; gio.kz0 = 0; gio.nzl = (int)nzc;
-  int rc;
-  if (xpose_ok<T>(nx, ny, nzc)) {                  // x pass -> transposed intermediate, y pass X -> W
-    std::vector<cplx<T>> X((size_t)nx * ny * nzc);
-    gio.base = X.data(); gio.g = xposed_x_geom<T>(nx, ny, nzc);
-    rc = dispatch_col<T, +1, GenColIO<T>, GenSel>(nx, gio, (long long)ny * nzc);
-    if (rc) return rc;
-    return xposed_yz<T>(nx, ny, nz, X.data(), W, s1, s2);
-  }
-  rc = dispatch_col<T, +1, GenColIO<T>, GenSel>(nx, gio, (long long)ny * nzc);
-  if (rc) return rc;
-  // y pass, in place
-  PlainColIO<T> pio; pio.base = W; pio.g = ColGeom{nzc, (long long)ny * nzc, nzc};
-  rc = dispatch_col<T, +1>(ny, pio, (long long)nx * nzc);
-  if (rc) return rc;
-  // z pass c2r, in place
-  return dispatch_row_c2r<T>((int)nzc, W, (long long)nx * ny, 1.0 / ((double)nx * ny * nz), s1, s2);
+  // x pass (generation or API-layout k-space fused into the load), into W or the blocked intermediate
+  const bool xp = xposed<T>(nx, ny, nzc);
+  std::vector<cplx<T>> X(xp ? (size_t)nx * ny * nzc : 0);
+  cplx<T>* Wx = xp ? X.data() : W;
+  const GenColIO<T> gio = gen_col_io<T>(Wx, xp ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nzc), gen ? gen->gp : kspace_params(nx, ny, nz), kspace, 0, (int)nzc);
+  if (int rc = dispatch_col<T, +1, GenColIO<T>, GenSel>(nx, gio, (long long)ny * nzc)) return rc;
+  return yz_passes<T>(nx, ny, nz, Wx, W, s1, s2);
 }
 
 // fix_fill_kernel (rf_kernels.h): the repaired kz = 0 slot of every mode (ix, iy) into the side buffer the FIX = 3 launch reads
 template <class IOF, class CT>
-void fill_fix_buffer(IOF iof, std::vector<CT>& buf) {
+void fill_fix_buffer(IOF iof, CT* buf) {
   const int nx = iof.gp.nx, ny = iof.gp.ny;
-  buf.resize((size_t)nx * ny);
   std::vector<char> lds(IOF::LDS_EXTRA + 16);
   iof.bind_seed();
   iof.prologue(0, 1, lds.data());
@@ -399,105 +374,80 @@ void fill_fix_buffer(IOF iof, std::vector<CT>& buf) {
     for (int ix = 0; ix < nx; ++ix) buf[(size_t)iy * nx + ix] = iof.fix_value((long long)iy * iof.nzl, ix, 0);
 }
 
-template <typename T, class IO>
+// One step of a fast generation pass as rf_col_gen_launch.h FastLaunch::step turns it into a launch: P = the variant's rf_select.h
+// FastPassOf, the IO type by the step's io, the kernel by its kind; the tiles by fast_step_tile.
+template <class P>
+int run_fast_step(const FastIoArgs<typename P::T>& a, const FastStep& st, const cplx<typename P::T>* tw) {
+  using C = typename P::C;
+  auto one = [&](auto io) {
+    if constexpr (P::HALVES) run_col2_pass<C, +1>(io, st, tw);
+    else run_col_pass<C, +1>(io, st, tw);
+    return 0;
+  };
+  switch (st.kind) {
+    case FAST_FIX_FILL:
+      if constexpr (P::side) { fill_fix_buffer(fast_col_io<typename P::IOF>(a), a.fixbuf); return 0; }
+      return -2;
+    case FAST_COLPAIR:
+      if constexpr (P::pairs) {
+        if (st.io == FAST_IO_LEAN) { run_colpair_pass<C, +1>(fast_col_io<typename P::IO0>(a), st, tw); return 0; }
+        if (st.io == FAST_IO_FIRST) { run_colpair_pass<C, +1>(fast_col_io<typename P::IOC>(a), st, tw); return 0; }
+      }
+      return -2;
+    default:
+      return st.io == FAST_IO_LEAN ? one(fast_col_io<typename P::IO0>(a)) : st.io == FAST_IO_REPAIR ? one(fast_col_io<typename P::IO1>(a)) : one(fast_col_io<typename P::IOC>(a));
+  }
+}
+// The variant and the launches of the native fast generation pass of a whole grid on one rank, as launch_col_fastgen chooses them:
+// fastgen_variant, its FastListOf entry at length nx, fastgen_sequence.  f(Cfg<FastPassOf>{}, sequence); -2: the library refuses.
+int g_pairs = 1;           // emu_set_pairs(0) clears FastPass::pairs: one tile per workgroup (ColFFT) where the library runs tile pairs
+template <typename T, class F>
+int with_fast_pass(int nx, const ColGeom& g, long long ncols, int nzl, F&& f) {
+  const FastVariant v = fastgen_variant(sizeof(T) == 8, nx, false, false, false, false, false);
+  return with_fast_variant(FastListOf<T>{}, v, -2, [&](auto e) {
+    return FastGen<T>::template at<decltype(e)>(nx, -2, [&](auto k) {
+      using P = typename decltype(k)::type;
+      if (!P::accepts(g, ncols, nzl, 0, 1 << 30)) return -2;
+      FastPass pass = P::pass;
+      if (!g_pairs) pass.pairs = false;
+      const FastSequence q = fastgen_sequence(pass, nzl, ncols, 0, true, g, true);
+      return q.valid ? f(k, q) : -2;
+    });
+  });
+}
+
+template <typename T>
 int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, double xlo, double xhi, double dkx,
                       cplx<T>* W, double* s1, double* s2) {
-  const long long nzc = nz / 2;
+  const long long nzc = nz / 2, ncols = (long long)ny * nzc;
   std::vector<FastRec> rec;
-  IO io;
-  io.base = W; io.g = ColGeom{(long long)ny * nzc, 0, (long long)ny * nzc}; io.kz0 = 0; io.nzl = (int)nzc; io.rec = nullptr;
-  FastGenParams& f = io.gp;
+  FastGenParams f;
+  memset(&f, 0, sizeof(f));
   double x0, dx;
   if (!build_fast_records(h.tab, xlo, xhi, rec, x0, dx)) return -3;
   if ((int)rec.size() > FAST_LDS_BINS) return -3;          // as build_fast (rf_capi.hip): such a plan runs the exact kernel
   f.nx = nx; f.ny = ny; f.nz = nz; f.dkx = (float)dkx; f.dky = (float)std::sqrt(h.gp.ky2[1]); f.dkz = (float)std::sqrt(h.gp.kz2[1]);
   f.rec = rec.data(); f.nbins = (int)rec.size();
   f.u_scale = (float)(0.5 * std::log10(2.0) / dx); f.u_off = (float)(-x0 / dx);
-  f.seed = seed; f.seed_dev = nullptr; f.noise = nullptr; f.noise32 = nullptr; f.rowtab = nullptr; f.seg_cap = 0; f.zpitch = nz / 2 + 1; f.zoff = 0; f.ppitch = nz / 2 + 2;
-  int rc;
-  if (xpose_ok<T>(nx, ny, nzc)) {
-    std::vector<cplx<T>> X((size_t)nx * ny * nzc);
-    io.base = X.data(); io.g = xposed_x_geom<T>(nx, ny, nzc);
-    rc = dispatch_col<T, +1, IO, GenSel>(nx, io, (long long)ny * nzc);
-    if (rc) return rc;
-    return xposed_yz<T>(nx, ny, nz, X.data(), W, s1, s2);
-  }
-  bool x_done = false;
-  // (where the library splits the pass -- kz runs of more than one whole tile -- its repair launch is the FIX = 3 kernel behind
-  // fix_fill_kernel; the emulator runs that kernel over every tile: tiles without kz = 0 take nothing from the side buffer, as
-  // the FIX = 0 launch does)
-  std::vector<cplx<T>> fixbuf;
-  if constexpr (sizeof(T) == 4) {
-    if (nx == 2048 && ((long long)ny * nzc) % 8 == 0) {      // the library's x pass at this length: Col2 over the 1024-point configuration
-      using C1 = GenSel<float, 1024>::type;
-      using IO2 = FastGenColIOT<3, 0, 0, 0, 2>;
-      IO2 io2;
-      io2.base = W; io2.g = io.g; io2.kz0 = 0; io2.nzl = (int)nzc; io2.rec = nullptr; io2.gp = io.gp; io2.pot = nullptr;
-      typename IO2::fill_io iof;
-      iof.base = W; iof.g = io.g; iof.kz0 = 0; iof.nzl = (int)nzc; iof.rec = nullptr; iof.gp = io.gp; iof.pot = nullptr;
-      fill_fix_buffer(iof, fixbuf);
-      io2.fixbuf = fixbuf.data();
-      auto tw2 = make_twiddles<float>(2048);
-      run_col2_pass<C1, +1, IO2>(io2, (long long)ny * nzc, tw2.data());
-      x_done = true;
+  f.seed = seed; f.zpitch = nz / 2 + 1; f.zoff = 0; f.ppitch = nz / 2 + 2;
+  const bool xp = xposed<T>(nx, ny, nzc);
+  std::vector<cplx<T>> X(xp ? (size_t)nx * ny * nzc : 0), fixbuf((size_t)nx * ny);
+  cplx<T>* Wx = xp ? X.data() : W;
+  const FastIoArgs<T> a{f, Wx, xp ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nzc), 0, (int)nzc, 0, 1 << 30, nullptr, fixbuf.data()};
+  g_fast_steps.clear();
+  auto tw = make_twiddles<T>(nx);
+  g_count_visits = true;
+  const int rc = with_fast_pass<T>(nx, a.g, ncols, (int)nzc, [&](auto k, const FastSequence& q) {
+    g_fast_visits.assign((size_t)(ncols / decltype(k)::type::C::TC), 0);
+    for (int i = 0; i < q.n; ++i) {
+      g_fast_steps.push_back(q.step[i]);
+      if (int e = run_fast_step<typename decltype(k)::type>(a, q.step[i], tw.data())) return e;
     }
-  }
-  if constexpr (sizeof(T) == 8) {
-    if (nx == 1024 && ((long long)ny * nzc) % 8 == 0) {      // float64, length 1024: Col2 over the 512-point configuration
-      using C1 = GenSel<double, 512>::type;
-      using IO2 = FastGenColIO64<3, 0, 0, 2>;
-      IO2 io2;
-      io2.base = W; io2.g = io.g; io2.kz0 = 0; io2.nzl = (int)nzc; io2.rec = nullptr; io2.gp = io.gp; io2.pot = nullptr;
-      typename IO2::fill_io iof;
-      iof.base = W; iof.g = io.g; iof.kz0 = 0; iof.nzl = (int)nzc; iof.rec = nullptr; iof.gp = io.gp; iof.pot = nullptr;
-      fill_fix_buffer(iof, fixbuf);
-      io2.fixbuf = fixbuf.data();
-      auto tw2 = make_twiddles<double>(1024);
-      run_col2_pass<C1, +1, IO2>(io2, (long long)ny * nzc, tw2.data());
-      x_done = true;
-    }
-  }
-  if constexpr (sizeof(T) == 4) {
-    using C = GenSel<float, 1024>::type;
-    if (!x_done && g_pairs && nx == 1024 && nzc > C::TC && nzc % (2 * C::TC) == 0) {      // float32, length 1024: tile pairs (ColPair), repair from the side buffer
-      using IOC = typename IO::template with_fix<3>;
-      IOC ioc;
-      ioc.base = W; ioc.g = io.g; ioc.kz0 = 0; ioc.nzl = (int)nzc; ioc.rec = nullptr; ioc.gp = io.gp; ioc.pot = nullptr;
-      typename IOC::fill_io iof;
-      iof.base = W; iof.g = io.g; iof.kz0 = 0; iof.nzl = (int)nzc; iof.rec = nullptr; iof.gp = io.gp; iof.pot = nullptr;
-      fill_fix_buffer(iof, fixbuf);
-      ioc.fixbuf = fixbuf.data();
-      auto tw = make_twiddles<float>(1024);
-      run_colpair_pass<C, +1, IOC>(ioc, (long long)ny * nzc, tw.data());
-      x_done = true;
-    }
-  }
-  if (!x_done && (nx == 512 || nx == 1024)) {               // the long whole-column passes: FIX = 3 where the library splits
-    using IOC = typename IO::template with_fix<3>;
-    const int tc = tile_cols<T>(nx, true);
-    if (nzc > tc && nzc % tc == 0) {
-      IOC ioc;
-      ioc.base = W; ioc.g = io.g; ioc.kz0 = 0; ioc.nzl = (int)nzc; ioc.rec = nullptr; ioc.gp = io.gp; ioc.pot = nullptr;
-      typename IOC::fill_io iof;
-      iof.base = W; iof.g = io.g; iof.kz0 = 0; iof.nzl = (int)nzc; iof.rec = nullptr; iof.gp = io.gp; iof.pot = nullptr;
-      fill_fix_buffer(iof, fixbuf);
-      ioc.fixbuf = fixbuf.data();
-      rc = dispatch_col<T, +1, IOC, GenSel>(nx, ioc, (long long)ny * nzc);
-      if (rc) return rc;
-      x_done = true;
-    }
-  }
-  if (!x_done) {
-    rc = dispatch_col<T, +1, IO, GenSel>(nx, io, (long long)ny * nzc);
-    if (rc) return rc;
-  }
-  const ColGeom gy{nzc, (long long)ny * nzc, nzc};
-  if (!pair_pass_2048<T, +1>(ny, W, gy, (long long)nx * nzc)) {
-    PlainColIO<T> pio; pio.base = W; pio.g = gy;
-    rc = dispatch_col<T, +1>(ny, pio, (long long)nx * nzc);
-    if (rc) return rc;
-  }
-  return dispatch_row_c2r<T>((int)nzc, W, (long long)nx * ny, 1.0 / ((double)nx * ny * nz), s1, s2);
+    return 0;
+  });
+  g_count_visits = false;
+  if (rc) return rc;
+  return yz_passes<T>(nx, ny, nz, Wx, W, s1, s2);
 }
 
 
@@ -952,40 +902,16 @@ template <typename T>
 int c2r_lognormal_impl(int nx, int ny, int nz, const cplx<T>* kspace, const double* growth, const double* density, cplx<T>* W,
                        double* sigma_out, double* s1, double* s2) {
   const long long nzc = nz / 2;
-  GenColIO<T> gio;
-  gio.base = W; gio.g = ColGeom{(long long)ny * nzc, 0, (long long)ny * nzc};
-  memset(&gio.gp, 0, sizeof(gio.gp)); gio.gp.nx = nx; gio.gp.ny = ny; gio.gp.nz = nz; gio.gp.zpitch = nz / 2 + 1;
-  gio.kspace = kspace; gio.kz0 = 0; gio.nzl = (int)nzc;
-  int rc = dispatch_col<T, +1, GenColIO<T>, GenSel>(nx, gio, (long long)ny * nzc);
-  if (rc) return rc;
-  // y pass with the accumulator: run tile by tile so that every "thread"'s acc is collected (the kernel's finish())
-  const int tc = tile_cols<T>(ny, false);
+  const GenColIO<T> gio = gen_col_io<T>(W, x_geom(ny, nzc), kspace_params(nx, ny, nz), kspace, 0, (int)nzc);
+  if (int rc = dispatch_col<T, +1, GenColIO<T>, GenSel>(nx, gio, (long long)ny * nzc)) return rc;
+  // y pass with the accumulator (launch_col_plain_acc: whole columns): every "thread"'s sum is collected after its tile (the kernel's finish())
   double S = 0;
-  {
-    auto tw = make_twiddles<T>(ny);
-    const long long ncols = (long long)nx * nzc;
-    if (ncols % tc) return -2;
-    switch (ny) {
-#define X(NN) case NN: { using C = typename ColSel<T, NN>::type; using IO = AccColIO<T>; using F = ColFFT<C, +1, IO>;                 \
-      std::vector<cplx<T>> lds((size_t)(C::LDS_BYTES + IO::LDS_EXTRA) / sizeof(cplx<T>) + 1);                                       \
-      std::vector<typename F::Regs> regs(C::NT);                                                                                    \
-      for (long long tile = 0; tile < ncols / C::TC; ++tile) {                                                                      \
-        IO io0; io0.base = W; io0.g = ColGeom{nzc, (long long)ny * nzc, nzc}; io0.partials = nullptr; io0.kz0 = 0; io0.nzl = (int)nzc; \
-        std::vector<IO> ios(C::NT, io0);                                                                                            \
-        const cplx<T>* ltw = tw.data();                                                                                             \
-        if (F::HAS_PROLOGUE) { for (int t = 0; t < C::NT; ++t) F::prologue(t, ios[t], tw.data(), lds.data()); if (C::NPASS >= 2) ltw = F::lds_tw(lds.data()); } \
-        for (int t = 0; t < C::NT; ++t) F::pass_first(t, tile, ios[t], lds.data());                                                 \
-        if (C::NPASS == 3) { for (int t = 0; t < C::NT; ++t) F::pass_mid_read(t, ltw, lds.data(), regs[t]);                        \
-                             for (int t = 0; t < C::NT; ++t) F::pass_mid_write(t, lds.data(), regs[t]); }                          \
-        if (C::NPASS >= 2) for (int t = 0; t < C::NT; ++t) F::pass_last(t, tile, ios[t], ltw, lds.data());                          \
-        double a = 0; for (int t = 0; t < C::NT; ++t) a += ios[t].weighted_sum();                                                              \
-        S += a;                                                                                                                     \
-      } break; }
-      RF_COL_SIZES(X)
-#undef X
-      default: return -1;
-    }
-  }
+  auto collect = [&](long long, const std::vector<AccColIO<T>>& ios) {
+    double a = 0;
+    for (const auto& io : ios) a += io.weighted_sum();
+    S += a;
+  };
+  if (int rc = dispatch_col<T, +1>(ny, acc_col_io<T>(W, y_geom(ny, nzc), nullptr, 0, (int)nzc), (long long)nx * nzc, collect)) return rc;
   const double n3 = (double)nx * ny * nz;
   double sigma = std::sqrt(S / ((double)nx * ny * n3 * n3));
   if (sizeof(T) == 4) sigma = (double)(float)sigma;
@@ -996,15 +922,10 @@ int c2r_lognormal_impl(int nx, int ny, int nz, const cplx<T>* kspace, const doub
     Bp[z] = (density ? density[z] : 1.0) / std::sqrt(t);
   }
   *sigma_out = sigma;
-  auto twz = make_twiddles<T>(2 * (int)nzc);
-  switch ((int)nzc) {
-#define X(MM) case MM: { constexpr int SP = (sizeof(T) == 8 && MM >= 512) ? 1 : 0;              /* as rf_k_row.hip launch_lognormal_t */  \
-    LognormalRowIO<T, SP> zio; zio.base = W; zio.scale = (T)(1.0 / n3); zio.M_of = (int)nzc; zio.Ap = Ap.data(); zio.Bp = Bp.data();       \
-    run_row_c2r<typename RowSel<T, MM>::type, LognormalRowIO<T, SP>>(zio, (long long)nx * ny, twz.data(), s1, s2); return 0; }
-    RF_ROW_SIZES(X)
-#undef X
-    default: return -1;
-  }
+  return dispatch_row_c2r<T>((int)nzc, (long long)nx * ny, s1, s2, [&](auto c) {
+    LognormalIO<T, decltype(c)::type::M> zio; zio.base = W; zio.scale = (T)(1.0 / n3); zio.M_of = (int)nzc; zio.Ap = Ap.data(); zio.Bp = Bp.data();
+    return zio;
+  });
 }
 
 // The loop behind emu_measure_power and emu_measure_multipoles (rf_core.h power_load / bin_cell over an array in array order, as the
@@ -1225,8 +1146,8 @@ int emu_realise_fast(int f64, int nx, int ny, int nz, const double* kx2, const d
                      double dkx, void* W, double* s1, double* s2) {
   GenHost h;
   fill_gen(h, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, 0, seed, nullptr);
-  if (f64) return realise_fast_impl<double, FastGenColIO64<1>>(nx, ny, nz, h, seed, xlo, xhi, dkx, (cplx<double>*)W, s1, s2);
-  return realise_fast_impl<float, FastGenColIO>(nx, ny, nz, h, seed, xlo, xhi, dkx, (cplx<float>*)W, s1, s2);
+  return f64 ? realise_fast_impl<double>(nx, ny, nz, h, seed, xlo, xhi, dkx, (cplx<double>*)W, s1, s2)
+             : realise_fast_impl<float>(nx, ny, nz, h, seed, xlo, xhi, dkx, (cplx<float>*)W, s1, s2);
 }
 
 // Row T alone: the fast float32 sigma(|k|^2) lookup (per-bin records, rf_core.h fast_sigma) next to the exact float64
@@ -1273,25 +1194,14 @@ int emu_generate_kspace(int f64, int nx, int ny, int nz, const double* kx2, cons
 
 // the gathering z pass alone: X = blocked intermediate [nx / rb][M / tc][ny][rb][tc] -> W dense real rows [nx][ny][2 M]
 int emu_row_c2r_xgather(int f64, int M, int nx, int ny, int tc, int rb, const void* X, void* W, double scale, double* s1, double* s2) {
-  auto run = [&](auto tag) -> int {
-    using T = decltype(tag);
-    if (!xgather_ok<T>(M, tc, rb) || nx % rb) return -2;
-    auto tw = make_twiddles<T>(2 * M);
-    XGatherRowIO<T> zio;
-    zio.src = (const cplx<T>*)X; zio.dst = (cplx<T>*)W; zio.scale = (T)scale; zio.M_of = M;
-    zio.seg_shift = ilog2ll(tc); zio.rb_shift = ilog2ll(rb); zio.ny_shift = ilog2ll(ny);
-    zio.kt_stride = (long long)ny * rb * tc; zio.xb_stride = (long long)(M / tc) * zio.kt_stride;
-    switch (M) {
-#define X(MM) case MM: run_row_c2r<typename RowSel<T, MM>::type, XGatherRowIO<T>>(zio, (long long)nx * ny, tw.data(), s1, s2); return 0;
-      RF_ROW_SIZES(X)
-#undef X
-      default: return -1;
-    }
-  };
-  return f64 ? run(double()) : run(float());
+  if (!row_c2r_xgather_ok(f64, M, tc, rb) || nx % rb) return -2;
+  return with_real(f64, [&](auto r) {
+    using R = decltype(r);
+    return xgather_row_c2r<typename R::type>(M, nx, ny, tc, rb, R::p(X), R::p(W), scale, s1, s2);
+  });
 }
 
-// 1 (default): c2r transforms hand x -> y through the transposed intermediate where the product would; 0: in place
+// 1: c2r transforms hand x -> y through the blocked intermediate where the library would (rf_select.h xpose_shape_ok); 0 (default): in place
 int emu_set_xposed(int on) { const int old = g_xposed; g_xposed = on; return old; }
 int emu_set_rowblock(int rb) { const int old = g_rowblock; g_rowblock = rb; return old; }
 // the longest line the generic path keeps whole (0 = the library's cap, 8192 complex64 / 4096 complex128): longer axes take the four-step
@@ -1301,8 +1211,34 @@ int emu_set_generic_tile(int tc) { const int old = g_generic_tile; g_generic_til
 // host threads per block of the generic path (1, the default: one "thread" with a no-op barrier).  With nth > 1 the block functions
 // run on nth threads with a real barrier; nth a multiple of the tile takes the kernels' own walk (GenericWalk::fixed)
 int emu_set_generic_threads(int nth) { const int old = g_generic_threads; g_generic_threads = nth > 1 ? (nth < 1024 ? nth : 1024) : 1; return old; }
-// 1 (default): the float32 generation pass of length 1024 on tile pairs (ColPair), as the product; 0: one tile per workgroup (ColFFT)
+// 1 (default): the float32 generation pass of length 1024 on tile pairs (ColPair), as the library; 0: one tile per workgroup (ColFFT)
 int emu_set_pairs(int on) { const int old = g_pairs; g_pairs = on; return old; }
+// 1 (default): in-place strided passes take the halves form (Col2) where launch_col_plain does; 0: whole columns everywhere
+int emu_set_col_halves(int on) { const int old = g_col_halves; g_col_halves = on; return old; }
+// The launches of a fast generation pass as five numbers per step (kind, io, count, mul, skip_period: rf_select.h FastStep), at most
+// `max` steps; returns their number.  emu_fast_steps: what the last emu_realise_fast ran; emu_fast_visits: how often that call
+// transformed each tile of the x pass (out[tile], at most `max` tiles; returns the number of tiles); emu_fastgen_sequence: rf_select.h
+// fastgen_sequence called directly for the pass of that grid (honours emu_set_xposed / _rowblock / _pairs), -2 where the library refuses
+static int copy_steps(const FastStep* st, int n, long long* out5, int max) {
+  for (int i = 0; i < n && i < max; ++i) {
+    const long long v[5] = {st[i].kind, st[i].io, st[i].count, st[i].mul, st[i].skip_period};
+    std::copy(v, v + 5, out5 + 5 * i);
+  }
+  return n;
+}
+int emu_fast_steps(long long* out5, int max) { return copy_steps(g_fast_steps.data(), (int)g_fast_steps.size(), out5, max); }
+long long emu_fast_visits(int* out, long long max) {
+  std::copy(g_fast_visits.begin(), g_fast_visits.begin() + std::min<long long>(max, (long long)g_fast_visits.size()), out);
+  return (long long)g_fast_visits.size();
+}
+int emu_fastgen_sequence(int f64, int nx, int ny, int nz, long long* out5, int max) {
+  return with_real(f64, [&](auto r) {
+    using T = typename decltype(r)::type;
+    const long long nzc = nz / 2;
+    const ColGeom g = xposed<T>(nx, ny, nzc) ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nzc);
+    return with_fast_pass<T>(nx, g, (long long)ny * nzc, (int)nzc, [&](auto, const FastSequence& q) { return copy_steps(q.step, q.n, out5, max); });
+  });
+}
 // FastGenColIOT::share_row (rf_fft_gen.h): the butterfly row of slot jl when L butterflies are dealt to slots of S per wave so that
 // the rows +-ix sit 32 lanes apart (the sigma exchange of the x pass); a host-side table for the bijection test
 // (xs2_phase < 0: the whole-column form XS = 1; 0 / 1: the even / odd phase of the two-half-transform form XS = 2)
@@ -1331,7 +1267,7 @@ long long emu_fastdiv_first_error(unsigned d, unsigned amax) {
   }
   return -1;
 }
-int emu_xpose_applies(int f64, int nx, int ny, int nz) { return f64 ? xpose_ok<double>(nx, ny, nz / 2) : xpose_ok<float>(nx, ny, nz / 2); }
+int emu_xpose_applies(int f64, int nx, int ny, int nz) { return f64 ? xposed<double>(nx, ny, nz / 2) : xposed<float>(nx, ny, nz / 2); }
 
 // full fused realisation: generation + x, y, z passes -> W (real [nx][ny][nz]) and (sum, sumsq)
 int emu_realise(int f64, int nx, int ny, int nz, const double* kx2, const double* ky2, const double* kz2,
@@ -1361,20 +1297,16 @@ int emu_c2c(int f64, int nx, int ny, int nz, int dir, void* data) {
   return dir > 0 ? c2c_impl<float, +1>(nx, ny, nz, (cplx<float>*)data) : c2c_impl<float, -1>(nx, ny, nz, (cplx<float>*)data);
 }
 
-// one strided FFT pass over data[(C / inner) * outer_stride + C % inner + row * row_stride]
+// one strided FFT pass over data[(C / inner) * outer_stride + C % inner + row * row_stride]: the whole-column configuration of length N
+// (the per-length test of ColFFT; the library keeps these kernels at 1024 / 2048 float32 for geometries the halves do not fit)
 int emu_col_fft(int f64, int N, int dir, void* data, long long ncols, long long inner, long long outer_stride,
                 long long row_stride) {
-  ColGeom g{inner, outer_stride, row_stride};
-  if (f64) {
-    PlainColIO<double> io; io.base = (cplx<double>*)data; io.g = g;
-    return dir > 0 ? dispatch_col<double, +1>(N, io, ncols) : dispatch_col<double, -1>(N, io, ncols);
-  }
-  if ((N == 2048 || N == 1024) && ncols % 8 == 0) {     // as the library does at these lengths: two half-length transforms per tile
-    if (dir > 0) pair_pass_2048<float, +1>(N, (cplx<float>*)data, g, ncols); else pair_pass_2048<float, -1>(N, (cplx<float>*)data, g, ncols);
-    return 0;
-  }
-  PlainColIO<float> io; io.base = (cplx<float>*)data; io.g = g;
-  return dir > 0 ? dispatch_col<float, +1>(N, io, ncols) : dispatch_col<float, -1>(N, io, ncols);
+  const ColGeom g{inner, outer_stride, row_stride};
+  return with_real(f64, [&](auto r) {
+    using R = decltype(r); using T = typename R::type;
+    PlainColIO<T> io; io.base = R::p(data); io.g = g;
+    return with_dir(dir, [&](auto d) { return dispatch_col<T, decltype(d)::value>(N, io, ncols); });
+  });
 }
 
 }  // extern "C"

@@ -81,8 +81,7 @@ int ensure_g(rf_plan* p) { RF_HIP(p->G.reserve(p->k_bytes)); return 0; }
 int xpose_row_block(const rf_plan* p) { return col_gen_row_block(p->f64, p->nx, 64); }      // x rows per block of the transposed intermediate
 bool xpose_ok(const rf_plan* p) {
   if (!p->xposed || p->generic || p->unpacked || p->nranks > 1 || p->force_slab) return false;
-  const int tcx = col_gen_tile_cols(p->f64, p->nx), tcy = col_tile_cols(p->f64, p->ny);
-  return tcx > 0 && tcx == tcy && p->nzl >= tcx && p->nzl % tcx == 0 && row_c2r_xgather_ok(p->f64, (int)p->nzc, tcx, xpose_row_block(p));
+  return xpose_shape_ok(p->f64, p->nx, p->ny, p->nzl, p->nzc, xpose_row_block(p));
 }
 int ensure_x(rf_plan* p) {
   if (xpose_ok(p)) RF_HIP(p->X.reserve(p->w_bytes));

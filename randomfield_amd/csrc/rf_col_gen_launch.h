@@ -11,8 +11,6 @@
 
 namespace rf {
 namespace {
-template <class IO, class = void> struct io_noise_src { static constexpr int value = 0; };
-template <class IO> struct io_noise_src<IO, typename std::enable_if<(IO::NOISE_SRC >= 0)>::type> { static constexpr int value = IO::NOISE_SRC; };
 // runs tiles  b * tile_mul + tile_add,  b in [0, ntiles)
 template <class C, class IO>
 hipError_t launch_col(const IO& io, long long ncols, const cplx<typename C::T>* tw, hipStream_t s, long long ntiles, long long tile_mul = 1,
@@ -38,56 +36,41 @@ hipError_t launch_col2(const IO& io, long long ncols, const cplx<typename C1::T>
   return tile_launch<col2_kernel<C1, +1, IO>>(ntiles, C1::NT, lds_of<C1, IO>(), s, io, tw2, ntiles, tile_mul, tile_add, skip_period);
 }
 
-// what a fast generation pass is called with ([x0, x1): the rows that are stored; fixbuf: the side buffer of repaired kz = 0 slots)
-template <typename T> struct FastArgs {
-  const FastGenParams& gp;
-  cplx<T>* W;
-  ColGeom g;
+// what a fast generation pass is called with: the IO's contents (rf_fft_gen.h FastIoArgs) + the launch's own
+template <typename T> struct FastArgs : FastIoArgs<T> {
   long long ncols;
-  int kz0, nzl;
   const cplx<T>* tw;
   hipStream_t s;
   hipEvent_t after_repair;
-  int x0, x1;
-  cplx<T>*pot, *fixbuf;
 };
-template <class IO, typename T> IO make_io(const FastArgs<T>& a) {
-  IO io;
-  io.base = a.x0 > 0 ? a.W - (long long)a.x0 * a.g.row_stride : a.W;      // row x0 of the transform lands on row 0 of W
-  io.g = a.g; io.gp = a.gp; io.kz0 = a.kz0; io.nzl = a.nzl; io.rec = nullptr; io.x0 = a.x0; io.x1 = a.x1; io.pot = a.pot;
-  if constexpr (IO::FIX_MODE == 3) io.fixbuf = a.fixbuf;
-  return io;
-}
 
-// The kernels of one variant on configuration C (HALVES: C is the half-length configuration of a Col2 pass) and its launches.
-// IOT<FIX>: the variant's IO with that repair mode -- 0 none (lean), 1 the owning lane's own, 3 from the side buffer.
-template <class C, template <int> class IOT, bool HALVES>
-struct FastPassOf {
-  using T = typename C::T;
-  using IO0 = IOT<0>;
-  using IO1 = IOT<1>;
-  static constexpr FastPass pass = fast_pass_of<C>(HALVES, io_noise_src<IO0>::value);
-  static constexpr bool side = pass.side, pairs = pass.pairs;
-  // the kz = 0 launch: the repaired slots from the side buffer (FIX = 3, filled by fix_fill_kernel just before) or the owning lane's own
-  using IOC = typename IO1::template with_fix<side ? 3 : 1>;
-  using IOF = typename IO1::fill_io;
+// The launches of one variant at one length: P = its rf_select.h FastPassOf (configuration, IO types, FastPass).
+template <class P>
+struct FastLaunch {
+  using C = typename P::C;
+  using T = typename P::T;
+  using IO0 = typename P::IO0;
+  using IO1 = typename P::IO1;
+  using IOC = typename P::IOC;
+  using IOF = typename P::IOF;
+  static constexpr bool HALVES = P::HALVES;
 
   template <class IO> static hipError_t one(const FastArgs<T>& a, const FastStep& st) {
-    if constexpr (HALVES) return launch_col2<C>(make_io<IO>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
-    else return launch_col<C>(make_io<IO>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+    if constexpr (HALVES) return launch_col2<C>(fast_col_io<IO>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+    else return launch_col<C>(fast_col_io<IO>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
   }
   static hipError_t step(const FastArgs<T>& a, const FastStep& st) {
     switch (st.kind) {
       case FAST_FIX_FILL:     // one thread per mode (rf_kernels.h fix_fill_kernel): out[iy * nx + ix]
-        if constexpr (side) {
+        if constexpr (P::side) {
           const long long n = (long long)a.gp.nx * a.gp.ny;
-          return tile_launch<fix_fill_kernel<IOF, cplx<T>>>((n + 255) / 256, 256, IOF::LDS_EXTRA, a.s, make_io<IOF>(a), a.fixbuf, a.gp.nx, a.gp.ny);
+          return tile_launch<fix_fill_kernel<IOF, cplx<T>>>((n + 255) / 256, 256, IOF::LDS_EXTRA, a.s, fast_col_io<IOF>(a), a.fixbuf, a.gp.nx, a.gp.ny);
         }
         return hipErrorInvalidValue;
       case FAST_COLPAIR:
-        if constexpr (pairs) {
-          if (st.io == FAST_IO_LEAN) return launch_colpair<C>(make_io<IO0>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
-          if (st.io == FAST_IO_FIRST) return launch_colpair<C>(make_io<IOC>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+        if constexpr (P::pairs) {
+          if (st.io == FAST_IO_LEAN) return launch_colpair<C>(fast_col_io<IO0>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
+          if (st.io == FAST_IO_FIRST) return launch_colpair<C>(fast_col_io<IOC>(a), a.ncols, a.tw, a.s, st.count, st.mul, st.add, st.skip_period);
         }
         return hipErrorInvalidValue;
       default:
@@ -95,13 +78,8 @@ struct FastPassOf {
     }
   }
   static hipError_t launch(const FastArgs<T>& a) {
-    if (!pow2(a.nzl) || a.ncols >= (1LL << 31) || a.g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) return hipErrorInvalidValue;   // the IO splits a column index by shift and mask
-    if (HALVES && !a.g.rows_ok(C::N / C::RL, C::NPASS)) return hipErrorInvalidValue;
-    // the slab-restricted instantiations test the workgroup-uniform row offset m * L of the last pass: the slab boundaries must be
-    // multiples of L = N / (radix of the last pass)
-    const bool full_rows = a.x0 <= 0 && a.x1 >= (HALVES ? 2 : 1) * C::N;
-    if (!full_rows && (HALVES || C::NPASS < 2 || a.x0 % (C::N / C::RL) || a.x1 % (C::N / C::RL))) return hipErrorInvalidValue;
-    const FastSequence q = fastgen_sequence(pass, a.nzl, a.ncols, a.kz0, full_rows, a.g, a.fixbuf != nullptr);
+    if (!P::accepts(a.g, a.ncols, a.nzl, a.x0, a.x1)) return hipErrorInvalidValue;
+    const FastSequence q = fastgen_sequence(P::pass, a.nzl, a.ncols, a.kz0, P::full_rows(a.x0, a.x1), a.g, a.fixbuf != nullptr);
     if (!q.valid) return hipErrorInvalidValue;
     for (int i = 0; i < q.n; ++i) {
       if (hipError_t e = step(a, q.step[i]); e != hipSuccess) return e;
@@ -117,7 +95,7 @@ struct FastPassOf {
       p.kernel<col2_kernel<C, +1, IO1>>(lds_of<C, IO1>());
     } else {
       p.kernel<col_kernel<C, +1, IO0>>(lds_of<C, IO0>());
-      if constexpr (pairs) {
+      if constexpr (P::pairs) {
         p.kernel<colpair_kernel<C, +1, IO0>>(lds_of<C, IO0>());
         p.kernel<colpair_kernel<C, +1, IOC>>(lds_of<C, IOC>());
       }
@@ -127,29 +105,19 @@ struct FastPassOf {
   }
 };
 
-// One dtype's fast generation pass: IOV<V, FIX> = the IO type of list entry V (rf_select.h FastListOf<T>).  `launch` indexes the list by
-// the variant chosen, `prepare` walks it.
-template <typename T, template <class, int> class IOV>
-struct FastGen {
-  static constexpr int NH = fastgen_halves_length(sizeof(T) == 8);      // the halves form: Col2 on the configuration of half that length
-  using CHalf = typename GenSel<T, NH / 2>::type;
-  template <class V> struct Bind { template <int FIX> using IO = typename IOV<V, FIX>::type; };
-  // f(the FastPassOf of entry V at length N); `otherwise` where V has no kernel at N
-  template <class V, class R, class F> static R at(int N, R otherwise, F&& f) {
-    if constexpr (V::halves) return N == NH ? f(Cfg<FastPassOf<CHalf, Bind<V>::template IO, true>>{}) : otherwise;
-    else return for_col_size(N, otherwise, [&](auto n) { return f(Cfg<FastPassOf<typename GenSel<T, decltype(n)::value>::type, Bind<V>::template IO, false>>{}); });
-  }
-  static hipError_t launch(int N, const FastVariant& v, const FastArgs<T>& a) {
-    return with_fast_variant(FastListOf<T>{}, v, hipErrorInvalidValue, [&](auto e) {
-      return at<decltype(e)>(N, hipErrorInvalidValue, [&](auto k) { return decltype(k)::type::launch(a); });
-    });
-  }
-  static hipError_t prepare(int N) {
-    Prepare p;
-    for_each_fast_variant(FastListOf<T>{}, 0, [&](auto e) { return at<decltype(e)>(N, 0, [&](auto k) { decltype(k)::type::prepare(p); return 0; }); });
-    return p.e;
-  }
-};
+// One dtype's fast generation pass (rf_select.h FastGen<T>, FastListOf<T>): `launch` indexes the list by the variant chosen, `prepare` walks it.
+template <typename T> hipError_t fastgen_launch(int N, const FastVariant& v, const FastArgs<T>& a) {
+  return with_fast_variant(FastListOf<T>{}, v, hipErrorInvalidValue, [&](auto e) {
+    return FastGen<T>::template at<decltype(e)>(N, hipErrorInvalidValue, [&](auto k) { return FastLaunch<typename decltype(k)::type>::launch(a); });
+  });
+}
+template <typename T> hipError_t fastgen_prepare(int N) {
+  Prepare p;
+  for_each_fast_variant(FastListOf<T>{}, 0, [&](auto e) {
+    return FastGen<T>::template at<decltype(e)>(N, 0, [&](auto k) { FastLaunch<typename decltype(k)::type>::prepare(p); return 0; });
+  });
+  return p.e;
+}
 
 }  // namespace
 

@@ -137,6 +137,19 @@ template <class IO> inline void set_xpose_order(IO& io, long long nhi, long long
   io.grp_shift = 0;                 // (kz tiles of one ix dispatched in groups of 2^grp_shift: measured, no gain -- DESIGN_HISTORY.md)
 }
 
+// ---- the IO objects as the launchers fill them (host side; the CPU emulator calls the same) ----
+// the accumulating in-place pass over columns C = hi * nzl + (kz - kz0)
+template <typename T> inline AccColIO<T> acc_col_io(cplx<T>* base, const ColGeom& g, double* partials, int kz0, int nzl) {
+  AccColIO<T> io; io.base = base; io.g = g; io.partials = partials; io.kz0 = kz0; io.nzl = nzl;
+  return io;
+}
+// src (geometry gs) -> dst (geometry gd) over ncols columns in tiles of tc: gd.inner = kz planes per run, ncols / gd.inner values of the slow index
+template <typename T> inline XposeColIO<T> xpose_col_io(const cplx<T>* src, const ColGeom& gs, cplx<T>* dst, const ColGeom& gd, long long ncols, int tc) {
+  XposeColIO<T> io; io.src = src; io.gs = gs; io.base = dst; io.g = gd;
+  set_xpose_order(io, ncols / gd.inner, gd.inner / tc);
+  return io;
+}
+
 // Does the IO split its load into an early memory part and a late arithmetic part (preload() / load_pre())?  Only the deviate-reading
 // generation pass does: its loads are issued at the very top of the kernel, in front of the table staging and its barrier.
 template <class IO, class = void> struct io_sigma_share { static constexpr bool value = false; };
@@ -468,6 +481,11 @@ template <typename T> struct Pair2DirectColIO : Pair2ColIO<T> {
   RF_HD void bind_tile(long long C0) { out = tab[(C0 >> this->g.inner_shift()) >> dest_shift]; }
   RF_HD void store(long long C0, int cl, int rb, int ro, const V16<T>& v) const { v16_store<T>(this->g.template at<false>(out, C0, cl, rb, ro), v); }
 };
+// either of the two over the array at `base` with plain geometry g: the halves load rows two apart, phase 1 one row further
+template <class IO, typename T> inline IO pair2_col_io(cplx<T>* base, const ColGeom& g) {
+  IO io; io.base = base; io.g = g; io.gin = g; io.gin.row_stride = 2 * g.row_stride; io.par_off = g.row_stride;
+  return io;
+}
 
 // exp(DIR * 2 pi i m / 16), m in [0, 8)
 template <int DIR, typename T> RF_HD cplx<T> w16_half(int m) {

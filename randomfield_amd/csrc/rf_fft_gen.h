@@ -442,4 +442,27 @@ struct FastGenColIO64 {
   }
 };
 
+// ---- the IO objects as the launchers fill them (host side; the CPU emulator calls the same) ----
+template <typename T, bool WIDE = false>
+inline GenColIO<T, WIDE> gen_col_io(cplx<T>* W, const ColGeom& g, const GenParams& gp, const cplx<T>* kspace, int kz0, int nzl) {
+  GenColIO<T, WIDE> io; io.base = W; io.g = g; io.gp = gp; io.kspace = kspace; io.kz0 = kz0; io.nzl = nzl;
+  return io;
+}
+// what the IO of a fast generation pass is made from ([x0, x1): the rows that are stored; fixbuf: the side buffer of repaired kz = 0 slots)
+template <typename T> struct FastIoArgs {
+  const FastGenParams& gp;
+  cplx<T>* W;
+  ColGeom g;
+  int kz0, nzl;
+  int x0, x1;
+  cplx<T>*pot, *fixbuf;
+};
+template <class IO, typename T> inline IO fast_col_io(const FastIoArgs<T>& a) {
+  IO io;
+  io.base = a.x0 > 0 ? a.W - (long long)a.x0 * a.g.row_stride : a.W;      // row x0 of the transform lands on row 0 of W
+  io.g = a.g; io.gp = a.gp; io.kz0 = a.kz0; io.nzl = a.nzl; io.rec = nullptr; io.x0 = a.x0; io.x1 = a.x1; io.pot = a.pot;
+  if constexpr (IO::FIX_MODE == 3) io.fixbuf = a.fixbuf;
+  return io;
+}
+
 }  // namespace rf

@@ -171,6 +171,19 @@ template <typename T> struct XGatherRowIO {
   }
 };
 
+// ---- the gathering IO objects as the launchers fill them (host side; the CPU emulator calls the same) ----
+template <typename T> inline GatherRowIO<T> gather_row_io(const cplx<T>* src, cplx<T>* dst, double scale, int M, int nzl, long long seg_stride) {
+  GatherRowIO<T> io; io.src = src; io.dst = dst; io.scale = (T)scale; io.M_of = M; io.nzl = nzl; io.seg_stride = seg_stride;
+  return io;
+}
+// tiles of tc columns, x blocks of rb rows, ny rows of y: all powers of two, tc dividing M
+template <typename T> inline XGatherRowIO<T> xgather_row_io(const cplx<T>* src, cplx<T>* dst, double scale, int M, int tc, int rb, int ny) {
+  XGatherRowIO<T> io; io.src = src; io.dst = dst; io.scale = (T)scale; io.M_of = M;
+  io.seg_shift = ilog2ll(tc); io.rb_shift = ilog2ll(rb); io.ny_shift = ilog2ll(ny);       // (rf_fft_col.h, included first by rf_fft.h)
+  io.kt_stride = (long long)ny * rb * tc; io.xb_stride = (long long)(M / tc) * io.kt_stride;
+  return io;
+}
+
 // z pass with the lognormal map in its epilogue: rho = exp(delta * Ap_z) * Bp_z with the float64 tables Ap = sqrt(log t) / sigma,
 // Bp = density / sqrt(t), t = 1 + (sigma growth_z)^2, formed on the device from the y pass's Parseval sum (AccColIO,
 // lognormal_tables_kernel).  The reference does the same map as four in-place numpy statements with a rounding to the array

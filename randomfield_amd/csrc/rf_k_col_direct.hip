@@ -41,18 +41,12 @@ template <class C1>
 hipError_t launch_pair(const cplx<float>* src, ColGeom g, cplx<float>* const* tab, int dest_shift, long long ncols, const cplx<float>* tw2, hipStream_t s) {
   using IO = Pair2DirectColIO<float>;
   if (!tiles_ok<C1>(g, ncols)) return hipErrorInvalidValue;
-  IO io; io.base = const_cast<cplx<float>*>(src); io.g = g; io.gin = g; io.gin.row_stride = 2 * g.row_stride; io.par_off = g.row_stride;
+  IO io = pair2_col_io<IO>(const_cast<cplx<float>*>(src), g);
   io.tab = tab; io.dest_shift = dest_shift;
   const long long ntiles = ncols / C1::TC;
   return tile_launch<col2_direct_kernel<C1, IO>>(ntiles, C1::NT, lds_of<C1, IO>(), s, io, tw2, ntiles);
 }
 }  // namespace
-
-// can the pass of length N store tile by tile to per-x-plane destinations?  (a tile must not straddle two x planes)
-bool col_direct_supported(int f64, int N, long long inner) {
-  const int tc = col_tile_cols(f64, N);
-  return tc > 0 && inner > 0 && (inner & (inner - 1)) == 0 && inner % tc == 0;
-}
 
 // (halves or whole columns: the in-place pass's own rule -- rf_select.h col_halves -- so the arithmetic per tile is the same)
 hipError_t launch_col_direct(int f64, int N, const void* src, ColGeom g, void* const* tab, int dest_shift, long long ncols, const void* tw,

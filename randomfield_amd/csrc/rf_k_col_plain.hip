@@ -31,9 +31,8 @@ template <class C1, int DIR>
 hipError_t launch_pair(cplx<float>* base, ColGeom g, long long ncols, const cplx<float>* tw2, hipStream_t s) {
   using IO = Pair2ColIO<float>;
   if (ncols % C1::TC || !pow2(g.inner)) return hipErrorInvalidValue;
-  IO io; io.base = base; io.g = g; io.gin = g; io.gin.row_stride = 2 * g.row_stride; io.par_off = g.row_stride;
   const long long ntiles = ncols / C1::TC;
-  return tile_launch<col2_kernel<C1, DIR, IO>>(ntiles, C1::NT, lds_of<C1, IO>(), s, io, tw2, ntiles, 1LL, 0LL, 0);
+  return tile_launch<col2_kernel<C1, DIR, IO>>(ntiles, C1::NT, lds_of<C1, IO>(), s, pair2_col_io<IO>(base, g), tw2, ntiles, 1LL, 0LL, 0);
 }
 }  // namespace
 
@@ -43,7 +42,7 @@ hipError_t launch_col_plain_acc(int f64, int N, void* base, ColGeom g, long long
   if (!pow2(nzl)) return hipErrorInvalidValue;
   return with_real(f64, [&](auto r) {
     using R = decltype(r); using T = typename R::type;
-    AccColIO<T> io; io.base = R::p(base); io.g = g; io.partials = partials; io.kz0 = kz0; io.nzl = nzl;
+    const AccColIO<T> io = acc_col_io(R::p(base), g, partials, kz0, nzl);
     return for_col_size(N, hipErrorInvalidValue, [&](auto n) {
       using C = typename ColSel<T, decltype(n)::value>::type;
       if (g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) return hipErrorInvalidValue;
@@ -60,32 +59,13 @@ hipError_t launch_col_xpose(int f64, int N, const void* src, ColGeom gs, void* d
   if (nhi & (nhi - 1)) return hipErrorInvalidValue;
   return with_real(f64, [&](auto r) {
     using R = decltype(r); using T = typename R::type;
-    XposeColIO<T> io; io.src = R::p(src); io.gs = gs; io.base = R::p(dst); io.g = gd;
     return for_col_size(N, hipErrorInvalidValue, [&](auto n) {
       using C = typename ColSel<T, decltype(n)::value>::type;
       if (gs.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>)) || gd.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>)) || !pow2(gs.inner) ||
           (gs.sub_shift > 0 && (1 << gs.sub_shift) < C::TC) || gd.inner % C::TC)
         return hipErrorInvalidValue;
-      set_xpose_order(io, nhi, gd.inner / C::TC);
-      return launch_one<C, +1>(io, ncols, R::p(tw), s);
+      return launch_one<C, +1>(xpose_col_io(R::p(src), gs, R::p(dst), gd, ncols, C::TC), ncols, R::p(tw), s);
     });
-  });
-}
-
-// can the strided pass of length N address this geometry?  (32-bit lane offsets everywhere; 64-bit ones exist for N >= 1024)
-bool col_plain_addressable(int f64, int N, ColGeom g) {
-  return with_real(f64, [&](auto r) {
-    using T = typename decltype(r)::type;
-    return for_col_size(N, false, [&](auto n) {
-      using C = typename ColSel<T, decltype(n)::value>::type;
-      return C::N >= 1024 || !g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>));
-    });
-  });
-}
-
-int col_tile_cols(int f64, int N) {
-  return with_real(f64, [&](auto r) {
-    return for_col_size(N, 0, [](auto n) { return (int)ColSel<typename decltype(r)::type, decltype(n)::value>::type::TC; });
   });
 }
 

@@ -5,6 +5,7 @@
 #include <atomic>
 #include "rf_configs.h"
 #include "rf_generic.h"
+#include "rf_select.h"      // the pure shape rules (col_tile_cols, col_gen_row_block, row_c2r_xgather_ok ...) live there
 
 namespace rf {
 
@@ -51,19 +52,14 @@ hipError_t launch_col_xpose(int f64, int N, const void* src, ColGeom gs, void* d
 // the inverse pass out of place with every output tile stored through tab[ix >> dest_shift] instead of `src`'s own base (device table of
 // per-destination base pointers; ix = the tile's index of the slow column axis: rf_fft.h DirectColIO) -- the y pass of a kz-slab rank
 // writing straight into the receive buffers of the exchange
-bool col_direct_supported(int f64, int N, long long inner);
 hipError_t launch_col_direct(int f64, int N, const void* src, ColGeom g, void* const* tab, int dest_shift, long long ncols, const void* tw,
                              hipStream_t s);
-int col_gen_tile_cols(int f64, int N);   // tile width of the generation-fused x pass of length N
-int col_gen_row_block(int f64, int N, int want);   // x rows per block of the transposed intermediate: `want`, or N when the pass cannot block
 // x pass of c2r fused with generation (kspace == nullptr) or reading an API-layout k array
 // [kz0, kz0+nzl) is the slab of packed kz planes this rank owns (0, nz/2 on one GPU)
 hipError_t launch_col_gen(int f64, int N, void* W, ColGeom g, long long ncols, const GenParams& gp,
                           const void* kspace, int kz0, int nzl, const void* tw, hipStream_t s);
 // x pass fused with the fast native generation (float32 arithmetic; float64 plans widen the result)
 // (when the kz = 0 tiles run as a separate repairing launch first, `after_repair` is recorded between the two)
-bool col_fastgen_supported(int f64, int N);   // false when tile + twiddles + generation tables exceed a CU's LDS (float64, N = 2048)
-bool col_replicate_supported(int f64, int N, int nranks);   // can the x pass of length N keep 1/nranks of its rows?
 // [x0, x1): rows that are stored (replicated-generation mode: W is then the local x slab, row x0 at its start);
 // the default keeps every row.
 hipError_t launch_col_fastgen(int f64, int N, void* W, ColGeom g, long long ncols, const FastGenParams& gp, int kz0, int nzl,
@@ -72,8 +68,6 @@ hipError_t launch_col_fastgen(int f64, int N, void* W, ColGeom g, long long ncol
 // (fixbuf: nx * ny complex of the plan's dtype -- the side buffer of repaired kz = 0 slots the pass fills and reads when it runs the
 // kz = 0 tiles as a launch of their own: rf_kernels.h fix_fill_kernel; required for N >= 512 on the rank that owns kz = 0)
 // (pot != nullptr, float32 only: the pass also stores delta(k) / k^2 into the API-layout array `pot` -- generate.py:200-217)
-bool col_plain_addressable(int f64, int N, ColGeom g);   // false: the pass would need 64-bit lane offsets and has none (N < 1024)
-int col_tile_cols(int f64, int N);   // tile width (columns) of the strided pass of length N, 0 if unsupported
 // z pass of c2r: rows of M = nz/2 complex -> nz reals, scaled; partials[2*tile] = (sum, sumsq)
 // the z pass of one slab (Wz, nrows rows) and the in-place y pass of another (Wy, ncols columns) in one launch (rf_k_yz.hip)
 bool yz_merged_supported(int f64, int ny, int M);
@@ -89,7 +83,6 @@ hipError_t launch_row_c2r_gather(int f64, int M, const void* src, void* dst, lon
 // the dense rows of W at `dst`; nrows = (x planes of the slab) * ny, in the order (x block, iy, row of the block)
 hipError_t launch_row_c2r_xgather(int f64, int M, const void* src, void* dst, long long nrows, double scale, int tc, int rb, int ny,
                                   const void* tw, double* partials, hipStream_t s);
-bool row_c2r_xgather_ok(int f64, int M, int tc, int rb);
 // y pass (inverse, in place) that also leaves the Parseval partials of its output, one per tile (rf_fft.h AccColIO): columns
 // C = hi * nzl + (kz - kz0)
 hipError_t launch_col_plain_acc(int f64, int N, void* base, ColGeom g, long long ncols, int kz0, int nzl, double* partials, const void* tw,
@@ -111,7 +104,6 @@ hipError_t launch_row_r2c(int f64, int M, void* W, long long nrows, const void* 
 hipError_t launch_row_c2c(int f64, int M, int dir, void* W, long long nrows, double scale, const void* tw, hipStream_t s);
 // packed device array [nx][ny][nz/2] -> API layout [nx][ny][nz/2+1] (separates the kz = 0 and nz/2 planes)
 hipError_t launch_unpack_kspace(int f64, const void* W, void* K, int nx, int ny, int nzl, int kz0, hipStream_t s);
-long long row_c2r_tiles(int f64, int M, long long nrows);
 
 // stand-in for the all-to-all of a kz-slab rank without a communicator (diagnostics): nblk <= 16 blocks of `bytes` bytes (a multiple of
 // 16) copied src[b] -> dst[b] by `workgroups` 256-thread workgroups

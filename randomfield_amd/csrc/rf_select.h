@@ -1,6 +1,7 @@
 // rf_select.h -- which kernel variant a tiled pass takes and which launches it makes, as pure host functions next to rf_configs.h
 // (plain C++, no HIP: tests/select_test.cpp walks them on the CPU).  The launchers of rf_k_*.hip turn what these return into kernel
-// instantiations (rf_tile_launch.h); nothing else in the tree decides between two tiled kernels.
+// instantiations (rf_tile_launch.h); the CPU emulator (emu/rf_emu.cpp) turns the same answers into loops over tiles.  Nothing else in
+// the tree decides between two tiled kernels.
 #pragma once
 #include <type_traits>
 #include "rf_configs.h"
@@ -33,6 +34,58 @@ template <class R, class F> R for_rowc_size(int M, R otherwise, F&& f) {
   switch (M) { RF_ROWC_SIZES(RF_SIZE_CASE) default: return otherwise; }
 }
 #undef RF_SIZE_CASE
+template <class C> struct Cfg { using type = C; };
+// f(Real<T>{}, Cfg<the row configuration>{}) for rows of M complex of either dtype
+template <class R, class F> R for_rows(int f64, int M, R otherwise, F&& f) {
+  return with_real(f64, [&](auto r) {
+    return for_row_size(M, otherwise, [&](auto m) { return f(r, Cfg<typename RowSel<typename decltype(r)::type, decltype(m)::value>::type>{}); });
+  });
+}
+// f(Real<T>{}, Cfg<SEL<T, N>::type>{}) for a strided pass of length N of either dtype (SEL: ColSel or GenSel)
+template <template <typename, int> class SEL, class R, class F> R for_cols(int f64, int N, R otherwise, F&& f) {
+  return with_real(f64, [&](auto r) {
+    return for_col_size(N, otherwise, [&](auto n) { return f(r, Cfg<typename SEL<typename decltype(r)::type, decltype(n)::value>::type>{}); });
+  });
+}
+
+// ---- shapes a pass can serve: pure arithmetic on the configurations --------------------------------------------------------------
+// tile width (columns) of the strided pass of length N, and of the generation-fused x pass; 0 if unsupported
+inline int col_tile_cols(int f64, int N) { return for_cols<ColSel>(f64, N, 0, [](auto, auto c) { return (int)decltype(c)::type::TC; }); }
+inline int col_gen_tile_cols(int f64, int N) { return for_cols<GenSel>(f64, N, 0, [](auto, auto c) { return (int)decltype(c)::type::TC; }); }
+// rows of x per block of the transposed intermediate (rf_fft.h xblock_x_geom): `want` if the last pass's uniform row offsets (multiples
+// of N / RL) are whole blocks, else N (no blocking)
+inline int col_gen_row_block(int f64, int N, int want) {
+  if (want <= 0 || want >= N || (want & (want - 1))) return N;
+  return for_cols<GenSel>(f64, N, N, [&](auto, auto c) { using C = typename decltype(c)::type; return (C::NPASS >= 2 && (C::N / C::RL) % want == 0) ? want : N; });
+}
+// can the strided pass of length N address this geometry?  (32-bit lane offsets everywhere; 64-bit ones exist for N >= 1024)
+inline bool col_plain_addressable(int f64, int N, ColGeom g) {
+  return for_cols<ColSel>(f64, N, false, [&](auto r, auto c) {
+    using C = typename decltype(c)::type;
+    return C::N >= 1024 || !g.needs_wide(C::LMAX, C::TC, (int)sizeof(typename decltype(r)::cx));
+  });
+}
+// can the pass of length N store tile by tile to per-x-plane destinations?  (a tile must not straddle two x planes)
+inline bool col_direct_supported(int f64, int N, long long inner) {
+  const int tc = col_tile_cols(f64, N);
+  return tc > 0 && inner > 0 && (inner & (inner - 1)) == 0 && inner % tc == 0;
+}
+// can the gathering z pass of rows of M complex serve tiles of tc columns and x blocks of rb rows?  (whole workgroups per (x block, iy))
+inline bool row_c2r_xgather_ok(int f64, int M, int tc, int rb) {
+  return for_rows(f64, M, false, [&](auto, auto c) { return tc > 0 && rb > 0 && rb % decltype(c)::type::NRT == 0 && M % tc == 0; });
+}
+// tiles (workgroups, moment partials) of the z pass over nrows rows; -1 if unsupported
+inline long long row_c2r_tiles(int f64, int M, long long nrows) {
+  return for_rows(f64, M, -1LL, [&](auto, auto c) { constexpr int NRT = decltype(c)::type::NRT; return (nrows + NRT - 1) / NRT; });
+}
+// the lognormal z pass: float64 rows of >= 512 complex keep the exp table in the tile's spare LDS slots (rf_fft.h LognormalRowIO)
+template <typename T, int MM> using LognormalIO = LognormalRowIO<T, (sizeof(T) == 8 && MM >= 512) ? 1 : 0>;
+// the shape part of "the x pass hands over through the blocked intermediate" (DESIGN.md section 3.8): x and y tiles of the same width,
+// kz runs of whole tiles, and a z pass that can gather.  nzl: kz planes of the x / y passes, nzc = nz / 2: the z pass's rows
+inline bool xpose_shape_ok(int f64, int nx, int ny, long long nzl, long long nzc, int row_block) {
+  const int tcx = col_gen_tile_cols(f64, nx), tcy = col_tile_cols(f64, ny);
+  return tcx > 0 && tcx == tcy && nzl >= tcx && nzl % tcx == 0 && row_c2r_xgather_ok(f64, (int)nzc, tcx, row_block);
+}
 
 // ---- the Col2 rule: which in-place (and direct) pass runs as two half-length transforms per tile ------------------------------
 // float32 only: length 2048 on the radix-8-first 1024-point configuration (with 32 parked registers the 16-first one would not fit
@@ -57,7 +110,6 @@ template <class C1> bool halves_fit(const ColGeom& g) {
   return !gin.needs_wide(C1::LMAX, C1::TC, eb) && !g.needs_wide(C1::LMAX, C1::TC, eb) && g.row_shift >= 30 && g.hi_shift >= 62 && g.sub_shift == 0;
 }
 // f(Cfg<half configuration>{}) for a length that has a halves form (any geometry), else nothing; was f called?
-template <class C> struct Cfg { using type = C; };
 template <class F> bool for_col_halves(int f64, int N, F&& f) {
   switch (col_halves(f64, N)) {
     case HALVES_OF_2048: f(Cfg<HalvesSel<HALVES_OF_2048>::type>{}); return true;
@@ -92,6 +144,13 @@ inline bool fastgen_supported(int f64, int N) {
     using T = typename decltype(r)::type;
     return for_col_size(N, false, [](auto n) { return GenSel<T, decltype(n)::value>::type::LDS_BYTES + FAST_LDS_BINS * (int)sizeof(FastRec) <= 160 * 1024; });
   });
+}
+inline bool col_fastgen_supported(int f64, int N) { return fastgen_supported(f64, N); }
+// replicated-generation mode stores rows [rank N/P, (rank+1) N/P) only and tests the row offset m * L of the last pass: available when
+// the x pass has an LDS stage and N/P is a multiple of L = N / (radix of the last pass)
+inline bool col_replicate_supported(int f64, int N, int nranks) {
+  if (!fastgen_supported(f64, N) || nranks < 1 || N % nranks) return false;
+  return for_col_size(N, false, [&](auto n) { using C = typename GenSel<float, decltype(n)::value>::type; return C::NPASS >= 2 && (C::N / nranks) % (C::N / C::RL) == 0; });
 }
 // slab: the SLAB instantiations guard their stores (replicated generation); pot: 1 = the pass also stores delta(k) / k^2, 2 = it
 // transforms pscale * delta(k) / k^2 instead; src: 0 native generator, 1 resident float64 deviates, 2 resident float32 pairs;
@@ -222,5 +281,47 @@ inline long long fast_step_tile(const FastStep& s, long long b) {
   if (s.skip_period > 0) t = t + t / (s.skip_period - 1) + 1;
   return t;
 }
+
+// ---- the fast generation pass: the types of one variant at one length -------------------------------------------------------------
+template <class IO, class = void> struct io_noise_src { static constexpr int value = 0; };
+template <class IO> struct io_noise_src<IO, typename std::enable_if<(IO::NOISE_SRC >= 0)>::type> { static constexpr int value = IO::NOISE_SRC; };
+// One variant on configuration C (HALVES: C is the half-length configuration of a Col2 pass).  IOT<FIX>: the variant's IO with that
+// repair mode -- 0 none (lean), 1 the owning lane's own, 3 from the side buffer.
+template <class C_, template <int> class IOT, bool HALVES_>
+struct FastPassOf {
+  using C = C_;
+  using T = typename C::T;
+  static constexpr bool HALVES = HALVES_;
+  using IO0 = IOT<0>;
+  using IO1 = IOT<1>;
+  static constexpr FastPass pass = fast_pass_of<C>(HALVES, io_noise_src<IO0>::value);
+  static constexpr bool side = pass.side, pairs = pass.pairs;
+  // the kz = 0 launch: the repaired slots from the side buffer (FIX = 3, filled by fix_fill_kernel just before) or the owning lane's own
+  using IOC = typename IO1::template with_fix<side ? 3 : 1>;
+  using IOF = typename IO1::fill_io;
+  // full_rows: every x row is kept.  The slab-restricted instantiations test the workgroup-uniform row offset m * L of the last pass: the
+  // slab boundaries must be multiples of L = N / (radix of the last pass)
+  static bool full_rows(int x0, int x1) { return x0 <= 0 && x1 >= (HALVES ? 2 : 1) * C::N; }
+  static bool accepts(const ColGeom& g, long long ncols, int nzl, int x0, int x1) {
+    if (nzl <= 0 || (nzl & (nzl - 1)) || ncols >= (1LL << 31) || g.needs_wide(C::LMAX, C::TC, (int)sizeof(cplx<T>))) return false;   // the IO splits a column index by shift and mask
+    if (HALVES && !g.rows_ok(C::N / C::RL, C::NPASS)) return false;
+    return full_rows(x0, x1) || !(HALVES || C::NPASS < 2 || x0 % (C::N / C::RL) || x1 % (C::N / C::RL));
+  }
+};
+// the IO type of list entry V (FastListOf<T>) with repair mode FIX
+template <typename T, class V, int FIX> struct FastIoOf { using type = FastGenColIOT<FIX, V::slab, V::pot, V::src, V::halves ? 2 : 1>; };
+template <class V, int FIX> struct FastIoOf<double, V, FIX> { using type = FastGenColIO64<FIX, V::slab, V::pot, V::halves ? 2 : 1>; };
+// One dtype's fast generation pass.  The halves form is Col2 on the configuration of half of NH (float64: length 1024 as two 512-point
+// transforms per tile, two workgroups per CU -- DESIGN.md 3.10).
+template <typename T> struct FastGen {
+  static constexpr int NH = fastgen_halves_length(sizeof(T) == 8);
+  using CHalf = typename GenSel<T, NH / 2>::type;
+  template <class V> struct Bind { template <int FIX> using IO = typename FastIoOf<T, V, FIX>::type; };
+  // f(Cfg<the FastPassOf of entry V at length N>{}); `otherwise` where V has no kernel at N
+  template <class V, class R, class F> static R at(int N, R otherwise, F&& f) {
+    if constexpr (V::halves) return N == NH ? f(Cfg<FastPassOf<CHalf, Bind<V>::template IO, true>>{}) : otherwise;
+    else return for_col_size(N, otherwise, [&](auto n) { return f(Cfg<FastPassOf<typename GenSel<T, decltype(n)::value>::type, Bind<V>::template IO, false>>{}); });
+  }
+};
 
 }  // namespace rf

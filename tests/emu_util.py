@@ -17,7 +17,8 @@ def _dp(a):
 
 
 def build(force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("emu/rf_emu.cpp", "rf_core.h", "rf_fft.h", "rf_configs.h", "rf_host.h", "rf_generic.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("emu/rf_emu.cpp", "rf_core.h", "rf_exp2_tab.h", "rf_fft.h", "rf_fft_col.h", "rf_fft_gen.h", "rf_fft_row.h",
+                                            "rf_configs.h", "rf_select.h", "rf_host.h", "rf_generic.h")]
     if force or not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-o", SO, srcs[0]])
     return SO
@@ -101,6 +102,33 @@ def realise_fast(nx, ny, nz, spacing, log10k, sigma, seed, dtype=np.float32):
                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(s1), ctypes.byref(s2))
     assert rc == 0, rc
     return out, s1.value, s2.value
+
+
+def _steps(call):
+    buf = (ctypes.c_longlong * 40)()
+    n = call(buf, 8)
+    assert 0 <= n <= 8, n
+    return [tuple(buf[5 * i:5 * i + 5]) for i in range(n)]
+
+
+def fast_steps():
+    """The launches the last realise_fast ran for its x pass: (kind, io, count, mul, skip_period) per step (rf_select.h FastStep)."""
+    return _steps(lib().emu_fast_steps)
+
+
+def fastgen_sequence(nx, ny, nz, f64=False):
+    """rf_select.h fastgen_sequence for the x pass of that grid, called directly (honours emu_set_xposed / emu_set_pairs)."""
+    return _steps(lambda buf, n: lib().emu_fastgen_sequence(int(f64), nx, ny, nz, buf, n))
+
+
+def fast_visits():
+    """How often the last realise_fast transformed each tile of its x pass."""
+    f = lib().emu_fast_visits
+    f.restype = ctypes.c_longlong
+    out = np.zeros(1 << 16, np.int32)
+    n = f(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_longlong(out.size))
+    assert 0 <= n <= out.size, n
+    return out[:n]
 
 
 def c2c(data, inverse):

@@ -1,5 +1,6 @@
 // select_test.cpp -- the pure host functions that choose the tiled kernels (randomfield_amd/csrc/rf_select.h): which fast generation
-// variant, which pass runs as Col2 halves, and which launches a fast generation pass makes.  Stand-alone: compiled with
+// variant, which pass runs as Col2 halves, which launches a fast generation pass makes, and the shapes each pass can serve (tile widths,
+// row blocks, the gathering z pass, the blocked intermediate, direct stores, replicated generation).  Stand-alone: compiled with
 // -fsanitize=address,undefined and run by tests/test_launch_select.py; exit status 0 = every check held.
 #include <cstdio>
 #include <vector>
@@ -180,6 +181,63 @@ void test_sequences() {
   CHECK(q3.valid && q3.n == 3 && q3.step[1].kind == FAST_COL);
 }
 
+// ---- the shapes a pass can serve: literal tables ----------------------------------------------------------------------------------------
+void test_shapes() {
+  const int N[9] = {8, 16, 32, 64, 128, 256, 512, 1024, 2048};
+  // tile widths: the in-place pass and the generating x pass use the same tiles at every length
+  const int tc[2][9] = {{32, 32, 32, 32, 32, 16, 16, 8, 8}, {16, 16, 16, 16, 16, 8, 8, 8, 4}};
+  // x rows per block of the blocked intermediate for want = 16 and 64 (0 and N: no blocking): `want` where the last pass's row offsets
+  // N / RL are whole blocks.  One-pass lengths (8, 16) never block; float64 1024 has RL = 16, so N / RL = 64
+  const int rb16[2][9] = {{8, 16, 32, 64, 16, 16, 16, 16, 16}, {8, 16, 32, 64, 16, 16, 16, 16, 16}};
+  const int rb64[2][9] = {{8, 16, 32, 64, 128, 256, 64, 64, 64}, {8, 16, 32, 64, 128, 256, 64, 64, 64}};
+  for (int f64 = 0; f64 < 2; ++f64)
+    for (int i = 0; i < 9; ++i) {
+      CHECK(col_tile_cols(f64, N[i]) == tc[f64][i] && col_gen_tile_cols(f64, N[i]) == tc[f64][i]);
+      CHECK(col_gen_row_block(f64, N[i], 0) == N[i] && col_gen_row_block(f64, N[i], N[i]) == N[i]);
+      CHECK(col_gen_row_block(f64, N[i], 16) == rb16[f64][i]);
+      CHECK(col_gen_row_block(f64, N[i], 64) == rb64[f64][i]);
+      CHECK(col_gen_row_block(f64, N[i], 24) == N[i]);                   // not a power of two
+    }
+  for (int f64 = 0; f64 < 2; ++f64)
+    for (int n : {0, 4, 100, 4096}) CHECK(col_tile_cols(f64, n) == 0 && col_gen_tile_cols(f64, n) == 0 && col_gen_row_block(f64, n, 16) == n);
+  // the gathering z pass: x blocks of whole workgroups (rb a multiple of NRT: 8 rows at M = 512 float32, 64 at M = 32, float64 64 at M = 16
+  // and 2 at M = 1024), whole tiles per row
+  struct { int f64, M, tc, rb; bool ok; } xg[] = {{0, 512, 8, 64, true}, {0, 512, 8, 8, true}, {0, 512, 8, 4, false}, {0, 32, 32, 64, true},
+      {0, 32, 32, 32, false}, {1, 16, 16, 32, false}, {1, 16, 16, 64, true}, {1, 1024, 8, 2, true}, {1, 1024, 8, 1, false}, {0, 512, 0, 64, false},
+      {0, 512, 8, 0, false}, {0, 512, 24, 64, false}, {0, 100, 4, 64, false}, {0, 2048, 8, 64, false}};
+  for (const auto& c : xg) CHECK(row_c2r_xgather_ok(c.f64, c.M, c.tc, c.rb) == c.ok);
+  CHECK(row_c2r_tiles(0, 512, 17) == 3 && row_c2r_tiles(1, 512, 17) == 5 && row_c2r_tiles(0, 8, 256) == 1 && row_c2r_tiles(0, 8, 257) == 2 &&
+        row_c2r_tiles(0, 100, 5) == -1);
+  // the blocked intermediate (nx, ny, nzl, nzc, row block): x and y tiles of one width, kz runs of whole tiles, a z pass that can gather
+  auto xp = [](int f64, int nx, int ny, long long nzl, long long nzc) { return xpose_shape_ok(f64, nx, ny, nzl, nzc, col_gen_row_block(f64, nx, 64)); };
+  CHECK(xp(0, 64, 64, 32, 32) && xp(0, 128, 64, 32, 32) && xp(0, 1024, 1024, 32, 32) && xp(1, 64, 64, 64, 64) && xp(0, 512, 512, 32, 32));
+  CHECK(!xp(0, 512, 16, 32, 32));                   // x tiles of 16 columns, y tiles of 32
+  CHECK(!xp(1, 32, 32, 16, 16));                    // 32 x rows per block, 64 rows per workgroup of the z pass
+  CHECK(!xp(0, 64, 64, 16, 16));                    // a kz run narrower than a tile
+  CHECK(!xp(0, 1024, 1024, 12, 32));                // ... and one of one and a half tiles
+  CHECK(!xp(0, 100, 64, 32, 32) && !xp(0, 64, 100, 32, 32) && !xp(0, 64, 64, 32, 100));
+  // direct stores: whole tiles per x plane (inner a power of two, a multiple of the tile width)
+  struct { int f64, N; long long inner; bool ok; } dr[] = {{0, 1024, 8, true}, {0, 1024, 4, false}, {0, 1024, 24, false}, {0, 1024, 16, true},
+      {0, 64, 32, true}, {0, 64, 16, false}, {0, 100, 64, false}, {0, 64, 0, false}, {0, 64, -32, false}, {1, 2048, 4, true}, {1, 2048, 2, false}};
+  for (const auto& c : dr) CHECK(col_direct_supported(c.f64, c.N, c.inner) == c.ok);
+  // replicated generation: a fast pass with an LDS stage whose slabs N / nranks are multiples of N / RL, i.e. nranks divides RL (8 at 64,
+  // 512, 1024; 4 at 32; 16 at 2048)
+  struct { int f64, N, nranks; bool ok; } rp[] = {{0, 1024, 1, true}, {0, 1024, 8, true}, {0, 1024, 16, false}, {0, 1024, 3, false}, {0, 1024, 0, false},
+      {0, 16, 1, false}, {0, 8, 2, false}, {0, 64, 8, true}, {0, 64, 16, false}, {0, 32, 4, true}, {0, 32, 8, false}, {0, 2048, 16, true},
+      {0, 2048, 32, false}, {1, 2048, 2, false}, {1, 1024, 8, true}, {0, 100, 2, false}};
+  for (const auto& c : rp) CHECK(col_replicate_supported(c.f64, c.N, c.nranks) == c.ok);
+  CHECK(col_fastgen_supported(0, 2048) && !col_fastgen_supported(1, 2048) && col_fastgen_supported(1, 1024) && !col_fastgen_supported(0, 100));
+  // 64-bit lane offsets exist from length 1024 on
+  const ColGeom small{64, 64 * 8, 64}, huge{1LL << 30, 0, 1LL << 30};
+  for (int f64 = 0; f64 < 2; ++f64) {
+    for (int n : N) CHECK(col_plain_addressable(f64, n, small) && col_plain_addressable(f64, n, huge) == (n >= 1024 || n == 8 || n == 16));
+    CHECK(!col_plain_addressable(f64, 100, small));
+  }
+  // the lognormal z pass keeps its exp table in spare LDS slots for float64 rows of >= 512 complex
+  CHECK((std::is_same<LognormalIO<double, 512>, LognormalRowIO<double, 1>>::value && std::is_same<LognormalIO<double, 1024>, LognormalRowIO<double, 1>>::value));
+  CHECK((std::is_same<LognormalIO<double, 256>, LognormalRowIO<double, 0>>::value && std::is_same<LognormalIO<float, 1024>, LognormalRowIO<float, 0>>::value));
+}
+
 // ---- yz_slabs: the partition of the nx planes for the y / z passes --------------------------------------------------------------------
 bool same(const YzSlabs& a, int planes, int count, int last) { return a.planes == planes && a.count == count && a.last == last; }
 void test_slabs() {
@@ -208,6 +266,7 @@ int main() {
   test_variants();
   test_halves();
   test_sequences();
+  test_shapes();
   test_slabs();
   if (g_failed) { std::printf("%d of %d checks FAILED\n", g_failed, g_checked); return 1; }
   std::printf("all checks passed (%d)\n", g_checked);

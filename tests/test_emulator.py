@@ -332,8 +332,11 @@ def test_row_table_of_resident_float32_deviates():
                                          ((512, 16, 64), np.complex64), ((512, 512, 64), np.complex64), ((1024, 1024, 64), np.complex64)])
 def test_transposed_intermediate_is_bit_identical(shape, dtype, default_power):
     """The blocked intermediate X [x block][kz tile][ny][rb][TC] (x pass stores contiguous chunks, y pass in place on X, z pass
-    gathers X -> W; rf_capi.hip queue_xyz, RF_FLAG_TRANSPOSED_INTERMEDIATE) only moves data: fields are bit-identical to the
-    passes on the plain layout."""
+    gathers X -> W; rf_capi.hip queue_xyz, RF_FLAG_TRANSPOSED_INTERMEDIATE) only moves data as long as the y pass takes the same
+    form on both sides: then fields are bit-identical to the passes on the plain layout.  The y pass on X is whole columns only
+    (XposeColIO), while the in-place pass on the plain layout runs float32 columns of 1024 / 2048 as two half-length transforms
+    (rf_select.h col_halves), which rounds differently -- in the library too.  The subject here is the data movement, so the
+    arithmetic is held fixed: emu_set_col_halves(0) keeps whole columns on both sides."""
     nx, ny, nz = shape
     L = emu_util.lib()
     old = L.emu_set_xposed(1)                    # (off by default, like the product's flag)
@@ -346,7 +349,7 @@ def test_transposed_intermediate_is_bit_identical(shape, dtype, default_power):
     cpu_ref.symmetrize_packed(ks)
     res = {}
     for on, rb in ((1, 64), (0, 64), (2, 16), (3, 0)):          # 64 = the product's block of x rows; 0 = unblocked
-        old, oldrb = L.emu_set_xposed(int(on > 0)), L.emu_set_rowblock(rb)
+        old, oldrb, oldhalves = L.emu_set_xposed(int(on > 0)), L.emu_set_rowblock(rb), L.emu_set_col_halves(0)
         try:
             res[on] = (emu_util.c2r(ks),) if nx >= 512 and ny >= 512 else (
                 emu_util.c2r(ks), emu_util.realise_fast(nx, ny, nz, 2.5, xt, st, seed=7,
@@ -354,6 +357,7 @@ def test_transposed_intermediate_is_bit_identical(shape, dtype, default_power):
         finally:
             L.emu_set_xposed(old)
             L.emu_set_rowblock(oldrb)
+            L.emu_set_col_halves(oldhalves)
     # (512, 16, 64): x and y tiles of different widths; (32, 32, 32) float64: fewer x rows than the z pass's rows per workgroup
     assert applies == (0 if shape in ((512, 16, 64), (32, 32, 32)) else 1)
     for v in (1, 2, 3):
@@ -446,6 +450,48 @@ def test_tile_pairs_give_the_single_tile_field(default_power):
     noise = cpu_ref.native_noise(23, nx, ny, nz, np.complex64)
     ref, rms = cpu_ref.generate_delta_field(nx, ny, nz, 2.5, k, Pk, noise=noise, double_fft=True)
     assert np.max(np.abs(pairs - ref)) <= 3e-5 * rms
+
+
+# rf_select.h: FastKind (fix fill, col, colpair, col2) and FastIo (lean, repair, first)
+_FF, _COL, _PAIR, _COL2 = 0, 1, 2, 3
+_LEAN, _REPAIR, _FIRST = 0, 1, 2
+# shape, float64, emu_set_pairs, the (kind, io) of every launch, tiles of the pass = ny * (nz / 2) / tile width
+FAST_SEQUENCES = [
+    ((8, 8, 16), False, 1, [(_COL, _REPAIR)], 2),                                            # a kz row fits one 32-column tile: unsplit
+    ((64, 8, 128), False, 1, [(_COL, _FIRST), (_COL, _LEAN)], 16),                             # split; short pass: the owning lane repairs
+    ((512, 8, 64), False, 1, [(_FF, _REPAIR), (_COL, _FIRST), (_COL, _LEAN)], 16),             # split; long pass: the side buffer
+    ((1024, 8, 32), False, 1, [(_FF, _REPAIR), (_PAIR, _FIRST)], 16),                          # tile pairs, one pair per ky row
+    ((1024, 8, 64), False, 1, [(_FF, _REPAIR), (_PAIR, _FIRST), (_PAIR, _LEAN)], 32),          # tile pairs, two pairs per ky row
+    ((1024, 8, 32), False, 0, [(_FF, _REPAIR), (_COL, _FIRST), (_COL, _LEAN)], 16),            # the same pass on single tiles
+    ((2048, 8, 16), False, 1, [(_COL2, _REPAIR)], 8),                                          # Col2 halves, unsplit
+    ((2048, 8, 32), False, 1, [(_FF, _REPAIR), (_COL2, _FIRST), (_COL2, _LEAN)], 16),          # Col2 halves, split
+    ((1024, 8, 32), True, 1, [(_FF, _REPAIR), (_COL2, _FIRST), (_COL2, _LEAN)], 16),           # the float64 halves form
+]
+
+
+@pytest.mark.parametrize("shape,f64,pairs,launches,ntiles", FAST_SEQUENCES)
+def test_emulated_fast_pass_runs_the_librarys_sequence(shape, f64, pairs, launches, ntiles, default_power):
+    """The emulated fast generation pass takes its variant, its IO types and its launches from the functions launch_col_fastgen calls
+    (rf_select.h fastgen_variant, FastGen::at, fastgen_sequence): the steps it ran equal fastgen_sequence called directly and the
+    literal list of this grid's branch, the first / lean launches together transform every tile exactly once, and the field meets the
+    tolerance of the fast-generation tests above (2e-5 rms, 3e-5 at lengths >= 1024)."""
+    nx, ny, nz = shape
+    k, Pk = default_power["k"], default_power["Pk"]
+    xt, st = cpu_ref.sigma_table(k, Pk, nx, ny, nz, 2.5)
+    old = emu_util.lib().emu_set_pairs(pairs)
+    try:
+        out, s1, s2 = emu_util.realise_fast(nx, ny, nz, 2.5, xt, st, seed=31, dtype=np.float64 if f64 else np.float32)
+        ran, direct, visits = emu_util.fast_steps(), emu_util.fastgen_sequence(nx, ny, nz, f64), emu_util.fast_visits()
+    finally:
+        emu_util.lib().emu_set_pairs(old)
+    assert ran == direct
+    assert [(kind, io) for kind, io, count, mul, skip in ran] == launches
+    assert visits.size == ntiles and np.all(visits == 1)
+    ct = np.complex128 if f64 else np.complex64
+    noise = cpu_ref.native_noise(31, nx, ny, nz, ct)
+    ref, rms = (cpu_ref.generate_delta_field(nx, ny, nz, 2.5, k, Pk, noise=noise, dtype=ct) if f64 else
+                cpu_ref.generate_delta_field(nx, ny, nz, 2.5, k, Pk, noise=noise, double_fft=True))
+    assert np.max(np.abs(out - ref)) <= (3e-5 if max(shape) >= 1024 else 2e-5) * rms
 
 
 @pytest.mark.parametrize("L,S", [(128, 16), (128, 32), (64, 16), (256, 16), (16, 16)])
