@@ -51,7 +51,9 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * And for the cloud-in-cell gather of a field at the particles and the shift by it -- rf_particles_gather, rf_particles_gather_download,
  * rf_particles_shift: rf_abi_features() & RF_FEATURE_PARTICLES_GATHER, the version stays 5.5.
  * And for the assignment scheme as an argument, with the triangular-shaped cloud as the second scheme -- rf_particles_paint_ex,
- * rf_particles_gather_ex: rf_abi_features() & RF_FEATURE_PARTICLES_TSC, the version stays 5.5. */
+ * rf_particles_gather_ex: rf_abi_features() & RF_FEATURE_PARTICLES_TSC, the version stays 5.5.
+ * And for the interlaced paint -- rf_particles_paint_shifted, rf_kspace_stash, rf_kspace_interlace, rf_particles_paint_interlaced:
+ * rf_abi_features() & RF_FEATURE_PARTICLES_INTERLACE, the version stays 5.5. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -84,8 +86,10 @@ enum {
   RF_FEATURE_POWER_MULTIPOLES = 1 << 18,   /* rf_measure_multipoles: the moments of mu^2 behind P0, P2, P4 along a grid axis, window compensation */
   RF_FEATURE_PARTICLES_GATHER = 1 << 19,   /* rf_particles_gather, rf_particles_gather_download, rf_particles_shift: the current real field
                                               interpolated at the particles (cloud in cell, the paint's adjoint), and the particles moved by it */
-  RF_FEATURE_PARTICLES_TSC = 1 << 20       /* rf_particles_paint_ex, rf_particles_gather_ex: the paint and the gather with the assignment scheme
+  RF_FEATURE_PARTICLES_TSC = 1 << 20,      /* rf_particles_paint_ex, rf_particles_gather_ex: the paint and the gather with the assignment scheme
                                               as an argument, RF_ASSIGN_CIC or RF_ASSIGN_TSC (triangular-shaped cloud, three cells per axis) */
+  RF_FEATURE_PARTICLES_INTERLACE = 1 << 21 /* rf_particles_paint_shifted, rf_kspace_stash, rf_kspace_interlace, rf_particles_paint_interlaced:
+                                              the paint on a grid shifted by half a cell and the two spectra combined (interlacing) */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -397,6 +401,40 @@ enum { RF_ASSIGN_CIC = 2, RF_ASSIGN_TSC = 3 };
  * Pass window order 3 ('tsc') to the window compensation of a measurement of a TSC-painted field. */
 int rf_particles_paint_ex(rf_plan* plan, const double* inv_h, int scheme, unsigned long long* dropped);
 int rf_particles_gather_ex(rf_plan* plan, const double* inv_h, int scheme, int slot, double coeff, int first, unsigned long long* dropped);
+
+/* ---- particles: the interlaced paint (rf_abi_features() & RF_FEATURE_PARTICLES_INTERLACE) -- */
+/* Interlacing (Sefusatti et al. 2016): the particles are painted a second time on a grid shifted by half a cell on every axis, and the
+ * two spectra are combined with the phase that undoes the shift; every aliased image with an odd sum of image indices cancels.
+ * rf_particles_paint_shifted: rf_particles_paint_ex with the shift as an argument.  half_cell = 0 is that call word for word; 1 paints
+ * the particle at u + 1/2 on all three axes; anything else is refused with nothing queued.  Per axis u, the drop rule (decided on u,
+ * before the shift), c, t in [0, 65536], j0 and j1 exactly as for cloud in cell; then, in integers (the shift is exact in 2^-16 units),
+ *   t2 = t + 32768,  carry = t2 >= 65536,  t' = carry ? t2 - 65536 : t2 in [0, 65535]     (t = 65536 gives t' = 32768 with a carry)
+ *   j0' = carry ? j1 : j0,  j1' = (j0' + 1) mod n        (on the wrapped index: it steps for every finite u)
+ *   w0' = 65536 - t',  w1' = t'
+ * and RF_ASSIGN_TSC takes (t', j0') where it took (t, j0).  Counts, delta, rf_particles_download_counts, the LIMIT of
+ * rf_particles_paint and "the same bits on every call and kernel form" are unchanged.  There is no shifted gather.
+ * rf_kspace_stash: S <- K, S a lazy second half spectrum of K's size and layout (counted by rf_plan_nbytes, freed with the plan, never
+ * stale before that: it is the caller's data).  Refused without k-space data.
+ * rf_kspace_interlace: K <- (S + p K) / 2 per cell, p = px[ix] py[iy] pz[iz]; S stays valid.  px, py, pz: nx, ny, nz/2 + 1 complex
+ * float64 entries as interleaved (re, im) pairs on the host, NULL = all ones; a non-finite entry is refused.  All in float64, every
+ * product and sum rounded on its own:
+ *   a = px py   (ar = xr yr - xi yi,  ai = xr yi + xi yr),   p = a pz,   q = p (double)K   (the same form),
+ *   K = (T)(0.5 ((double)S + q))  per component, one rounding to the plan's type.
+ * Refused without a stash ("no stashed spectrum") or without k-space data.  The tables that undo the half-cell shift are
+ * p_a[i] = exp(+i pi m / n_a), m the signed mode number of index i, with p_a[0] = 1 and p_a[n_a / 2] = 0 (the Hermitian part of
+ * exp(+-i pi / 2): the combined spectrum stays Hermitian, and the planes at an axis' own Nyquist index hold half the first spectrum).
+ * rf_particles_paint_interlaced: the whole sequence -- paint (half_cell = 0), forward transform, stash, paint (half_cell = 1), forward
+ * transform, combine, rf_execute_c2r.  Afterwards K holds the interlaced spectrum (valid k-space data: RF_POWER_FROM_KSPACE reads it
+ * without a further transform), the current field is its inverse transform with moments as after any c2r, A holds the SHIFTED paint's
+ * counts, and *dropped is the first paint's count (the second's equals it; the call blocks for it once, at its end).  The first transform writes its spectrum straight into S.
+ * rf_elapsed_ms covers the whole call; rf_kernel_ms is refused after it.
+ * Packed single-rank plans, tiled and generic, both dtypes.  c2c plans, nranks > 1, missing displacements, a bad scheme or half_cell and
+ * a non-finite table entry are refused with nothing queued.  Q, G, the stored potential and the second-order potential are never touched. */
+int rf_particles_paint_shifted(rf_plan* plan, const double* inv_h, int scheme, int half_cell, unsigned long long* dropped);
+int rf_kspace_stash(rf_plan* plan);
+int rf_kspace_interlace(rf_plan* plan, const double* px, const double* py, const double* pz);
+int rf_particles_paint_interlaced(rf_plan* plan, const double* inv_h, int scheme, const double* px, const double* py, const double* pz,
+                                  unsigned long long* dropped);
 
 /* ---- binned power spectrum (rf_abi_features() & RF_FEATURE_POWER_MEASURE) -- */
 /* The estimator that closes P(k) -> delta(x) -> P^(k): one sweep of the half spectrum [nx][ny][nz/2+1] of unnormalised forward-transform

@@ -35,7 +35,7 @@ FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
             "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17, "power_multipoles": 1 << 18,
-            "particles_gather": 1 << 19, "particles_tsc": 1 << 20}
+            "particles_gather": 1 << 19, "particles_tsc": 1 << 20, "particles_interlace": 1 << 21}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -97,6 +97,10 @@ SIGNATURES = {
     "rf_particles_paint_ex": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_particles_gather_ex": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_particles_paint_shifted": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rf_kspace_stash": (ctypes.c_int, [ctypes.c_void_p]),
+    "rf_kspace_interlace": (ctypes.c_int, [ctypes.c_void_p, _c_dp, _c_dp, _c_dp]),
+    "rf_particles_paint_interlaced": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rf_particles_gather_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rf_particles_shift": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
@@ -722,16 +726,55 @@ class DevicePlan(object):
         check(self._lib.rf_particles_download(self._h, int(axis), out.ctypes.data_as(ctypes.c_void_p)), "rf_particles_download")
         return out
 
-    def particles_paint(self, inv_h, scheme=2):
+    def particles_paint(self, inv_h, scheme=2, half_cell=False):
         """Cloud-in-cell mass assignment of the displaced lattice particles (rf_particles_paint): delta_cic becomes the current real
         field; ``inv_h``: the three 1 / (grid spacing).  ``scheme``: 2 cloud in cell, 3 triangular-shaped cloud
-        (rf_particles_paint_ex).  Returns the number of particles dropped for a non-finite displacement."""
+        (rf_particles_paint_ex).  ``half_cell``: the particles at u + 1/2 on every axis, the second grid of an interlaced paint
+        (rf_particles_paint_shifted; True / False, or the C call's integer passed through).  Returns the number of particles dropped
+        for a non-finite displacement."""
         h = _f64(np.asarray(inv_h, np.float64).reshape(3))
         dropped = ctypes.c_ulonglong(0)
-        if scheme == 2:
+        if half_cell:
+            check(self._lib.rf_particles_paint_shifted(self._h, _dp(h), int(scheme), int(half_cell), ctypes.byref(dropped)), "rf_particles_paint_shifted")
+        elif scheme == 2:
             check(self._lib.rf_particles_paint(self._h, _dp(h), ctypes.byref(dropped)), "rf_particles_paint")
         else:
             check(self._lib.rf_particles_paint_ex(self._h, _dp(h), int(scheme), ctypes.byref(dropped)), "rf_particles_paint_ex")
+        return int(dropped.value)
+
+    def _phase_tables(self, tables, what):
+        """three per-axis complex128 tables (each may be None = all ones) as the C calls take them: interleaved float64 pairs"""
+        lengths = (self.nx, self.ny, self.nz // 2 + 1)
+        tabs = [None] * 3 if tables is None else list(tables)
+        if len(tabs) != 3:
+            raise ValueError("%s: tables are three per-axis arrays" % what)
+        for a in range(3):
+            if tabs[a] is not None:
+                tabs[a] = np.ascontiguousarray(np.asarray(tabs[a], np.complex128).ravel())
+                if len(tabs[a]) != lengths[a]:
+                    raise ValueError("%s: table %d needs %d entries" % (what, a, lengths[a]))
+        return tabs
+
+    def kspace_stash(self):
+        """S <- K (rf_kspace_stash): the k buffer's half spectrum put aside in a second buffer of its size, kept until the plan goes"""
+        check(self._lib.rf_kspace_stash(self._h), "rf_kspace_stash")
+
+    def kspace_interlace(self, tables=None):
+        """K <- (S + p K) / 2 with the stashed spectrum S and p = px[ix] py[iy] pz[iz] (rf_kspace_interlace).  ``tables``: None or
+        three complex tables of nx, ny, nz/2 + 1 finite entries (each may be None = all ones);
+        ``powertools.interlace_phases(shape)`` gives the ones that undo the half-cell shift."""
+        tabs = self._phase_tables(tables, "kspace_interlace")
+        check(self._lib.rf_kspace_interlace(self._h, *[None if t is None else t.ctypes.data_as(_c_dp) for t in tabs]), "rf_kspace_interlace")
+
+    def particles_paint_interlaced(self, inv_h, scheme=2, tables=None):
+        """The interlaced paint in one call (rf_particles_paint_interlaced): paint, r2c, stash, shifted paint, r2c, combine with
+        ``tables`` (as :meth:`kspace_interlace`), c2r.  The k buffer holds the interlaced spectrum, the current field is its inverse
+        transform.  Returns the number of particles dropped."""
+        h = _f64(np.asarray(inv_h, np.float64).reshape(3))
+        tabs = self._phase_tables(tables, "particles_paint_interlaced")
+        dropped = ctypes.c_ulonglong(0)
+        check(self._lib.rf_particles_paint_interlaced(self._h, _dp(h), int(scheme), *[None if t is None else t.ctypes.data_as(_c_dp) for t in tabs],
+                                                      ctypes.byref(dropped)), "rf_particles_paint_interlaced")
         return int(dropped.value)
 
     def particles_download_counts(self):

@@ -709,6 +709,18 @@ struct EmuTsc {
   template <class... A> static double gather_global(A&&... a) { return tsc_gather_global(std::forward<A>(a)...); }
   template <class... A> static double gather_tiled(A&&... a) { return tsc_gather_tiled(std::forward<A>(a)...); }
 };
+// the same two schemes with the half-cell shift of an interlaced paint's second grid (rf_core.h cic_axis_half; the HALF instantiations of
+// rf_k_particles.hip's paint operations): only how a particle is located differs
+struct EmuCicHalf : EmuCic {
+  template <typename T> static bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return cic_particle_half<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
+};
+struct EmuTscHalf : EmuTsc {
+  template <typename T> static bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    return tsc_particle_half<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
+  }
+};
 
 // The two walks of rf_k_particles.hip over an operation Op -- what it does before a brick's particles (prologue), with one particle's
 // eight cells, with a dropped particle and after the brick (epilogue), over a tile of Op::Cell.  cic_global_kernel: one "lane" per particle.
@@ -1047,6 +1059,37 @@ int emu_particles_paint_ex(int f64, int scheme, int nx, int ny, int nz, const vo
   memset(A, 0, (size_t)nx * ny * nz * 8);
   return scheme == 3 ? particles_paint_impl<EmuTsc>(f64, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped)
                      : particles_paint_impl<EmuCic>(f64, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
+}
+// the same with the half-cell shift as an argument (rf_particles_paint_shifted): half_cell = 0 is emu_particles_paint_ex, 1 paints the
+// particles at u + 1/2 on every axis (rf_core.h cic_axis_half), anything else is refused
+int emu_particles_paint_shifted(int f64, int scheme, int half_cell, int nx, int ny, int nz, const void* sx, const void* sy, const void* sz,
+                                const double* inv_h, int form, int bx, int by, int bz, int halo, int nth, unsigned long long* A, unsigned long long* dropped) {
+  if (half_cell == 0) return emu_particles_paint_ex(f64, scheme, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
+  if (half_cell != 1 || (scheme != 2 && scheme != 3)) return -1;
+  if (nx < 1 || ny < 1 || nz < 1 || !(sx && sy && sz && inv_h && A && dropped) || (form != 1 && form != 2) || nth < 1 || nth > 1024) return -1;
+  if (form == 2 && (bx < 1 || by < 1 || bz < 1 || halo < 1)) return -1;
+  memset(A, 0, (size_t)nx * ny * nz * 8);
+  return scheme == 3 ? particles_paint_impl<EmuTscHalf>(f64, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped)
+                     : particles_paint_impl<EmuCicHalf>(f64, nx, ny, nz, sx, sy, sz, inv_h, form, bx, by, bz, halo, nth, A, dropped);
+}
+// The interlacing combine K <- (S + p K) / 2 over two half spectra [nx][ny][nz/2 + 1] (rf_core.h interlace_mul / interlace_cell, the
+// functions interlace_kernel calls per cell): px, py, pz are nx, ny, nz/2 + 1 interleaved (re, im) float64 pairs, null = all ones
+int emu_kspace_interlace(int f64, int nx, int ny, int nz, const void* S, void* K, const double* px, const double* py, const double* pz) {
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || !(S && K) || S == K) return -1;
+  const int nzh = nz / 2 + 1;
+  for (int ix = 0; ix < nx; ++ix)
+    for (int iy = 0; iy < ny; ++iy) {
+      const double xr = px ? px[2 * ix] : 1.0, xi = px ? px[2 * ix + 1] : 0.0, yr = py ? py[2 * iy] : 1.0, yi = py ? py[2 * iy + 1] : 0.0;
+      double ar, ai;
+      interlace_mul(xr, xi, yr, yi, ar, ai);
+      const long long row = ((long long)ix * ny + iy) * nzh;
+      for (int iz = 0; iz < nzh; ++iz) {
+        const double zr = pz ? pz[2 * iz] : 1.0, zi = pz ? pz[2 * iz + 1] : 0.0;
+        if (f64) ((cplx<double>*)K)[row + iz] = interlace_cell<double>(((const cplx<double>*)S)[row + iz], ((cplx<double>*)K)[row + iz], ar, ai, zr, zi);
+        else ((cplx<float>*)K)[row + iz] = interlace_cell<float>(((const cplx<float>*)S)[row + iz], ((cplx<float>*)K)[row + iz], ar, ai, zr, zi);
+      }
+    }
+  return 0;
 }
 // the tiled form's traffic for these particles, by the kernel's own rule: out4 = {particles that leave their brick's tile, their adds
 // straight into A, non-zero tile cells flushed, dropped particles}

@@ -907,7 +907,8 @@ unsigned rf_abi_features(void) {
   return RF_FEATURE_REALISE | RF_FEATURE_R2C | RF_FEATURE_C2C | RF_FEATURE_LOGNORMAL | RF_FEATURE_POTENTIAL | RF_FEATURE_LENSING |
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
          RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE | RF_FEATURE_LPT2 |
-         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES | RF_FEATURE_PARTICLES_GATHER | RF_FEATURE_PARTICLES_TSC;
+         RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES | RF_FEATURE_PARTICLES_GATHER | RF_FEATURE_PARTICLES_TSC |
+         RF_FEATURE_PARTICLES_INTERLACE;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1067,7 +1068,7 @@ int rf_plan_destroy(rf_plan* p) {
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
   *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes + p->PG.bytes +
-            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes;      // (+ resident deviates and the replay's scratch runs)
+            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes + p->KS.bytes;      // (+ resident deviates and the replay's scratch runs)
   return 0;
 }
 
@@ -1242,15 +1243,16 @@ int queue_r2c_slab_cols(rf_plan* p, hipStream_t s) {
 // single-rank forward transform of the field in W.  Generic plans: rows -> half spectrum in K, then the y and x forward passes
 // (rf_generic.h generic_r2c_seq); W is untouched.  Tiled plans: the three passes in place in W, then (unpack) the API-layout array K;
 // without it W is left packed (slot kz = 0 = A0 + i A_nyq), K and what it holds as they were (rf_measure_power reads W directly).
-int queue_r2c_single(rf_plan* p, bool unpack) {
+// spectrum: where the half spectrum goes when it is not K (the stash of an interlaced paint: K and what it holds stay as they were)
+int queue_r2c_single(rf_plan* p, bool unpack, void* spectrum) {
   const long long nzc = p->nzc;
   const ColGeom gx{(long long)p->ny * nzc, 0, (long long)p->ny * nzc}, gy{nzc, (long long)p->ny * nzc, nzc};
   if (p->generic) {
     if (int rc = ensure_k(p)) return rc;
     if (generic_any_long(p)) { if (int rc = ensure_g(p)) return rc; if (int rc = ensure_g2(p)) return rc; }
     HipGenericOps ops{p, p->stream};
-    if (int rc = generic_r2c_seq(ops, p->gdims, p->W.ptr, p->K.ptr, p->G.ptr, p->G2.ptr)) return rc;
-    p->has.kspace_ready();            // the real field in W is untouched on this path
+    if (int rc = generic_r2c_seq(ops, p->gdims, p->W.ptr, spectrum ? spectrum : p->K.ptr, p->G.ptr, p->G2.ptr)) return rc;
+    if (!spectrum) p->has.kspace_ready();            // the real field in W is untouched on this path
     return 0;
   }
   if (unpack) { if (int rc = ensure_k(p)) return rc; }
@@ -1259,8 +1261,8 @@ int queue_r2c_single(rf_plan* p, bool unpack) {
   RF_HIP(launch_col_plain(p->f64, p->nx, -1, p->W.ptr, gx, (long long)p->ny * nzc, p->tw_x.ptr, p->stream));   // x forward
   p->has.field_consumed();    // the field buffer now holds packed k space
   if (unpack) {
-    RF_HIP(launch_unpack_kspace(p->f64, p->W.ptr, p->K.ptr, p->nx, p->ny, (int)nzc, 0, p->stream));
-    p->has.kspace_ready();
+    RF_HIP(launch_unpack_kspace(p->f64, p->W.ptr, spectrum ? spectrum : p->K.ptr, p->nx, p->ny, (int)nzc, 0, p->stream));
+    if (!spectrum) p->has.kspace_ready();
   }
   return 0;
 }
@@ -1285,7 +1287,7 @@ int rf_execute_r2c(rf_plan* p) {
     return 0;
   }
   RF_HIP(p->tl.begin(p->stream, false));
-  if (int rc = queue_r2c_single(p, true)) return rc;
+  if (int rc = queue_r2c_single(p, true, nullptr)) return rc;
   RF_HIP(p->tl.end(p->stream));
   return 0;
 }
@@ -1873,11 +1875,28 @@ int rf_particles_paint(rf_plan* p, const double* inv_h, unsigned long long* drop
 
 // the same with the assignment scheme as an argument of the call (RF_ASSIGN_CIC, RF_ASSIGN_TSC); any other is refused with nothing queued
 int rf_particles_paint_ex(rf_plan* p, const double* inv_h, int scheme, unsigned long long* dropped) {
+  return rf_particles_paint_shifted(p, inv_h, scheme, 0, dropped);
+}
+
+// what every paint refuses, with nothing queued
+static int paint_refuse(rf_plan* p, const double* inv_h, int scheme, int half_cell, const unsigned long long* dropped) {
   if (int rc = particles_check(p, "the cloud-in-cell paint runs on single-rank plans")) return rc;
   RF_REQUIRE(inv_h && dropped, "null argument");
   RF_REQUIRE(scheme == RF_ASSIGN_CIC || scheme == RF_ASSIGN_TSC, "scheme is RF_ASSIGN_CIC (2) or RF_ASSIGN_TSC (3)");
+  RF_REQUIRE(half_cell == 0 || half_cell == 1, "half_cell is 0 or 1");
   RF_REQUIRE(p->Q.ptr, "no particle displacements: call rf_particles_accumulate or rf_particles_upload first");
-  if (int rc = inv_h_check(inv_h)) return rc;
+  return inv_h_check(inv_h);
+}
+static int paint_queue(rf_plan* p, const double* inv_h, int scheme, int half_cell);
+
+// ... and with the half-cell shift of an interlaced paint's second grid (rf_core.h cic_axis_half): half_cell = 0 is rf_particles_paint_ex
+int rf_particles_paint_shifted(rf_plan* p, const double* inv_h, int scheme, int half_cell, unsigned long long* dropped) {
+  if (int rc = paint_refuse(p, inv_h, scheme, half_cell, dropped)) return rc;
+  if (int rc = paint_queue(p, inv_h, scheme, half_cell)) return rc;
+  return drop_read(p, dropped);
+}
+// the paint itself, queued: the arguments were checked, and the drop counter is left on the device for drop_read (a host synchronisation)
+static int paint_queue(rf_plan* p, const double* inv_h, int scheme, int half_cell) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_a(p)) return rc;
   const size_t n = particle_cells(p);
@@ -1891,13 +1910,104 @@ int rf_particles_paint_ex(rf_plan* p, const double* inv_h, int scheme, unsigned 
   RF_HIP(hipMemsetAsync(p->A.ptr, 0, n * 8, p->stream));
   RF_HIP(drop_clear(p));
   RF_HIP(p->tl.mark(rft::X, p->stream));
-  RF_HIP(launch_cic_paint(p->f64, scheme, form, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
+  RF_HIP(launch_cic_paint(p->f64, scheme, form, half_cell, p->Q.ptr, (unsigned long long*)p->A.ptr, (unsigned long long*)p->pa_drop.ptr, p->nx, p->ny, p->nz, inv_h, p->stream));
   RF_HIP(p->tl.mark(rft::Y, p->stream));
   RF_HIP(launch_cic_convert(p->f64, (const unsigned long long*)p->A.ptr, p->W.ptr, (long long)n, p->stream));
   RF_HIP(p->tl.mark(rft::Z, p->stream));
   RF_HIP(p->tl.end(p->stream));
   p->has.field_written(p->W.ptr);
   p->has.counts_ready();
+  return 0;
+}
+
+// ---- the interlaced paint: a stashed second half spectrum and the combine (rf_core.h interlace_cell; rf_k_misc.hip interlace_kernel) ----
+static int kspace_pair_check(rf_plan* p) {
+  RF_REQUIRE(p, "null plan");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the stashed spectrum and the interlacing combine live on single-rank plans");
+  return 0;
+}
+static int ensure_ks(rf_plan* p) { RF_HIP(p->KS.reserve(p->k_bytes)); return 0; }
+// the three phase tables (null: all ones): refused unless every entry is finite ...
+static int interlace_tables_check(rf_plan* p, const double* const (&tab)[3]) {
+  const int len[3] = {p->nx, p->ny, p->nz / 2 + 1};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; tab[a] && i < 2 * len[a]; ++i) RF_REQUIRE(std::isfinite(tab[a][i]), "bad phase table: every entry must be finite");
+  return 0;
+}
+// ... and on the device when this returns, dev[a] the device address of table a or null
+static int interlace_tables_upload(rf_plan* p, const double* const (&tab)[3], const double* (&dev)[3]) {
+  const int len[3] = {p->nx, p->ny, p->nz / 2 + 1};
+  if (!tab[0] && !tab[1] && !tab[2]) { dev[0] = dev[1] = dev[2] = nullptr; return 0; }
+  const size_t need = 2 * ((size_t)len[0] + len[1] + len[2]) * sizeof(double);
+  if (p->il_tab.bytes < need) RF_HIP(hipStreamSynchronize(p->stream));
+  RF_HIP(p->il_tab.reserve(need));
+  double* d = p->il_tab.get();
+  for (int a = 0; a < 3; ++a) {
+    dev[a] = tab[a] ? d : nullptr;
+    if (tab[a]) RF_HIP(hipMemcpyAsync(d, tab[a], 2 * (size_t)len[a] * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    d += 2 * len[a];
+  }
+  RF_HIP(hipStreamSynchronize(p->stream));            // (the caller's arrays are its own again)
+  return 0;
+}
+
+// S <- K
+int rf_kspace_stash(rf_plan* p) {
+  if (int rc = kspace_pair_check(p)) return rc;
+  RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_ks(p)) return rc;
+  RF_HIP(p->tl.begin(p->stream, false));
+  RF_HIP(hipMemcpyAsync(p->KS.ptr, p->K.ptr, p->k_bytes, hipMemcpyDeviceToDevice, p->stream));
+  RF_HIP(p->tl.end(p->stream));
+  p->has.stash_ready();
+  return 0;
+}
+
+// K <- (S + p K) / 2; the stash stays as it is
+int rf_kspace_interlace(rf_plan* p, const double* px, const double* py, const double* pz) {
+  if (int rc = kspace_pair_check(p)) return rc;
+  RF_REQUIRE(p->KS.ptr && p->has.stash(), "no stashed spectrum: call rf_kspace_stash first");
+  RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
+  const double* const tab[3] = {px, py, pz};
+  if (int rc = interlace_tables_check(p, tab)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  const double* dev[3];
+  if (int rc = interlace_tables_upload(p, tab, dev)) return rc;
+  RF_HIP(p->tl.begin(p->stream, false));
+  RF_HIP(launch_interlace(p->f64, p->KS.ptr, p->K.ptr, dev[0], dev[1], dev[2], p->nx, p->ny, p->nz, p->stream));
+  RF_HIP(p->tl.end(p->stream));
+  return 0;
+}
+
+// The whole interlaced paint: paint, forward transform (its spectrum written straight into the stash: no copy sweep), the shifted paint,
+// forward transform, combine, inverse transform.  Afterwards K holds the interlaced spectrum, the field is its inverse transform with
+// moments, A holds the SHIFTED paint's counts; *dropped is the first paint's count (the second's equals it: the rule is decided on u).
+// rf_elapsed_ms covers the whole call; rf_kernel_ms is refused.  Everything is queued without a host synchronisation in between: the
+// drop counter is read once, behind the last step -- the second paint cleared and counted it again, to the same value.
+static int paint_interlaced_steps(rf_plan* p, const double* inv_h, int scheme, const double* const (&dev)[3]) {
+  if (int rc = paint_queue(p, inv_h, scheme, 0)) return rc;
+  if (int rc = queue_r2c_single(p, true, p->KS.ptr)) return rc;
+  p->has.stash_ready();
+  if (int rc = paint_queue(p, inv_h, scheme, 1)) return rc;
+  if (int rc = queue_r2c_single(p, true, nullptr)) return rc;
+  RF_HIP(launch_interlace(p->f64, p->KS.ptr, p->K.ptr, dev[0], dev[1], dev[2], p->nx, p->ny, p->nz, p->stream));
+  return rf_execute_c2r(p);
+}
+int rf_particles_paint_interlaced(rf_plan* p, const double* inv_h, int scheme, const double* px, const double* py, const double* pz,
+                                  unsigned long long* dropped) {
+  if (int rc = paint_refuse(p, inv_h, scheme, 0, dropped)) return rc;
+  const double* const tab[3] = {px, py, pz};
+  if (int rc = interlace_tables_check(p, tab)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  if (int rc = ensure_k(p)) return rc;
+  if (int rc = ensure_ks(p)) return rc;
+  const double* dev[3];
+  if (int rc = interlace_tables_upload(p, tab, dev)) return rc;
+  RF_HIP(p->tl.span_begin(p->stream));
+  if (int rc = paint_interlaced_steps(p, inv_h, scheme, dev)) { p->tl.span_abandon(); return rc; }
+  RF_HIP(p->tl.span_end(p->stream));
   return drop_read(p, dropped);
 }
 
@@ -2035,7 +2145,7 @@ int measure_bins(rf_plan* p, int source, const double* k_edges, int nbins, DevBu
     tab_dev += clen[a];
   }
   RF_HIP(p->tl.begin(p->stream, false));
-  if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false)) return rc; }     // tiled plans: W packed, no K
+  if (source == RF_POWER_FROM_FIELD) { if (int rc = queue_r2c_single(p, false, nullptr)) return rc; }     // tiled plans: W packed, no K
   PowerParams& gp = bin_geom(g);
   gp.nx = p->nx; gp.ny = p->ny; gp.nz = p->nz;
   gp.nbins = nbins;

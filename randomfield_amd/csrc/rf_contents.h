@@ -1,6 +1,6 @@
 // rf_contents.h -- what a plan's device buffers hold: the one record behind every refusal that keeps a call from reading garbage ("no
 // real-space field on the device", "no k-space data", "no realisation has been computed", "no auxiliary field", "no second-order
-// potential", "no painted counts", "no deviates resident").  The entry points ask it through the predicates and change it through the
+// potential", "no painted counts", "no stashed spectrum", "no deviates resident").  The entry points ask it through the predicates and change it through the
 // named transitions, one call per event; nothing else writes it.  Allocation ("is there a buffer at all": K.ptr, P.ptr, L.ptr, A.ptr ...)
 // is not its business and stays with the buffers.  Plain C++, no HIP (tests/contents_test.cpp walks it on the CPU); the buffers are
 // opaque addresses that are never dereferenced here.  DESIGN.md section 3.19 has the table in words.
@@ -17,6 +17,7 @@ struct Contents {
   bool aux() const { return k_ == K::aux; }                                    // ... an auxiliary REAL field (the lensing potential)
   bool potential2() const { return p2_; }                                      // L holds the second-order potential of the stored one
   bool counts() const { return counts_; }                                      // A holds the counts of a paint
+  bool stash() const { return stash_; }                                        // the stash holds a half spectrum put aside by rf_kspace_stash
   bool deviates64() const { return dev_ == Dev::f64; }                         // `noise` holds float64 deviates in cell order
   bool deviates32() const { return dev_ == Dev::f32; }                         // the replay's runs hold float32 pairs
   bool deviates() const { return dev_ != Dev::none; }
@@ -49,13 +50,15 @@ struct Contents {
   void potential2_stale()                  { p2_ = false; }
   void counts_ready()                      { counts_ = true; }
   void counts_stale()                      { counts_ = false; }
+  // the stashed half spectrum: the caller's data, so nothing but the plan's end makes it stale -- there is no way back
+  void stash_ready()                       { stash_ = true; }
 
  private:
   enum class K { nothing, spectrum, aux };
   enum class Dev { none, f64, f32 };
   void* where_ = nullptr;
   int slot_ = 0;
-  bool real_ = false, moments_ = false, p2_ = false, counts_ = false;
+  bool real_ = false, moments_ = false, p2_ = false, counts_ = false, stash_ = false;
   K k_ = K::nothing;
   Dev dev_ = Dev::none;
 };

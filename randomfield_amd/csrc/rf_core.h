@@ -831,9 +831,8 @@ RF_HD void tsc_weights(uint32_t t, uint32_t (&w)[3]) {
   w[2] = (uint32_t)(((uint64_t)tau * tau) >> 17);
   w[1] = 65536u - w[0] - w[2];
 }
-RF_HD bool tsc_axis(double s, double inv_h, int i, int n, TscAxis& o) {
-  CicAxis a;
-  if (!cic_axis(s, inv_h, i, n, a)) return false;
+// the three cells and weights from the cloud-in-cell terms (c, j0, j1, t = w1) of the same axis
+RF_HD void tsc_of_cic(const CicAxis& a, int n, TscAxis& o) {
   const bool up = a.w1 >= 32768u;
   const int jc = up ? a.j1 : a.j0;
   o.clo = a.c + (up ? 0.0 : -1.0);
@@ -841,6 +840,11 @@ RF_HD bool tsc_axis(double s, double inv_h, int i, int n, TscAxis& o) {
   o.j[1] = jc;
   o.j[2] = jc + 1 == n ? 0 : jc + 1;
   tsc_weights(a.w1, o.w);
+}
+RF_HD bool tsc_axis(double s, double inv_h, int i, int n, TscAxis& o) {
+  CicAxis a;
+  if (!cic_axis(s, inv_h, i, n, a)) return false;
+  tsc_of_cic(a, n, o);
   return true;
 }
 // the three axes of one particle; false: dropped
@@ -925,6 +929,65 @@ RF_HD double tsc_gather_tiled(const TscAxis& x, const TscAxis& y, const TscAxis&
   if (sx < 0 || sy < 0 || sz < 0) return tsc_gather_global(x, y, z, ny, nz, load_global);
   const int py = t.tz(), px = t.ty() * py, base = sx * px + sy * py + sz;
   return tsc_gather_cells(x, y, z, [&](int cx, int cy, int cz) { return load_tile(base + cx * px + cy * py + cz); });
+}
+
+// ------------------------------- particles: interlaced paint (half-cell shift) --
+// The second grid of an interlaced paint (Sefusatti et al. 2016): the same particles on a grid shifted by half a cell on every axis, which
+// is the particle at u + 1/2 on the grid as it stands.  Per axis u, the drop rule (decided on u, BEFORE the shift), c, t in [0, 65536], j0
+// and j1 are cic_axis's; then, all in integers (2^-16 cell units, so the shift is exact):
+//   t2 = t + 32768,  carry = t2 >= 65536,  t' = carry ? t2 - 65536 : t2  in [0, 65535]      (t = 65536 gives t' = 32768 with a carry)
+//   j0' = carry ? j1 : j0,  j1' = (j0' + 1) mod n     on the WRAPPED index, never through c: for |u| >= 2^53, where c + 1 == c, it still steps
+//   c'  = c + carry                                   float64; the tile-slot tests alone read it
+//   w0' = 65536 - t',  w1' = t'
+// The triangular-shaped cloud takes (t', j0', c') where it took (t, j0, c) (tsc_of_cic).  Counts, cic_delta, the 65536-particles-per-cell
+// limit and "the same bits on every call and kernel form" carry over.  The shift is on all three axes at once; the gather has none.
+RF_HD void cic_axis_half(int n, CicAxis& a) {
+  const uint32_t t2 = a.w1 + 32768u;
+  const bool carry = t2 >= 65536u;
+  const uint32_t t = carry ? t2 - 65536u : t2;
+  if (carry) { a.c += 1.0; a.j0 = a.j1; }
+  a.j1 = a.j0 + 1 == n ? 0 : a.j0 + 1;
+  a.w0 = 65536u - t;
+  a.w1 = t;
+}
+template <typename T>
+RF_HD bool cic_particle_half(T sx, T sy, T sz, const double* inv_h, int ix, int iy, int iz, int nx, int ny, int nz, CicAxis& x, CicAxis& y, CicAxis& z) {
+  if (!cic_particle<T>(sx, sy, sz, inv_h, ix, iy, iz, nx, ny, nz, x, y, z)) return false;
+  cic_axis_half(nx, x); cic_axis_half(ny, y); cic_axis_half(nz, z);
+  return true;
+}
+template <typename T>
+RF_HD bool tsc_particle_half(T sx, T sy, T sz, const double* inv_h, int ix, int iy, int iz, int nx, int ny, int nz, TscAxis& x, TscAxis& y, TscAxis& z) {
+  CicAxis a, b, c;
+  if (!cic_particle_half<T>(sx, sy, sz, inv_h, ix, iy, iz, nx, ny, nz, a, b, c)) return false;
+  tsc_of_cic(a, nx, x); tsc_of_cic(b, ny, y); tsc_of_cic(c, nz, z);
+  return true;
+}
+
+// The combine: K <- (S + p K) / 2 per cell of two half spectra, p = px[ix] py[iy] pz[iz] the phase that undoes the shift (float64 complex
+// tables; powertools.interlace_phases has the default ones).  All in float64, EVERY product and EVERY sum rounded on its own (never
+// contracted: pragma / volatile as mul_then_add), so numpy repeats it bit for bit with one array operation per rounding:
+//   a = px py      ar = xr yr - xi yi,  ai = xr yi + xi yr          (interlace_mul; uniform along a z row)
+//   p = a pz,  q = p (double)K                                      (the same form)
+//   K = (T)(0.5 ((double)S + q))  per component, one rounding to T  (the halving is exact)
+RF_HD void interlace_mul(double xr, double xi, double yr, double yi, double& r, double& i) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const double rr = xr * yr, ii = xi * yi, ri = xr * yi, ir = xi * yr;
+  r = rr - ii;
+  i = ri + ir;
+#else
+  volatile double rr = xr * yr, ii = xi * yi, ri = xr * yi, ir = xi * yr;
+  r = rr - ii;
+  i = ri + ir;
+#endif
+}
+template <typename T>
+RF_HD cplx<T> interlace_cell(cplx<T> s, cplx<T> k, double ar, double ai, double zr, double zi) {
+  double pr, pi, qr, qi;
+  interlace_mul(ar, ai, zr, zi, pr, pi);
+  interlace_mul(pr, pi, (double)k.x, (double)k.y, qr, qi);
+  return mk<T>((T)(0.5 * ((double)s.x + qr)), (T)(0.5 * ((double)s.y + qi)));
 }
 
 // ------------------------------------------------- fast native generation --

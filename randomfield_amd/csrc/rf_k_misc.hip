@@ -244,6 +244,55 @@ __global__ __launch_bounds__(256) void derivative_kernel(const cplx<T>* S, cplx<
   }
 }
 
+// The interlacing combine K <- (S + p K) / 2 over two half spectra [nx][ny][nzh] (rf_core.h interlace_cell), p = px[ix] py[iy] pz[iz]
+// from three float64 complex tables (null: all ones).  Two streaming reads and one write per cell and nothing else: the cells are taken
+// FLAT, 16 bytes per lane and array as the other elementwise sweeps take them (VEC = 2 cells of a float32 plan, 1 of a float64 one), so
+// that a wave's accesses are 1024 contiguous bytes on whole cache lines wherever the rows start -- a row is nzh = nz/2 + 1 cells, an odd
+// number, so a walk along rows would start most of them in the middle of a line, leave the last wave of every row one lane wide, and a
+// vector of two cells may lie across two rows.  The price is (ix, iy, iz) per cell, and the division is paid once: a lane divides for
+// its first cell (below 2^21: 32-bit), steps to the vector's next cell by one with carries, and from one vector to its next adds the
+// grid stride's own (ix, iy, iz), worked out on the host, with two carries.  The tables come through the caches: px and py change once
+// in nzh cells, pz is at most 16 KB that every row reads again.  Every axis of a plan is even: the arrays are whole numbers of vectors.
+struct InterlaceStride { int dx, dy, dz; };      // the grid stride in cells, gridDim.x * blockDim.x * VEC, as (rows / ny, rows % ny, cells % nzh)
+template <typename T>
+__global__ __launch_bounds__(256) void interlace_kernel(const cplx<T>* __restrict__ S, cplx<T>* __restrict__ K, const double* __restrict__ px,
+                                                        const double* __restrict__ py, const double* __restrict__ pz, long long nvec, int ny, int nzh,
+                                                        InterlaceStride st) {
+  constexpr int VEC = 16 / (int)sizeof(cplx<T>);
+  typedef T vt __attribute__((ext_vector_type(2 * VEC)));
+  const unsigned first = blockIdx.x * blockDim.x + threadIdx.x, cell = first * VEC, row = cell / (unsigned)nzh;
+  int iz = (int)(cell - row * (unsigned)nzh), ix = (int)(row / (unsigned)ny), iy = (int)(row - (unsigned)ix * (unsigned)ny);
+  const long long step = (long long)gridDim.x * blockDim.x;
+  for (long long i = first; i < nvec; i += step) {
+    const vt s = __builtin_nontemporal_load(reinterpret_cast<const vt*>(S) + i);
+    const vt k = __builtin_nontemporal_load(reinterpret_cast<const vt*>(K) + i);
+    vt o;
+    int jx = ix, jy = iy, jz = iz;                   // the vector's cells, one after the other
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const double xr = px ? px[2 * jx] : 1.0, xi = px ? px[2 * jx + 1] : 0.0;
+      const double yr = py ? py[2 * jy] : 1.0, yi = py ? py[2 * jy + 1] : 0.0;
+      const double zr = pz ? pz[2 * jz] : 1.0, zi = pz ? pz[2 * jz + 1] : 0.0;
+      double ar, ai;
+      interlace_mul(xr, xi, yr, yi, ar, ai);
+      const cplx<T> c = interlace_cell<T>(mk<T>(s[2 * e], s[2 * e + 1]), mk<T>(k[2 * e], k[2 * e + 1]), ar, ai, zr, zi);
+      o[2 * e] = c.x; o[2 * e + 1] = c.y;
+      if (e + 1 < VEC && ++jz == nzh) {
+        jz = 0;
+        if (++jy == ny) { jy = 0; ++jx; }
+      }
+    }
+    __builtin_nontemporal_store(o, reinterpret_cast<vt*>(K) + i);
+    iz += st.dz;
+    int carry = iz >= nzh;
+    if (carry) iz -= nzh;
+    iy += st.dy + carry;                             // (dy + 1 <= ny: one subtraction brings it back)
+    carry = iy >= ny;
+    if (carry) iy -= ny;
+    ix += st.dx + carry;
+  }
+}
+
 // One step of the 2LPT source (rf_core.h lpt2_step) over dense real arrays: 16 bytes per lane and array, grid-strided, every cell on
 // its own.  A step touches only the arrays it needs: FIRST H -> T; DIAG2 H, T -> S, T; DIAG3 H, T, S -> S; OFF H, S -> S; LAST H, S -> H.
 template <typename T, int VEC, int STEP>
@@ -608,6 +657,21 @@ static hipError_t lpt2_accumulate_t(int step, T* H, T* Tacc, T* Sacc, long long 
 hipError_t launch_lpt2_accumulate(int f64, int step, void* H, void* T, void* S, long long n, hipStream_t s) {
   return f64 ? lpt2_accumulate_t<double, 2>(step, (double*)H, (double*)T, (double*)S, n, s)
              : lpt2_accumulate_t<float, 4>(step, (float*)H, (float*)T, (float*)S, n, s);
+}
+
+hipError_t launch_interlace(int f64, const void* S, void* K, const double* px, const double* py, const double* pz, int nx, int ny, int nz, hipStream_t s) {
+  if (nx < 1 || ny < 1 || nz < 2 || !S || !K || S == K) return hipErrorInvalidValue;
+  const int nzh = nz / 2 + 1;
+  const int vec = f64 ? 1 : 2;                       // cells in 16 bytes
+  const long long ncell = (long long)nx * ny * nzh;
+  if (ncell % vec || (uintptr_t)S % 16 || (uintptr_t)K % 16) return hipErrorInvalidValue;
+  const long long nvec = ncell / vec;
+  const unsigned grid = grid_for(nvec, 256);        // (the strides beyond it: tests/test_gpu_interlace.py)
+  const long long step = (long long)grid * 256 * vec, rows = step / nzh;
+  const InterlaceStride st = {(int)(rows / ny), (int)(rows % ny), (int)(step % nzh)};
+  if (f64) hipLaunchKernelGGL(interlace_kernel<double>, dim3(grid), dim3(256), 0, s, (const cplx<double>*)S, (cplx<double>*)K, px, py, pz, nvec, ny, nzh, st);
+  else hipLaunchKernelGGL(interlace_kernel<float>, dim3(grid), dim3(256), 0, s, (const cplx<float>*)S, (cplx<float>*)K, px, py, pz, nvec, ny, nzh, st);
+  return hipGetLastError();
 }
 
 hipError_t launch_scale_copy(int f64, const void* P, void* K, long long n, int zpitch, int ppitch, double scale, hipStream_t s) {

@@ -8,6 +8,8 @@
 //   GatherOp  the scatter's adjoint (rf_core.h cic_gather_value): the field gathered at the particles, no atomics but the drop counter's.
 // The operation also names the assignment scheme -- its per-axis type (Op::Axis) and how a particle is located (Op::locate): cloud in
 // cell for these two, the triangular-shaped cloud (27 cells, rf_core.h tsc_*) for TscPaintOp / TscGatherOp, which inherit the rest.
+// The two paint operations also come shifted by half a cell on every axis (HALF; rf_core.h cic_axis_half): the second grid of an
+// interlaced paint, whose two spectra rf_k_misc.hip's interlace_kernel combines.
 #include "rf_kernels.h"
 #include "rf_launch.h"
 
@@ -30,12 +32,15 @@ extern __shared__ __attribute__((aligned(16))) u64 cic_lds[];
 // eight cells do not all fall inside the tile add straight into A as the global form does.  The tile is flushed with one global atomic
 // per non-zero tile cell, indices wrapped periodically there: neighbouring bricks' halos overlap, bricks at the grid's edge are partial,
 // and on a grid smaller than the tile several tile cells alias one cell of A -- the atomic flush covers all three.
-template <typename T>
+// HALF: the particle at u + 1/2 on every axis (rf_core.h cic_axis_half), the second grid of an interlaced paint.  A template parameter of
+// the operation, so the unshifted instantiations are the code they were; everything past locate() is shared.
+template <typename T, bool HALF = false>
 struct PaintOp {
   typedef u64 Cell;
   typedef CicAxis Axis;
   u64* __restrict__ A;
   static __device__ bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    if (HALF) return cic_particle_half<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
     return cic_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
   }
   __device__ void prologue(const CicTile&, const CicGrid&, int tid) const {
@@ -96,10 +101,11 @@ struct GatherOp {
 // The same two operations with the triangular-shaped cloud (rf_core.h tsc_axis ... tsc_gather_tiled): 27 cells per particle where cloud
 // in cell has eight.  The tile, its clearing, staging and flush are the cloud-in-cell operations' own; only what happens with one
 // particle differs.
-template <typename T>
+template <typename T, bool HALF = false>
 struct TscPaintOp : PaintOp<T> {
   typedef TscAxis Axis;
   static __device__ bool locate(T sx, T sy, T sz, const CicGrid& g, int ix, int iy, int iz, Axis& x, Axis& y, Axis& z) {
+    if (HALF) return tsc_particle_half<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
     return tsc_particle<T>(sx, sy, sz, g.inv_h, ix, iy, iz, g.nx, g.ny, g.nz, x, y, z);
   }
   __device__ void particle(long long, const Axis& x, const Axis& y, const Axis& z, const CicGrid& g) const {
@@ -255,16 +261,24 @@ hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double c
              : particles_accumulate_t<float, 4>((const float*)W, (float*)Q, coeff, first, n, s);
 }
 
-hipError_t launch_cic_paint(int f64, int scheme, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
-                            const double* inv_h, hipStream_t s) {
-  if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2)) return hipErrorInvalidValue;
+namespace {
+template <bool HALF>
+hipError_t cic_paint_t(int f64, int scheme, int form, const void* Q, u64* A, u64* dropped, int nx, int ny, int nz, const double* inv_h, hipStream_t s) {
   if (scheme == 3) {
-    return f64 ? cic_launch(form, (const double*)Q, TscPaintOp<double>{{A}}, dropped, nx, ny, nz, inv_h, s)
-               : cic_launch(form, (const float*)Q, TscPaintOp<float>{{A}}, dropped, nx, ny, nz, inv_h, s);
+    return f64 ? cic_launch(form, (const double*)Q, TscPaintOp<double, HALF>{{A}}, dropped, nx, ny, nz, inv_h, s)
+               : cic_launch(form, (const float*)Q, TscPaintOp<float, HALF>{{A}}, dropped, nx, ny, nz, inv_h, s);
   }
   if (scheme != 2) return hipErrorInvalidValue;
-  return f64 ? cic_launch(form, (const double*)Q, PaintOp<double>{A}, dropped, nx, ny, nz, inv_h, s)
-             : cic_launch(form, (const float*)Q, PaintOp<float>{A}, dropped, nx, ny, nz, inv_h, s);
+  return f64 ? cic_launch(form, (const double*)Q, PaintOp<double, HALF>{A}, dropped, nx, ny, nz, inv_h, s)
+             : cic_launch(form, (const float*)Q, PaintOp<float, HALF>{A}, dropped, nx, ny, nz, inv_h, s);
+}
+}  // namespace
+
+hipError_t launch_cic_paint(int f64, int scheme, int form, int half_cell, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny,
+                            int nz, const double* inv_h, hipStream_t s) {
+  if (nx < 1 || ny < 1 || nz < 1 || (form != 1 && form != 2) || (half_cell != 0 && half_cell != 1)) return hipErrorInvalidValue;
+  return half_cell ? cic_paint_t<true>(f64, scheme, form, Q, A, dropped, nx, ny, nz, inv_h, s)
+                   : cic_paint_t<false>(f64, scheme, form, Q, A, dropped, nx, ny, nz, inv_h, s);
 }
 
 void cic_paint_geometry(int* brick3, int* halo) {

@@ -146,8 +146,13 @@ hipError_t launch_particles_accumulate(int f64, const void* W, void* Q, double c
 // (rf_core.h cic_particle; PaintOp over cic_global_kernel / cic_tiled_kernel): form 1 = global atomics, form 2 = LDS tiles flushed with
 // global atomics; *dropped (cleared by the caller) counts the particles with a non-finite displacement.  Same A from both forms.
 // scheme: 2 = cloud in cell, 3 = triangular-shaped cloud (rf_core.h tsc_particle; TscPaintOp over the same walks, tile and launcher).
-hipError_t launch_cic_paint(int f64, int scheme, int form, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny, int nz,
-                            const double* inv_h, hipStream_t s);
+// half_cell: 0, or 1 = the particles at u + 1/2 on every axis (rf_core.h cic_axis_half; the operations' HALF instantiations).
+hipError_t launch_cic_paint(int f64, int scheme, int form, int half_cell, const void* Q, unsigned long long* A, unsigned long long* dropped, int nx, int ny,
+                            int nz, const double* inv_h, hipStream_t s);
+// the interlacing combine K <- (S + p K) / 2 over two API-layout half spectra [nx][ny][nz/2 + 1] (rf_k_misc.hip interlace_kernel;
+// rf_core.h interlace_cell).  px, py, pz: device tables of nx, ny, nz/2 + 1 interleaved (re, im) float64 pairs, null = all ones.
+// S and K must be different arrays.
+hipError_t launch_interlace(int f64, const void* S, void* K, const double* px, const double* py, const double* pz, int nx, int ny, int nz, hipStream_t s);
 // the brick (cells per axis) and the halo of form 2's tile
 void cic_paint_geometry(int* brick3, int* halo);
 // the cloud-in-cell gather, the scatter's adjoint (rf_core.h cic_gather_value): the dense real field W at the lattice particles displaced

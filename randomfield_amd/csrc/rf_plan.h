@@ -178,6 +178,10 @@ struct rf_plan {
   // particle's lattice cell as Q is and counted by rf_plan_nbytes; the drop counter is pa_drop.  gather_form: 0 auto, 1 global, 2 tiled.
   rfc::DevBuf<> PG;
   int gather_form = 0;
+  // lazy, rf_kspace_stash: a second half spectrum of K's size and layout (k_bytes, counted by rf_plan_nbytes) -- the first grid's spectrum
+  // of an interlaced paint; has.stash().  il_tab: the combine's three phase tables on the device, (nx + ny + nz/2 + 1) float64 pairs.
+  rfc::DevBuf<> KS;
+  rfc::DevBuf<double> il_tab;
   rfc::DevBuf<> tw_x, tw_y, tw_z;
   rfc::DevBuf<double> kx2, ky2, kz2;
   rfc::DevBuf<double> xt, st, sl;
@@ -281,6 +285,6 @@ int rms_from_stats(rf_plan* p, int n, double* rms_out);
 int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStream_t s);
 int queue_r2c_slab_rows(rf_plan* p, hipStream_t s);
 int queue_r2c_slab_cols(rf_plan* p, hipStream_t s);
-int queue_r2c_single(rf_plan* p, bool unpack);
+int queue_r2c_single(rf_plan* p, bool unpack, void* spectrum);
 int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_host, bool whole);
 }  // namespace rfc

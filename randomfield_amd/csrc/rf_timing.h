@@ -22,14 +22,29 @@ struct Timeline {
   std::vector<Mark> marks;             // of the current call only
   bool detailed = false;               // the call takes marks (a timed realisation); else start and end alone (batches, transforms)
   bool complete = false;               // end() has closed the call; begin() clears it, so a call that fails half way leaves nothing to read
+  bool spanning = false;               // a call made of timed calls is open (span_begin): their begin() keeps its start
 
   Error begin(typename Api::Stream s, bool detail) {
     complete = detailed = false;
     marks.clear();
     if (Error e = ev.ensure(2, 0); e != Api::ok) return e;
     detailed = detail;
-    return Api::event_record(ev[0], s);
+    return spanning ? Api::ok : Api::event_record(ev[0], s);
   }
+  // A call that is a sequence of timed calls (rf_particles_paint_interlaced): the start is recorded here and every begin() up to
+  // span_end() leaves it alone, so rf_elapsed_ms covers the whole sequence.  span_end() closes it as a call without marks.
+  Error span_begin(typename Api::Stream s) {
+    spanning = false;
+    if (Error e = begin(s, false); e != Api::ok) return e;
+    spanning = true;
+    return Api::ok;
+  }
+  Error span_end(typename Api::Stream s) {
+    spanning = detailed = false;
+    marks.clear();
+    return end(s);
+  }
+  void span_abandon() { spanning = complete = false; }      // the sequence failed half way: nothing to read
   // detailed timelines only: what ran on s since the previous mark (or the start) belongs to `part`.  out: the mark's event, for a
   // launcher that records it AGAIN further on (the split generation pass, between its two launches): that moves the boundary later,
   // and never past the next mark, which is recorded after the launcher has returned.

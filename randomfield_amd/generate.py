@@ -20,6 +20,7 @@ Out of scope here (host-only side-cars of the reference):
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
@@ -38,6 +39,15 @@ def _assignment_order(assignment):
     return orders[assignment]
 
 
+def _replaces_kspace(method):
+    """a Generator method that may write the k buffer: the spectrum of the last interlaced paint is gone (``source='kspace'``)"""
+    @functools.wraps(method)
+    def wrapper(self, *args, **kwargs):
+        self._interlaced = None
+        return method(self, *args, **kwargs)
+    return wrapper
+
+
 class _DevicePotential(object):
     """Marker for a saved delta(k)/k**2 field that lives in device memory."""
 
@@ -47,6 +57,7 @@ class _DevicePotential(object):
     def download(self):
         """Host copy (nx, ny, nz/2+1) of the saved potential."""
         dev = self._generator.plan_c2r.device
+        self._generator._interlaced = None
         dev.load_potential(1.0)
         return dev.download_k()
 
@@ -82,6 +93,7 @@ class _RegeneratedPotential(object):
         ``convert_delta_to_density`` / ``calculate_newtonian_potential`` had left there is gone (download the field first)."""
         self.check_current()
         dev = self._generator.plan_c2r.device
+        self._generator._interlaced = None
         dev.realise_potential(self.seed, self.noise)
         dev.load_potential(1.0)
         self._generator._field_on_host = False
@@ -190,6 +202,7 @@ class Generator(object):
         self.potential = None
         self._lpt2 = None                   # second-order potential of the current field: the array (numpy) / its potential object (hip)
         self._particles = None              # particle displacements: the (3, nx, ny, nz) array (numpy) / True once the device buffer is filled (hip)
+        self._interlaced = None             # the spectrum of the last interlaced paint: the complex128 array (numpy) / True (hip: in the k buffer)
         self._gathered = None               # gathered values: the (3, nx, ny, nz) array (numpy) / True once a gather has run (hip)
         self.particles_dropped = 0
 
@@ -252,6 +265,7 @@ class Generator(object):
                 seed = self.plan_c2r.agree_on(seed >> 12)          # 52 bits survive the float64 all-reduce
         return int(seed) & (2 ** 64 - 1)
 
+    @_replaces_kspace
     def generate_delta_field(self, smoothing_length_Mpc_h=0., seed=None, save_potential=True, show_plot=False,
                              save_plot_name=None, *, download=True):
         """
@@ -372,6 +386,7 @@ class Generator(object):
         else:
             dev.realise(dseed, noise)
 
+    @_replaces_kspace
     def generate_density_field(self, smoothing_length_Mpc_h=0., seed=None, *, download=True):
         """
         ``generate_delta_field(save_potential=False)`` followed by ``convert_delta_to_density(apply_lognormal_transform=True)``
@@ -421,7 +436,7 @@ class Generator(object):
             self._field_on_host = True
         return self.plan_c2r.data_out
 
-    def measure_power_spectrum(self, field=None, *, k_edges=None, nbins=None, window=None):
+    def measure_power_spectrum(self, field=None, *, k_edges=None, nbins=None, window=None, source="field"):
         """
         Binned power spectrum of a field on this grid (an extension; the reference has no such method): the estimator that
         closes P(k) -> delta(x) -> P^(k).
@@ -446,24 +461,31 @@ class Generator(object):
         ``window`` (None, ``'ngp'`` / ``'cic'`` / ``'tsc'``, or three per-axis tables as ``powertools.window_compensation`` makes
         them) divides a mass-assignment window out of |delta(k)|**2: ``'Pk'`` is then the compensated monopole of
         :meth:`measure_power_multipoles` (``rf_measure_multipoles``).  With the default nothing changes.
+
+        ``source``: ``'field'`` (the default: everything above) or ``'kspace'``, which measures the spectrum left by the last
+        ``paint_particles(interlaced=True)`` without transforming anything and leaves field and spectrum as they are.  It raises
+        ``RuntimeError`` if there is no such spectrum or a later call of this object has replaced it; ``field=`` together with it is
+        a ``ValueError``.  Among the calls that replace it is every ``source='field'`` measurement, on both backends and every grid
+        (the device transforms the field into the k buffer on grids that are no power of two; the rule is the same everywhere so that
+        one sequence of calls behaves alike): measure with ``source='kspace'`` first, then the field.
         """
         if self.distributed:
             raise NotImplementedError("measure_power_spectrum runs on single-GPU plans.")
+        self._check_source(field, source)
         if window is not None:
-            res = self.measure_power_multipoles(field, los=2, k_edges=k_edges, nbins=nbins, window=window)
+            res = self.measure_power_multipoles(field, los=2, k_edges=k_edges, nbins=nbins, window=window, source=source)
             out = np.empty(len(res), [("k", float), ("Pk", float), ("nmodes", np.uint64)])
             out["k"], out["Pk"], out["nmodes"] = res["k"], res["P0"], res["nmodes"]
             return out
         shape, k_edges = self._power_inputs(field, k_edges, nbins)
         if self.backend == "numpy":
-            kdata = np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
-            sums = powertools.bin_power(kdata, self.grid_spacing_Mpc_h, k_edges)
+            sums = powertools.bin_power(self._numpy_spectrum(source), self.grid_spacing_Mpc_h, k_edges)
         else:
             from . import _hip
-            sums = self.plan_c2r.device.measure_power(k_edges, _hip.RF_POWER_FROM_FIELD)
+            sums = self.plan_c2r.device.measure_power(k_edges, self._hip_source(source))
         return powertools.power_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
 
-    def measure_power_multipoles(self, field=None, *, los=2, k_edges=None, nbins=None, window=None):
+    def measure_power_multipoles(self, field=None, *, los=2, k_edges=None, nbins=None, window=None, source="field"):
         """
         Monopole, quadrupole and hexadecapole of the binned power spectrum with the line of sight along grid axis ``los`` (0, 1, 2:
         plane-parallel) -- what a mock painted in redshift space (:meth:`particle_displacements` with ``rsd_axis``) is measured with.
@@ -476,9 +498,11 @@ class Generator(object):
         |delta(k)|**2 (each may be None).  The compensation is the standard one for well-mixed particles, not an exact inverse of
         the paint of a cold lattice.  Returns a structured array with the fields ``'k'``, ``'P0'``, ``'P2'``, ``'P4'``, ``'nmodes'``;
         empty bins hold NaN.  hip backend: one sweep on the device (``rf_measure_multipoles``), the same bits on every call.
+        ``source`` as in :meth:`measure_power_spectrum`.
         """
         if self.distributed:
             raise NotImplementedError("measure_power_multipoles runs on single-GPU plans.")
+        self._check_source(field, source)
         if los not in (0, 1, 2):
             raise ValueError("Invalid los: {0!r} (expected 0, 1 or 2).".format(los))
         if isinstance(window, str):
@@ -487,12 +511,35 @@ class Generator(object):
             window = powertools._compensation_tables(window, tuple(self.plan_c2r.shape))
         shape, k_edges = self._power_inputs(field, k_edges, nbins)
         if self.backend == "numpy":
-            kdata = np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
-            sums = powertools.bin_multipoles(kdata, self.grid_spacing_Mpc_h, k_edges, los, window)
+            sums = powertools.bin_multipoles(self._numpy_spectrum(source), self.grid_spacing_Mpc_h, k_edges, los, window)
         else:
             from . import _hip
-            sums = self.plan_c2r.device.measure_multipoles(k_edges, los, _hip.RF_POWER_FROM_FIELD, window)
+            sums = self.plan_c2r.device.measure_multipoles(k_edges, los, self._hip_source(source), window)
         return powertools.multipole_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
+
+    def _check_source(self, field, source):
+        if source not in ("field", "kspace"):
+            raise ValueError("Invalid source: {0!r} (expected 'field' or 'kspace').".format(source))
+        if source == "kspace":
+            if field is not None:
+                raise ValueError("source='kspace' measures the spectrum of the last interlaced paint: it takes no field.")
+            if self._interlaced is None:
+                raise RuntimeError("No interlaced spectrum: call paint_particles(interlaced=True) first (a later call that writes "
+                                   "the k buffer replaces it).")
+
+    def _numpy_spectrum(self, source):
+        """the half spectrum a numpy-backend measurement bins"""
+        if source == "kspace":
+            return self._interlaced
+        self._interlaced = None                  # (as on the hip backend: one rule for both)
+        return np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
+
+    def _hip_source(self, source):
+        from . import _hip
+        if source == "kspace":
+            return _hip.RF_POWER_FROM_KSPACE
+        self._interlaced = None                  # (generic plans leave the field's spectrum in the k buffer; tiled ones follow the same rule)
+        return _hip.RF_POWER_FROM_FIELD
 
     def _power_inputs(self, field, k_edges, nbins):
         """the edges of a power spectrum measurement, and ``field`` (if given) made the current field: (shape, k_edges)"""
@@ -559,6 +606,7 @@ class Generator(object):
         self._field_on_host = False
         return self.download_field() if download else None
 
+    @_replaces_kspace
     def calculate_newtonian_potential(self, light_cone=True, show_plot=False, save_plot_name=None, *,
                                       scale=None, download=True):
         """
@@ -602,6 +650,7 @@ class Generator(object):
         self._field_on_host = False
         return self.download_field() if download else None
 
+    @_replaces_kspace
     def calculate_displacement_field(self, axis, light_cone=False, *, order=1, scale=1.0, factor_z=None, download=True):
         """
         One component of the vector field of the saved potential (an extension: the reference keeps delta(k)/k**2 "for later
@@ -736,6 +785,7 @@ class Generator(object):
             self.potential = _DevicePotential(self)
         return dev
 
+    @_replaces_kspace
     def lpt2_source(self, download=True):
         """
         The source of the second-order potential, S(r) = sum over a < b of H_aa H_bb - H_ab**2 (see
@@ -756,6 +806,7 @@ class Generator(object):
         self._field_on_host = False
         return self.download_field() if download else None
 
+    @_replaces_kspace
     def _second_order_displacement(self, axis, dk, scale, factor, download):
         shape = self.plan_c2r.shape
         scale2 = 3.0 / 7.0 * float(scale) ** 2
@@ -863,7 +914,7 @@ class Generator(object):
             out[axis] = np.mod(q * h + Q[axis].astype(np.float64), n * h)
         return out
 
-    def paint_particles(self, download=True, *, assignment="cic"):
+    def paint_particles(self, download=True, *, assignment="cic", interlaced=False):
         """
         Cloud-in-cell mass assignment of the displaced particles onto the grid: delta_cic = (mass per cell) - 1 becomes the current
         field, so ``measure_power_spectrum()`` with no argument measures the particles.  The weights are integers in units of
@@ -876,11 +927,23 @@ class Generator(object):
         integer weights of the same unit (``particles.py``; hip backend: ``rf_particles_paint_ex``), bit for bit the same on both
         backends.  Pass the same name as ``window=`` to :meth:`measure_power_spectrum` / :meth:`measure_power_multipoles` to divide
         the assignment window out of the painted field: ``window='cic'`` after ``assignment='cic'``, ``window='tsc'`` after ``'tsc'``.
+
+        ``interlaced=True`` (Sefusatti et al. 2016): the particles are painted a second time on a grid shifted by half a cell on
+        every axis and the two spectra are combined with the phase that undoes the shift, ``(delta1 + p delta2) / 2`` with the
+        tables of ``powertools.interlace_phases``: every aliased image with an odd sum of image indices cancels, the dominant first
+        image on each axis among them, which the window compensation alone does not remove.  The current field, and the array
+        returned, is the inverse transform of the combined spectrum; the spectrum itself is kept, and
+        ``measure_power_spectrum(source='kspace', window=...)`` / ``measure_power_multipoles(source='kspace', ...)`` measure it
+        without another transform.  hip backend: ``rf_particles_paint_interlaced``, everything on the device.  numpy backend:
+        ``rfftn`` / ``irfftn`` in float64 on the two deltas as rounded to the plan's real type.
         """
         order = _assignment_order(assignment)
         if self._particles is None:
             raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
         inv_h = [1.0 / float(self.grid_spacing_Mpc_h)] * 3
+        self._interlaced = None
+        if interlaced:
+            return self._paint_interlaced(inv_h, order, download)
         if self.backend == "numpy":
             from . import particles
             A, self.particles_dropped = particles.paint_counts(self._particles, inv_h, order)
@@ -890,6 +953,27 @@ class Generator(object):
         self.particles_dropped = self.plan_c2r.device.particles_paint(inv_h, order)
         self._field_on_host = False
         return self.download_field() if download else None
+
+    def _paint_interlaced(self, inv_h, order, download):
+        shape = tuple(self.plan_c2r.shape)
+        tables = powertools.interlace_phases(shape)
+        if self.backend == "hip":
+            self.particles_dropped = self.plan_c2r.device.particles_paint_interlaced(inv_h, order, tables)
+            self._interlaced = True
+            self._field_on_host = False
+            return self.download_field() if download else None
+        from . import particles
+        rtype = self.plan_c2r.data_out.dtype
+        spectra = []
+        for half in (False, True):
+            A, dropped = particles.paint_counts(self._particles, inv_h, order, half_cell=half)
+            spectra.append(np.fft.rfftn(particles.counts_to_delta(A, rtype).astype(np.float64), axes=(0, 1, 2)))
+            if not half:
+                self.particles_dropped = dropped
+        self._interlaced = powertools.interlace_combine(spectra[0], spectra[1], tables)
+        self.plan_c2r.data_out[...] = np.fft.irfftn(self._interlaced, s=shape, axes=(0, 1, 2))
+        self._field_on_host = True
+        return self.plan_c2r.data_out if download else None
 
     def interpolate_at_particles(self, field=None, *, slot=0, coeff=1.0, first=True, download=True, assignment="cic"):
         """
@@ -951,6 +1035,7 @@ class Generator(object):
             return
         self.plan_c2r.device.particles_shift(axis, slot, coeff)
 
+    @_replaces_kspace
     def calculate_lensing_potential(self, i_min=None, show_plot=False, save_plot_name=None):
         """
         Calculate the lensing potential psi(r) (generate.py:352-416):

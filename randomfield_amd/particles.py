@@ -16,7 +16,7 @@ import numpy as np
 WEIGHT_ONE = 1 << 48
 
 
-def _axis(s, inv_h, axis):
+def _axis(s, inv_h, axis, half=False):
     n = s.shape[axis]
     u = np.asarray(s, np.float64) * np.float64(inv_h)
     ok = np.isfinite(u)
@@ -28,13 +28,18 @@ def _axis(s, inv_h, axis):
     r = np.where(r < 0, r + n, r)
     r = np.where(r >= n, r - n, r)
     j0 = r.astype(np.int64)
+    if half:        # the particle at u + 1/2, in integers: t + 32768 with its carry into the WRAPPED index (never through c)
+        t2 = t + np.uint64(32768)
+        carry = t2 >= np.uint64(65536)
+        t = np.where(carry, t2 - np.uint64(65536), t2)
+        j0 = np.where(carry, (j0 + 1) % n, j0)
     return ok, (j0, (j0 + 1) % n), (np.uint64(65536) - t, t)
 
 
-def _axis_tsc(s, inv_h, axis):
+def _axis_tsc(s, inv_h, axis, half=False):
     """the three cells and weights of the triangular-shaped cloud from the cloud-in-cell terms of the same axis"""
     n = s.shape[axis]
-    ok, (j0, j1), (_, t) = _axis(s, inv_h, axis)
+    ok, (j0, j1), (_, t) = _axis(s, inv_h, axis, half)
     up = t >= np.uint64(32768)
     tau = np.where(up, t - np.uint64(32768), t + np.uint64(32768))
     jc = np.where(up, j1, j0)
@@ -43,19 +48,22 @@ def _axis_tsc(s, inv_h, axis):
     return ok, ((jc - 1) % n, jc, (jc + 1) % n), (wm, np.uint64(65536) - wm - wp, wp)
 
 
-def _terms(s, inv_h, order):
+def _terms(s, inv_h, order, half=False):
     if order not in (2, 3):
         raise ValueError("Invalid order: {0!r} (expected 2, cloud in cell, or 3, triangular-shaped cloud).".format(order))
     axis = _axis if order == 2 else _axis_tsc
-    return [axis(s[a], inv_h[a], a) for a in range(3)]
+    return [axis(s[a], inv_h[a], a, half) for a in range(3)]
 
 
-def paint_counts(displacements, inv_h, order=2):
+def paint_counts(displacements, inv_h, order=2, half_cell=False):
     """``(A, dropped)``: the uint64 accumulator grid of the particles displaced by ``displacements`` (3, nx, ny, nz) and the number
-    of dropped particles.  ``order``: 2 cloud in cell, 3 triangular-shaped cloud."""
+    of dropped particles.  ``order``: 2 cloud in cell, 3 triangular-shaped cloud.  ``half_cell``: the particles at u + 1/2 on every
+    axis -- the second grid of an interlaced paint (csrc/rf_core.h ``cic_axis_half``): per axis t2 = t + 32768, carry = t2 >= 65536,
+    t' = t2 - 65536 if carry else t2, j0' = (j0 + 1) mod n if carry else j0; the triangular-shaped cloud takes (t', j0') in place of
+    (t, j0).  Particles are dropped by u, before the shift."""
     s = np.asarray(displacements)
     shape = s.shape[1:]
-    terms = _terms(s, inv_h, order)
+    terms = _terms(s, inv_h, order, bool(half_cell))
     ok = terms[0][0] & terms[1][0] & terms[2][0]
     A = np.zeros(int(np.prod(shape)), np.uint64)
     if order == 3:

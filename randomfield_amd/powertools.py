@@ -136,6 +136,58 @@ def window_compensation(shape, scheme):
     return tuple(tabs)
 
 
+def interlace_phases(shape):
+    """The three per-axis complex128 tables ``p_a[i] = exp(+i pi m / n_a)`` (lengths nx, ny, nz/2 + 1; m the signed mode number of
+    index i, from cos / sin of ``pi * m / n`` in float64) that undo the half-cell shift of an interlaced paint's second grid: with the
+    particles at u + 1/2 that grid's spectrum is ``exp(-i pi m / n)`` per axis times the unshifted one, so the interlaced field is
+    ``(delta1 + p delta2) / 2`` with p = px[ix] py[iy] pz[iz] (``rf_kspace_interlace``; Sefusatti et al. 2016).
+
+    ``p_a[0] = 1`` exactly.  ``p_a[n_a / 2] = 0`` exactly: the Hermitian part of ``exp(+-i pi / 2)``.  That keeps
+    ``p(-k) = conj(p(k))``, so the combined spectrum is Hermitian and its inverse transform is the real field; the planes at an axis'
+    own Nyquist index therefore hold ``delta1 / 2``.  They lie at |k| >= k_Nyq, beyond what a measurement up to k_Nyq reads."""
+    nx, ny, nz = (int(n) for n in shape)
+    tabs = []
+    for n, count in ((nx, nx), (ny, ny), (nz, nz // 2 + 1)):
+        m = np.rint(np.fft.fftfreq(n) * n)[:count]
+        arg = np.pi * m / n
+        p = np.cos(arg) + 1j * np.sin(arg)
+        p[0] = 1.0
+        if n % 2 == 0:
+            p[n // 2] = 0.0
+        tabs.append(p.astype(np.complex128))
+    return tuple(tabs)
+
+
+def interlace_combine(stashed, kdata, tables=None):
+    """``(S + p K) / 2`` per cell of two half spectra with p = px[ix] py[iy] pz[iz] -- the numpy statement of the definition the
+    device call ``rf_kspace_interlace`` implements (csrc/rf_core.h interlace_cell).  ``tables``: None or three complex per-axis tables
+    (each may be None = all ones).  All in float64 on real arrays, one numpy operation per rounding: a = px py
+    (ar = xr yr - xi yi, ai = xr yi + xi yr), p = a pz and q = p K in the same form, then 0.5 (S + q) per component, rounded once
+    to the type of ``kdata``."""
+    S, K = np.asarray(stashed), np.asarray(kdata)
+    tabs = [None] * 3 if tables is None else list(tables)
+    parts = []
+    for a, n in enumerate(K.shape):
+        t = np.ones(n, np.complex128) if tabs[a] is None else np.asarray(tabs[a], np.complex128).ravel()
+        if len(t) != n:
+            raise ValueError("phase table {0} needs {1} entries.".format(a, n))
+        index = [None] * 3
+        index[a] = slice(None)
+        parts.append((np.ascontiguousarray(t.real)[tuple(index)], np.ascontiguousarray(t.imag)[tuple(index)]))
+
+    def mul(xr, xi, yr, yi):
+        rr, ii, ri, ir = xr * yr, xi * yi, xr * yi, xi * yr
+        return rr - ii, ri + ir
+    with np.errstate(invalid="ignore", over="ignore"):
+        ar, ai = mul(*parts[0], *parts[1])
+        pr, pi = mul(ar, ai, *parts[2])
+        qr, qi = mul(pr, pi, K.real.astype(np.float64), K.imag.astype(np.float64))
+        out = np.empty(K.shape, K.dtype)
+        out.real = 0.5 * (S.real.astype(np.float64) + qr)
+        out.imag = 0.5 * (S.imag.astype(np.float64) + qi)
+    return out
+
+
 def _compensation_tables(compensation, shape):
     lengths = (shape[0], shape[1], shape[2] // 2 + 1)
     tabs = [None] * 3 if compensation is None else list(compensation)
