@@ -16,17 +16,16 @@ evaluated per cell inside the first FFT pass of one fused GPU pipeline
 ``save_potential=True`` needs it.
 
 Out of scope here (host-only side-cars of the reference):
-``calculate_lensing_potential`` and ``plot_slice``.
+``plot_slice``.
 """
 from __future__ import annotations
 
 import functools
-import os
 
 import numpy as np
 
-from . import cosmotools, powertools, transform
-from . import random as rf_random
+from . import _backends, powertools, transform
+from ._backends import _DevicePotential, _RegeneratedPotential  # noqa: F401  (hip-backend objects, importable from here as before)
 
 __all__ = ["Generator"]
 
@@ -43,61 +42,9 @@ def _replaces_kspace(method):
     """a Generator method that may write the k buffer: the spectrum of the last interlaced paint is gone (``source='kspace'``)"""
     @functools.wraps(method)
     def wrapper(self, *args, **kwargs):
-        self._interlaced = None
+        self._backend.interlaced = None
         return method(self, *args, **kwargs)
     return wrapper
-
-
-class _DevicePotential(object):
-    """Marker for a saved delta(k)/k**2 field that lives in device memory."""
-
-    def __init__(self, generator):
-        self._generator = generator
-
-    def download(self):
-        """Host copy (nx, ny, nz/2+1) of the saved potential."""
-        dev = self._generator.plan_c2r.device
-        self._generator._interlaced = None
-        dev.load_potential(1.0)
-        return dev.download_k()
-
-
-class _RegeneratedPotential(object):
-    """The saved potential of a ``generate_delta_field(save_potential=True)`` call that was NOT written to memory: the native
-    generator is keyed by (seed, cell) and the replayed reference stream stays resident on the device, so delta(k)/k**2 is
-    formed again inside the generation pass when :meth:`Generator.calculate_newtonian_potential` asks for it
-    (rf_realise_scaled_potential) -- the default call writes 20 instead of 28 B/cell and the later transform reads nothing."""
-
-    def __init__(self, generator, seed, noise):
-        self._generator, self.seed, self.noise = generator, seed, noise
-        dev = generator.plan_c2r.device
-        # the device state this potential is a function of: the power / k tables, and (replayed stream) the resident deviates
-        self._epochs = (dev.power_epoch, dev.noise_epoch if noise is not None else None)
-
-    def check_current(self):
-        """Raise unless the device plan still holds what the delta field was made from.  The reference's stored
-        ``self.potential`` cannot change behind the caller's back; a regenerated one could, if somebody replaced the resident
-        deviates (``reference_noise``, a same-seed batch, host deviates) or the power tables (``set_power``) through
-        ``plan_c2r.device`` in between -- the result would silently belong to another field."""
-        dev = self._generator.plan_c2r.device
-        now = (dev.power_epoch, dev.noise_epoch if self.noise is not None else None)
-        if now != self._epochs:
-            what = "power / k tables" if now[0] != self._epochs[0] else "resident deviates"
-            raise RuntimeError("The saved potential of the last generate_delta_field() call can no longer be formed: the device "
-                               "plan's {0} have changed since.  Generate the field again, or use "
-                               "Generator(store_potential=True) to keep delta(k)/k**2 in memory.".format(what))
-
-    def download(self):
-        """Host copy (nx, ny, nz/2+1) of the potential.  Runs the storing form of the call (rf_realise_potential) with the same
-        seed.  Side effect: the plan's FIELD buffer is overwritten with the delta field of that seed again -- whatever
-        ``convert_delta_to_density`` / ``calculate_newtonian_potential`` had left there is gone (download the field first)."""
-        self.check_current()
-        dev = self._generator.plan_c2r.device
-        self._generator._interlaced = None
-        dev.realise_potential(self.seed, self.noise)
-        dev.load_potential(1.0)
-        self._generator._field_on_host = False
-        return dev.download_k()
 
 
 class Generator(object):
@@ -191,20 +138,17 @@ class Generator(object):
                 chunks = 1
             if self.plan_c2r.device.nranks > 1 and chunks > 1:
                 self.plan_c2r.device.set_exchange_chunks(chunks)
-            # generate.py:79-80: the forward plan over the same memory (here: this rank's window of the field in, its kz planes out)
-            self.plan_r2c = self.plan_c2r.create_reverse_plan(reuse_output=True, overwrite=True)
         else:
             self.plan_c2r = transform.Plan(shape=(nx, ny, nz), dtype_in=dtype, packed=True, overwrite=True,
                                            inverse=True, use_pyfftw=True, backend=self.backend)
-            self.plan_r2c = self.plan_c2r.create_reverse_plan(reuse_output=True, overwrite=True)
+        # generate.py:79-80: the forward plan over the same memory (a distributed rank: its window of the field in, its kz planes out)
+        self.plan_r2c = self.plan_c2r.create_reverse_plan(reuse_output=True, overwrite=True)
         self.grid_spacing_Mpc_h = grid_spacing_Mpc_h
         self.k_min, self.k_max = powertools.get_k_bounds(self.plan_c2r.data_in, grid_spacing_Mpc_h, packed=True)
         self.potential = None
-        self._lpt2 = None                   # second-order potential of the current field: the array (numpy) / its potential object (hip)
-        self._particles = None              # particle displacements: the (3, nx, ny, nz) array (numpy) / True once the device buffer is filled (hip)
-        self._interlaced = None             # the spectrum of the last interlaced paint: the complex128 array (numpy) / True (hip: in the k buffer)
-        self._gathered = None               # gathered values: the (3, nx, ny, nz) array (numpy) / True once a gather has run (hip)
         self.particles_dropped = 0
+        # (everything that touches the field, and what of it is kept between calls: _backends.py)
+        self._backend = _backends.HipBackend(self) if self.backend == "hip" else _backends.NumpyBackend(self)
 
         if nz % num_plot_sections != 0:
             raise ValueError("Z-axis does not evenly divided into {0} plot sections.".format(num_plot_sections))
@@ -236,7 +180,6 @@ class Generator(object):
 
         self.delta_field_rms = None
         self.smoothed_power = None
-        self._field_on_host = False
         if self.backend == "hip":
             dev = self.plan_c2r.device
             dev.set_kgrid(*powertools.ksq_axes(nx, ny, nz, grid_spacing_Mpc_h))
@@ -258,13 +201,6 @@ class Generator(object):
     def shape(self):
         return self.plan_c2r.shape
 
-    def _native_seed(self, seed):
-        if seed is None:
-            seed = int.from_bytes(os.urandom(8), "little")
-            if self.distributed:
-                seed = self.plan_c2r.agree_on(seed >> 12)          # 52 bits survive the float64 all-reduce
-        return int(seed) & (2 ** 64 - 1)
-
     @_replaces_kspace
     def generate_delta_field(self, smoothing_length_Mpc_h=0., seed=None, save_potential=True, show_plot=False,
                              save_plot_name=None, *, download=True):
@@ -282,109 +218,20 @@ class Generator(object):
         """
         if show_plot or save_plot_name is not None:
             raise NotImplementedError("plot_slice is outside the accelerated path (see DESIGN.md).")
-        nx, ny, nz = self.plan_c2r.shape
-        self.smoothed_power = powertools.filter_power(self.power, smoothing_length_Mpc_h)
-        self._lpt2 = None
-        self._particles = None               # (displacements belong to the field they were made for or set beside)
-        self._gathered = None                # (... and so do the values gathered at them)
-
-        if self.backend == "numpy":
-            data = self.plan_c2r.data_in
-            powertools.fill_with_log10k(data, spacing=self.grid_spacing_Mpc_h, packed=True)
-            powertools.tabulate_sigmas(data, power=self.smoothed_power, spacing=self.grid_spacing_Mpc_h, packed=True)
-            rf_random.randomize(data, seed=seed)
-            transform.symmetrize(data, packed=True)
-            if save_potential:
-                if self.potential is None or isinstance(self.potential, _DevicePotential):
-                    self.potential = np.empty_like(data)
-                self.potential.imag = 0.
-                kx2, ky2, kz2 = powertools.create_ksq_grids(self.potential, spacing=self.grid_spacing_Mpc_h,
-                                                            packed=True)
-                np.add(kx2, ky2, out=self.potential.real, casting="same_kind")
-                np.add(self.potential.real, kz2, out=self.potential.real, casting="same_kind")
-                with np.errstate(divide="ignore"):
-                    np.reciprocal(self.potential.real, out=self.potential.real)
-                self.potential[0, 0, 0] = 0.
-                self.potential *= data
-            else:
-                self.potential = None
-            delta = self.plan_c2r.execute()
-            self.delta_field_rms = np.std(delta.reshape(-1))
-            self._field_on_host = True
-        else:
-            dev = self.plan_c2r.device
-            log10_k, sigma = powertools.sigma_table(self.smoothed_power, (nx, ny, nz), self.grid_spacing_Mpc_h)
-            # same power and smoothing as the tables the device plan holds: nothing to upload (a stream sync and a table rebuild
-            # per call otherwise); the plan itself remembers what it was last given, whoever gave it
-            dev.set_power(log10_k, sigma, if_changed=True)
-            realised = False
-            # generate.py:184-189,230 returns a HOST array, and the device -> host copy is 15 x the realisation at 1024^3: armed with
-            # the plan's host buffer, the realisation below delivers slab by slab behind its z pass (rf_set_host_sink)
-            sink = bool(download) and not self.distributed and dev.arm_host_sink(self.plan_c2r.data_out_padded, padded=True)
-            self._sink_armed = sink
-            if self.rng == "reference":
-                # RandomState(seed).normal (random.py:24): MT19937 + polar method replayed on the GPU from the seed's
-                # 624-word start state -- integer seeds, array seeds (init_by_array) and None alike; no host deviates
-                if seed is None and self.distributed:
-                    seed = self.plan_c2r.agree_on(int.from_bytes(os.urandom(4), "little"))
-                # (a complex64 plan keeps float32 copies of the deviates: its cells sigma * g are float32 anyway)
-                single = self.plan_c2r.data_out.dtype == np.float32
-                if self.distributed and dev.nranks > 1 and dev.tiled and dev.share_segments()[0] >= dev.nranks:
-                    # one stream, P ranks: each replays 1/P of it, one all-to-all of deviates (rf_mt_share_*); the first
-                    # time round under the watchdog that names a rank which never arrived (slab.Deadline)
-                    if getattr(self, "_shared_replay_ran", False):
-                        dev.reference_noise_shared(seed, single=single)
-                    else:
-                        with self.plan_c2r.dist.deadline("first shared replay of the reference stream"):
-                            dev.reference_noise_shared(seed, single=single)
-                        self._shared_replay_ran = True
-                elif (single and not self.distributed and not (save_potential and self.store_potential)
-                      and dev.can_batch_reference()):
-                    # one device call: the replay and the passes queued back to back (no host synchronisation between them,
-                    # untimed passes: the z pass of a slab shares its launch with the y pass of the next) -- a same-seed
-                    # batch of one (rf_realise_batch_reference); the deviates stay resident as float32 pairs
-                    dev.realise_batch_reference([seed], want_rms=False)
-                    realised = True
-                else:
-                    dev.reference_noise(seed, single=single)
-                noise = "resident"
-                dseed = 0
-            else:
-                noise = None
-                dseed = self._native_seed(seed)
-            if save_potential:
-                # generate.py:200-217.  Native noise: delta(k)/k**2 is a second store stream of the generation pass;
-                # otherwise the library runs rows K,T,R,S -> k-space, the division, and the c2r transform.
-                if not self.store_potential and dev.can_regenerate_potential(noise):
-                    # nothing to store: the potential can be formed again from the seed / the resident deviates on demand
-                    if not realised:
-                        self._realise(dev, dseed, noise)
-                    self.potential = _RegeneratedPotential(self, dseed, noise)
-                else:
-                    dev.realise_potential(dseed, noise)
-                    self.potential = _DevicePotential(self)
-            else:
-                if not realised:
-                    self._realise(dev, dseed, noise)    # fused: k-space never materialised
-                self.potential = None
-            mean, std = dev.moments()
-            self.delta_field_rms = self.plan_c2r.data_out.dtype.type(std)
-            self._field_on_host = bool(sink and dev.host_sink_delivered())
-            self._sink_armed = False
-            delta = self.download_field() if download else None
-
-        if self.verbose:
-            print("Delta field has standard deviation {0:.3f}.".format(self.delta_field_rms))
+        self._begin_field(smoothing_length_Mpc_h)
+        delta, rms, self.potential = self._backend.realise_delta(self.smoothed_power, seed, save_potential, download)
+        self._set_rms(rms)
         return delta
 
-    def _realise(self, dev, dseed, noise):
-        """One fused realisation on the device.  Native generator on a single-GPU tiled plan: replayed from a captured
-        one-realisation hipGraph (rf_realise_batch with one seed, read from device memory) -- the call is ~35 kernel launches, and
-        their launch gaps are 5 % of a 1024^3 realisation when issued one by one; everything else issues them eagerly."""
-        if noise is None and not self.distributed and dev.tiled and dev.nranks == 1 and not getattr(self, "_sink_armed", False):
-            dev.realise_batch(np.array([dseed], np.uint64), want_rms=False)       # (a captured graph keeps its field on the device: not with a host sink)
-        else:
-            dev.realise(dseed, noise)
+    def _begin_field(self, smoothing_length_Mpc_h):
+        """every new field: its smoothed power, and nothing left of the particles and the second-order potential of the last one"""
+        self.smoothed_power = powertools.filter_power(self.power, smoothing_length_Mpc_h)
+        self._backend.new_field()
+
+    def _set_rms(self, rms):
+        self.delta_field_rms = self.plan_c2r.data_out.dtype.type(rms)
+        if self.verbose:
+            print("Delta field has standard deviation {0:.3f}.".format(self.delta_field_rms))
 
     @_replaces_kspace
     def generate_density_field(self, smoothing_length_Mpc_h=0., seed=None, *, download=True):
@@ -400,41 +247,22 @@ class Generator(object):
         """
         growth = self._need_table("growth_function")
         density = self._need_table("mean_matter_density")
-        dev = self.plan_c2r.device if self.backend == "hip" else None
-        fused = dev is not None and not self.distributed and dev.nranks == 1 and dev.tiled
-        if not fused:
-            self.generate_delta_field(smoothing_length_Mpc_h, seed, save_potential=False, download=False) if self.backend == "hip" \
-                else self.generate_delta_field(smoothing_length_Mpc_h, seed, save_potential=False)
+        if not self._backend.fused_density:
+            self.generate_delta_field(smoothing_length_Mpc_h, seed, save_potential=False, download=False)
             return self.convert_delta_to_density(apply_lognormal_transform=True, download=download)
-        nx, ny, nz = self.plan_c2r.shape
-        self.smoothed_power = powertools.filter_power(self.power, smoothing_length_Mpc_h)
-        log10_k, sigma = powertools.sigma_table(self.smoothed_power, (nx, ny, nz), self.grid_spacing_Mpc_h)
-        dev.set_power(log10_k, sigma, if_changed=True)
-        tables = (np.asarray(growth, np.float64).tobytes(), np.asarray(density, np.float64).tobytes())
-        if getattr(dev, "_z_tables_key", None) != tables:
-            dev.set_z_tables(growth, density)
-            dev._z_tables_key = tables
-        if self.rng == "reference":
-            dev.reference_noise(seed, single=self.plan_c2r.data_out.dtype == np.float32)
-            rms = dev.realise_lognormal(0, "resident")
-        else:
-            rms = dev.realise_lognormal(self._native_seed(seed), None)
+        self._begin_field(smoothing_length_Mpc_h)
+        rms = self._backend.realise_density(self.smoothed_power, growth, density, seed)
         self.potential = None
-        self._lpt2 = None
-        self._particles = None               # (displacements belong to the field they were made for or set beside)
-        self._gathered = None                # (... and so do the values gathered at them)
-        self.delta_field_rms = self.plan_c2r.data_out.dtype.type(rms)
-        self._field_on_host = False
-        if self.verbose:
-            print("Delta field has standard deviation {0:.3f}.".format(self.delta_field_rms))
+        self._set_rms(rms)
         return self.download_field() if download else None
 
     def download_field(self):
         """Copy the device-resident field into the plan's host buffer and return the view."""
-        if self.backend == "hip" and not self._field_on_host:
-            self.plan_c2r.device.download_real(self.plan_c2r.data_out_padded, padded=True)
-            self._field_on_host = True
-        return self.plan_c2r.data_out
+        return self._backend.field_to_host()
+
+    @property
+    def _field_on_host(self):
+        return self._backend.field_on_host
 
     def measure_power_spectrum(self, field=None, *, k_edges=None, nbins=None, window=None, source="field"):
         """
@@ -477,12 +305,8 @@ class Generator(object):
             out = np.empty(len(res), [("k", float), ("Pk", float), ("nmodes", np.uint64)])
             out["k"], out["Pk"], out["nmodes"] = res["k"], res["P0"], res["nmodes"]
             return out
-        shape, k_edges = self._power_inputs(field, k_edges, nbins)
-        if self.backend == "numpy":
-            sums = powertools.bin_power(self._numpy_spectrum(source), self.grid_spacing_Mpc_h, k_edges)
-        else:
-            from . import _hip
-            sums = self.plan_c2r.device.measure_power(k_edges, self._hip_source(source))
+        shape, k_edges = self._power_inputs(field, k_edges, nbins, source)
+        sums = self._backend.binned_sums(k_edges, source)
         return powertools.power_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
 
     def measure_power_multipoles(self, field=None, *, los=2, k_edges=None, nbins=None, window=None, source="field"):
@@ -509,12 +333,8 @@ class Generator(object):
             window = powertools.window_compensation(tuple(self.plan_c2r.shape), window)
         elif window is not None:
             window = powertools._compensation_tables(window, tuple(self.plan_c2r.shape))
-        shape, k_edges = self._power_inputs(field, k_edges, nbins)
-        if self.backend == "numpy":
-            sums = powertools.bin_multipoles(self._numpy_spectrum(source), self.grid_spacing_Mpc_h, k_edges, los, window)
-        else:
-            from . import _hip
-            sums = self.plan_c2r.device.measure_multipoles(k_edges, los, self._hip_source(source), window)
+        shape, k_edges = self._power_inputs(field, k_edges, nbins, source)
+        sums = self._backend.binned_sums(k_edges, source, los, window)
         return powertools.multipole_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
 
     def _check_source(self, field, source):
@@ -523,25 +343,11 @@ class Generator(object):
         if source == "kspace":
             if field is not None:
                 raise ValueError("source='kspace' measures the spectrum of the last interlaced paint: it takes no field.")
-            if self._interlaced is None:
+            if self._backend.interlaced is None:
                 raise RuntimeError("No interlaced spectrum: call paint_particles(interlaced=True) first (a later call that writes "
                                    "the k buffer replaces it).")
 
-    def _numpy_spectrum(self, source):
-        """the half spectrum a numpy-backend measurement bins"""
-        if source == "kspace":
-            return self._interlaced
-        self._interlaced = None                  # (as on the hip backend: one rule for both)
-        return np.fft.rfftn(np.asarray(self.plan_c2r.data_out, np.float64), axes=(0, 1, 2))
-
-    def _hip_source(self, source):
-        from . import _hip
-        if source == "kspace":
-            return _hip.RF_POWER_FROM_KSPACE
-        self._interlaced = None                  # (generic plans leave the field's spectrum in the k buffer; tiled ones follow the same rule)
-        return _hip.RF_POWER_FROM_FIELD
-
-    def _power_inputs(self, field, k_edges, nbins):
+    def _power_inputs(self, field, k_edges, nbins, source):
         """the edges of a power spectrum measurement, and ``field`` (if given) made the current field: (shape, k_edges)"""
         shape = tuple(self.plan_c2r.shape)
         if k_edges is None:
@@ -551,6 +357,10 @@ class Generator(object):
             raise ValueError("k_edges must have nbins + 1 entries.")
         if field is not None:
             self._make_current(field)
+        if source == "field":
+            # one rule for both backends and every grid: the device transforms the field into the k buffer on grids that are no power
+            # of two, so the spectrum of the last interlaced paint is gone
+            self._backend.interlaced = None
         return shape, k_edges
 
     def _make_current(self, field):
@@ -559,10 +369,16 @@ class Generator(object):
         field = np.asarray(field)
         if field.shape != shape:
             raise ValueError("field must have the shape {0}.".format(shape))
-        self.plan_c2r.data_out[...] = field
-        self._field_on_host = True
-        if self.backend == "hip":
-            self.plan_c2r.device.upload_real(self.plan_c2r.data_out_padded, padded=True)
+        self._backend.make_current(field)
+
+    def _need_particles(self):
+        if self._backend.particles is None:
+            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+
+    @staticmethod
+    def _check_slot(slot):
+        if slot not in (0, 1, 2):
+            raise ValueError("Invalid slot: {0!r} (expected 0, 1 or 2).".format(slot))
 
     def _need_table(self, name):
         value = getattr(self, name)
@@ -586,25 +402,7 @@ class Generator(object):
             raise RuntimeError("No delta field has been generated.")
         growth = self._need_table("growth_function")
         density = self._need_table("mean_matter_density")
-        nz = self.plan_c2r.shape[2]
-        if self.backend == "numpy":
-            delta = self.plan_c2r.data_out
-            if apply_lognormal_transform:
-                delta = cosmotools.apply_lognormal_transform(delta, growth, sigma=self.delta_field_rms)
-            else:
-                delta *= growth
-                delta += 1
-            delta *= density
-            return delta
-        dev = self.plan_c2r.device
-        if apply_lognormal_transform:
-            a_z, b_z = cosmotools.lognormal_tables(growth, self.delta_field_rms, nz)
-            dev.lognormal(a_z, b_z, float(self.delta_field_rms))
-        else:
-            dev.affine_z(growth, 1.0)
-        dev.scale_z(density)
-        self._field_on_host = False
-        return self.download_field() if download else None
+        return self._backend.delta_to_density(growth, density, self.delta_field_rms, apply_lognormal_transform, download)
 
     @_replaces_kspace
     def calculate_newtonian_potential(self, light_cone=True, show_plot=False, save_plot_name=None, *,
@@ -626,29 +424,10 @@ class Generator(object):
                 raise RuntimeError("calculate_newtonian_potential needs scale= (or a cosmology= object with Om0).")
             H0 = 100.0 / 3.0856775814913673e19          # 100 km/s/Mpc in 1/s
             scale = -1.5 * H0 ** 2 * float(om0)
-        factor = None
+        growth = redshifts = None
         if light_cone:
-            factor = self._need_table("growth_function") / (1 + self._need_table("redshifts"))
-        if self.backend == "numpy":
-            self.plan_c2r.data_in[:] = self.potential
-            self.plan_c2r.data_in *= scale
-            field = self.plan_c2r.execute()
-            if light_cone:
-                field *= self._need_table("growth_function")
-                field /= 1 + self._need_table("redshifts")
-            return field
-        dev = self.plan_c2r.device
-        if isinstance(self.potential, _RegeneratedPotential):
-            self.potential.check_current()
-            dev.realise_scaled_potential(self.potential.seed, self.potential.noise, scale, factor_z=factor)
-            factor = None           # (applied by the z pass itself)
-        else:
-            dev.load_potential(scale)
-            dev.execute_c2r()
-        if factor is not None:
-            dev.scale_z(factor)
-        self._field_on_host = False
-        return self.download_field() if download else None
+            growth, redshifts = self._need_table("growth_function"), self._need_table("redshifts")
+        return self._backend.newtonian(self.potential, scale, growth, redshifts, download)
 
     @_replaces_kspace
     def calculate_displacement_field(self, axis, light_cone=False, *, order=1, scale=1.0, factor_z=None, download=True):
@@ -691,99 +470,24 @@ class Generator(object):
             raise NotImplementedError("calculate_displacement_field runs on single-GPU plans (distributed=False).")
         if self.potential is None:
             raise RuntimeError("No saved potential field.")
-        if isinstance(axis, str):
-            if axis not in ("x", "y", "z"):
-                raise ValueError("Invalid axis: {0!r} (expected 0, 1, 2, 'x', 'y' or 'z').".format(axis))
+        if isinstance(axis, str) and axis in ("x", "y", "z"):
             axis = "xyz".index(axis)
         if axis not in (0, 1, 2):
             raise ValueError("Invalid axis: {0!r} (expected 0, 1, 2, 'x', 'y' or 'z').".format(axis))
         axis = int(axis)
         shape = self.plan_c2r.shape
-        nz = shape[2]
         if factor_z is not None:
-            factor = np.asarray(factor_z, float).reshape(nz)
+            factor = np.asarray(factor_z, float).reshape(shape[2])
         elif light_cone:
             factor = self._need_table("growth_function")
+            if order == 2:
+                factor = factor * factor
         else:
             factor = None
         dk = 2 * np.pi / (shape[axis] * self.grid_spacing_Mpc_h)
-        if order == 2:
-            if factor_z is None and light_cone:
-                factor = factor * factor
-            return self._second_order_displacement(axis, dk, scale, factor, download)
-        if self.backend == "numpy":
-            n = shape[axis]
-            m = np.arange(nz // 2 + 1) if axis == 2 else np.fft.fftfreq(n, 1.0 / n)
-            m = np.where(np.abs(m) == n // 2, 0.0, m)          # the axis' Nyquist mode (n is even: transform.Plan accepts nothing else)
-            # (the factor is rounded to the array's COMPLEX type here, where the device rounds the real factor once and multiplies the
-            # two parts -- rf_core.h grad_cell; both are two roundings per component, the fields agree to a few float32 ulp)
-            ik = (1j * scale * dk * m).reshape([-1 if a == axis else 1 for a in range(3)])
-            self.plan_c2r.data_in[:] = self.potential
-            self.plan_c2r.data_in *= ik.astype(self.plan_c2r.data_in.dtype)
-            field = self.plan_c2r.execute()
-            if factor is not None:
-                field *= factor
-            return field
-        from . import _hip
-        dev = self.plan_c2r.device
-        if isinstance(self.potential, _RegeneratedPotential):
-            self.potential.check_current()
-            if self.potential.noise is None:
-                dev.generate(self.potential.seed, None)                      # delta(k) again: one generation sweep
-                dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_KSPACE)
-            else:
-                # the replayed reference stream is resident as float32 pairs, which only the fused generation pass reads (rf_generate
-                # wants float64 deviates): run the storing form of the call once, as _RegeneratedPotential.download() does -- the field
-                # buffer is about to be overwritten anyway -- and keep what it stored for the other components
-                dev.realise_potential(self.potential.seed, self.potential.noise)
-                self.potential = _DevicePotential(self)
-                dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_POTENTIAL)
-        else:
-            dev.execute_gradient(axis, scale, dk, _hip.RF_GRAD_FROM_POTENTIAL)
-        if factor is not None:
-            dev.scale_z(factor)
-        self._field_on_host = False
-        return self.download_field() if download else None
-
-    # ---- second order (2LPT) ------------------------------------------------
-    def _dk3(self):
-        return [2 * np.pi / (n * self.grid_spacing_Mpc_h) for n in self.plan_c2r.shape]
-
-    def _modes(self, axis):
-        """signed mode numbers along ``axis`` of the half spectrum (broadcastable), 0 at the axis' Nyquist index"""
-        shape = self.plan_c2r.shape
-        n = shape[axis]
-        m = np.arange(shape[2] // 2 + 1, dtype=float) if axis == 2 else np.fft.fftfreq(n, 1.0 / n)
-        m = np.where(np.abs(m) == n // 2, 0.0, m)
-        return m.reshape([-1 if a == axis else 1 for a in range(3)])
-
-    def _lpt2_source_numpy(self):
-        """S(x) in the plan's real type (a new array): the six Hessian components through the plan's own inverse transform, the
-        factor rounded to the array's complex type as the first-order branch rounds its own"""
-        dk3 = self._dk3()
-        ctype = self.plan_c2r.data_in.dtype
-        H = {}
-        for a in range(3):
-            for b in range(a, 3):
-                f = -(dk3[a] * self._modes(a)) * (dk3[b] * self._modes(b))
-                self.plan_c2r.data_in[:] = self.potential
-                self.plan_c2r.data_in *= (f + 0j).astype(ctype)
-                H[a, b] = self.plan_c2r.execute().copy()
-        S = H[0, 0] * H[1, 1]
-        S += (H[0, 0] + H[1, 1]) * H[2, 2]
-        for ab in ((0, 1), (0, 2), (1, 2)):
-            S -= H[ab] * H[ab]
-        return S
-
-    def _stored_device_potential(self):
-        """hip backend: the potential in device memory -- a regenerated one is stored by running the storing form of the realisation
-        once (as the rng='reference' branch of the first-order method)"""
-        dev = self.plan_c2r.device
-        if isinstance(self.potential, _RegeneratedPotential):
-            self.potential.check_current()
-            dev.realise_potential(self.potential.seed, self.potential.noise)
-            self.potential = _DevicePotential(self)
-        return dev
+        # (second order: the 3/7 and the square of the first order's coefficient)
+        coeff = scale if order == 1 else 3.0 / 7.0 * float(scale) ** 2
+        return self._backend.gradient(order, axis, coeff, dk, factor, download)
 
     @_replaces_kspace
     def lpt2_source(self, download=True):
@@ -796,45 +500,7 @@ class Generator(object):
             raise NotImplementedError("lpt2_source runs on single-GPU plans (distributed=False).")
         if self.potential is None:
             raise RuntimeError("No saved potential field.")
-        if self.backend == "numpy":
-            self.plan_c2r.data_out[...] = self._lpt2_source_numpy()
-            self._field_on_host = True
-            return self.plan_c2r.data_out
-        dev = self._stored_device_potential()
-        self._lpt2 = None                          # (the accumulators take the second-order potential's memory)
-        dev.lpt2_source(self._dk3())
-        self._field_on_host = False
-        return self.download_field() if download else None
-
-    @_replaces_kspace
-    def _second_order_displacement(self, axis, dk, scale, factor, download):
-        shape = self.plan_c2r.shape
-        scale2 = 3.0 / 7.0 * float(scale) ** 2
-        if self.backend == "numpy":
-            if self._lpt2 is None:
-                kx2, ky2, kz2 = (np.asarray(a, np.float64) for a in powertools.ksq_axes(*shape, self.grid_spacing_Mpc_h))
-                k2 = (kx2[:, None, None] + ky2[None, :, None]) + kz2[None, None, :]
-                k2[0, 0, 0] = 1.0
-                phi2 = np.fft.rfftn(np.asarray(self._lpt2_source_numpy(), np.float64), axes=(0, 1, 2)) / k2
-                phi2[0, 0, 0] = 0.0
-                self._lpt2 = phi2.astype(self.plan_c2r.data_in.dtype)
-            ik = 1j * scale2 * dk * self._modes(axis)
-            self.plan_c2r.data_in[:] = self._lpt2
-            self.plan_c2r.data_in *= ik.astype(self.plan_c2r.data_in.dtype)
-            field = self.plan_c2r.execute()
-            if factor is not None:
-                field *= factor
-            return field
-        from . import _hip
-        dev = self._stored_device_potential()
-        if self._lpt2 is not self.potential or not dev.lpt2_valid:
-            dev.lpt2_potential(self._dk3())
-            self._lpt2 = self.potential
-        dev.execute_gradient(axis, scale2, dk, _hip.RF_GRAD_FROM_POTENTIAL2)
-        if factor is not None:
-            dev.scale_z(factor)
-        self._field_on_host = False
-        return self.download_field() if download else None
+        return self._backend.lpt2_source(download)
 
     # ---- particles: the displaced lattice and its cloud-in-cell paint ---------
     def particle_displacements(self, order=2, D1=1.0, download=True, *, rsd_axis=None, f1=0.0, f2=None):
@@ -856,29 +522,17 @@ class Generator(object):
             raise ValueError("Invalid order: {0!r} (expected 1 or 2).".format(order))
         if rsd_axis is not None and rsd_axis not in (0, 1, 2):
             raise ValueError("Invalid rsd_axis: {0!r} (expected None, 0, 1 or 2).".format(rsd_axis))
-        rtype = self.plan_c2r.data_out.dtype.type
         d1, d2 = float(D1), float(D1) * float(D1)
         coeffs = [(d1, d2)] * 3
         if rsd_axis is not None:
             g1 = float(f1)
             g2 = 2.0 * g1 if f2 is None else float(f2)
             coeffs[rsd_axis] = (d1 * (1.0 + g1), d2 * (1.0 + g2))
-        if self.backend == "numpy":
-            Q = np.empty((3,) + tuple(self.plan_c2r.shape), rtype)
-            for axis in range(3):
-                Q[axis] = rtype(coeffs[axis][0]) * self.calculate_displacement_field(axis, order=1)
-                if order == 2:
-                    Q[axis] += rtype(coeffs[axis][1]) * self.calculate_displacement_field(axis, order=2)
-            self._particles = Q
-            return self._download_particles() if download else None
         for axis in range(3):
-            self.calculate_displacement_field(axis, order=1, download=False)
-            dev = self.plan_c2r.device
-            dev.particles_accumulate(axis, coeffs[axis][0], first=True)
-            if order == 2:
-                self.calculate_displacement_field(axis, order=2, download=False)
-                dev.particles_accumulate(axis, coeffs[axis][1], first=False)
-        self._particles = True
+            for n in range(order):
+                self.calculate_displacement_field(axis, order=n + 1, download=False)
+                self._backend.accumulate_displacement(axis, coeffs[axis][n], first=n == 0)
+        self._backend.displacements_complete()
         return self._download_particles() if download else None
 
     def set_particle_displacements(self, s):
@@ -889,20 +543,11 @@ class Generator(object):
         s = np.asarray(s)
         if s.shape != (3,) + tuple(self.plan_c2r.shape):
             raise ValueError("displacements must have the shape {0}.".format((3,) + tuple(self.plan_c2r.shape)))
-        s = np.ascontiguousarray(s, self.plan_c2r.data_out.dtype)
-        if self.backend == "numpy":
-            self._particles = s.copy()
-            return
-        for axis in range(3):
-            self.plan_c2r.device.particles_upload(axis, s[axis])
-        self._particles = True
+        self._backend.set_displacements(np.ascontiguousarray(s, self.plan_c2r.data_out.dtype))
 
     def _download_particles(self):
-        if self._particles is None:
-            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
-        if self.backend == "numpy":
-            return self._particles.copy()              # (a new array on both backends)
-        return np.stack([self.plan_c2r.device.particles_download(axis) for axis in range(3)])
+        self._need_particles()
+        return self._backend.download_displacements()
 
     def particle_positions(self):
         """float64 ``(3, nx, ny, nz)``: (q h + s) mod L per axis, q the lattice index, h the grid spacing, L = n h the box length."""
@@ -938,42 +583,12 @@ class Generator(object):
         ``rfftn`` / ``irfftn`` in float64 on the two deltas as rounded to the plan's real type.
         """
         order = _assignment_order(assignment)
-        if self._particles is None:
-            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+        self._need_particles()
         inv_h = [1.0 / float(self.grid_spacing_Mpc_h)] * 3
-        self._interlaced = None
-        if interlaced:
-            return self._paint_interlaced(inv_h, order, download)
-        if self.backend == "numpy":
-            from . import particles
-            A, self.particles_dropped = particles.paint_counts(self._particles, inv_h, order)
-            self.plan_c2r.data_out[...] = particles.counts_to_delta(A, self.plan_c2r.data_out.dtype)
-            self._field_on_host = True
-            return self.plan_c2r.data_out if download else None
-        self.particles_dropped = self.plan_c2r.device.particles_paint(inv_h, order)
-        self._field_on_host = False
+        self._backend.interlaced = None
+        tables = powertools.interlace_phases(tuple(self.plan_c2r.shape)) if interlaced else None
+        self.particles_dropped = self._backend.paint(inv_h, order, tables)
         return self.download_field() if download else None
-
-    def _paint_interlaced(self, inv_h, order, download):
-        shape = tuple(self.plan_c2r.shape)
-        tables = powertools.interlace_phases(shape)
-        if self.backend == "hip":
-            self.particles_dropped = self.plan_c2r.device.particles_paint_interlaced(inv_h, order, tables)
-            self._interlaced = True
-            self._field_on_host = False
-            return self.download_field() if download else None
-        from . import particles
-        rtype = self.plan_c2r.data_out.dtype
-        spectra = []
-        for half in (False, True):
-            A, dropped = particles.paint_counts(self._particles, inv_h, order, half_cell=half)
-            spectra.append(np.fft.rfftn(particles.counts_to_delta(A, rtype).astype(np.float64), axes=(0, 1, 2)))
-            if not half:
-                self.particles_dropped = dropped
-        self._interlaced = powertools.interlace_combine(spectra[0], spectra[1], tables)
-        self.plan_c2r.data_out[...] = np.fft.irfftn(self._interlaced, s=shape, axes=(0, 1, 2))
-        self._field_on_host = True
-        return self.plan_c2r.data_out if download else None
 
     def interpolate_at_particles(self, field=None, *, slot=0, coeff=1.0, first=True, download=True, assignment="cic"):
         """
@@ -999,23 +614,13 @@ class Generator(object):
         order = _assignment_order(assignment)
         if self.distributed:
             raise NotImplementedError("particles live on single-GPU plans (distributed=False).")
-        if slot not in (0, 1, 2):
-            raise ValueError("Invalid slot: {0!r} (expected 0, 1 or 2).".format(slot))
-        if self._particles is None:
-            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
+        self._check_slot(slot)
+        self._need_particles()
         if field is not None:
             self._make_current(field)                            # (as measure_power_spectrum(field=...) does)
         inv_h = [1.0 / float(self.grid_spacing_Mpc_h)] * 3
-        if self.backend == "numpy":
-            from . import particles
-            if self._gathered is None:
-                self._gathered = np.zeros((3,) + tuple(self.plan_c2r.shape), self.plan_c2r.data_out.dtype)
-            _, self.particles_dropped = particles.gather(self._particles, inv_h, self.plan_c2r.data_out, coeff, first, self._gathered[slot], order)
-            return self._gathered[slot].copy() if download else None
-        dev = self.plan_c2r.device
-        self.particles_dropped = dev.particles_gather(inv_h, slot, coeff, first, order)
-        self._gathered = True
-        return dev.particles_gather_download(slot) if download else None
+        self.particles_dropped, values = self._backend.gather(inv_h, slot, coeff, first, order, download)
+        return values
 
     def shift_particles(self, axis, slot=None, coeff=1.0):
         """Move the particles along ``axis`` by the gathered values: ``s[axis] += coeff * G[slot]`` (``slot=None``: the slot of the
@@ -1023,17 +628,11 @@ class Generator(object):
         if axis not in (0, 1, 2):
             raise ValueError("Invalid axis: {0!r} (expected 0, 1 or 2).".format(axis))
         slot = axis if slot is None else slot
-        if slot not in (0, 1, 2):
-            raise ValueError("Invalid slot: {0!r} (expected 0, 1 or 2).".format(slot))
-        if self._particles is None:
-            raise RuntimeError("No particle displacements: call particle_displacements() or set_particle_displacements() first.")
-        if self._gathered is None:
+        self._check_slot(slot)
+        self._need_particles()
+        if self._backend.gathered is None:
             raise RuntimeError("No gathered values: call interpolate_at_particles() first.")
-        if self.backend == "numpy":
-            rtype = self.plan_c2r.data_out.dtype.type
-            self._particles[axis] += rtype(coeff) * self._gathered[slot]
-            return
-        self.plan_c2r.device.particles_shift(axis, slot, coeff)
+        self._backend.shift(axis, slot, coeff)
 
     @_replaces_kspace
     def calculate_lensing_potential(self, i_min=None, show_plot=False, save_plot_name=None):
@@ -1066,20 +665,7 @@ class Generator(object):
             cosK = np.ones_like(DA, dtype=float)
         cotK = np.ones_like(cosK)
         cotK[1:] = cosK[1:] / DA[1:]
-        if self.backend == "numpy":
-            dPhi = self.plan_c2r.data_out
-            psi = np.empty_like(dPhi)
-            h = float(self.grid_spacing_Mpc_h)
-            for i in range(nDC, i_min, -1):
-                psi[:, :, i_min:i] = dPhi[:, :, i_min:i]
-                psi[:, :, i_min:i] *= -2 * (cotK[i_min:i] - cotK[i - 1])
-                psi[:, :, i - 1] = cosmotools.simps_avg(psi[:, :, i_min:i], h)
-            if i_min > 0:
-                psi[:, :, :i_min] = 0.
-            return psi
-        dev = self.plan_c2r.device
-        dev.lensing_potential(cotK, self.grid_spacing_Mpc_h, i_min)
-        return dev.download_aux()
+        return self._backend.lensing(cotK, i_min)
 
     def plot_slice(self, *args, **kwargs):
         raise NotImplementedError("plot_slice is outside the accelerated path (see DESIGN.md).")

@@ -2561,3 +2561,32 @@ def test_host_sink_delivers_the_field_slab_by_slab(hip, dpower, shape, dtype):
             c = gen.generate_delta_field(seed=11, save_potential=True)      # the default call
             assert np.array_equal(c, a)
             gen.plan_c2r.device.close()
+
+
+def test_failed_realisation_leaves_no_host_sink_armed(hip, monkeypatch):
+    """generate_delta_field arms the host sink before the realisation: if that raises (here a Python exception from a replaced
+    ``dev.realise``; nothing fails on the GPU), the plan is disarmed again -- the next call that keeps its field on the device
+    must not deliver into the old host buffer, and its field is the one a fresh Generator makes, bit for bit."""
+    from randomfield_amd import Generator
+    shape, seed = (16, 16, 16), 21
+    gen = Generator(*shape, SPACING, rng="native")
+    dev = gen.plan_c2r.device
+
+    def failing(*args, **kwargs):
+        raise RuntimeError("realise failed")
+    fresh = Generator(*shape, SPACING, rng="native")
+    want = fresh.generate_delta_field(seed=seed, save_potential=False).copy()
+    for ask_the_plan in (True, False):          # (asking disarms by itself: the second round leaves that to the Generator alone)
+        with monkeypatch.context() as m:
+            m.setattr(dev, "realise", failing)
+            with pytest.raises(RuntimeError, match="realise failed"):
+                gen.generate_delta_field(seed=seed)                      # (download=True: the sink is armed, so the call takes dev.realise)
+        if ask_the_plan:
+            assert not dev.host_sink_delivered()
+        gen.plan_c2r.data_out_padded[...] = np.nan
+        assert gen.generate_delta_field(seed=seed, save_potential=False, download=False) is None
+        assert not gen._field_on_host and np.isnan(gen.plan_c2r.data_out_padded).all()
+        got = gen.download_field()
+        assert np.array_equal(got, want) and got.std() > 0
+    for g in (gen, fresh):
+        g.plan_c2r.device.close()
