@@ -940,6 +940,27 @@ int c2r_lognormal_impl(int nx, int ny, int nz, const cplx<T>* kspace, const doub
   });
 }
 
+// rf_realise_scaled_potential(factor_z) behind its generation pass, on an uploaded k-space array: x and y passes plain, the z pass with
+// the per-z factor in its store (ScaleZRowIO), the row configuration from for_rows as launch_row_c2r_zscale takes it
+template <typename T>
+int c2r_zscale_impl(int nx, int ny, int nz, const cplx<T>* kspace, const double* factor_z, cplx<T>* W, double* s1, double* s2) {
+  const long long nzc = nz / 2;
+  const GenColIO<T> gio = gen_col_io<T>(W, x_geom(ny, nzc), kspace_params(nx, ny, nz), kspace, 0, (int)nzc);
+  if (int rc = dispatch_col<T, +1, GenColIO<T>, GenSel>(nx, gio, (long long)ny * nzc)) return rc;
+  if (int rc = plain_col_pass<T, +1>(ny, W, y_geom(ny, nzc), (long long)nx * nzc)) return rc;
+  auto tw = make_twiddles<T>(2 * (int)nzc);
+  return for_rows(sizeof(T) == 8, (int)nzc, -1, [&](auto r, auto c) {
+    using C = typename decltype(c)::type;
+    if constexpr (std::is_same<typename decltype(r)::type, T>::value) {
+      ScaleZRowIO<T> io; io.base = W; io.scale = (T)(1.0 / ((double)nx * ny * nz)); io.M_of = (int)nzc; io.Sz = factor_z;
+      run_row_c2r<C, ScaleZRowIO<T>>(io, (long long)nx * ny, tw.data(), s1, s2);
+      return 0;
+    } else {
+      return -1;
+    }
+  });
+}
+
 // The loop behind emu_measure_power and emu_measure_multipoles (rf_core.h power_load / bin_cell over an array in array order, as the
 // device sweep's cells).  g arrives cleared but for the estimator's own fields; edges: nbins + 1 edges in k, squared here as the host
 // side of the device calls squares them.
@@ -1180,6 +1201,28 @@ int emu_c2r_lognormal(int f64, int nx, int ny, int nz, const void* kspace, const
                       double* sigma_out, double* s1, double* s2) {
   return f64 ? c2r_lognormal_impl<double>(nx, ny, nz, (const cplx<double>*)kspace, growth, density, (cplx<double>*)W, sigma_out, s1, s2)
              : c2r_lognormal_impl<float>(nx, ny, nz, (const cplx<float>*)kspace, growth, density, (cplx<float>*)W, sigma_out, s1, s2);
+}
+
+int emu_c2r_zscale(int f64, int nx, int ny, int nz, const void* kspace, const double* factor_z, void* W, double* s1, double* s2) {
+  return f64 ? c2r_zscale_impl<double>(nx, ny, nz, (const cplx<double>*)kspace, factor_z, (cplx<double>*)W, s1, s2)
+             : c2r_zscale_impl<float>(nx, ny, nz, (const cplx<float>*)kspace, factor_z, (cplx<float>*)W, s1, s2);
+}
+// exp_scaled64 by itself on n arguments (units of ln2 / 64).  stride 1: on rf_exp2_tab, as LognormalRowIO<double, 0> reads it; stride 18
+// (LognormalRowIO<double, 1>::ESTRIDE): on the copy that IO's own stage() leaves in the pad slots of a tile of rows of 512 complex128,
+// every other double of that tile NaN
+int emu_exp_scaled64(const double* t, double* out, long long n, int stride) {
+  using IO = LognormalRowIO<double, 1>;
+  if (stride == 1) {
+    for (long long i = 0; i < n; ++i) out[i] = exp_scaled64<1>(t[i], rf_exp2_tab);
+    return 0;
+  }
+  if (stride != IO::ESTRIDE) return -1;
+  using C = RowSel<double, 512>::type;
+  std::vector<double> lds((size_t)C::LDS_BYTES / sizeof(double), std::nan(""));
+  IO io{};
+  for (int tid = 0; tid < C::NT; ++tid) io.stage<C>(tid, lds.data());
+  for (long long i = 0; i < n; ++i) out[i] = exp_scaled64<IO::ESTRIDE>(t[i], io.etab);
+  return 0;
 }
 
 // fused realisation with the fast native generation (float32 arithmetic; f64 != 0: float64 plan, values widened);

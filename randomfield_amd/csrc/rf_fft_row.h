@@ -198,8 +198,10 @@ RF_HD double exp_t(double x) { return exp(x); }
 // correctly rounded), the last a degree-4 polynomial (|r| <= 0.0055: the first dropped term is 4e-14; round 4: degree 5).  11 float64-rate instructions
 // and one ds_read_b64 per element where the library's exp takes ~22 (no table: a degree-11 polynomial, range checks); the z pass of a
 // float64 plan issues 16 of them per thread.  |error| <= 4e-14 relative (the dropped term) + 1 ulp of the result + the rounding of t
-// (ulp(t) ln2 / 128 <= 6e-16 at |x| = 5.5, the same size as the rounding of the product delta * Ap that both forms share).  Out-of-range arguments saturate through
-// the conversion and ldexp (inf / 0), NaN propagates through r.
+// (ulp(t) ln2 / 128 <= 6e-16 at |x| = 5.5, the same size as the rounding of the product delta * Ap that both forms share).  FINITE out-of-range arguments saturate through
+// the conversion and ldexp (inf / 0); NaN propagates through f, and so does an INFINITE argument: rint(t) = t, f = inf - inf = NaN, so
+// exp_scaled64(+-inf) is NaN where libm's exp gives inf / 0 (the tables of the map are finite: delta * Ap is infinite only if delta is).
+// tests/test_emulator_epilogue_matrix.py pins the error bound over the whole finite range and these edge values.
 #if defined(__HIP_DEVICE_COMPILE__)
 static __device__ const double rf_exp2_tab[64] = {RF_EXP2_TAB_VALUES};
 #else

@@ -36,8 +36,18 @@ hipError_t tile_launch(long long grid, int nt, int lds_bytes, hipStream_t s, A..
 }
 
 inline bool pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
-// dynamic LDS of a strided pass: the tile and its twiddles + the IO's own tables
-template <class C, class IO> constexpr int lds_of() { return C::LDS_BYTES + IO::LDS_EXTRA; }
+// dynamic LDS of a strided pass: the tile and its twiddles + the IO's own tables -- and never less than the NT / 64 doubles through
+// which an IO with a finish() step (AccColIO) adds up its waves at the start of the workgroup's LDS (rf_kernels.h col_body): the
+// one-pass configurations (lengths 8 and 16) have no tile, and with no LDS at all the partial sums were dropped -- every tile's
+// Parseval partial, and so the sigma of rf_realise_lognormal, came out 0 on plans with ny = 8 or 16
+template <class IO, class = void> struct io_finish_bytes { static constexpr int of(int) { return 0; } };
+template <class IO> struct io_finish_bytes<IO, typename std::enable_if<IO::HAS_FINISH>::type> {
+  static constexpr int of(int nthreads) { return nthreads / 64 * (int)sizeof(double); }
+};
+template <class C, class IO> constexpr int lds_of() {
+  constexpr int pass = C::LDS_BYTES + IO::LDS_EXTRA, red = io_finish_bytes<IO>::of(C::NT);
+  return pass > red ? pass : red;
+}
 
 // a run of preparations that stops at the first failure
 struct Prepare {

@@ -80,6 +80,52 @@ def c2r(kspace):
     return out, s1.value, s2.value
 
 
+def c2r_lognormal(kspace, growth, density=None):
+    """rf_realise_lognormal behind its generation pass: (rho, sigma, sum, sum of squares) -- the accumulating y pass (AccColIO), the
+    tables from its sigma, the map in the z pass's store (LognormalRowIO)"""
+    nx, ny, nzh = kspace.shape
+    nz = 2 * (nzh - 1)
+    rt = np.float32 if kspace.dtype == np.complex64 else np.float64
+    out = np.empty((nx, ny, nz), rt)
+    sig, s1, s2 = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    ks = np.ascontiguousarray(kspace)
+    growth = np.ascontiguousarray(growth, np.float64)
+    density = None if density is None else np.ascontiguousarray(density, np.float64)
+    assert growth.shape == (nz,) and (density is None or density.shape == (nz,))
+    rc = lib().emu_c2r_lognormal(int(kspace.dtype == np.complex128), nx, ny, nz, ks.ctypes.data_as(ctypes.c_void_p), _dp(growth), _dp(density),
+                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(sig), ctypes.byref(s1), ctypes.byref(s2))
+    assert rc == 0, rc
+    return out, sig.value, s1.value, s2.value
+
+
+def c2r_zscale(kspace, factor_z):
+    """c2r with plane z times factor_z[z] in the z pass's store (ScaleZRowIO): (field, sum, sum of squares)"""
+    nx, ny, nzh = kspace.shape
+    nz = 2 * (nzh - 1)
+    rt = np.float32 if kspace.dtype == np.complex64 else np.float64
+    out = np.empty((nx, ny, nz), rt)
+    s1, s2 = ctypes.c_double(), ctypes.c_double()
+    ks = np.ascontiguousarray(kspace)
+    fz = np.ascontiguousarray(factor_z, np.float64)
+    assert fz.shape == (nz,)
+    rc = lib().emu_c2r_zscale(int(kspace.dtype == np.complex128), nx, ny, nz, ks.ctypes.data_as(ctypes.c_void_p), _dp(fz),
+                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(s1), ctypes.byref(s2))
+    assert rc == 0, rc
+    return out, s1.value, s2.value
+
+
+def exp_scaled64(t, stride=1):
+    """exp_scaled64 (rf_fft_row.h) of arguments in units of ln2 / 64: stride 1 on rf_exp2_tab, 18 on the copy LognormalRowIO<double, 1>
+    stages into the pad slots of its tile"""
+    t = np.ascontiguousarray(t, np.float64)
+    out = np.empty_like(t)
+    f = lib().emu_exp_scaled64
+    f.argtypes = [_c_dp, _c_dp, ctypes.c_longlong, ctypes.c_int]
+    rc = f(_dp(t), _dp(out), t.size, int(stride))
+    assert rc == 0, rc
+    return out
+
+
 def col_fft(data, N, direction, ncols, inner, outer_stride, row_stride):
     f = lib().emu_col_fft
     f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_longlong] * 4

@@ -772,6 +772,42 @@ def test_lensing_potential_kernel_against_oracle(hip, shape):
         plan.close()
 
 
+@pytest.mark.parametrize("ct", [np.complex64, np.complex128], ids=["c64", "c128"])
+@pytest.mark.parametrize("nz", [6, 22, 130, 258, 300, 1000])
+def test_lensing_potential_kernel_on_generic_row_lengths(hip, nz, ct):
+    """lensing_kernel's guarded scalar route: rows that are no whole number of 64-lane segments (256 float32 / 128 float64
+    samples) -- shorter than one, one or several and a partial one, and rows of nz = 2 (mod 4) samples, whose starts are not
+    16-byte aligned -- flat and curved, with i_min at the row's start, inside the first segment, inside the second where
+    the row has two, and on the last two samples.  Against the oracle at the tolerances of the test above."""
+    shape = (6, 10, nz)
+    dtype, tol = (np.float32, 2e-6) if ct == np.complex64 else (np.float64, 1e-12)
+    seg = 64 * (16 // np.dtype(dtype).itemsize)
+    spacing = 2.5
+    DC = np.arange(nz) * spacing
+    DA = DC * (1 + 0.02 * np.arange(nz) / nz)
+    i_mins = {0, 3, nz - 2, nz - 1}
+    if nz > seg:
+        inside_second = seg + min(5, nz - seg - 1)
+        assert seg <= inside_second < min(nz, 2 * seg)
+        i_mins.add(inside_second)
+    phi = np.random.RandomState(nz).normal(size=shape).astype(dtype)
+    plan = hip.DevicePlan(*shape, ct)
+    assert nz % seg != 0 and not plan.tiled
+    plan.upload_real(phi)
+    for K in (0.0, -3e-8, 2e-8):
+        cot = cpu_ref.cot_k(DC, DA, K)
+        for i_min in sorted(i_mins):
+            plan.lensing_potential(cot, spacing, i_min)
+            psi = plan.download_aux()
+            ref = cpu_ref.lensing_potential(phi, DC, DA, K=K, i_min=i_min)
+            assert psi.dtype == dtype and psi.shape == shape
+            err, scale = float(np.max(np.abs(psi - ref))), float(np.max(np.abs(ref)))
+            print("lensing %s %s K = %g, i_min = %d: measured / bound = %.3g" % (shape, dtype.__name__, K, i_min, err / (tol * scale + 1e-300)))
+            assert err <= tol * scale + 1e-300, (K, i_min)
+            assert np.array_equal(plan.download_real(), phi)               # the input field is untouched
+    plan.close()
+
+
 def test_generator_lensing_potential(hip):
     """The drop-in sequence generate_delta_field(save_potential=True) -> calculate_newtonian_potential ->
     calculate_lensing_potential on the GPU against the oracle applied to the downloaded Newtonian potential."""
@@ -1539,6 +1575,32 @@ def test_generic_shape_plans(hip):
     ref = (f.astype(np.float64) * np.exp(-z) + 1) * (1 + z)
     assert np.max(np.abs(dp.download_real() - ref)) <= 1e-5 * np.abs(ref).max()
     dp.close()
+    # the same three maps on a float64 plan of that shape (vectors of two doubles) and on a float32 generic plan whose nz % 4 == 0
+    # selects the 4-wide kernels.  lognormal: relative 1e-12 (float64: test_config5_float64_lognormal_full_size's bound for
+    # rf_lognormal) / 1e-5 (float32: the bound above).  affine_z then scale_z against the float64 expression: each call rounds its
+    # result once to the plan's dtype, float32 plans round the table entry and the product besides -- under 2.5 eps of the largest
+    # magnitude in all; the bound is 4 eps
+    for shape, ct, ln_tol in (((10, 14, 22), np.complex128, 1e-12), ((12, 10, 20), np.complex64, 1e-5)):
+        nz = shape[2]
+        dp = hip.DevicePlan(*shape, ct)
+        rt = dp.real_dtype.type
+        assert not dp.tiled and (nz % 4 == 0) == (ct == np.complex64)
+        f = np.random.RandomState(nz).normal(size=shape).astype(rt)          # (a stream of its own: the plans below keep their inputs)
+        z = np.linspace(0, 0.1, nz)
+        dp.upload_real(f, padded=False)
+        dp.lognormal(*cosmotools.lognormal_tables(np.exp(-z), 1.5, nz), 1.5)
+        ref = cpu_ref.lognormal(f.copy(), np.exp(-z), sigma=rt(1.5))
+        got = dp.download_real()
+        assert got.dtype == rt and got.shape == shape and np.max(np.abs(got - ref) / ref) <= ln_tol
+        dp.upload_real(f, padded=False)
+        dp.affine_z(np.exp(-z), 1.0)
+        ref = f.astype(np.float64) * np.exp(-z) + 1
+        got = dp.download_real()
+        assert got.dtype == rt and np.max(np.abs(got - ref)) <= 4 * np.finfo(rt).eps * np.abs(ref).max()
+        dp.scale_z(1 + z)
+        ref = ref * (1 + z)
+        assert np.max(np.abs(dp.download_real() - ref)) <= 4 * np.finfo(rt).eps * np.abs(ref).max()
+        dp.close()
     for shape in ((4, 6, 8), (40, 60, 80), (10, 14, 22), (12, 18, 6)):
         nx, ny, nz = shape
         for ct, tol in ((np.complex64, 2e-6), (np.complex128, 1e-14)):
