@@ -80,7 +80,7 @@ int ensure_g(rf_plan* p) { RF_HIP(p->G.reserve(p->k_bytes)); return 0; }
 // can gather (whole workgroups per x block and iy, whole segments per thread group).
 int xpose_row_block(const rf_plan* p) { return col_gen_row_block(p->f64, p->nx, 64); }      // x rows per block of the transposed intermediate
 bool xpose_ok(const rf_plan* p) {
-  if (!p->xposed || p->generic || p->unpacked || p->nranks > 1 || p->force_slab) return false;
+  if (!p->xposed || !route(p).single()) return false;
   return xpose_shape_ok(p->f64, p->nx, p->ny, p->nzl, p->nzc, xpose_row_block(p));
 }
 int ensure_x(rf_plan* p) {
@@ -214,17 +214,15 @@ int build_fast(rf_plan* p) {
   return 0;
 }
 
+// bytes of a sub-slab of the exchange in the field buffer (one sub-slab: the whole kz slab)
+size_t chunk_bytes(const rf_plan* p) { return p->w_bytes / (size_t)route(p).chunks; }
+
 // x pass (generation or API k-space fused into its load) into buffer W on stream sx
 // Replicated-generation mode of a multi-rank plan (RF_FLAG_REPLICATED_GENERATION): the native generator is keyed by
 // the global cell index and the x pass reads nothing, so a rank can generate ALL of k space on the fly, run the
 // full x-FFT and store only its own x slab [rank*nxl, (rank+1)*nxl); the y and z passes are then local and no
 // all-to-all is needed (only the 2-double all-reduce of the moments).  It trades P-fold redundant x-pass arithmetic
 // for the exchange: a win when the exchange is slower than (P-1) x passes -- 2 GPUs share ONE xGMI link.
-// sub-slabs of the exchange (1: the whole kz slab at once); only plans that exchange have them
-int slab_chunks(const rf_plan* p) {
-  return (p->xchunks > 1 && (p->nranks > 1 || p->force_slab) && !p->replicate && !p->generic && !p->unpacked) ? p->xchunks : 1;
-}
-size_t chunk_bytes(const rf_plan* p) { return p->w_bytes / (size_t)slab_chunks(p); }
 
 // (kz0c, nzlc >= 0: a sub-slab of this rank's planes instead of all of them -- W then points at the sub-slab's own region)
 // (tl: the fast generation's kz = 0 tiles are rf_kernel_ms's entry 4; the caller marks the end of the pass)
@@ -232,12 +230,12 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   // resident deviates (the numpy stream replayed by rf_noise_mt19937) take the fast float32 sigma path too; host-supplied
   // deviates (RF_NOISE_EXTERNAL, the parity mode) keep the exact reference dtype chain
   // (float32 copies of the deviates exist for this path only, and it can store the potential too; float64 ones cannot)
+  const bool rep = route(p).replicates();
   const bool fast_noise = !kspace && gp.noise_mode == NOISE_EXTERNAL && cd.resident_fast && p->have_fast && !p->exact_gen &&
-                          !p->f64 && !(p->replicate && p->nranks > 1) && (p->has.deviates32() || !cd.pot_target);
+                          !p->f64 && !rep && (p->has.deviates32() || !cd.pot_target);
   RF_REQUIRE(kspace || gp.noise_mode != NOISE_EXTERNAL || fast_noise || p->has.deviates64(),
              "only float32 copies of the deviates are resident: this path (exact chain / float64 plan) needs rf_noise_mt19937's float64 ones");
   const bool fast = (!kspace && gp.noise_mode == NOISE_PHILOX && p->have_fast && !p->exact_gen) || fast_noise;
-  const bool rep = p->replicate && p->nranks > 1;
   RF_REQUIRE(!rep || fast, "replicated generation needs the native generator (fast path)");
   const long long nzl = nzlc >= 0 ? nzlc : (rep ? p->nzc : p->nzl);     // kz planes generated by this call (nz/2 on one GPU)
   const int kz0 = kz0c >= 0 ? kz0c : (rep ? 0 : p->kz0);
@@ -263,15 +261,10 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   return 0;
 }
 
-// Does this plan exchange by storing its y pass's output straight into the peers' receive buffers (rf_plan.h `direct`)?
-bool direct_active(const rf_plan* p) {
-  return p->direct && (p->nranks > 1 || p->force_slab) && !p->replicate && !p->generic && !p->unpacked;
-}
-
 // The device table of destination bases the storing y pass reads (rf_fft.h DirectColIO): for receive buffer b, sub-slab c and
 // destination rank h, cell `off` of block h of the local sub-slab lands at  R_h + (rank * C + c) * blk_c + off  =  tab + h * blk_c + off.
 int rebuild_peer_tab(rf_plan* p) {
-  const int C = slab_chunks(p), P = p->nranks;
+  const int C = route(p).chunks, P = p->nranks;
   RF_REQUIRE((int)p->peer_R[0].size() == P && (int)p->peer_R[1].size() == P, "direct exchange: the peers' receive buffers are not known");
   RF_REQUIRE(col_direct_supported(p->f64, p->ny, p->nzl / C),
              "direct exchange: a y-pass tile would straddle two x planes (nz / (2 ranks chunks) is narrower than the tile)");
@@ -301,7 +294,7 @@ int direct_barrier(rf_plan* p, hipStream_t s) {
 
 // the y pass of sub-slab c (the whole kz slab when the plan does not chunk) out of W into the peers' receive buffers number `rbuf`
 int queue_y_direct(rf_plan* p, const void* W, int rbuf, hipStream_t s, int c) {
-  const int C = slab_chunks(p);
+  const int C = route(p).chunks;
   RF_REQUIRE(p->peer_tab.get() && p->peer_tab_chunks == C && c >= 0 && c < C, "direct exchange: the destination table does not match the plan's exchange chunks");
   RF_REQUIRE(p->peer_R[rbuf][p->rank] != nullptr, "direct exchange: the second receive buffer does not exist");
   const long long nzc_ = p->nzl / C;
@@ -313,47 +306,48 @@ int queue_y_direct(rf_plan* p, const void* W, int rbuf, hipStream_t s, int c) {
   return 0;
 }
 
-// The forward half of a plan in direct mode: sub-slab by sub-slab the x pass on stream A and the storing y pass on stream Y (Y == A: one
-// stream; Y != A: the stores of sub-slab c -- link-bound on a real job -- run beside the x pass of sub-slab c + 1).  The caller has
-// put the barrier that frees the receive buffers in front of it on Y.  tl (Y == A or sub-slabs): the marks of queue_xy; in sub-slabs the
-// whole forward half is the x entry (Y != A: the stores are still running on Y -- the x passes' end stands for both, as in the chunked rccl path).
-int direct_forward(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, int rbuf, hipStream_t A, hipStream_t Y, Timeline* tl) {
-  const int C = slab_chunks(p);
-  const long long nzc_ = p->nzl / C;
-  if (Y != A) RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
-  for (int c = 0; c < C; ++c) {
-    if (C == 1) { if (int rc = queue_x(p, cd, gp, kspace, W, A, tl)) return rc; }
-    else if (int rc = queue_x(p, cd, gp, kspace, (char*)W + (size_t)c * chunk_bytes(p), A, nullptr, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
-    if (C == 1) RF_HIP(mark(tl, rft::X, A));
-    if (Y != A) RF_HIP(hop(p->chunk_ev[c], A, Y));
-    if (int rc = queue_y_direct(p, W, rbuf, Y, c)) return rc;
-  }
-  RF_HIP(mark(tl, C == 1 ? rft::Y : rft::X, A));
-  return 0;
-}
+int queue_exchange_rccl(rf_plan* p, const void* W, void* R, hipStream_t s, int chunk = -1, bool plain = false);
 
-// x pass (generation or API k-space fused into its load) + y pass of buffer W on stream s, with a mark behind either.
-// the forward half of ONE sub-slab c of a plan that exchanges in chunks: x pass + y pass on its nzl / xchunks planes (region c of W)
-int queue_xy_chunk(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, int c) {
-  const int C = slab_chunks(p);
-  const long long nzc_ = p->nzl / C;
-  char* Wc = (char*)W + (size_t)c * chunk_bytes(p);
-  if (int rc = queue_x(p, cd, gp, kspace, Wc, s, nullptr, p->kz0 + c * (int)nzc_, (int)nzc_)) return rc;
+// The forward half of a plan that exchanges, sub-slab by sub-slab (one sub-slab: the whole kz slab), W -> receive buffers.  Per sub-slab c:
+// the x pass on A into region c of W, then either the storing y pass on E into the peers' receive buffers number `rbuf` (r.direct), or the
+// plain y pass in place on A and, where the caller hands over the receive buffer R, the sub-slab's grouped send / receive on E.
+// E != A: what goes to E follows the x / y pass of its sub-slab behind chunk_ev[c] and runs beside the x pass of sub-slab c + 1 (the stores
+// and the sends are link-bound on a real job); the caller has put E behind whatever frees the receive buffers.
+// tl: one sub-slab marks the x entry behind the x pass and the y entry behind the y pass; in sub-slabs the whole forward half is the x
+// entry (E != A: E is still busy -- the x passes' end stands for both).
+int queue_forward(rf_plan* p, const Route& r, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, int rbuf, void* R,
+                  hipStream_t A, hipStream_t E, Timeline* tl) {
+  const int C = r.chunks, nzc_ = p->nzl / C;
   const ColGeom gy{nzc_, (long long)p->ny * nzc_, nzc_};
-  RF_HIP(launch_col_plain(p->f64, p->ny, +1, Wc, gy, (long long)p->nx * nzc_, p->tw_y.ptr, s));
+  if (E != A) RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
+  for (int c = 0; c < C; ++c) {
+    char* Wc = (char*)W + (size_t)c * chunk_bytes(p);
+    if (C == 1) { if (int rc = queue_x(p, cd, gp, kspace, W, A, tl)) return rc; }
+    else if (int rc = queue_x(p, cd, gp, kspace, Wc, A, nullptr, p->kz0 + c * nzc_, nzc_)) return rc;
+    if (C == 1) RF_HIP(mark(tl, rft::X, A));
+    if (r.direct) {
+      if (E != A) RF_HIP(hop(p->chunk_ev[c], A, E));
+      if (int rc = queue_y_direct(p, W, rbuf, E, c)) return rc;
+    } else {
+      RF_HIP(launch_col_plain(p->f64, p->ny, +1, Wc, gy, (long long)p->nx * nzc_, p->tw_y.ptr, A));
+    }
+    if (C == 1) RF_HIP(mark(tl, rft::Y, A));
+    if (!r.direct && R) {
+      if (E != A) RF_HIP(hop(p->chunk_ev[c], A, E));
+      if (int rc = queue_exchange_rccl(p, W, R, E, c)) return rc;
+    }
+  }
+  if (C > 1) RF_HIP(mark(tl, rft::X, A));
   return 0;
 }
 
-// (a plan in direct mode: the y pass stores into the peers' receive buffers `rbuf`, and what follows is the z pass, not an exchange)
+// x pass (generation or API k-space fused into its load) + y pass of buffer W on stream s, with a mark behind either: the forward half
+// without its exchange (the step-wise rf_slab_forward*, the batches).  A plan in direct mode stores into the peers' receive buffers
+// `rbuf`, and what follows is the z pass, not an exchange.
 int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, Timeline* tl, int rbuf) {
-  if (direct_active(p)) return direct_forward(p, cd, gp, kspace, W, rbuf, s, s, tl);
-  if (slab_chunks(p) > 1) {
-    for (int c = 0; c < slab_chunks(p); ++c)
-      if (int rc = queue_xy_chunk(p, cd, gp, kspace, W, s, c)) return rc;
-    RF_HIP(mark(tl, rft::X, s));             // (sub-slabs: the whole forward half is the x entry)
-    return 0;
-  }
-  const bool rep = p->replicate && p->nranks > 1;
+  const Route r = route(p);
+  if (r.exchanges()) return queue_forward(p, r, cd, gp, kspace, W, rbuf, nullptr, s, s, tl);
+  const bool rep = r.replicates();
   const long long nzl = rep ? p->nzc : p->nzl, nxp = rep ? p->nxl : p->nx;      // the local array is [nxp][ny][nzl]
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
   if (int rc = queue_x(p, cd, gp, kspace, W, s, tl)) return rc;
@@ -367,7 +361,7 @@ int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ks
 // (dense real [nxl][ny][nz]) into W, then the local (sum, sumsq)
 int queue_z_slab(rf_plan* p, const void* R, void* W, double* stats_out, hipStream_t s) {
   const long long nrows = (long long)p->nxl * p->ny;
-  const long long nzseg = p->nzl / slab_chunks(p);            // planes per received segment: nranks * chunks of them make a row
+  const long long nzseg = p->nzl / route(p).chunks;            // planes per received segment: nranks * chunks of them make a row
   RF_HIP(launch_row_c2r_gather(p->f64, p->nzc, R, W, nrows, inv_cells(p), (int)nzseg, nrows * nzseg, p->tw_z.ptr, p->partials.get(), s));
   RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
   p->has.field_gathered(W);
@@ -388,9 +382,9 @@ int replicated_z(rf_plan* p, int slot, int allreduce, Timeline* tl) {
 // [x in slab h][all y][kz in slab g], which is contiguous in W because x is the slowest axis.
 // (chunk >= 0: sub-slab `chunk` only -- RF_FLAG_EXCHANGE_CHUNKS; -1: everything, all chunks of a chunked plan in ONE group;
 // plain = true: the unchunked block layout whatever the flag says, as the forward transform's reverse exchange uses it)
-int queue_exchange_rccl(rf_plan* p, const void* W, void* R, hipStream_t s, int chunk = -1, bool plain = false) {
+int queue_exchange_rccl(rf_plan* p, const void* W, void* R, hipStream_t s, int chunk, bool plain) {
   RF_REQUIRE(p->nranks == 1 || p->comm != nullptr || p->standin_wg > 0, "rf_comm_init has not been called on this multi-rank plan");
-  const int C = plain ? 1 : slab_chunks(p);
+  const int C = plain ? 1 : route(p).chunks;
   const size_t blk = (size_t)p->nxl * p->ny * p->nzl * p->csize / (size_t)C, cb = p->w_bytes / (size_t)C;
   const int c0 = chunk >= 0 ? chunk : 0, c1 = chunk >= 0 ? chunk + 1 : C;
   // block h of sub-slab c of W -> segment (this rank, c) of rank h's R
@@ -438,6 +432,21 @@ int ensure_batch_buffers(rf_plan* p) {
   return 0;
 }
 
+// What both pipelined batches end with, the last z pass being queued on A: the moments of all n realisations in ONE all-reduce on S, the
+// stream that drives the communicator inside the batch (S != A: behind the last z pass's event, and A waits for it through `back`); the
+// call's end; the last field in the buffer of its turn -- or none, after a stand-in (this rank's own data lies in the segments)
+int batch_tail(rf_plan* p, int n, hipStream_t A, hipStream_t S, hipEvent_t z_done, hipEvent_t back, void* last, bool standin) {
+  if (p->nranks > 1 && p->comm) {        // (no communicator: a virtual rank under a stand-in, local moments only)
+    if (S != A) RF_HIP(hipStreamWaitEvent(S, z_done, 0));
+    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, S));
+    if (S != A) RF_HIP(hop(back, S, A));
+  }
+  RF_HIP(p->tl.end(A));
+  p->has.field_ready(last, n - 1);
+  if (standin) p->has.not_a_field();
+  return 0;
+}
+
 // Pipelined batch of a plan in direct mode.  The y pass of realisation i stores into the PEERS' receive buffers i % 2 -- it is the
 // exchange, and on a real job it runs at the speed of the links -- so it goes to the exchange stream Y, where it runs beside the z pass of
 // realisation i - 1 and the x pass of realisation i + 1 on the compute stream A; B(i), a tiny all-reduce on Y, tells every rank that
@@ -448,11 +457,11 @@ int ensure_batch_buffers(rf_plan* p) {
 // z(i) waits for B(i): every peer's stores of realisation i have landed; x(i + 2), which overwrites the send buffer y(i) read, follows
 // z(i) on A.  The local HBM traffic is that of the passes alone: no send-side reads, no receive-side writes by copy kernels.
 // (direct_overlap = 0: everything on A in the order x(i) y(i) z(i - 1) B(i).)
-int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
+int slab_batch_direct(rf_plan* p, const Route& r, const uint64_t* seeds, int n) {
   RF_REQUIRE(p->nranks == 1 || p->comm || p->direct_standin, "virtual ranks linked for the direct exchange run step by step (rf_slab_forward, rf_slab_backward)");
   void* Wb[2] = {p->W.ptr, p->W2.ptr};
   void* Rb[2] = {p->R.ptr, p->R2.ptr};
-  const hipEvent_t *ev_fwd = p->pev.ev.data(), *ev_bar = ev_fwd + 2, *ev_z = ev_fwd + 4;
+  const hipEvent_t *ev_bar = p->pev.ev.data() + 2, *ev_z = ev_bar + 2;
   const bool two = p->direct_overlap != 0;
   hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
   RF_HIP(p->tl.begin(A, false));
@@ -462,8 +471,7 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
     const int b = i & 1, pb = (i - 1) & 1;
     if (i < n) {
       // (sub-slab by sub-slab when the plan chunks: x(c) on A, the stores of sub-slab c on Y behind an event)
-      if (int rc = direct_forward(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, A, Y, nullptr)) return rc;
-      (void)ev_fwd;
+      if (int rc = queue_forward(p, r, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, nullptr, A, Y, nullptr)) return rc;
     }
     if (i >= 1) {
       if (two) RF_HIP(hipStreamWaitEvent(A, ev_bar[pb], 0));
@@ -476,16 +484,8 @@ int slab_batch_direct(rf_plan* p, const uint64_t* seeds, int n) {
       if (two) RF_HIP(hipEventRecord(ev_bar[b], Y));
     }
   }
-  if (p->nranks > 1 && p->comm) {                                 // the moments of all n realisations: one all-reduce, on the stream that drives the communicator
-    const int lb = (n - 1) & 1;
-    if (two) RF_HIP(hipStreamWaitEvent(Y, ev_z[lb], 0));
-    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, Y));
-    if (two) RF_HIP(hop(ev_bar[lb], Y, A));
-  }
-  RF_HIP(p->tl.end(A));
-  p->has.field_ready(Wb[(n - 1) & 1], n - 1);                     // the last field lies in the buffer of its turn
-  if (p->direct_standin) p->has.not_a_field();                    // (the stores went to this rank's own buffers)
-  return 0;
+  const int lb = (n - 1) & 1;
+  return batch_tail(p, n, A, Y, ev_z[lb], ev_bar[lb], Wb[lb], p->direct_standin);
 }
 
 // room for the (sum, sumsq) pairs of n realisations (captured batch graphs carry the array's address: they go)
@@ -502,10 +502,11 @@ int ensure_stats(rf_plan* p, int n) {
 //   compute: x,y(0) | x,y(1)   z(0) | x,y(2)   z(1) | ...            (in order on p->stream)
 //   exchange:        | exch(0)       | exch(1)       | ...            (in order on p->comm_stream)
 // z(i) waits for exch(i); exch(i) waits for x,y(i) and -- because it overwrites R[i%2] -- for z(i-2).
-// One all-reduce of all n (sum, sumsq) pairs at the end.
-int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
+// One all-reduce of all n (sum, sumsq) pairs at the end, on the exchange stream too: ONE communicator is only ever driven from ONE
+// stream inside a batch.
+int slab_batch(rf_plan* p, const Route& r, const uint64_t* seeds, int n) {
   if (int rc = ensure_stats(p, n)) return rc;
-  if (p->replicate && p->nranks > 1) {          // no exchange to overlap: realisations back to back, one all-reduce at the end
+  if (r.replicates()) {          // no exchange to overlap: realisations back to back, one all-reduce at the end
     RF_HIP(p->tl.begin(p->stream, false));
     for (int i = 0; i < n; ++i) {
       if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W.ptr, p->stream, nullptr)) return rc;
@@ -516,7 +517,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
     return 0;
   }
   if (int rc = ensure_batch_buffers(p)) return rc;
-  if (direct_active(p)) return slab_batch_direct(p, seeds, n);
+  if (r.direct) return slab_batch_direct(p, r, seeds, n);
   void* Wb[2] = {p->W.ptr, p->W2.ptr};
   void* Rb[2] = {p->R.ptr, p->R2.ptr};
   const hipEvent_t *ev_fwd = p->pev.ev.data(), *ev_exch = ev_fwd + 2, *ev_z = ev_fwd + 4;
@@ -525,7 +526,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
   for (int i = 0; i <= n; ++i) {
     if (i < n) {
       const int b = i & 1;
-      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], A, nullptr)) return rc;
+      if (int rc = queue_forward(p, r, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], 0, nullptr, A, A, nullptr)) return rc;
       RF_HIP(hop(ev_fwd[b], A, C));
       if (i >= 2) RF_HIP(hipStreamWaitEvent(C, ev_z[b], 0));          // R[b] still being read by z(i-2)?
       if (int rc = queue_exchange_rccl(p, Wb[b], Rb[b], C)) return rc;
@@ -538,18 +539,8 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
       RF_HIP(hipEventRecord(ev_z[pb], A));
     }
   }
-  if (p->nranks > 1 && p->comm) {        // (no communicator: a virtual rank under rf_slab_set_exchange_standin, local moments only)
-    // ONE communicator is only ever driven from ONE stream inside a batch: the moments' all-reduce goes to the exchange
-    // stream too, behind the last z pass (event), and the compute stream waits for it
-    const int lb = (n - 1) & 1;
-    RF_HIP(hipStreamWaitEvent(C, ev_z[lb], 0));
-    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2 * (size_t)n, ncclFloat64, ncclSum, p->comm, C));
-    RF_HIP(hop(ev_exch[lb], C, A));
-  }
-  RF_HIP(p->tl.end(A));
-  p->has.field_ready(Wb[(n - 1) & 1], n - 1);      // the last field lies in the buffer of its turn
-  if (p->nranks > 1 && !p->comm) p->has.not_a_field();      // (a stand-in exchange leaves this rank's own data in the segments)
-  return 0;
+  const int lb = (n - 1) & 1;
+  return batch_tail(p, n, A, C, ev_z[lb], ev_exch[lb], Wb[lb], p->nranks > 1 && !p->comm);
 }
 
 // x planes per slab of the y / z passes of a single-rank plan (0: whole-grid passes).  The y pass of a slab leaves it in the
@@ -557,7 +548,7 @@ int slab_batch(rf_plan* p, const uint64_t* seeds, int n) {
 // (1024^3 float32, MI355X, 20 realisations per graph: 4.74 ms whole grid, 4.53-4.57 ms with 64-plane = 256 MiB slabs, 4.66 with 56,
 // 4.70 with 72 ... 128, 4.74 with 48, 5.6 ms with 16; 2048^3: 44.5 -> 43.7-43.9 ms; 512^3: 0.545 -> 0.537 ms).
 int yz_slab_planes(const rf_plan* p) {
-  if (p->nranks > 1 || p->force_slab || p->generic || p->unpacked || p->yz_slab == 0) return 0;
+  if (!route(p).single() || p->yz_slab == 0) return 0;
   const long long plane = (long long)p->ny * p->nzl * (long long)p->csize;
   long long B = p->yz_slab;
   if (B < 0) {
@@ -748,103 +739,78 @@ int generic_c2r(rf_plan* p, const void* K, double* stats_out, Timeline* tl, cons
   return 0;
 }
 
-// What the exchanging branches of queue_c2r end with, the receive buffer being complete for stream A: the gathering z pass on A, then
-// the all-reduce of the moments on S, the stream that drives the communicator in this call (S != A: behind an event hop each way)
-// (the timeline: the exchange, the z pass and its moments are the z entry, the all-reduce what is left until the call's end)
-int gather_and_reduce(rf_plan* p, hipStream_t A, hipStream_t S, Timeline* tl) {
-  hipEvent_t ev = S != A ? p->chunk_ev[slab_chunks(p)] : nullptr;
+// ONE realisation / transform of a plan that exchanges, on the plan's stream A and the exchange stream E.  E == A when the kz slab goes
+// as a whole, and for the direct form with direct_overlap == 0; in sub-slabs what crosses the links -- the grouped send / receive of
+// sub-slab c, or its storing y pass -- goes to the exchange stream and runs beside the forward passes of sub-slab c + 1.  Direct: the
+// barrier in front keeps the stores away from a peer that still reads (or, in the forward transform's reverse exchange, sends from) its
+// receive buffer; the one behind tells every rank that all stores have landed.  The communicator is driven from ONE stream per call: E,
+// the all-reduce of the moments too.
+// (the timeline: behind the forward half's marks the exchange, the z pass and its moments are the z entry, the all-reduce what is left)
+int exchange_c2r(rf_plan* p, const Route& r, const CallDesc& cd, const GenParams& gp, const void* kspace, Timeline* tl) {
+  if (r.direct) RF_REQUIRE(p->nranks == 1 || p->comm || p->direct_standin, "virtual ranks linked for the direct exchange run step by step (rf_slab_forward, rf_slab_backward)");
+  const int C = r.chunks;
+  hipStream_t A = p->stream, E = A;
+  if (r.direct || C > 1) {
+    RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
+    RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
+    if (C > 1 && !(r.direct && p->direct_overlap == 0)) E = p->comm_stream;
+  }
+  if (E != A) RF_HIP(hop(p->chunk_ev[C], A, E));               // 1. (whatever used R / the communicator before on the plan's stream)
+  if (r.direct) { if (int rc = direct_barrier(p, E)) return rc; }                                                   // 2.
+  if (int rc = queue_forward(p, r, cd, gp, kspace, p->W.ptr, 0, p->R.ptr, A, E, tl)) return rc;                  // 3.
+  if (r.direct) { if (int rc = direct_barrier(p, E)) return rc; }                                                   // 4.
+  if (E != A) RF_HIP(hop(p->chunk_ev[C], E, A));                                                                   // 5.
+  // 6. the receive buffer is complete for A: the gathering z pass there, then the global (sum, sumsq) -- one 2-double all-reduce on E
   if (int rc = queue_z_slab(p, p->R.ptr, p->W.ptr, p->stats.get(), A)) return rc;
   RF_HIP(mark(tl, rft::Z, A));
-  if (p->nranks > 1 && p->comm) {       // global (sum, sumsq): one 2-double all-reduce
-    if (ev) RF_HIP(hop(ev, A, S));
-    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2, ncclFloat64, ncclSum, p->comm, S));
-    if (ev) RF_HIP(hop(ev, S, A));
+  if (p->nranks > 1 && p->comm) {
+    if (E != A) RF_HIP(hop(p->chunk_ev[C], A, E));
+    RF_NCCL(g_rccl.AllReduce(p->stats.get(), p->stats.get(), 2, ncclFloat64, ncclSum, p->comm, E));
+    if (E != A) RF_HIP(hop(p->chunk_ev[C], E, A));
   }
   RF_HIP(tl->end(A));
   p->has.moments_ready(0);
+  // 7. a stand-in leaves this rank's own data in the segments (direct: the stores went to its own buffers): no field came out
+  if (r.direct ? p->direct_standin : (p->nranks > 1 && !p->comm)) p->has.not_a_field();
   return 0;
 }
 
-// one realisation / transform on the plan's stream into the primary buffer; a timed call: every branch marks its passes and ends the timeline
+// one realisation / transform on the plan's stream into the primary buffer; a timed call: every route marks its passes and ends the timeline
 int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace) {
   Timeline* tl = &p->tl;
   RF_HIP(tl->begin(p->stream, true));
-  if (p->generic) {
-    // per-kernel times (rf_kernel_ms): start | generation launch | EXTRA | x | X | y | Y | contiguous | Z | reduce | end
-    if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->has.deviates64(), "no float64 deviates resident on the device");
-    const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and what it holds stay as they are
-    if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
-      if (int rc = ensure_k(p)) return rc;
-      RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
-      RF_HIP(mark(tl, rft::EXTRA, p->stream));
-      p->has.kspace_ready();
-      kspace = p->K.ptr;
+  const Route r = route(p);
+  switch (r.kind) {
+    case Route::C2C:
+      return fail(1, "this call does not apply to an unpacked c2c plan");        // (every entry point has said so before it came here)
+    case Route::Generic: {
+      // per-kernel times (rf_kernel_ms): start | generation launch | EXTRA | x | X | y | Y | contiguous | Z | reduce | end
+      if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->has.deviates64(), "no float64 deviates resident on the device");
+      const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and what it holds stay as they are
+      if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
+        if (int rc = ensure_k(p)) return rc;
+        RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
+        RF_HIP(mark(tl, rft::EXTRA, p->stream));
+        p->has.kspace_ready();
+        kspace = p->K.ptr;
+      }
+      if (int rc = generic_c2r(p, kspace, p->stats.get(), tl, fused ? &gp : nullptr)) return rc;
+      RF_HIP(tl->end(p->stream));
+      break;
     }
-    if (int rc = generic_c2r(p, kspace, p->stats.get(), tl, fused ? &gp : nullptr)) return rc;
-    RF_HIP(tl->end(p->stream));
-    p->has.field_ready(p->W.ptr, 0);
-    return 0;
+    case Route::Single:          // one GPU: x pass, then the y / z passes (slab by slab on large grids)
+      if (int rc = queue_xyz(p, cd, gp, kspace, p->W.ptr, p->stream, p->stats.get(), tl)) return rc;
+      break;
+    case Route::Replicated:
+      if (int rc = queue_xy(p, cd, gp, kspace, p->W.ptr, p->stream, tl)) return rc;
+      if (int rc = replicated_z(p, 0, 1, tl)) return rc;
+      RF_HIP(tl->end(p->stream));
+      break;
+    case Route::Exchange:
+      return exchange_c2r(p, r, cd, gp, kspace, tl);
   }
-  if (p->nranks == 1 && !p->force_slab) {       // one GPU: x pass, then the y / z passes (slab by slab on large grids)
-    if (int rc = queue_xyz(p, cd, gp, kspace, p->W.ptr, p->stream, p->stats.get(), tl)) return rc;
-    p->has.field_ready(p->W.ptr, 0);
-    return 0;
-  }
-  if (direct_active(p)) {
-    // ONE realisation of a plan in direct mode: the storing y pass is the exchange.  Unchunked: x, B, y, B, z on the plan's stream.  In
-    // sub-slabs: the stores of sub-slab c go to the exchange stream and run beside the x pass of sub-slab c + 1.  The barrier in front
-    // keeps the stores away from a peer that still reads (or, in the forward transform's reverse exchange, sends from) its receive
-    // buffer; the one behind tells every rank that all stores have landed.  The communicator is driven from ONE stream per call.
-    RF_REQUIRE(p->nranks == 1 || p->comm || p->direct_standin, "virtual ranks linked for the direct exchange run step by step (rf_slab_forward, rf_slab_backward)");
-    const int C = slab_chunks(p);
-    const bool two = p->direct_overlap != 0 && C > 1;
-    RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
-    RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
-    hipStream_t A = p->stream, Y = two ? p->comm_stream : p->stream;
-    if (two) RF_HIP(hop(p->chunk_ev[C], A, Y));
-    if (int rc = direct_barrier(p, Y)) return rc;
-    if (int rc = direct_forward(p, cd, gp, kspace, p->W.ptr, 0, A, Y, tl)) return rc;
-    if (int rc = direct_barrier(p, Y)) return rc;
-    if (two) RF_HIP(hop(p->chunk_ev[C], Y, A));
-    if (int rc = gather_and_reduce(p, A, Y, tl)) return rc;
-    if (p->direct_standin) p->has.not_a_field();        // (the stores went to this rank's own buffers: no field came out)
-    return 0;
-  }
-  if (slab_chunks(p) > 1) {
-    // ONE realisation, exchange overlapped with its own forward half: sub-slab c is generated and x / y-transformed on the plan's
-    // stream, its grouped send / receive goes to the exchange stream behind an event, the forward half of sub-slab c + 1 follows
-    // at once; the gathering z pass waits for the last sub-slab's exchange.  (The communicator is driven from the exchange stream
-    // only, the final all-reduce of the moments too.)
-    const int C = slab_chunks(p);
-    RF_HIP(p->comm_stream.create(hipStreamNonBlocking));
-    RF_HIP(p->chunk_ev.ensure(C + 1, hipEventDisableTiming));
-    hipStream_t A = p->stream, X = p->comm_stream;
-    RF_HIP(hop(p->chunk_ev[C], A, X));                         // (whatever used R / the communicator before on the plan's stream)
-    for (int c = 0; c < C; ++c) {
-      if (int rc = queue_xy_chunk(p, cd, gp, kspace, p->W.ptr, A, c)) return rc;
-      RF_HIP(hop(p->chunk_ev[c], A, X));
-      if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, X, c)) return rc;
-    }
-    RF_HIP(mark(tl, rft::X, A));                               // (the whole forward half is the x entry)
-    RF_HIP(hop(p->chunk_ev[C], X, A));
-    if (int rc = gather_and_reduce(p, A, X, tl)) return rc;
-    if (p->nranks > 1 && !p->comm) p->has.not_a_field();        // (stand-in exchange)
-    return 0;
-  }
-  if (int rc = queue_xy(p, cd, gp, kspace, p->W.ptr, p->stream, tl)) return rc;
-  if (p->replicate && p->nranks > 1) {
-    if (int rc = replicated_z(p, 0, 1, tl)) return rc;
-    RF_HIP(tl->end(p->stream));
-    p->has.field_ready(p->W.ptr, 0);
-    return 0;
-  }
-  if (p->nranks > 1 || p->force_slab) {
-    if (int rc = queue_exchange_rccl(p, p->W.ptr, p->R.ptr, p->stream)) return rc;
-    if (int rc = gather_and_reduce(p, p->stream, p->stream, tl)) return rc;
-    if (p->nranks > 1 && !p->comm) p->has.not_a_field();        // (stand-in exchange)
-    return 0;
-  }
-  return fail(1, "queue_c2r: unreachable");
+  p->has.field_ready(p->W.ptr, 0);
+  return 0;
 }
 
 template <typename T> int upload_twiddles(DevBuf<>& dst, int n) {
@@ -1211,7 +1177,7 @@ int rf_execute_c2r(rf_plan* p) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
-  RF_REQUIRE(!(p->replicate && p->nranks > 1), "replicated-generation plans have no distributed k-space buffer");
+  RF_REQUIRE(!route(p).replicates(), "replicated-generation plans have no distributed k-space buffer");
   RF_HIP(hipSetDevice(p->device));
   return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr);
 }
@@ -1278,7 +1244,7 @@ int rf_execute_r2c(rf_plan* p) {
   if (p->nranks > 1) {
     // transform.py:278-301 on x-slab / kz-slab ranks: rows, the all-to-all in the other direction (block g of R -> rank g,
     // arriving as block h of W: the same grouped send / receive with the buffers swapped), columns
-    RF_REQUIRE(!p->generic && !p->replicate, "the multi-rank forward transform runs on the tiled kernels of exchange-mode plans");
+    RF_REQUIRE(route(p).exchanges(), "the multi-rank forward transform runs on the tiled kernels of exchange-mode plans");
     RF_HIP(p->tl.begin(p->stream, false));
     if (int rc = queue_r2c_slab_rows(p, p->stream)) return rc;
     if (int rc = queue_exchange_rccl(p, p->R.ptr, p->W.ptr, p->stream, -1, true)) return rc;
@@ -1313,7 +1279,7 @@ int rf_realise(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
 // scaled copy of that would be.  Needs the fast generation pass (rf_can_regenerate_potential); returns the real field in place of
 // the current one, like rf_load_potential + rf_execute_c2r.
 int rf_can_regenerate_potential(rf_plan* p, int mode) {
-  if (!p || p->unpacked || p->generic || !p->have_fast || p->exact_gen || (p->replicate && p->nranks > 1)) return 0;
+  if (!p || p->unpacked || p->generic || !p->have_fast || p->exact_gen || route(p).replicates()) return 0;
   if (mode == RF_NOISE_NATIVE) return 1;
   if (mode == RF_NOISE_RESIDENT) return (p->has.deviates32() && !p->f64) ? 1 : 0;
   return 0;
@@ -1335,7 +1301,7 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   // (decided from the plan's FLAG: the blocked intermediate X is allocated lazily inside queue_c2r, and its gathering z pass has no
   // per-z factor -- testing p->X here dropped the factor on the first call after RF_FLAG_TRANSPOSED_INTERMEDIATE was set)
   if (int rc = ensure_x(p)) return rc;
-  const bool fuse_z = factor_z && p->nranks == 1 && !p->force_slab && !xpose_ok(p);
+  const bool fuse_z = factor_z && route(p).single() && !xpose_ok(p);
   if (factor_z) RF_HIP(hipMemcpyAsync(p->ztab.get(), factor_z, (size_t)p->nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
   cd.zscale = fuse_z ? p->ztab.get() : nullptr;
   if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
@@ -1374,7 +1340,7 @@ int rms_from_stats(rf_plan* p, int n, double* rms_out) {
 int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_host, bool whole) {
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
   RF_REQUIRE(mode == RF_NOISE_NATIVE || mode == RF_NOISE_EXTERNAL || mode == RF_NOISE_RESIDENT, "invalid noise mode");
-  RF_REQUIRE(!(p->replicate && p->nranks > 1), "replicated-generation plans keep no k-space potential: clear RF_FLAG_REPLICATED_GENERATION");
+  RF_REQUIRE(!route(p).replicates(), "replicated-generation plans keep no k-space potential: clear RF_FLAG_REPLICATED_GENERATION");
   RF_HIP(hipSetDevice(p->device));
   // fused: delta(k) / k^2 is a second store stream of the generation pass -- native generator (float32 and float64 plans)
   // or resident float32 deviates (float32 plans)
@@ -1448,7 +1414,7 @@ static int batch_prepare(rf_plan* p, int n) {
 int rf_realise_batch_prepare(rf_plan* p, int n) {
   RF_REQUIRE(p, "null plan");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  if (p->nranks > 1 || p->force_slab || p->generic) return 0;     // slab / generic batches are not graph-captured
+  if (!route(p).single()) return 0;     // slab / generic batches are not graph-captured
   return batch_prepare(p, n);
 }
 
@@ -1456,13 +1422,14 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
   RF_REQUIRE(p && seeds, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(n >= 1, "need at least one seed");
-  if (p->nranks > 1 || p->force_slab) {
+  const Route r = route(p);
+  if (r.exchanges() || r.replicates()) {
     RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
     RF_HIP(hipSetDevice(p->device));
-    if (int rc = slab_batch(p, seeds, n)) return rc;
+    if (int rc = slab_batch(p, r, seeds, n)) return rc;
     return rms_out ? rms_from_stats(p, n, rms_out) : 0;
   }
-  if (p->generic) {             // no graph: realisations one after the other
+  if (r.kind == Route::Generic) {             // no graph: realisations one after the other
     RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
     RF_HIP(hipSetDevice(p->device));
     if (int rc = ensure_stats(p, n)) return rc;
@@ -1547,7 +1514,7 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
   RF_REQUIRE(p->ln_tables, "rf_set_z_tables must be called first");
-  RF_REQUIRE(p->nranks == 1 && !p->force_slab && !p->generic, "rf_realise_lognormal is for single-GPU plans with power-of-two axes");
+  RF_REQUIRE(route(p).single(), "rf_realise_lognormal is for single-GPU plans with power-of-two axes");
   RF_REQUIRE(mode == RF_NOISE_NATIVE || mode == RF_NOISE_EXTERNAL || mode == RF_NOISE_RESIDENT, "unknown noise mode");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
@@ -2217,7 +2184,7 @@ int rf_download_k(rf_plan* p, void* host) {
 int rf_upload_real(rf_plan* p, const void* host, int layout) {
   RF_REQUIRE(p && host, "null argument");
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
-  RF_REQUIRE(!p->replicate || p->nranks == 1, "replicated-generation plans keep no exchange buffers");
+  RF_REQUIRE(!route(p).replicates(), "replicated-generation plans keep no exchange buffers");
   RF_HIP(hipSetDevice(p->device));
   const size_t rsize = p->csize / 2;
   const size_t width = (size_t)p->nz * rsize;
@@ -2253,7 +2220,7 @@ int rf_download_real(rf_plan* p, void* host, int layout, int x0, int x1) {
 // host = NULL disarms.
 int rf_set_host_sink(rf_plan* p, void* host, int layout) {
   RF_REQUIRE(p, "null plan");
-  RF_REQUIRE(!p->unpacked && !p->generic && p->nranks == 1 && !p->force_slab, "a host sink serves single-GPU packed plans on the tiled kernels");
+  RF_REQUIRE(route(p).single(), "a host sink serves single-GPU packed plans on the tiled kernels");
   RF_REQUIRE(layout == RF_LAYOUT_DENSE || layout == RF_LAYOUT_PADDED, "invalid layout");
   RF_HIP(hipSetDevice(p->device));
   RF_HIP(hipStreamSynchronize(p->stream));

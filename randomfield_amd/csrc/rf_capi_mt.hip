@@ -199,7 +199,7 @@ int rf_mt_share_segments(rf_plan* p, int* nseg_total, int* seg_first, int* seg_c
 int rf_mt_share_begin(rf_plan* p, const uint32_t* state624, int single, unsigned long long* counts_out) {
   RF_REQUIRE(p && state624 && counts_out, "null argument");
   RF_REQUIRE(!p->unpacked && !p->generic, "the distributed replay serves packed plans on the tiled kernels");
-  RF_REQUIRE(!p->replicate, "replicated-generation plans draw native deviates only");
+  RF_REQUIRE(!route(p).replicates(), "replicated-generation plans draw native deviates only");
   RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
   RF_REQUIRE(p->nranks >= 1 && p->nranks <= 64, "unsupported number of ranks");
   if (single && p->f64) single = 0;                      // float64 cells: keep the exact deviates
@@ -400,7 +400,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   RF_REQUIRE(n >= 1, "need at least one seed");
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
   RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
-  RF_REQUIRE(p->nranks == 1 && !p->force_slab && !p->generic && !p->f64 && p->have_fast && !p->exact_gen,
+  RF_REQUIRE(route(p).single() && !p->f64 && p->have_fast && !p->exact_gen,
              "rf_realise_batch_reference is for single-GPU complex64 plans on the fast generation path; loop rf_noise_mt19937 + rf_realise otherwise");
   RF_HIP(hipSetDevice(p->device));
   MtGeom g;
@@ -493,7 +493,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
 }
 
 int rf_can_batch_reference(rf_plan* p) {
-  if (!p || p->unpacked || p->nranks != 1 || p->force_slab || p->generic || p->f64 || !p->have_fast || p->exact_gen || !p->have_kgrid ||
+  if (!p || !route(p).single() || p->f64 || !p->have_fast || p->exact_gen || !p->have_kgrid ||
       !p->have_power || !p->mt_pos.get() || p->mt_npos.empty())
     return 0;
   MtGeom g;

@@ -104,8 +104,8 @@ int rf_slab_exchange_local(rf_plan** plans, int n) {
     RF_HIP(hipStreamSynchronize(plans[g]->stream));
   }
   const rf_plan* p0 = plans[0];
-  const int C = slab_chunks(p0);
-  for (int g = 0; g < n; ++g) RF_REQUIRE(slab_chunks(plans[g]) == C, "every rank must use the same number of exchange chunks");
+  const int C = route(p0).chunks;
+  for (int g = 0; g < n; ++g) RF_REQUIRE(route(plans[g]).chunks == C, "every rank must use the same number of exchange chunks");
   const size_t blk = (size_t)p0->nxl * p0->ny * p0->nzl * p0->csize / (size_t)C, cb = p0->w_bytes / (size_t)C;
   for (int g = 0; g < n; ++g)        // sender g, receiver h: block h of sub-slab c of W_g -> segment (g, c) of R_h
     for (int h = 0; h < n; ++h)
@@ -170,8 +170,9 @@ int direct_reset(rf_plan* p) {
   RF_HIP(p->peer_tab.release());
   return 0;
 }
+// may the plan's y pass store tile by tile into the receive buffers?  (packed, tiled, not replicating; a tile inside one x plane)
 bool direct_shape_ok(const rf_plan* p) {
-  return !p->unpacked && !p->generic && col_direct_supported(p->f64, p->ny, p->nzl / slab_chunks(p));
+  return !p->unpacked && !p->generic && !route(p).replicates() && col_direct_supported(p->f64, p->ny, p->nzl / route(p).chunks);
 }
 // What a rank tells the others about its two receive buffers: [2 IPC handles][ok flag, 8 bytes][PCI bus id of its device, 32 bytes], RF_DIRECT_RECORD_BYTES per rank
 constexpr size_t DIRECT_REC = 192;
@@ -179,7 +180,7 @@ static_assert(2 * sizeof(hipIpcMemHandle_t) + 8 + 32 <= DIRECT_REC, "record too 
 // this rank's record (all zero = "not here": shape without a storing y pass, no buffers, no handles)
 bool direct_fill_record(rf_plan* p, unsigned char* mine) {
   memset(mine, 0, DIRECT_REC);
-  if (!(direct_shape_ok(p) && !p->replicate) || ensure_batch_buffers(p) != 0) return false;
+  if (!direct_shape_ok(p) || ensure_batch_buffers(p) != 0) return false;
   hipIpcMemHandle_t hd[2];
   if (hipIpcGetMemHandle(&hd[0], p->R.ptr) != hipSuccess || hipIpcGetMemHandle(&hd[1], p->R2.ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
   memcpy(mine, hd, sizeof(hd));
@@ -249,7 +250,7 @@ int rf_comm_enable_direct(rf_plan* p, int enable, int* enabled) {
   if (p->direct) { *enabled = 1; return 0; }
   if (int rc = direct_reset(p)) return rc;
   const int P = p->nranks;
-  bool ok = direct_shape_ok(p) && !p->replicate;
+  bool ok = direct_shape_ok(p);
   if (ok && ensure_batch_buffers(p) != 0) ok = false;
   if (P == 1) {                                  // the forced slab path of a single rank: its own buffers are all there is
     if (!ok) return 0;
@@ -316,7 +317,7 @@ int rf_slab_link_direct(rf_plan** plans, int n, int enable) {
   for (int g = 0; g < n; ++g) {
     RF_REQUIRE(plans[g] && plans[g]->nranks == n && plans[g]->rank == g, "plans must be ranks 0..n-1 of one n-rank job");
     RF_REQUIRE(plans[g]->device == plans[0]->device && plans[g]->comm == nullptr, "virtual ranks live on one device and have no communicator");
-    RF_REQUIRE(!enable || (direct_shape_ok(plans[g]) && !plans[g]->replicate), "this plan's y-pass tiles would straddle x planes (or it replicates its generation): no direct exchange");
+    RF_REQUIRE(!enable || direct_shape_ok(plans[g]), "this plan's y-pass tiles would straddle x planes (or it replicates its generation): no direct exchange");
   }
   RF_HIP(hipSetDevice(plans[0]->device));
   for (int g = 0; g < n; ++g) {
@@ -355,7 +356,7 @@ int rf_slab_direct_import(rf_plan* p, const void* records, int nranks, int* enab
   RF_HIP(hipSetDevice(p->device));
   drop_graphs(p);
   if (int rc = direct_reset(p)) return rc;
-  if (!(direct_shape_ok(p) && !p->replicate) || ensure_batch_buffers(p) != 0) return 0;
+  if (!direct_shape_ok(p) || ensure_batch_buffers(p) != 0) return 0;
   std::vector<void*> R0, R1;
   if (!direct_map_peers(p, (const unsigned char*)records, R0, R1)) return direct_reset(p);
   p->peer_R[0] = R0; p->peer_R[1] = R1;
@@ -377,7 +378,7 @@ int rf_slab_set_direct_standin(rf_plan* p, int on, int overlap) {
   if (int rc = direct_reset(p)) return rc;
   p->direct_standin = false;
   if (!on) return 0;
-  RF_REQUIRE(direct_shape_ok(p) && !p->replicate, "this plan's y-pass tiles would straddle x planes (or it replicates its generation): no direct exchange");
+  RF_REQUIRE(direct_shape_ok(p), "this plan's y-pass tiles would straddle x planes (or it replicates its generation): no direct exchange");
   if (int rc = ensure_batch_buffers(p)) return rc;
   const long long blk = (long long)p->nxl * p->ny * p->nzl * (long long)p->csize;
   p->peer_R[0].resize(p->nranks); p->peer_R[1].resize(p->nranks);

@@ -1,7 +1,8 @@
 // rf_plan.h -- the plan object behind the C-ABI and the helpers its translation units share (rf_capi.hip: plans, inputs,
 // realisations, transforms, host <-> device; rf_capi_mt.hip: the MT19937 replay and its sharing between ranks; rf_capi_slab.hip: the
 // communicator and the slab pipeline in separate steps).  What the plan's buffers HOLD belongs to none of the three: it is the member
-// `has` (rf_contents.h), asked and changed through its predicates and transitions only.  Internal: nothing here crosses the C-ABI.
+// `has` (rf_contents.h), asked and changed through its predicates and transitions only; WHICH PIPELINE the plan runs is route(p) (rf_route.h),
+// worked out from the plan's facts per question.  Internal: nothing here crosses the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -20,6 +21,7 @@
 #include "rf_host.h"
 #include "rf_launch.h"
 #include "rf_owned.h"
+#include "rf_route.h"
 #include "rf_select.h"
 #include "rf_timing.h"
 
@@ -255,6 +257,14 @@ struct rf_plan {
 };
 
 namespace rfc {
+// which pipeline the plan runs (rf_route.h), from the plan's facts as they are NOW: asked per question, never kept
+inline Route route(const rf_plan* p) {
+  RouteFacts f;
+  f.unpacked = p->unpacked; f.generic = p->generic; f.nranks = p->nranks; f.force_slab = p->force_slab;
+  f.replicate = p->replicate; f.direct = p->direct; f.xchunks = p->xchunks;
+  return route_of(f);
+}
+
 // What ONE call asks of the passes it queues.  The entry point builds it on its stack and hands it down by const reference
 // (queue_c2r ... queue_x / queue_yz / make_fast); a default-constructed one is a plain realisation.  Nothing of it outlives the call.
 struct CallDesc {
@@ -271,7 +281,6 @@ int ensure_k(rf_plan* p);
 int ensure_x(rf_plan* p);
 int ensure_noise(rf_plan* p);
 bool xpose_ok(const rf_plan* p);
-int slab_chunks(const rf_plan* p);
 GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev);
 int upload_noise(rf_plan* p, int mode, const double* noise_host);
 int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, Timeline* tl, int kz0c = -1, int nzlc = -1);

@@ -5,7 +5,9 @@
 
 Prints one line per result -- `shape dtype call: sha256` -- for fields, k space, moments and potentials over a matrix of tiny grids chosen
 so that every branch of the tiled launchers is reached (rf_select.h: whole columns and Col2 halves, split and unsplit generation passes,
-tile pairs, the side buffer and the owning lane's repair, the merged y+z launch, 64-bit lane offsets ...).  A call the library refuses
+tile pairs, the side buffer and the owning lane's repair, the merged y+z launch, 64-bit lane offsets ...), and, first, over every
+exchanging form of a plan's route (rf_route.h: grouped copy or storing y pass, whole or in sub-slabs, single calls and pipelined batches, the
+two stand-ins of a virtual rank).  A call the library refuses
 prints the refusal text instead of a digest.  Run it once per build (the default is the library of this tree) and diff the two outputs:
 every line must be equal.  Under `rocprofv3 --kernel-trace -- python tools/launch_parity.py LIB` the ordered list of (kernel, grid,
 workgroup) of two builds can be compared the same way.  Each call takes milliseconds; this is a comparison tool, not a test of values."""
@@ -178,11 +180,73 @@ def c2c_plan(shape, dtype, key):
     plan.close()
 
 
+def exchanging_forms(shape, dtype, power, key):
+    """Every exchanging form of the single calls and of the pipelined batch on a single-rank plan forced onto the slab path: grouped
+    copy or storing y pass, whole or in two sub-slabs (a single-rank plan runs the direct form with direct_overlap = 1, the default:
+    only the stand-in below sets it)."""
+    nx, ny, nz = shape
+    noise = np.random.RandomState(5).normal(size=2 * nx * ny * (nz // 2 + 1))
+    seeds = np.array([3, 4, 5], np.uint64)
+    plan = tables(_hip.DevicePlan(nx, ny, nz, dtype), power)
+    plan.set_force_slab_path(True)
+    for direct in (False, True):
+        for chunks in (1, 2):
+            tag = "%s forced slab %s chunks=%d" % (key, "direct" if direct else "rccl", chunks)
+            record(tag + " set", lambda: np.array([plan.set_exchange_chunks(chunks) is None, plan.enable_direct_exchange(direct)]))
+            record(tag + " realise native", lambda: ((plan.realise(seed=11),) + field(plan))[1:])
+            record(tag + " realise host noise", lambda: ((plan.realise(noise=noise),) + field(plan))[1:])
+            record(tag + " realise_potential native", lambda: ((plan.realise_potential(seed=11),) + field(plan) + (potential(plan),))[1:])
+            record(tag + " realise_potential host noise", lambda: ((plan.realise_potential(noise=noise),) + field(plan) + (potential(plan),))[1:])
+            record(tag + " batch n=3", lambda: (plan.realise_batch(seeds), plan.download_real(), np.array(plan.moments())))
+    plan.close()
+
+
+def standin_tails(shape, dtype, power, key):
+    """One rank of a 2-rank job without a communicator under the two stand-ins: the real schedule of a multi-GPU rank, whose result is
+    not a field -- the download's refusal is the record, the local moments come out"""
+    nx, ny, nz = shape
+    seeds = np.array([3, 4, 5], np.uint64)
+    try:
+        plan = tables(_hip.DevicePlan(nx, ny, nz, dtype, nranks=2, rank=1), power)
+    except (RuntimeError, ValueError) as exc:
+        LINES.append("%s stand-in: REFUSED %s" % (key, " ".join(str(exc).split())))
+        print(LINES[-1], flush=True)
+        return
+
+    def calls(tag):
+        record(tag + " realise moments", lambda: (plan.realise(seed=11), np.array(plan.moments()))[1:])
+        record(tag + " realise field", plan.download_real)
+        record(tag + " batch n=3 rms", lambda: (plan.realise_batch(seeds), np.array(plan.moments())))
+        record(tag + " batch n=3 field", plan.download_real)
+
+    for chunks in (1, 2):
+        tag = "%s stand-in chunks=%d" % (key, chunks)
+        record(tag + " set", lambda: np.array([plan.set_exchange_chunks(chunks) is None]))
+        record(tag + " exchange on", lambda: np.array([plan.set_exchange_standin(8) is None]))
+        calls(tag + " exchange")
+        for overlap in (True, False):
+            record(tag + " direct overlap=%d on" % overlap, lambda: np.array([plan.set_direct_standin(True, overlap) is None]))
+            calls(tag + " direct overlap=%d" % overlap)
+        record(tag + " direct off", lambda: np.array([plan.set_direct_standin(False) is None]))
+    plan.close()
+
+
+# the smallest power-of-two grids (float64, float32) on which rf_plan_set_flag takes 2 exchange chunks of a single-rank plan in direct mode
+# (nz / 4 planes per sub-slab = one y-pass tile: col_direct_supported), the (64, 32, 128) of the matrix above, which takes them too, and
+# (64, 32, 256), where a rank of a 2-rank job takes them as well (the stand-ins in sub-slabs)
+ROUTE_SHAPES = [(8, 8, 64), (8, 8, 128), (64, 32, 128), (64, 32, 256)]
+
+
 def main():
     if len(sys.argv) > 1:
         _hip.LIB_PATH = os.path.abspath(sys.argv[1])
     _hip.require_gpu()
     power = powertools.load_default_power()
+    for shape in ROUTE_SHAPES:
+        for dtype in (np.complex64, np.complex128):
+            key = "%dx%dx%d %s" % (shape + (np.dtype(dtype).name,))
+            exchanging_forms(shape, dtype, power, key)
+            standin_tails(shape, dtype, power, key)
     for shape in SHAPES:
         for dtype in (np.complex64, np.complex128):
             key = "%dx%dx%d %s" % (shape + (np.dtype(dtype).name,))
