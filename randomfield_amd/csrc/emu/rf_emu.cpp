@@ -401,25 +401,77 @@ int run_fast_step(const FastIoArgs<typename P::T>& a, const FastStep& st, const 
 // The variant and the launches of the native fast generation pass of a whole grid on one rank, as launch_col_fastgen chooses them:
 // fastgen_variant, its FastListOf entry at length nx, fastgen_sequence.  f(Cfg<FastPassOf>{}, sequence); -2: the library refuses.
 int g_pairs = 1;           // emu_set_pairs(0) clears FastPass::pairs: one tile per workgroup (ColFFT) where the library runs tile pairs
+// What launch_col_fastgen (rf_k_col_gen.hip) is told besides the grid: pot 0 / 1 (a potential array is stored) / 2 (the pass transforms
+// pscale delta(k) / k^2); src 0 native generator / 1 resident float64 deviates / 2 float32 pairs in the replay's runs (first: the
+// exclusive scan of the per-segment counts, nseg + 1 entries; cap: slots per segment); the rows [x0, x1) that are kept (replicated
+// generation: x0 > 0 or x1 < nx) and the kz planes [kz0, kz0 + nzl) of a kz-slab rank.  The defaults are one rank's whole grid.
+struct FastCall {
+  int pot = 0;
+  double pscale = 1.0;
+  int src = 0;
+  const double* noise64 = nullptr;
+  const cplx<float>* noise32 = nullptr;
+  const unsigned long long* first = nullptr;
+  int nseg = 0;
+  unsigned long long cap = 0;
+  int x0 = 0, x1 = 1 << 30, kz0 = 0, nzl = -1;       // nzl < 0: all nz / 2 planes
+  bool loads = false;                                // the pass's loads alone (fast_loads), no transform
+  bool slab(int nx) const { return x0 > 0 || x1 < nx; }
+  FastVariant variant(int f64, int nx) const { return fastgen_variant(f64, nx, pot == 2, src == 1, src == 2, pot == 1, slab(nx)); }
+};
+// The cells one variant's pass LOADS -- what its IO generates for row r of column C, the kz = 0 slot replaced by the owning lane's
+// repair as ColFFT::pass_first replaces it (FIX = 1) -- with no transform behind them: out [N][ncols], row = mode index ix
+template <class P>
+int fast_loads(const FastIoArgs<typename P::T>& a, long long ncols, cplx<typename P::T>* out) {
+  using C = typename P::C;
+  using IO = typename P::IO1;
+  using V = V16<typename P::T>;
+  constexpr int L = C::N / C::R1;
+  IO io = fast_col_io<IO>(a);
+  std::vector<char> lds(IO::LDS_EXTRA + 16);
+  io.bind_seed();
+  io.prologue(0, 1, lds.data());
+  for (int phase = 0; phase < (P::HALVES ? 2 : 1); ++phase) {
+    if constexpr (P::HALVES) io.set_phase(phase);
+    for (long long C0 = 0; C0 < ncols; C0 += V::CPL)
+      for (int r = 0; r < C::N; ++r) {
+        const int rb = r % L, ro = r - rb;
+        V v = io.load(C0, 0, rb, ro);
+        if (io.needs_fix(C0)) v.c[0] = io.fix_value(C0, rb, ro);
+        const long long ix = P::HALVES ? 2 * r + phase : r;
+        for (int k = 0; k < V::CPL; ++k) out[ix * ncols + C0 + k] = v.c[k];
+      }
+  }
+  return 0;
+}
 template <typename T, class F>
-int with_fast_pass(int nx, const ColGeom& g, long long ncols, int nzl, F&& f) {
-  const FastVariant v = fastgen_variant(sizeof(T) == 8, nx, false, false, false, false, false);
+int with_fast_pass(int nx, const ColGeom& g, long long ncols, int nzl, const FastCall& c, F&& f) {
+  const FastVariant v = c.variant(sizeof(T) == 8, nx);
   return with_fast_variant(FastListOf<T>{}, v, -2, [&](auto e) {
     return FastGen<T>::template at<decltype(e)>(nx, -2, [&](auto k) {
       using P = typename decltype(k)::type;
-      if (!P::accepts(g, ncols, nzl, 0, 1 << 30)) return -2;
+      if (!P::accepts(g, ncols, nzl, c.x0, c.x1)) return -2;
       FastPass pass = P::pass;
       if (!g_pairs) pass.pairs = false;
-      const FastSequence q = fastgen_sequence(pass, nzl, ncols, 0, true, g, true);
+      const FastSequence q = fastgen_sequence(pass, nzl, ncols, c.kz0, P::full_rows(c.x0, c.x1), g, true);
       return q.valid ? f(k, q) : -2;
     });
   });
 }
 
+// The x pass of one call -- one rank's rows [x0, x1) and planes [kz0, kz0 + nzl) -- into the whole grid's intermediate
+// W [nx][ny][nz / 2] (Wx: the blocked intermediate instead, whole-grid calls only), and its potential array P [nx][ny][ppitch] (pot = 1).
 template <typename T>
-int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, double xlo, double xhi, double dkx,
-                      cplx<T>* W, double* s1, double* s2) {
-  const long long nzc = nz / 2, ncols = (long long)ny * nzc;
+int fast_x_pass(int nx, int ny, int nz, const GenHost& h, uint64_t seed, double xlo, double xhi, double dkx, const FastCall& c,
+                cplx<T>* W, cplx<T>* Wx, cplx<T>* P) {
+  constexpr int f64 = sizeof(T) == 8;
+  const long long nzc = nz / 2;
+  const int nzl = c.nzl < 0 ? (int)nzc : c.nzl;
+  const long long ncols = (long long)ny * nzl;
+  const bool whole_z = c.kz0 == 0 && nzl == nzc;
+  if (nzl <= 0 || c.kz0 < 0 || c.kz0 + nzl > nzc || (c.src != 0 && !whole_z) || (Wx != W && (!whole_z || c.slab(nx)))) return -2;
+  if (c.loads && (Wx != W || c.slab(nx))) return -2;
+  if ((c.pot == 1) != (P != nullptr) || (c.src == 1 && !c.noise64) || (c.src == 2 && !(c.noise32 && c.first && c.nseg > 0))) return -2;
   std::vector<FastRec> rec;
   FastGenParams f;
   memset(&f, 0, sizeof(f));
@@ -429,16 +481,32 @@ int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, d
   f.nx = nx; f.ny = ny; f.nz = nz; f.dkx = (float)dkx; f.dky = (float)std::sqrt(h.gp.ky2[1]); f.dkz = (float)std::sqrt(h.gp.kz2[1]);
   f.rec = rec.data(); f.nbins = (int)rec.size();
   f.u_scale = (float)(0.5 * std::log10(2.0) / dx); f.u_off = (float)(-x0 / dx);
-  f.seed = seed; f.zpitch = nz / 2 + 1; f.zoff = 0; f.ppitch = nz / 2 + 2;
-  const bool xp = xposed<T>(nx, ny, nzc);
-  std::vector<cplx<T>> X(xp ? (size_t)nx * ny * nzc : 0), fixbuf((size_t)nx * ny);
-  cplx<T>* Wx = xp ? X.data() : W;
-  const FastIoArgs<T> a{f, Wx, xp ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nzc), 0, (int)nzc, 0, 1 << 30, nullptr, fixbuf.data()};
+  // the side arrays of a rank: its own planes, then the Nyquist plane (make_fast and rf_plan_create, rf_capi.hip)
+  f.seed = seed; f.zpitch = nzl + 1; f.zoff = c.kz0; f.ppitch = f64 ? nzl + 1 : nzl + (nzl >= 256 ? 64 : 2);
+  f.pscale = c.pscale; f.emit_potential = c.pot == 2 ? 1 : 0;
+  std::vector<RowLoc> rowtab;
+  if (c.src == 1) f.noise = c.noise64;
+  if (c.src == 2) {                                        // mt_rowtab_kernel: entry iy nx + ix
+    int bad = 0;
+    rowtab.resize((size_t)nx * ny);
+    for (int ix = 0; ix < nx; ++ix)
+      for (int iy = 0; iy < ny; ++iy)
+        rowtab[(size_t)iy * nx + ix] = make_rowloc(c.first, c.nseg, ((unsigned long long)ix * ny + iy) * (unsigned)(nzc + 1), (unsigned)(nzc + 1), &bad);
+    if (bad) return -4;
+    f.noise32 = c.noise32; f.rowtab = rowtab.data(); f.seg_cap = c.cap;
+  }
+  // a kz slab is generated into an array of its own planes, as on its rank, and copied into the whole grid's
+  std::vector<cplx<T>> own(whole_z ? 0 : (size_t)nx * ny * nzl), fixbuf((size_t)nx * ny);
+  const ColGeom g = Wx != W ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nzl);
+  cplx<T>* dst = Wx != W ? Wx : whole_z ? W : own.data();
+  if (c.x0 > 0) dst += (long long)c.x0 * g.row_stride;     // (fast_col_io moves the base back by x0 rows: row x0 lands on row x0 of W)
+  const FastIoArgs<T> a{f, dst, g, c.kz0, nzl, c.x0, c.x1, P, fixbuf.data()};
   g_fast_steps.clear();
   auto tw = make_twiddles<T>(nx);
   g_count_visits = true;
-  const int rc = with_fast_pass<T>(nx, a.g, ncols, (int)nzc, [&](auto k, const FastSequence& q) {
+  const int rc = with_fast_pass<T>(nx, a.g, ncols, nzl, c, [&](auto k, const FastSequence& q) {
     g_fast_visits.assign((size_t)(ncols / decltype(k)::type::C::TC), 0);
+    if (c.loads) return fast_loads<typename decltype(k)::type>(a, ncols, dst);
     for (int i = 0; i < q.n; ++i) {
       g_fast_steps.push_back(q.step[i]);
       if (int e = run_fast_step<typename decltype(k)::type>(a, q.step[i], tw.data())) return e;
@@ -447,7 +515,23 @@ int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, d
   });
   g_count_visits = false;
   if (rc) return rc;
-  return yz_passes<T>(nx, ny, nz, Wx, W, s1, s2);
+  if (!whole_z)
+    for (long long col = 0; col < (long long)nx * ny; ++col)
+      std::copy(own.begin() + col * nzl, own.begin() + (col + 1) * nzl, W + col * nzc + c.kz0);
+  return 0;
+}
+
+// finish: the y and z passes behind the x pass (the last of the calls that fill W between them)
+template <typename T>
+int realise_fast_impl(int nx, int ny, int nz, const GenHost& h, uint64_t seed, double xlo, double xhi, double dkx, const FastCall& c,
+                      bool finish, cplx<T>* W, cplx<T>* P, double* s1, double* s2) {
+  const long long nzc = nz / 2;
+  const bool whole = c.kz0 == 0 && (c.nzl < 0 || c.nzl == nzc) && !c.slab(nx);
+  const bool xp = whole && finish && !c.loads && xposed<T>(nx, ny, nzc);
+  std::vector<cplx<T>> X(xp ? (size_t)nx * ny * nzc : 0);
+  cplx<T>* Wx = xp ? X.data() : W;
+  if (int rc = fast_x_pass<T>(nx, ny, nz, h, seed, xlo, xhi, dkx, c, W, Wx, P)) return rc;
+  return finish && !c.loads ? yz_passes<T>(nx, ny, nz, Wx, W, s1, s2) : 0;
 }
 
 
@@ -1227,14 +1311,39 @@ int emu_exp_scaled64(const double* t, double* out, long long n, int stride) {
 
 // fused realisation with the fast native generation (float32 arithmetic; f64 != 0: float64 plan, values widened);
 // [xlo, xhi] = log10 k range of the grid (padded)
+// emu_realise_fast_ex: the same with everything launch_col_fastgen is told (FastCall above) -- pot 0 / 1 / 2 with pscale; src 0 / 1
+// (noise64: float64 deviates in the API layout) / 2 (noise32: float32 pairs in the replay's runs of `cap` slots per segment, first:
+// exclusive scan of the per-segment counts, nseg + 1 entries); rows [x0, x1) and planes [kz0, kz0 + nzl) (nzl < 0: all).  W is the
+// whole grid's buffer: a call with finish = 0 runs its x pass into it and returns, the last call (finish != 0) also runs the y and z
+// passes, so the ranks of a job are one call each; finish = 2: no transform at all -- W receives the packed cells the pass loads
+// (fast_loads: [nx][ny][nzl] complex, the kz = 0 slot repaired), the pass's own k-space values.  P (pot = 1): the call's potential array [nx][ny][ppitch], ppitch as
+// rf_plan_create sets it (nzl + 1 cells, padded to nzl + 2 or nzl + 64 on float32 plans), rows of its own planes + the Nyquist plane.
+int emu_realise_fast_ex(int f64, int nx, int ny, int nz, const double* kx2, const double* ky2, const double* kz2,
+                        const double* log10k, const double* sigma, int nt, uint64_t seed, double xlo, double xhi, double dkx,
+                        int pot, double pscale, int src, const double* noise64, const void* noise32, const unsigned long long* first, int nseg,
+                        unsigned long long cap, int x0, int x1, int kz0, int nzl, int finish, void* W, void* P, double* s1, double* s2) {
+  GenHost h;
+  fill_gen(h, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, 0, seed, nullptr);
+  FastCall c;
+  c.pot = pot; c.pscale = pscale; c.src = src; c.noise64 = noise64; c.noise32 = (const cplx<float>*)noise32; c.first = first; c.nseg = nseg; c.cap = cap;
+  c.x0 = x0; c.x1 = x1; c.kz0 = kz0; c.nzl = nzl; c.loads = finish == 2;
+  return f64 ? realise_fast_impl<double>(nx, ny, nz, h, seed, xlo, xhi, dkx, c, finish != 0, (cplx<double>*)W, (cplx<double>*)P, s1, s2)
+             : realise_fast_impl<float>(nx, ny, nz, h, seed, xlo, xhi, dkx, c, finish != 0, (cplx<float>*)W, (cplx<float>*)P, s1, s2);
+}
 int emu_realise_fast(int f64, int nx, int ny, int nz, const double* kx2, const double* ky2, const double* kz2,
                      const double* log10k, const double* sigma, int nt, uint64_t seed, double xlo, double xhi,
                      double dkx, void* W, double* s1, double* s2) {
-  GenHost h;
-  fill_gen(h, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, 0, seed, nullptr);
-  return f64 ? realise_fast_impl<double>(nx, ny, nz, h, seed, xlo, xhi, dkx, (cplx<double>*)W, s1, s2)
-             : realise_fast_impl<float>(nx, ny, nz, h, seed, xlo, xhi, dkx, (cplx<float>*)W, s1, s2);
+  return emu_realise_fast_ex(f64, nx, ny, nz, kx2, ky2, kz2, log10k, sigma, nt, seed, xlo, xhi, dkx, 0, 1.0, 0, nullptr, nullptr, nullptr, 0, 0,
+                             0, 1 << 30, 0, -1, 1, W, nullptr, s1, s2);
 }
+// rf_select.h fastgen_variant as five numbers (valid, slab, pot, src, halves); col_replicate_supported
+int emu_fastgen_variant(int f64, int N, int emit, int n64, int n32, int pot, int slab, int* out5) {
+  const FastVariant v = fastgen_variant(f64, N, emit != 0, n64 != 0, n32 != 0, pot != 0, slab != 0);
+  const int r[5] = {v.valid, v.slab, v.pot, v.src, v.halves};
+  std::copy(r, r + 5, out5);
+  return v.valid;
+}
+int emu_col_replicate_supported(int f64, int N, int nranks) { return col_replicate_supported(f64, N, nranks); }
 
 // Row T alone: the fast float32 sigma(|k|^2) lookup (per-bin records, rf_core.h fast_sigma) next to the exact float64
 // interpolation of the same table, for n values of |k|^2 -- bounds the table-lookup error separately from the
@@ -1317,13 +1426,21 @@ long long emu_fast_visits(int* out, long long max) {
   std::copy(g_fast_visits.begin(), g_fast_visits.begin() + std::min<long long>(max, (long long)g_fast_visits.size()), out);
   return (long long)g_fast_visits.size();
 }
-int emu_fastgen_sequence(int f64, int nx, int ny, int nz, long long* out5, int max) {
+// emu_fastgen_sequence_ex: of the variant the flags select (emit, n64, n32, pot as emu_fastgen_variant), rows [x0, x1) and planes
+// [kz0, kz0 + nzl) (nzl < 0: all) -- a kz-slab rank's pass runs on the geometry of its own planes
+int emu_fastgen_sequence_ex(int f64, int nx, int ny, int nz, int emit, int n64, int n32, int pot, int x0, int x1, int kz0, int nzl, long long* out5, int max) {
   return with_real(f64, [&](auto r) {
     using T = typename decltype(r)::type;
-    const long long nzc = nz / 2;
-    const ColGeom g = xposed<T>(nx, ny, nzc) ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nzc);
-    return with_fast_pass<T>(nx, g, (long long)ny * nzc, (int)nzc, [&](auto, const FastSequence& q) { return copy_steps(q.step, q.n, out5, max); });
+    const long long nzc = nz / 2, nl = nzl < 0 ? nzc : nzl;
+    FastCall c;
+    c.pot = emit ? 2 : pot ? 1 : 0; c.src = n64 ? 1 : n32 ? 2 : 0; c.x0 = x0; c.x1 = x1; c.kz0 = kz0; c.nzl = (int)nl;
+    const bool whole = kz0 == 0 && nl == nzc && !c.slab(nx);
+    const ColGeom g = whole && xposed<T>(nx, ny, nzc) ? xposed_x_geom<T>(nx, ny, nzc) : x_geom(ny, nl);
+    return with_fast_pass<T>(nx, g, (long long)ny * nl, (int)nl, c, [&](auto, const FastSequence& q) { return copy_steps(q.step, q.n, out5, max); });
   });
+}
+int emu_fastgen_sequence(int f64, int nx, int ny, int nz, long long* out5, int max) {
+  return emu_fastgen_sequence_ex(f64, nx, ny, nz, 0, 0, 0, 0, 0, 1 << 30, 0, -1, out5, max);
 }
 // FastGenColIOT::share_row (rf_fft_gen.h): the butterfly row of slot jl when L butterflies are dealt to slots of S per wave so that
 // the rows +-ix sit 32 lanes apart (the sigma exchange of the x pass); a host-side table for the bijection test

@@ -150,6 +150,65 @@ def realise_fast(nx, ny, nz, spacing, log10k, sigma, seed, dtype=np.float32):
     return out, s1.value, s2.value
 
 
+def realise_fast_ex(nx, ny, nz, spacing, log10k, sigma, seed, dtype=np.float32, pot=0, pscale=1.0, noise64=None, noise32=None, first=None, cap=0,
+                    x0=0, x1=1 << 30, kz0=0, nzl=-1, finish=True, field=None):
+    """emu_realise_fast_ex: realise_fast with everything the launcher is told -- pot 0 / 1 (a potential array is returned) / 2 (the
+    pass transforms pscale delta(k) / k^2); resident deviates as float64 (noise64, API layout) or as float32 pairs in the replay's
+    runs (noise32 [nseg * cap][2], first: exclusive scan of the per-segment counts); rows [x0, x1); planes [kz0, kz0 + nzl).
+    The ranks of a job are one call each on the same buffer: finish=False runs the x pass only and returns the buffer, which the
+    next call takes as field=...; the last one runs the y and z passes too.  finish="loads": no transform -- the buffer receives
+    the packed cells the pass loads, complex [nx][ny][nz / 2] (view it as the plan's complex dtype).  Returns (field, sum, sum of squares, potential of
+    this call [nx][ny][nzl + 1] or None)."""
+    args, keep = _gen_args(nx, ny, nz, spacing, log10k, sigma, seed, None)
+    k0 = 2 * np.pi / spacing
+    xlo = np.log10(k0 / max(nx, ny, nz)) - 0.01
+    xhi = np.log10(k0 * np.sqrt(3) / 2) + 0.01
+    f64 = int(np.dtype(dtype) == np.float64)
+    out = np.zeros((nx, ny, nz), dtype) if field is None else field
+    assert out.shape == (nx, ny, nz) and out.dtype == np.dtype(dtype) and out.flags.c_contiguous
+    nl = nz // 2 if nzl < 0 else nzl
+    ppitch = nl + 1 if f64 else nl + (64 if nl >= 256 else 2)
+    P = np.zeros((nx, ny, ppitch), np.complex128 if f64 else np.complex64) if pot == 1 else None
+    src = 0
+    if noise64 is not None:
+        src, noise64 = 1, np.ascontiguousarray(noise64, np.float64)
+        assert noise64.size == 2 * nx * ny * (nz // 2 + 1)
+    nseg = 0
+    if noise32 is not None:
+        src, noise32, first = 2, np.ascontiguousarray(noise32, np.float32), np.ascontiguousarray(first, np.uint64)
+        nseg = len(first) - 1
+        assert noise32.size == 2 * nseg * cap
+    s1, s2 = ctypes.c_double(), ctypes.c_double()
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+    rc = lib().emu_realise_fast_ex(f64, nx, ny, nz, *args[:6], ctypes.c_uint64(seed), ctypes.c_double(xlo), ctypes.c_double(xhi),
+                                   ctypes.c_double(k0 / nx), int(pot), ctypes.c_double(pscale), src, _dp(noise64), vp(noise32), vp(first), nseg,
+                                   ctypes.c_ulonglong(cap), int(x0), int(x1), int(kz0), int(nzl), 2 if finish == "loads" else int(bool(finish)), vp(out), vp(P),
+                                   ctypes.byref(s1), ctypes.byref(s2))
+    assert rc == 0, rc
+    return out, s1.value, s2.value, (P[:, :, :nl + 1] if P is not None else None)
+
+
+def fastgen_variant(f64, N, emit=False, n64=False, n32=False, pot=False, slab=False):
+    """rf_select.h fastgen_variant: (slab, pot, src, halves), None where it is invalid"""
+    out = (ctypes.c_int * 5)()
+    valid = lib().emu_fastgen_variant(int(f64), N, int(emit), int(n64), int(n32), int(pot), int(slab), out)
+    return (out[1], out[2], out[3], bool(out[4])) if valid else None
+
+
+def col_replicate_supported(f64, N, nranks):
+    return bool(lib().emu_col_replicate_supported(int(f64), N, nranks))
+
+
+def fastgen_sequence_ex(nx, ny, nz, f64=False, emit=False, n64=False, n32=False, pot=False, x0=0, x1=1 << 30, kz0=0, nzl=-1):
+    """rf_select.h fastgen_sequence for the variant the flags select, rows [x0, x1) and planes [kz0, kz0 + nzl); None where the
+    library refuses"""
+    buf = (ctypes.c_longlong * 40)()
+    n = lib().emu_fastgen_sequence_ex(int(f64), nx, ny, nz, int(emit), int(n64), int(n32), int(pot), int(x0), int(x1), int(kz0), int(nzl), buf, 8)
+    if n < 0:
+        return None
+    return [tuple(buf[5 * i:5 * i + 5]) for i in range(n)]
+
+
 def _steps(call):
     buf = (ctypes.c_longlong * 40)()
     n = call(buf, 8)
