@@ -114,13 +114,13 @@ bool generic_shape(int nx, int ny, int nz, int f64, GenericAxis& ax, GenericAxis
   return true;
 }
 
-GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev) {
+GenParams make_gen(rf_plan* p, uint64_t seed, int mode) {
   GenParams g;
   g.nx = p->nx; g.ny = p->ny; g.nz = p->nz;
   g.kx2 = p->kx2.get(); g.ky2 = p->ky2.get(); g.kz2 = p->kz2.get();
   g.xt = p->xt.get(); g.st = p->st.get(); g.sl = p->sl.get(); g.bin = p->bin.get();
   g.nt = p->nt; g.nbins = p->nbins; g.x0 = p->x0; g.inv_dx = p->inv_dx;
-  g.noise_mode = (mode == RF_NOISE_RESIDENT) ? (int)RF_NOISE_EXTERNAL : mode; g.seed = seed; g.seed_dev = nullptr; (void)seed_from_dev;   // graph batches point seed_dev at seeds_dev[i]
+  g.noise_mode = (mode == RF_NOISE_RESIDENT) ? (int)RF_NOISE_EXTERNAL : mode; g.seed = seed; g.seed_dev = nullptr;   // graph batches point seed_dev at seeds_dev[i]
   g.noise = p->noise.get();
   g.zpitch = p->nzl + 1; g.zoff = p->kz0;      // side arrays (noise, K, P) hold this rank's planes + the Nyquist plane
   return g;
@@ -227,16 +227,11 @@ size_t chunk_bytes(const rf_plan* p) { return p->w_bytes / (size_t)route(p).chun
 // (kz0c, nzlc >= 0: a sub-slab of this rank's planes instead of all of them -- W then points at the sub-slab's own region)
 // (tl: the fast generation's kz = 0 tiles are rf_kernel_ms's entry 4; the caller marks the end of the pass)
 int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, Timeline* tl, int kz0c, int nzlc) {
-  // resident deviates (the numpy stream replayed by rf_noise_mt19937) take the fast float32 sigma path too; host-supplied
-  // deviates (RF_NOISE_EXTERNAL, the parity mode) keep the exact reference dtype chain
-  // (float32 copies of the deviates exist for this path only, and it can store the potential too; float64 ones cannot)
-  const bool rep = route(p).replicates();
-  const bool fast_noise = !kspace && gp.noise_mode == NOISE_EXTERNAL && cd.resident_fast && p->have_fast && !p->exact_gen &&
-                          !p->f64 && !rep && (p->has.deviates32() || !cd.pot_target);
-  RF_REQUIRE(kspace || gp.noise_mode != NOISE_EXTERNAL || fast_noise || p->has.deviates64(),
-             "only float32 copies of the deviates are resident: this path (exact chain / float64 plan) needs rf_noise_mt19937's float64 ones");
-  const bool fast = (!kspace && gp.noise_mode == NOISE_PHILOX && p->have_fast && !p->exact_gen) || fast_noise;
-  RF_REQUIRE(!rep || fast, "replicated generation needs the native generator (fast path)");
+  // which kernel, on which deviates, and whether it serves the call's stored / emitted potential: rf_source.h (resident deviates take
+  // the fast float32 sigma path too; host-supplied ones, the parity mode, keep the exact reference dtype chain)
+  const Source src = source(p, cd.ask(kspace != nullptr));
+  RF_REQUIRE(!src.refused(), src.refusal);
+  const bool rep = route(p).replicates(), fast = src.fast();
   const long long nzl = nzlc >= 0 ? nzlc : (rep ? p->nzc : p->nzl);     // kz planes generated by this call (nz/2 on one GPU)
   const int kz0 = kz0c >= 0 ? kz0c : (rep ? 0 : p->kz0);
   // W == p->X: the blocked intermediate [x block][kz tile][ny][rb][TC] -- a tile (all nx rows of TC adjacent kz of one iy) is
@@ -247,11 +242,11 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   hipEvent_t after_repair = nullptr;
   if (fast) RF_HIP(mark(tl, rft::EXTRA, sx, &after_repair));       // in front of the pass; recorded again by the launcher if it splits
   FastGenParams fgp = make_fast(p, cd, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
-  if (fast_noise && p->has.deviates32()) {
+  if (src.reads_pairs32()) {
     fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch.ptr);      // (a later float64 replay reuses the scratch: the float32 claim goes with it)
     fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt_rowtab.ptr); fgp.seg_cap = p->seg_cap;
   }
-  else if (fast_noise) fgp.noise = gp.noise;
+  else if (src.kind == Source::FastDeviates64) fgp.noise = gp.noise;
   if (fast)
     RF_HIP(launch_col_fastgen(p->f64, p->nx, W, gx, (long long)p->ny * nzl, fgp,
                               kz0, (int)nzl, p->tw_x.ptr, sx, after_repair,
@@ -471,7 +466,7 @@ int slab_batch_direct(rf_plan* p, const Route& r, const uint64_t* seeds, int n) 
     const int b = i & 1, pb = (i - 1) & 1;
     if (i < n) {
       // (sub-slab by sub-slab when the plan chunks: x(c) on A, the stores of sub-slab c on Y behind an event)
-      if (int rc = queue_forward(p, r, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], b, nullptr, A, Y, nullptr)) return rc;
+      if (int rc = queue_forward(p, r, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE), nullptr, Wb[b], b, nullptr, A, Y, nullptr)) return rc;
     }
     if (i >= 1) {
       if (two) RF_HIP(hipStreamWaitEvent(A, ev_bar[pb], 0));
@@ -509,7 +504,7 @@ int slab_batch(rf_plan* p, const Route& r, const uint64_t* seeds, int n) {
   if (r.replicates()) {          // no exchange to overlap: realisations back to back, one all-reduce at the end
     RF_HIP(p->tl.begin(p->stream, false));
     for (int i = 0; i < n; ++i) {
-      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, p->W.ptr, p->stream, nullptr)) return rc;
+      if (int rc = queue_xy(p, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE), nullptr, p->W.ptr, p->stream, nullptr)) return rc;
       if (int rc = replicated_z(p, i, i + 1 == n ? n : 0, nullptr)) return rc;
     }
     RF_HIP(p->tl.end(p->stream));
@@ -526,7 +521,7 @@ int slab_batch(rf_plan* p, const Route& r, const uint64_t* seeds, int n) {
   for (int i = 0; i <= n; ++i) {
     if (i < n) {
       const int b = i & 1;
-      if (int rc = queue_forward(p, r, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE, false), nullptr, Wb[b], 0, nullptr, A, A, nullptr)) return rc;
+      if (int rc = queue_forward(p, r, CallDesc(), make_gen(p, seeds[i], RF_NOISE_NATIVE), nullptr, Wb[b], 0, nullptr, A, A, nullptr)) return rc;
       RF_HIP(hop(ev_fwd[b], A, C));
       if (i >= 2) RF_HIP(hipStreamWaitEvent(C, ev_z[b], 0));          // R[b] still being read by z(i-2)?
       if (int rc = queue_exchange_rccl(p, Wb[b], Rb[b], C)) return rc;
@@ -785,7 +780,8 @@ int queue_c2r(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* k
       return fail(1, "this call does not apply to an unpacked c2c plan");        // (every entry point has said so before it came here)
     case Route::Generic: {
       // per-kernel times (rf_kernel_ms): start | generation launch | EXTRA | x | X | y | Y | contiguous | Z | reduce | end
-      if (!kspace) RF_REQUIRE(gp.noise_mode != NOISE_EXTERNAL || p->has.deviates64(), "no float64 deviates resident on the device");
+      const Source src = source(p, cd.ask(kspace != nullptr));      // (a generic plan runs the exact chain: float64 deviates or none)
+      RF_REQUIRE(!src.refused(), src.refusal);
       const bool fused = !kspace && p->fused_generic;  // generation inside the x pass: K and what it holds stay as they are
       if (!kspace && !fused) {                        // rows K,T,R,S into the API-layout buffer first
         if (int rc = ensure_k(p)) return rc;
@@ -1046,7 +1042,7 @@ int rf_diag_live_resources(size_t* device_bytes, int* events, int* streams) {
 
 int rf_diag_generation_path(rf_plan* p, int* fast) {
   RF_REQUIRE(p && fast, "null argument");
-  *fast = (p->have_fast && !p->exact_gen) ? 1 : 0;
+  *fast = source(p, SourceAsk()).fast() ? 1 : 0;      // what a NATIVE x pass would run
   return 0;
 }
 
@@ -1166,8 +1162,9 @@ int rf_generate(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   RF_HIP(hipSetDevice(p->device));
   if (int rc = ensure_k(p)) return rc;        // a kz-slab rank holds (and generates) its own planes + the Nyquist plane
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  RF_REQUIRE(mode != RF_NOISE_RESIDENT || p->has.deviates64(), "rf_generate needs float64 deviates: only float32 copies are resident");
-  RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, make_gen(p, seed, mode, false), p->stream));
+  const Source src = source(p, SourceAsk::fill_k(mode));      // the exact chain into K: Philox, or float64 deviates
+  RF_REQUIRE(!src.refused(), src.refusal);
+  RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, make_gen(p, seed, mode), p->stream));
   if (mode == RF_NOISE_EXTERNAL) RF_HIP(hipStreamSynchronize(p->stream));  // host noise buffer may be released by the caller
   p->has.kspace_ready();
   return 0;
@@ -1179,7 +1176,7 @@ int rf_execute_c2r(rf_plan* p) {
   RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
   RF_REQUIRE(!route(p).replicates(), "replicated-generation plans have no distributed k-space buffer");
   RF_HIP(hipSetDevice(p->device));
-  return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr);
+  return queue_c2r(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE), p->K.ptr);
 }
 
 }  // extern "C"
@@ -1265,9 +1262,7 @@ int rf_realise(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
   RF_REQUIRE(mode == RF_NOISE_NATIVE || mode == RF_NOISE_EXTERNAL || mode == RF_NOISE_RESIDENT, "invalid noise mode");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  CallDesc cd;
-  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
-  if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
+  if (int rc = queue_c2r(p, CallDesc(mode), make_gen(p, seed, mode), nullptr)) return rc;
   if (mode == RF_NOISE_EXTERNAL) RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -1279,10 +1274,8 @@ int rf_realise(rf_plan* p, uint64_t seed, int mode, const double* noise_host) {
 // scaled copy of that would be.  Needs the fast generation pass (rf_can_regenerate_potential); returns the real field in place of
 // the current one, like rf_load_potential + rf_execute_c2r.
 int rf_can_regenerate_potential(rf_plan* p, int mode) {
-  if (!p || p->unpacked || p->generic || !p->have_fast || p->exact_gen || route(p).replicates()) return 0;
-  if (mode == RF_NOISE_NATIVE) return 1;
-  if (mode == RF_NOISE_RESIDENT) return (p->has.deviates32() && !p->f64) ? 1 : 0;
-  return 0;
+  if (!p || (mode != RF_NOISE_NATIVE && mode != RF_NOISE_EXTERNAL && mode != RF_NOISE_RESIDENT)) return 0;
+  return source(p, SourceAsk::x_pass(false, mode, SourceAsk::Emitted)).emits_potential() ? 1 : 0;      // what rf_realise_scaled_potential's x pass will ask
 }
 
 int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scale, const double* factor_z) {
@@ -1292,8 +1285,7 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   RF_REQUIRE(rf_can_regenerate_potential(p, mode), "this plan / noise mode stores its potential (rf_realise_potential): nothing to regenerate from");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, nullptr)) return rc;
-  CallDesc cd;
-  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
+  CallDesc cd(mode);
   cd.emit_potential = true;
   cd.emit_pscale = p->f64 ? scale : (double)(float)scale;
   // the light-cone factor per plane z (generate.py:344-347): in the z pass's own store where the plan runs the plain single-rank
@@ -1304,7 +1296,7 @@ int rf_realise_scaled_potential(rf_plan* p, uint64_t seed, int mode, double scal
   const bool fuse_z = factor_z && route(p).single() && !xpose_ok(p);
   if (factor_z) RF_HIP(hipMemcpyAsync(p->ztab.get(), factor_z, (size_t)p->nz * sizeof(double), hipMemcpyHostToDevice, p->stream));
   cd.zscale = fuse_z ? p->ztab.get() : nullptr;
-  if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode, false), nullptr)) return rc;
+  if (int rc = queue_c2r(p, cd, make_gen(p, seed, mode), nullptr)) return rc;
   if (factor_z && !fuse_z) {
     RF_HIP(launch_affine_z(p->f64, p->has.where(), (long long)p->nxl * p->ny, p->nz, p->ztab.get(), 0.0, p->stream));
     p->has.field_modified();
@@ -1343,21 +1335,18 @@ int potential_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_h
   RF_REQUIRE(!route(p).replicates(), "replicated-generation plans keep no k-space potential: clear RF_FLAG_REPLICATED_GENERATION");
   RF_HIP(hipSetDevice(p->device));
   // fused: delta(k) / k^2 is a second store stream of the generation pass -- native generator (float32 and float64 plans)
-  // or resident float32 deviates (float32 plans)
-  const bool fused = ((mode == RF_NOISE_NATIVE) || (mode == RF_NOISE_RESIDENT && p->has.deviates32() && !p->f64)) && p->have_fast &&
-                     !p->exact_gen && !p->generic;
-  if (!fused) {
+  // or resident float32 deviates (float32 plans): the x pass's own decision, asked what its call will ask
+  if (!source(p, SourceAsk::x_pass(false, mode, SourceAsk::Stored)).stores_potential()) {
     if (int rc = rf_generate(p, seed, mode, noise_host)) return rc;
     if (int rc = rf_save_potential(p)) return rc;
     if (whole) return rf_execute_c2r(p);
-    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, nullptr);
+    return queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE), p->K.ptr, p->W.ptr, p->stream, nullptr);
   }
   if (int rc = ensure_p(p)) return rc;
   p->has.potential2_stale();                         // (P is rewritten: a second-order potential made from the old one is stale)
-  CallDesc cd;
+  CallDesc cd(mode);
   cd.pot_target = p->P.ptr;
-  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
-  const GenParams gp = make_gen(p, seed, mode, false);
+  const GenParams gp = make_gen(p, seed, mode);
   return whole ? queue_c2r(p, cd, gp, nullptr) : queue_xy(p, cd, gp, nullptr, p->W.ptr, p->stream, nullptr);
 }
 }  // namespace rfc
@@ -1372,7 +1361,7 @@ int rf_realise_potential(rf_plan* p, uint64_t seed, int mode, const double* nois
 // issue the n realisations of a batch on the plan's stream (under stream capture)
 static int batch_issue(rf_plan* p, int n) {
   for (int i = 0; i < n; ++i) {
-    GenParams gp = make_gen(p, 0, RF_NOISE_NATIVE, true);
+    GenParams gp = make_gen(p, 0, RF_NOISE_NATIVE);
     gp.seed_dev = p->seeds_dev.get() + i;
     if (int rc = queue_xyz(p, CallDesc(), gp, nullptr, p->W.ptr, p->stream, p->stats.get() + 2 * i, nullptr)) return rc;
   }
@@ -1437,7 +1426,7 @@ int rf_realise_batch(rf_plan* p, const uint64_t* seeds, int n, double* rms_out) 
     if (!fused) { if (int rc = ensure_k(p)) return rc; }
     RF_HIP(p->tl.begin(p->stream, false));
     for (int i = 0; i < n; ++i) {
-      const GenParams gp = make_gen(p, seeds[i], RF_NOISE_NATIVE, false);
+      const GenParams gp = make_gen(p, seeds[i], RF_NOISE_NATIVE);
       if (!fused) RF_HIP(launch_gen_kspace(p->f64, p->K.ptr, gp, p->stream));
       if (int rc = generic_c2r(p, p->K.ptr, p->stats.get() + 2 * i, nullptr, fused ? &gp : nullptr)) return rc;
     }
@@ -1518,12 +1507,11 @@ int rf_realise_lognormal(rf_plan* p, uint64_t seed, int mode, const double* nois
   RF_REQUIRE(mode == RF_NOISE_NATIVE || mode == RF_NOISE_EXTERNAL || mode == RF_NOISE_RESIDENT, "unknown noise mode");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  CallDesc cd;
-  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
+  const CallDesc cd(mode);
   const long long nzl = p->nzl, ntiles = (long long)p->nx * nzl / col_tile_cols(p->f64, p->ny);
   RF_HIP(p->ypart.reserve(ntiles * sizeof(double)));
   hipStream_t s = p->stream;
-  const GenParams gp = make_gen(p, seed, mode, false);
+  const GenParams gp = make_gen(p, seed, mode);
   const ColGeom gy{nzl, (long long)p->ny * nzl, nzl};
   const double n3 = (double)p->nx * (double)p->ny * (double)p->nz, scale = inv_cells(p);
   double *growth = p->lntab.get(), *dens = p->lntab.get() + p->nz, *A = p->lntab.get() + 2 * p->nz, *B = p->lntab.get() + 3 * p->nz, *sig = p->lntab.get() + 4 * p->nz;

@@ -75,6 +75,9 @@ int mt_geom(rf_plan* p, int single, MtGeom& g) {
   g.need = (size_t)g.nseg * g.cap * (single ? 2 * sizeof(float) : 2 * sizeof(double));
   return 0;
 }
+// the float32 form locates a row's pairs through a table that allows ONE segment boundary per row: segments (cap attempts,
+// ~0.785 cap pairs) must be longer than a row by a wide margin, or the float64 form (moved into cell order) serves
+bool pairs32_fit(const rf_plan* p, const MtGeom& g) { return g.cap >= 4ull * (unsigned long long)(p->nzc + 1); }
 int mt_ensure_buffers(rf_plan* p, const MtGeom& g) {
   RF_HIP(p->mt_states.reserve((size_t)g.nseg * 624 * sizeof(uint32_t)));
   const size_t seg = ((size_t)g.nseg + 1) * sizeof(unsigned long long);
@@ -124,7 +127,7 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
   RF_REQUIRE(p && state624, "null argument");
   // `single` is a request: plans without the fast float32 generation pass (float64, generic shapes, exact-generation
   // flag, tables too dense for the per-bin records) read float64 deviates and get them
-  if (single && (p->f64 || p->generic || !p->have_fast || p->exact_gen)) single = 0;
+  if (single && !resident_reads_pairs32(source_facts(p))) single = 0;
   RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
   RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
   RF_HIP(hipSetDevice(p->device));
@@ -132,9 +135,7 @@ int rf_noise_mt19937_ex(rf_plan* p, const uint32_t* state624, unsigned long long
     if (int rc = ensure_noise(p)) return rc;
   MtGeom g;
   if (int rc = mt_geom(p, single, g)) return rc;
-  // the float32 form locates a row's pairs through a table that allows ONE segment boundary per row: segments (cap attempts,
-  // ~0.785 cap pairs) must be longer than a row by a wide margin, or the float64 form (moved into cell order) serves
-  if (single && g.cap < 4ull * (unsigned long long)(p->nzc + 1)) {
+  if (single && !pairs32_fit(p, g)) {
     single = 0;
     if (int rc = ensure_noise(p)) return rc;
     if (int rc = mt_geom(p, single, g)) return rc;
@@ -400,12 +401,12 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
   RF_REQUIRE(n >= 1, "need at least one seed");
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
   RF_REQUIRE(p->mt_pos.get() && !p->mt_npos.empty(), "rf_mt_set_jump must be called first");
-  RF_REQUIRE(route(p).single() && !p->f64 && p->have_fast && !p->exact_gen,
+  RF_REQUIRE(route(p).single() && resident_reads_pairs32(source_facts(p)),
              "rf_realise_batch_reference is for single-GPU complex64 plans on the fast generation path; loop rf_noise_mt19937 + rf_realise otherwise");
   RF_HIP(hipSetDevice(p->device));
   MtGeom g;
   if (int rc = mt_geom(p, 1, g)) return rc;
-  RF_REQUIRE(g.cap >= 4ull * (unsigned long long)(p->nzc + 1), "the replay's segments are too short for the float32 form on this grid: loop rf_noise_mt19937 + rf_realise");
+  RF_REQUIRE(pairs32_fit(p, g), "the replay's segments are too short for the float32 form on this grid: loop rf_noise_mt19937 + rf_realise");
   if (int rc = mt_ensure_buffers(p, g)) return rc;
   if (int rc = ensure_x(p)) return rc;
   RF_HIP(hipStreamSynchronize(p->stream));
@@ -441,8 +442,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
     RF_HIP(hipEventRecord(p->bev[0], R));
     return 0;
   };
-  CallDesc cd;
-  cd.resident_fast = true;
+  const CallDesc cd(RF_NOISE_RESIDENT);
   auto issue = [&]() -> int {
     RF_HIP(p->tl.begin(S, false));
     RF_HIP(hop(p->bev[1], S, R));                         // (whatever ran on the main stream before the batch has finished with the runs)
@@ -451,7 +451,7 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
       RF_HIP(hipStreamWaitEvent(S, p->bev[0], 0));        // the runs of seed i are complete
       p->has.deviates32_ready();                          // (queue_x selects the float32-pair kernel by it; cleared again on failure)
       const bool xp = p->X.ptr && xpose_ok(p);
-      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT, false), nullptr, xp ? p->X.ptr : p->W.ptr, S, nullptr)) return rc;
+      if (int rc = queue_x(p, cd, make_gen(p, 0, RF_NOISE_RESIDENT), nullptr, xp ? p->X.ptr : p->W.ptr, S, nullptr)) return rc;
       RF_HIP(hipEventRecord(p->bev[1], S));               // the generation pass of seed i has read the runs
       if (i + 1 < n) {
         RF_HIP(hipStreamWaitEvent(R, p->bev[1], 0));
@@ -493,12 +493,11 @@ int rf_realise_batch_reference(rf_plan* p, const uint32_t* states, int n, double
 }
 
 int rf_can_batch_reference(rf_plan* p) {
-  if (!p || !route(p).single() || p->f64 || !p->have_fast || p->exact_gen || !p->have_kgrid ||
-      !p->have_power || !p->mt_pos.get() || p->mt_npos.empty())
+  if (!p || !route(p).single() || !resident_reads_pairs32(source_facts(p)) || !p->have_kgrid || !p->have_power || !p->mt_pos.get() || p->mt_npos.empty())
     return 0;
   MtGeom g;
   if (mt_geom(p, 1, g)) return 0;
-  return g.cap >= 4ull * (unsigned long long)(p->nzc + 1) ? 1 : 0;
+  return pairs32_fit(p, g) ? 1 : 0;
 }
 
 int rf_download_noise(rf_plan* p, double* host, unsigned long long first, unsigned long long count) {

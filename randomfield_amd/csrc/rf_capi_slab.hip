@@ -71,9 +71,7 @@ int rf_slab_forward(rf_plan* p, uint64_t seed, int mode, const double* noise_hos
   RF_REQUIRE(p->have_kgrid && p->have_power, "rf_set_kgrid and rf_set_power must be called first");
   RF_HIP(hipSetDevice(p->device));
   if (int rc = upload_noise(p, mode, noise_host)) return rc;
-  CallDesc cd;
-  cd.resident_fast = (mode == RF_NOISE_RESIDENT);
-  if (int rc = queue_xy(p, cd, make_gen(p, seed, mode, false), nullptr, p->W.ptr, p->stream, nullptr)) return rc;
+  if (int rc = queue_xy(p, CallDesc(mode), make_gen(p, seed, mode), nullptr, p->W.ptr, p->stream, nullptr)) return rc;
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;
 }
@@ -90,7 +88,7 @@ int rf_slab_forward_ex(rf_plan* p, uint64_t seed, int mode, const double* noise_
     if (int rc = potential_forward(p, seed, mode, noise_host, false)) return rc;
   } else {
     RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate, rf_load_potential or rf_upload_k first");
-    if (int rc = queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE, false), p->K.ptr, p->W.ptr, p->stream, nullptr)) return rc;
+    if (int rc = queue_xy(p, CallDesc(), make_gen(p, 0, RF_NOISE_NATIVE), p->K.ptr, p->W.ptr, p->stream, nullptr)) return rc;
   }
   RF_HIP(hipStreamSynchronize(p->stream));
   return 0;

@@ -1,8 +1,8 @@
 // rf_plan.h -- the plan object behind the C-ABI and the helpers its translation units share (rf_capi.hip: plans, inputs,
 // realisations, transforms, host <-> device; rf_capi_mt.hip: the MT19937 replay and its sharing between ranks; rf_capi_slab.hip: the
 // communicator and the slab pipeline in separate steps).  What the plan's buffers HOLD belongs to none of the three: it is the member
-// `has` (rf_contents.h), asked and changed through its predicates and transitions only; WHICH PIPELINE the plan runs is route(p) (rf_route.h),
-// worked out from the plan's facts per question.  Internal: nothing here crosses the C-ABI.
+// `has` (rf_contents.h), asked and changed through its predicates and transitions only; WHICH PIPELINE the plan runs is route(p) (rf_route.h) and
+// WHICH GENERATOR fills an x pass source(p, ask) (rf_source.h), worked out from the plan's facts per question.  Internal: nothing here crosses the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -23,6 +23,7 @@
 #include "rf_owned.h"
 #include "rf_route.h"
 #include "rf_select.h"
+#include "rf_source.h"
 #include "rf_timing.h"
 
 namespace rfc {
@@ -265,14 +266,27 @@ inline Route route(const rf_plan* p) {
   return route_of(f);
 }
 
+// which generator fills an x pass of the plan (rf_source.h), from the plan's facts as they are at the moment of the call
+inline SourceFacts source_facts(const rf_plan* p) {
+  SourceFacts f;
+  f.f64 = p->f64 != 0; f.have_fast = p->have_fast; f.exact_gen = p->exact_gen; f.kind = route(p).kind;
+  f.deviates = p->has.deviates32() ? SourceFacts::Pairs32 : p->has.deviates64() ? SourceFacts::Float64 : SourceFacts::None;
+  return f;
+}
+inline Source source(const rf_plan* p, const SourceAsk& ask) { return source_of(source_facts(p), ask); }
+static_assert(SourceAsk::Native == RF_NOISE_NATIVE && SourceAsk::External == RF_NOISE_EXTERNAL && SourceAsk::Resident == RF_NOISE_RESIDENT, "noise modes");
+
 // What ONE call asks of the passes it queues.  The entry point builds it on its stack and hands it down by const reference
-// (queue_c2r ... queue_x / queue_yz / make_fast); a default-constructed one is a plain realisation.  Nothing of it outlives the call.
+// (queue_c2r ... queue_x / queue_yz / make_fast); a default-constructed one is a plain NATIVE realisation, or the transform of a given k-space array.  Nothing of it outlives the call.
 struct CallDesc {
-  bool resident_fast = false;             // draw from the device-resident deviates (RF_NOISE_RESIDENT)
+  explicit CallDesc(int noise_mode = RF_NOISE_NATIVE) : mode(noise_mode) {}
+  int mode;                               // the noise mode as the API names it (RF_NOISE_RESIDENT: draw from the device-resident deviates)
   bool emit_potential = false;            // transform emit_pscale * delta(k) / k^2 instead of delta(k) (rf_realise_scaled_potential)
   double emit_pscale = 0.0;
   const double* zscale = nullptr;         // the z pass multiplies plane z by zscale[z] (device table: ztab)
   void* pot_target = nullptr;             // the x pass also stores delta(k) / k^2 there (rf_realise_potential)
+  // what the call's x pass asks of source(p, ...) (kspace: it transforms that array instead of generating)
+  SourceAsk ask(bool kspace) const { return SourceAsk::x_pass(kspace, mode, emit_potential ? SourceAsk::Emitted : pot_target ? SourceAsk::Stored : SourceAsk::Nothing); }
 };
 
 // (defined in rf_capi.hip)
@@ -281,7 +295,7 @@ int ensure_k(rf_plan* p);
 int ensure_x(rf_plan* p);
 int ensure_noise(rf_plan* p);
 bool xpose_ok(const rf_plan* p);
-GenParams make_gen(rf_plan* p, uint64_t seed, int mode, bool seed_from_dev);
+GenParams make_gen(rf_plan* p, uint64_t seed, int mode);
 int upload_noise(rf_plan* p, int mode, const double* noise_host);
 int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t sx, Timeline* tl, int kz0c = -1, int nzlc = -1);
 int queue_xy(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* kspace, void* W, hipStream_t s, Timeline* tl, int rbuf = 0);
