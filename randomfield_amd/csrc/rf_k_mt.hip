@@ -188,10 +188,13 @@ __global__ __launch_bounds__(MT_JUMP_THREADS) void mt_jump_kernel(const uint32_t
 //     f = sqrt(-2 ln r2 / r2) with the hardware log2 / rcp / sqrt.  Final for 2^-9 <= r2 <= 1 - 2^-8 (78 % of the attempts) and for
 //     r2 >= 1 + 1e-6 (rejected for certain).
 //   the bands r2 > 1 - 2^-8 (ln r2 -> 0 loses the relative accuracy of r2; acceptance uncertain within 1e-6 of 1) and r2 < 2^-9 (the
-//     5-sigma deviates: the left-out +-2^-27 would be more than 2.4e-7 of x), and every lane of the float64 form: numpy's own float64
+//     5-sigma deviates: the left-out +-2^-27 would be more than 2.4e-7 of x), the attempts with r2 < 5 * 2^-9 one of whose components is
+//     below 2^-6 (0.17 % of the attempts: f = 31 ... 80 there lifts such a component to a deviate of up to 0.5 ... 1.2, of which the
+//     left-out +-2^-27 was up to 1.3e-6 -- found by tests/test_gpu_replay_matrix.py on 4.2 M cells; without them the fast path keeps
+//     |g| > 0.5 within 1e-6), and every lane of the float64 form: numpy's own float64
 //     arithmetic -- x = a 2^-26 + (b 2^-52 - 1) in two fused multiply-adds (every step of numpy's (a 2^26 + b) / 2^53, 2u - 1 is exact
 //     in float64, so this is the same number), r2 with both products rounded as numpy's C code rounds them, 0 < r2 < 1.  One wave
-//     iteration in four holds such a lane and pays ~60 float64-rate instructions and two more temperings.
+//     iteration in three holds such a lane and pays ~60 float64-rate instructions and two more temperings.
 //   (Round 5 replaced the float64 band path by compensated float32 arithmetic -- d = r2 - 1 from the exact squares of the 28-bit
 //   integers by TwoSum / fused-multiply-add residuals, log1p by its series, float64 only for |d| < 2^-11: no acceptance differed over
 //   4e7 modelled attempts, and the replay took exactly as long (3.74 - 3.78 against 3.73 - 3.77 ms per 1024^3, profiles/r05_ab/
@@ -224,7 +227,9 @@ __device__ __forceinline__ bool mt_polar_attempt(const unsigned raw_x, const uns
     const float hi1 = (float)S1, hi2 = (float)S2;
     const float x1f = hi1 * 0x1p-27f, x2f = hi2 * 0x1p-27f;
     const float r2f = fmaf(x1f, x1f, x2f * x2f);
-    if (r2f <= 0.99609375f && r2f >= 0.001953125f) {                       // the fast path is final
+    // (a component |x| < 2^-6 next to r2 < 5 * 2^-9: f > 30.8 can lift it to |g| > 0.48, of which the left-out +-2^-27 is up to 1.2e-6)
+    const bool small_x = r2f < 0.009765625f && fminf(fabsf(x1f), fabsf(x2f)) < 0.015625f;
+    if (r2f <= 0.99609375f && r2f >= 0.001953125f && !small_x) {           // the fast path is final
       exact = false;
       acc = true;
       const float inv = __builtin_amdgcn_rcpf(r2f);

@@ -72,6 +72,7 @@ import numpy as np
 
 import axis_matrix as am
 import epilogue_matrix as em
+from replay_matrix import stream_segments          # noqa: F401  (the oracle of the replayed stream lives with the replay's table)
 from oracle import cpu_ref
 
 C64, C128 = am.C64, am.C128
@@ -284,25 +285,6 @@ def oracle_for(vid, shape, dtype, power):
 
 
 # ---- the replayed stream on the host: per-segment accepted counts ------------------------------------------------------------
-def stream_segments(seed, ncells, blocks):
-    """exclusive scan `first` (nseg + 1 entries) of the accepted polar attempts per segment of `blocks` x 624 words of
-    RandomState(seed)'s stream, as many segments as the replay runs for ncells cells: mt19937.sequence / temper and numpy's
-    acceptance rule (legacy_gauss: 0 < r2 < 1 on 53-bit doubles from two words each)"""
-    from randomfield_amd import mt19937
-    total_blocks = -(-4 * mt19937.attempts_needed(ncells) // 624)
-    nseg = -(-total_blocks // blocks)
-    words = mt19937.temper(mt19937.sequence(mt19937.seed_state(seed), nseg * blocks * 624)).astype(np.uint64).reshape(-1, 4)
-    x = [((words[:, 2 * i] >> np.uint64(5)).astype(np.float64) * 67108864.0 + (words[:, 2 * i + 1] >> np.uint64(6)).astype(np.float64)) / 9007199254740992.0
-         for i in (0, 1)]
-    x1, x2 = 2.0 * x[0] - 1.0, 2.0 * x[1] - 1.0
-    r2 = x1 * x1 + x2 * x2
-    ok = (r2 < 1.0) & (r2 != 0.0)
-    counts = ok.reshape(nseg, blocks * 156).sum(axis=1)
-    first = np.zeros(nseg + 1, np.uint64)
-    first[1:] = np.cumsum(counts)
-    return first
-
-
 def stream_runs(seed, first, blocks):
     """the float32 pairs of the stream where the one-pass replay leaves them: segment s's accepted pairs densely from slot
     s x 156 blocks, [nseg x cap][2]"""
