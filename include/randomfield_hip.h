@@ -53,7 +53,9 @@ enum { RF_LAYOUT_DENSE = 0, RF_LAYOUT_PADDED = 1 };
  * And for the assignment scheme as an argument, with the triangular-shaped cloud as the second scheme -- rf_particles_paint_ex,
  * rf_particles_gather_ex: rf_abi_features() & RF_FEATURE_PARTICLES_TSC, the version stays 5.5.
  * And for the interlaced paint -- rf_particles_paint_shifted, rf_kspace_stash, rf_kspace_interlace, rf_particles_paint_interlaced:
- * rf_abi_features() & RF_FEATURE_PARTICLES_INTERLACE, the version stays 5.5. */
+ * rf_abi_features() & RF_FEATURE_PARTICLES_INTERLACE, the version stays 5.5.
+ * And for the binned bispectrum -- rf_measure_bispectrum, rf_bispectrum_release: rf_abi_features() & RF_FEATURE_BISPECTRUM, the version
+ * stays 5.5. */
 #define RF_ABI_MAJOR 5
 #define RF_ABI_MINOR 5
 #define RF_ABI_VERSION ((RF_ABI_MAJOR << 16) | RF_ABI_MINOR)
@@ -88,8 +90,9 @@ enum {
                                               interpolated at the particles (cloud in cell, the paint's adjoint), and the particles moved by it */
   RF_FEATURE_PARTICLES_TSC = 1 << 20,      /* rf_particles_paint_ex, rf_particles_gather_ex: the paint and the gather with the assignment scheme
                                               as an argument, RF_ASSIGN_CIC or RF_ASSIGN_TSC (triangular-shaped cloud, three cells per axis) */
-  RF_FEATURE_PARTICLES_INTERLACE = 1 << 21 /* rf_particles_paint_shifted, rf_kspace_stash, rf_kspace_interlace, rf_particles_paint_interlaced:
+  RF_FEATURE_PARTICLES_INTERLACE = 1 << 21, /* rf_particles_paint_shifted, rf_kspace_stash, rf_kspace_interlace, rf_particles_paint_interlaced:
                                               the paint on a grid shifted by half a cell and the two spectra combined (interlacing) */
+  RF_FEATURE_BISPECTRUM = 1 << 22          /* rf_measure_bispectrum, rf_bispectrum_release: the FFT estimator of the binned bispectrum */
 };
 unsigned rf_abi_features(void);
 const char* rf_last_error(void);
@@ -468,6 +471,36 @@ int rf_measure_power(rf_plan* plan, int source, const double* k_edges, int nbins
 int rf_measure_multipoles(rf_plan* plan, int source, int los_axis, const double* k_edges, int nbins,
                           const double* comp_x, const double* comp_y, const double* comp_z,
                           unsigned long long* count, double* sum_k, double* m0, double* m2, double* m4);
+
+/* ---- binned bispectrum (rf_abi_features() & RF_FEATURE_BISPECTRUM) -- */
+/* The FFT estimator of the bispectrum (Scoccimarro 2015; Sefusatti et al. 2016) of the half spectrum in the k buffer.  k_edges: nbins + 1
+ * strictly increasing edges in k, k_edges[0] >= 0, 1 <= nbins <= 32, squared once in float64; cell (ix, iy, iz) with
+ * k^2 = (kx2[ix] + ky2[iy]) + kz2[iz] belongs to shell b iff e2[b] <= k^2 < e2[b+1] and the DC cell to none: rf_measure_power's bins,
+ * bit for bit.  For every shell, D_b(x) = the inverse transform (1/N, as rf_execute_c2r) of the spectrum restricted to shell b.
+ * triples: ntriples x 3 bin indices, 1 <= ntriples <= 8192, every triple 0 <= b1 <= b2 <= b3 < nbins, duplicates allowed.
+ *   sum3[t] = sum over all N = nx ny nz cells x of D_b1(x) D_b2(x) D_b3(x),
+ * every term ((double)D1 (double)D2) (double)D3 with both products rounded on their own, the terms summed in float64 in a fixed order
+ * without floating-point atomics: the same plan, data, edges and triples give the same bits on every call.  In exact arithmetic
+ * N^2 sum3[t] is the sum of delta(k1) delta(k2) delta(k3) over all ORDERED triangles k_i in shell b_i with k1 + k2 + k3 = 0 modulo
+ * the grid -- triangles that close only through aliasing included (none exists while the last edge is at most 2/3 of the Nyquist
+ * frequency).  unit != 0: delta = 1 inside the shells, so that N^2 sum3[t] is the integer number of those triangles.  With
+ * V = N spacing^3 the estimate is B = (V^2 / N^3) sum3_data / sum3_unit.
+ * amp_x, amp_y, amp_z: float64 tables of nx, ny, nz/2 + 1 finite positive entries, each may be NULL (= ones): delta(k) is multiplied by
+ * amp = (amp_x[ix] amp_y[iy]) amp_z[iz] in float64 and rounded once per component to the plan's type (window compensation: the square
+ * roots of rf_measure_multipoles' tables); with three NULLs the kept cells are taken bit for bit.  Ignored (not even checked) when
+ * unit != 0.
+ * Reads the k buffer and the tables of rf_set_kgrid.  The k buffer, its validity, the stash, both potentials and the particle arrays
+ * are untouched, bit for bit.  The field buffer is the transforms' workspace: afterwards there is no real-space field on any kind of
+ * plan (rf_download_real refuses).  Lazy memory, counted by rf_plan_nbytes and freed by rf_bispectrum_release or with the plan: one
+ * masked half spectrum (the k buffer's size), nbins shell fields (the field buffer's size each), and
+ * 8 (12321 + nx + ny + nz/2 + 1 + rows ntriples) bytes of tables and per-workgroup partials, rows as rf_bispectrum_geometry
+ * (randomfield_hip_diag.h) reports them; a plan that has not transformed anything yet also allocates the transforms' own scratch.
+ * Packed single-rank plans, tiled and generic, both dtypes.  c2c plans, nranks > 1, RF_FLAG_FORCE_SLAB_PATH, a missing kgrid, missing
+ * k-space data, bad edges, a bad triple and a bad table entry are refused with nothing queued and nothing allocated.  Blocks until
+ * sum3 is on the host; rf_elapsed_ms covers the call, rf_kernel_ms gives [0] the shell filters, [1] the transforms, [2] the reduction. */
+int rf_measure_bispectrum(rf_plan* plan, const double* k_edges, int nbins, const int* triples, int ntriples,
+                          const double* amp_x, const double* amp_y, const double* amp_z, int unit, double* sum3);
+int rf_bispectrum_release(rf_plan* plan);      /* frees the call's lazy buffers */
 
 /* ---- host <-> device (layout conversion to/from the reference's arrays) -- */
 int rf_upload_k(rf_plan* plan, const void* host);            /* (nx, ny, nz/2+1) complex */

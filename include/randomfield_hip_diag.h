@@ -71,6 +71,15 @@ int rf_particles_paint_geometry(rf_plan* plan, int* brick3, int* halo);
 /* which kernel rf_particles_gather runs: 0 = the library's choice, 1 = global (one lane per particle, eight loads of the field from
  * memory), 2 = tiled (the paint's brick + halo tile of the field staged in LDS, particles that leave it read memory).  Same bits. */
 int rf_particles_set_gather_form(rf_plan* plan, int form);
+/* shell field b of the last rf_measure_bispectrum, dense [nx][ny][nz] of the plan's real type; refused before a call, after
+ * rf_bispectrum_release and for b outside the last call's bins */
+int rf_bispectrum_download_shell(rf_plan* plan, int b, void* host);
+/* the workgroup cap of rf_measure_bispectrum's kernels (0 = the default: 1024 for the reduction, 4096 for the shell filter), so that a
+ * test reaches their grid-stride loops on a grid of a few MB.  The reduction's sums keep their definition; their bits depend on the cap. */
+int rf_bispectrum_set_max_workgroups(rf_plan* plan, int n);
+/* how the reduction of a call with these counts would run on this plan: cells per LDS chunk, workgroups (per tile of triples), and the
+ * rows of per-workgroup partials (workgroups x cell groups) that enter the documented size of the call's lazy memory */
+int rf_bispectrum_geometry(rf_plan* plan, int nbins, int ntriples, int* chunk_cells, int* workgroups, int* partial_rows);
 
 /* What the plans of this process hold right now: bytes of device memory, HIP events, HIP streams (every allocation a plan makes is an
  * owning member of it, csrc/rf_owned.h).  Back at their earlier values once the plans made in between are destroyed: "freed with the plan",

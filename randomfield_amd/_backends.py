@@ -19,6 +19,16 @@ class _Backend(object):
         self.field_on_host = False          # the plan's host buffer holds the current field
         # None, or as the backend holds them: displacements, gathered values, the last interlaced spectrum, the second-order potential
         self.particles = self.gathered = self.interlaced = self.lpt2 = None
+        self._unit_sums = {}                # bispectrum: the unit run's sums per (edges, triples), a function of the grid alone
+
+    def unit_sums(self, k_edges, triples, run):
+        """the triangle-count sums of a bispectrum measurement: ``run()`` once per (edges, triples), the last few kept"""
+        key = (np.asarray(k_edges, np.float64).tobytes(), np.asarray(triples, np.intc).tobytes())
+        if key not in self._unit_sums:
+            if len(self._unit_sums) >= 8:
+                self._unit_sums.pop(next(iter(self._unit_sums)))
+            self._unit_sums[key] = run()
+        return self._unit_sums[key]
 
     @property
     def gen(self):
@@ -77,6 +87,18 @@ class NumpyBackend(_Backend):
         if los is None:
             return powertools.bin_power(spectrum, self.spacing, k_edges)
         return powertools.bin_multipoles(spectrum, self.spacing, k_edges, los, window)
+
+    def bispectrum_sums(self, k_edges, triples, source, window=None):
+        """-> (the per-bin sums of P(k) on the same edges and spectrum -- compensated with ``window`` --, sum3, sum3 of the unit run)"""
+        spectrum = self.interlaced if source == "kspace" else np.fft.rfftn(np.asarray(self.plan.data_out, np.float64), axes=(0, 1, 2))
+        if window is None:
+            power = powertools.bin_power(spectrum, self.spacing, k_edges)
+        else:
+            power = powertools.bin_multipoles(spectrum, self.spacing, k_edges, 2, window)[:3]
+        amp = None if window is None else [None if t is None else np.sqrt(t) for t in window]
+        sum3 = powertools.bin_bispectrum(spectrum, self.spacing, k_edges, triples, amp)
+        unit = self.unit_sums(k_edges, triples, lambda: powertools.bin_bispectrum(spectrum, self.spacing, k_edges, triples, unit=True))
+        return power, sum3, unit
 
     def delta_to_density(self, growth, density, rms, lognormal, download):
         delta = self.plan.data_out
@@ -376,6 +398,20 @@ class HipBackend(_Backend):
         if los is None:
             return self.dev.measure_power(k_edges, source)
         return self.dev.measure_multipoles(k_edges, los, source, window)
+
+    def bispectrum_sums(self, k_edges, triples, source, window=None):
+        """as :meth:`NumpyBackend.bispectrum_sums`: the field transformed into the k buffer first (``source='field'``), then everything
+        reads the k buffer; the device copy of the field is consumed"""
+        if source != "kspace":
+            self.dev.execute_r2c()
+        if window is None:
+            power = self.dev.measure_power(k_edges, _hip.RF_POWER_FROM_KSPACE)
+        else:
+            power = self.dev.measure_multipoles(k_edges, 2, _hip.RF_POWER_FROM_KSPACE, window)[:3]
+        amp = None if window is None else [None if t is None else np.sqrt(t) for t in window]
+        sum3 = self.dev.measure_bispectrum(k_edges, triples, amp)
+        unit = self.unit_sums(k_edges, triples, lambda: self.dev.measure_bispectrum(k_edges, triples, unit=True))
+        return power, sum3, unit
 
     def delta_to_density(self, growth, density, rms, lognormal, download):
         if lognormal:

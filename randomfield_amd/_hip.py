@@ -35,7 +35,7 @@ FEATURES = {"realise": 1 << 0, "r2c": 1 << 1, "c2c": 1 << 2, "lognormal": 1 << 3
             "mt19937": 1 << 6, "mt19937_shared": 1 << 7, "multi_rank": 1 << 8, "generic_shapes": 1 << 9, "exchange_chunks": 1 << 10,
             "diagnostics": 1 << 11, "direct_exchange": 1 << 12, "generic_fused": 1 << 13, "gradient": 1 << 14,
             "power_measure": 1 << 15, "lpt2": 1 << 16, "particles": 1 << 17, "power_multipoles": 1 << 18,
-            "particles_gather": 1 << 19, "particles_tsc": 1 << 20, "particles_interlace": 1 << 21}
+            "particles_gather": 1 << 19, "particles_tsc": 1 << 20, "particles_interlace": 1 << 21, "bispectrum": 1 << 22}
 
 # name -> (restype, argtypes); every symbol of include/randomfield_hip.h (the consumer surface) ...
 SIGNATURES = {
@@ -106,6 +106,9 @@ SIGNATURES = {
     "rf_measure_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp]),
     "rf_measure_multipoles": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp,
                                             ctypes.POINTER(ctypes.c_ulonglong), _c_dp, _c_dp, _c_dp, _c_dp]),
+    "rf_measure_bispectrum": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _c_dp, _c_dp, _c_dp,
+                                            ctypes.c_int, _c_dp]),
+    "rf_bispectrum_release": (ctypes.c_int, [ctypes.c_void_p]),
     "rf_lensing_potential": (ctypes.c_int, [ctypes.c_void_p, _c_dp, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "rf_download_aux": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "rf_upload_k": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -140,6 +143,9 @@ DIAG_SIGNATURES = {
     "rf_particles_set_paint_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rf_particles_paint_geometry": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "rf_particles_set_gather_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rf_bispectrum_download_shell": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rf_bispectrum_set_max_workgroups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rf_bispectrum_geometry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "rf_set_merged_yz": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rf_merged_yz_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]),
     "rf_yz_slabs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -861,6 +867,52 @@ class DevicePlan(object):
                                               count.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), *[_dp(v) for v in sums]),
               "rf_measure_multipoles")
         return (count,) + tuple(sums)
+
+    def measure_bispectrum(self, edges, triples, amp=None, unit=False):
+        """The triple sums of the FFT bispectrum estimator over the k buffer (rf_measure_bispectrum): ``edges`` are ``nbins + 1``
+        increasing edges in k (at most 32 bins), ``triples`` an ``(ntriples, 3)`` integer array of bins b1 <= b2 <= b3 (at most 8192
+        rows); returns the float64 array ``sum3[t] = sum_x D_b1 D_b2 D_b3`` of the shell fields D_b.  ``amp``: None or three float64
+        tables of nx, ny, nz/2 + 1 finite positive factors multiplied onto delta(k) (each may be None); ``unit=True`` sets delta = 1
+        inside the shells (N**2 sum3 is then the number of closed triangles) and ignores ``amp``.  The k buffer is only read; the
+        device copy of the field is consumed on every kind of plan.  The call's memory (a masked spectrum and ``nbins`` shell fields)
+        stays until :meth:`bispectrum_release`."""
+        e = _f64(np.asarray(edges, np.float64).ravel())
+        nbins = len(e) - 1
+        tri = np.ascontiguousarray(np.asarray(triples).reshape(-1, 3), dtype=np.intc)
+        lengths = (self.nx, self.ny, self.nz // 2 + 1)
+        tabs = [None] * 3 if amp is None else list(amp)
+        if len(tabs) != 3:
+            raise ValueError("measure_bispectrum: amp is three per-axis tables")
+        for a in range(3):
+            if tabs[a] is not None:
+                tabs[a] = _f64(np.asarray(tabs[a], np.float64).ravel())
+                if len(tabs[a]) != lengths[a]:
+                    raise ValueError("measure_bispectrum: amp table %d needs %d entries" % (a, lengths[a]))
+        sum3 = np.zeros(max(len(tri), 1), np.float64)
+        check(self._lib.rf_measure_bispectrum(self._h, _dp(e), nbins, tri.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(tri),
+                                              *[None if t is None else _dp(t) for t in tabs], int(bool(unit)), _dp(sum3)),
+              "rf_measure_bispectrum")
+        return sum3[:len(tri)]
+
+    def bispectrum_release(self):
+        """free the lazy memory of :meth:`measure_bispectrum` (rf_bispectrum_release)"""
+        check(self._lib.rf_bispectrum_release(self._h), "rf_bispectrum_release")
+
+    def bispectrum_download_shell(self, b):
+        """diagnostic: shell field ``b`` of the last :meth:`measure_bispectrum`, an (nx, ny, nz) array of the plan's real type"""
+        out = np.empty((self.nx, self.ny, self.nz), self.real_dtype)
+        check(self._lib.rf_bispectrum_download_shell(self._h, int(b), out.ctypes.data_as(ctypes.c_void_p)), "rf_bispectrum_download_shell")
+        return out
+
+    def bispectrum_set_max_workgroups(self, n=0):
+        """diagnostic: the workgroup cap of :meth:`measure_bispectrum`'s kernels, 0 = the library's own"""
+        check(self._lib.rf_bispectrum_set_max_workgroups(self._h, int(n)), "rf_bispectrum_set_max_workgroups")
+
+    def bispectrum_geometry(self, nbins, ntriples):
+        """diagnostic: ``(chunk_cells, workgroups, partial_rows)`` of the reduction of a call with these counts (rf_bispectrum_geometry)"""
+        v = [ctypes.c_int(0) for _ in range(3)]
+        check(self._lib.rf_bispectrum_geometry(self._h, int(nbins), int(ntriples), *[ctypes.byref(x) for x in v]), "rf_bispectrum_geometry")
+        return tuple(x.value for x in v)
 
     # -- host <-> device --------------------------------------------------
     @property

@@ -1273,6 +1273,56 @@ int emu_measure_multipoles(int f64, int nx, int ny, int nz, int packed, int los,
   double* const sums[4] = {sum_k, m0, m2, m4};
   return measure_bins(f64, nx, ny, nz, packed, kx2, ky2, kz2, S, edges, nbins, g, count, sums);
 }
+// The shell filter of rf_measure_bispectrum (rf_core.h shell_cell, the function shell_filter_kernel calls per cell): M = the API-layout
+// half spectrum K restricted to shell `shell` of the nbins + 1 edges (squared here as the host side of the device call squares them);
+// ax, ay, az: tables of nx, ny, nz/2 + 1 finite positive entries or null; unit != 0: 1 inside the shell, the tables ignored
+int emu_kspace_shell(int f64, int nx, int ny, int nz, const double* kx2, const double* ky2, const double* kz2, const void* K, const double* edges,
+                     int nbins, int shell, const double* ax, const double* ay, const double* az, int unit, void* M) {
+  if (nx < 1 || ny < 1 || nz < 2 || (nz & 1) || nbins < 1 || nbins > BISPECTRUM_MAX_BINS || shell < 0 || shell >= nbins ||
+      !(kx2 && ky2 && kz2 && K && M && edges) || K == M || !(edges[0] >= 0.0))
+    return -1;
+  for (int b = 0; b < nbins; ++b) if (!(edges[b] < edges[b + 1])) return -1;
+  const double* amp[3] = {ax, ay, az};
+  const int alen[3] = {nx, ny, nz / 2 + 1};
+  for (int a = 0; a < 3 && !unit; ++a)
+    for (int i = 0; amp[a] && i < alen[a]; ++i) if (!(std::isfinite(amp[a][i]) && amp[a][i] > 0.0)) return -1;
+  ShellParams g;
+  memset(&g, 0, sizeof(g));
+  g.p.nx = nx; g.p.ny = ny; g.p.nz = nz; g.p.nbins = nbins;
+  g.p.kx2 = kx2; g.p.ky2 = ky2; g.p.kz2 = kz2;
+  g.unit = unit != 0;
+  if (!unit) { g.ax = ax; g.ay = ay; g.az = az; }
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = edges[b] * edges[b];
+  const int nzh = nz / 2 + 1;
+  for (int ix = 0; ix < nx; ++ix)
+    for (int iy = 0; iy < ny; ++iy) {
+      const long long row = ((long long)ix * ny + iy) * nzh;
+      for (int iz = 0; iz < nzh; ++iz) {
+        if (f64) ((cplx<double>*)M)[row + iz] = shell_cell<double>(g, e2.data(), shell, ((const cplx<double>*)K)[row + iz], ix, iy, iz);
+        else ((cplx<float>*)M)[row + iz] = shell_cell<float>(g, e2.data(), shell, ((const cplx<float>*)K)[row + iz], ix, iy, iz);
+      }
+    }
+  return 0;
+}
+// The triple sums of rf_measure_bispectrum over nbins dense fields F[nbins][ncells] of the plan's real type (rf_core.h bispectrum_add,
+// the function bispectrum_sum_kernel calls per term): out[t] = sum over the cells, in cell order, of D_b1 D_b2 D_b3 for the ntriples
+// triples (b1, b2, b3), 0 <= b1 <= b2 <= b3 < nbins.  The device sums the same terms in its own fixed order.
+int emu_bispectrum_sums(int f64, long long ncells, int nbins, const void* F, const int* triples, int ntriples, double* out) {
+  if (ncells < 1 || nbins < 1 || nbins > BISPECTRUM_MAX_BINS || ntriples < 1 || ntriples > BISPECTRUM_MAX_TRIPLES || !(F && triples && out)) return -1;
+  for (int t = 0; t < ntriples; ++t)
+    if (!(0 <= triples[3 * t] && triples[3 * t] <= triples[3 * t + 1] && triples[3 * t + 1] <= triples[3 * t + 2] && triples[3 * t + 2] < nbins)) return -1;
+  for (int t = 0; t < ntriples; ++t) {
+    const long long o1 = triples[3 * t] * ncells, o2 = triples[3 * t + 1] * ncells, o3 = triples[3 * t + 2] * ncells;
+    double s = 0.0;
+    for (long long i = 0; i < ncells; ++i) {
+      if (f64) s = bispectrum_add(s, ((const double*)F)[o1 + i], ((const double*)F)[o2 + i], ((const double*)F)[o3 + i]);
+      else s = bispectrum_add(s, (double)((const float*)F)[o1 + i], (double)((const float*)F)[o2 + i], (double)((const float*)F)[o3 + i]);
+    }
+    out[t] = s;
+  }
+  return 0;
+}
 int emu_generic_r2c(int f64, int nx, int ny, int nz, const void* W, void* K) {
   return f64 ? generic_r2c_impl<double>(nx, ny, nz, (const double*)W, (cplx<double>*)K)
              : generic_r2c_impl<float>(nx, ny, nz, (const float*)W, (cplx<float>*)K);

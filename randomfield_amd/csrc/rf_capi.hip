@@ -592,7 +592,7 @@ int sink_finish(rf_plan* p) {
 // the call's last pass being queued here, its end -- in front of the last slab's copy to a host sink, which waits on the host.
 int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* stats_out, Timeline* tl) {
   const long long nzl = p->nzl;
-  const bool sink = p->sink_host != nullptr && !cd.zscale && !capturing(s);      // (a captured batch keeps its fields on the device)
+  const bool sink = p->sink_host != nullptr && !cd.zscale && !cd.intermediate && !capturing(s);      // (a captured batch keeps its fields on the device)
   const double scale = inv_cells(p);
   const bool xp = p->X.ptr && xpose_ok(p);
   const long long rb = xpose_row_block(p), tc = col_tile_cols(p->f64, p->ny);
@@ -629,7 +629,7 @@ int queue_yz(rf_plan* p, const CallDesc& cd, void* W, hipStream_t s, double* sta
       if (i > 0) if (int rc = sink_copy(p, W, x0 - B, B, i - 1)) return rc;                          // (slab i - 1, while the GPU runs slab i)
     }
   }
-  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
+  if (!cd.intermediate) RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, s));
   if (tl) RF_HIP(tl->end(s));
   if (sink) {
     if (int rc = sink_copy(p, W, (long long)(sl.count - 1) * B, sl.last, sl.count - 1)) return rc;
@@ -721,16 +721,19 @@ int ensure_g2(rf_plan* p) {
 // from != null: the x pass takes its cells from that descriptor instead of loading K (generic_c2r_from_seq) -- GenParams: it generates
 // the half spectrum (RF_FLAG_FUSED_GENERIC_GENERATION; K is ignored); GradParams / HessParams: K is the array whose gradient / Hessian
 // component is transformed, and is only read.  tl: marks behind the x pass, the y pass and the contiguous pass.
+// dst != null: the field goes there instead of the plan's field buffer -- an intermediate of the call (rf_measure_bispectrum's shell
+// fields): its moments are not reduced and stats_out is not written.
 template <class From>
-int generic_c2r(rf_plan* p, const void* K, double* stats_out, Timeline* tl, const From* from) {
+int generic_c2r(rf_plan* p, const void* K, double* stats_out, Timeline* tl, const From* from, void* dst = nullptr) {
   if (int rc = ensure_g(p)) return rc;
   if (int rc = ensure_g2(p)) return rc;
   HipGenericOps ops{p, p->stream, tl};
   const double scale = inv_cells(p);
-  if (from) { if (int rc = generic_c2r_from_seq(ops, p->gdims, *from, K, p->G.ptr, p->G2.ptr, p->W.ptr, scale)) return rc; }
-  else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G.ptr, p->G2.ptr, p->W.ptr, scale)) return rc;
+  void* W = dst ? dst : p->W.ptr;
+  if (from) { if (int rc = generic_c2r_from_seq(ops, p->gdims, *from, K, p->G.ptr, p->G2.ptr, W, scale)) return rc; }
+  else if (int rc = generic_c2r_seq(ops, p->gdims, K, p->G.ptr, p->G2.ptr, W, scale)) return rc;
   if (int rc = ops.enter(3)) return rc;
-  RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, p->stream));
+  if (!dst) RF_HIP(launch_reduce_partials(p->partials.get(), p->npartials, stats_out, p->partials.get() + 2 * p->npartials, p->stream));
   return 0;
 }
 
@@ -870,7 +873,7 @@ unsigned rf_abi_features(void) {
          RF_FEATURE_MT19937 | RF_FEATURE_MT19937_SHARED | RF_FEATURE_MULTI_RANK | RF_FEATURE_GENERIC_SHAPES | RF_FEATURE_EXCHANGE_CHUNKS |
          RF_FEATURE_DIRECT_EXCHANGE | RF_FEATURE_DIAGNOSTICS | RF_FEATURE_GENERIC_FUSED | RF_FEATURE_GRADIENT | RF_FEATURE_POWER_MEASURE | RF_FEATURE_LPT2 |
          RF_FEATURE_PARTICLES | RF_FEATURE_POWER_MULTIPOLES | RF_FEATURE_PARTICLES_GATHER | RF_FEATURE_PARTICLES_TSC |
-         RF_FEATURE_PARTICLES_INTERLACE;
+         RF_FEATURE_PARTICLES_INTERLACE | RF_FEATURE_BISPECTRUM;
 }
 
 const char* rf_last_error(void) { return g_err.c_str(); }
@@ -1030,7 +1033,8 @@ int rf_plan_destroy(rf_plan* p) {
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
   *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes + p->PG.bytes +
-            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes + p->KS.bytes;      // (+ resident deviates and the replay's scratch runs)
+            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes + p->KS.bytes +      // (+ resident deviates and the replay's scratch runs)
+            p->bs_mask.bytes + p->bs_fields.bytes + p->bs_part.bytes;
   return 0;
 }
 
@@ -2146,6 +2150,134 @@ int rf_measure_multipoles(rf_plan* p, int source, int los_axis, const double* k_
   g.los = los_axis;
   const double** const comp_dev[3] = {&g.cx, &g.cy, &g.cz};
   return measure_bins(p, source, k_edges, nbins, p->mp_buf, g, comp, comp_dev, count, sums);
+}
+
+// ---- the binned bispectrum (rf_core.h shell_cell / bispectrum_add; rf_k_bispectrum.hip) ----
+static int bispectrum_check(rf_plan* p) {
+  RF_REQUIRE(p, "null plan");
+  RF_REQUIRE(!p->unpacked, "this call does not apply to an unpacked c2c plan");
+  RF_REQUIRE(p->nranks == 1, "the bispectrum measurement runs on single-rank plans");
+  return 0;
+}
+// the 8-byte words of bs_part in front of the partials: [squared edges][result][packed triples][amplitude tables]
+static size_t bispectrum_head_words(const rf_plan* p) {
+  return (BISPECTRUM_MAX_BINS + 1) + BISPECTRUM_MAX_TRIPLES + BISPECTRUM_MAX_TRIPLES / 2 + ((size_t)p->nx + p->ny + p->nz / 2 + 1);
+}
+// the inverse transform of the masked half spectrum M into the dense real array D, an intermediate of the call: no moments, no host sink
+static int bispectrum_c2r(rf_plan* p, const void* M, void* D) {
+  if (p->generic) return generic_c2r<GenParams>(p, M, nullptr, nullptr, nullptr, D);
+  CallDesc cd;
+  cd.intermediate = true;
+  return queue_xyz(p, cd, make_gen(p, 0, RF_NOISE_NATIVE), M, D, p->stream, nullptr, nullptr);
+}
+// For every shell b: filter K into the masked spectrum, transform that into shell field b; then all triples in one reduction.
+// rf_kernel_ms afterwards: [0] the shell filters, [1] the transforms, [2] the reduction, the others 0.
+int rf_measure_bispectrum(rf_plan* p, const double* k_edges, int nbins, const int* triples, int ntriples, const double* amp_x, const double* amp_y,
+                          const double* amp_z, int unit, double* sum3) {
+  if (int rc = bispectrum_check(p)) return rc;
+  RF_REQUIRE(k_edges && triples && sum3, "null argument");
+  RF_REQUIRE(nbins >= 1 && nbins <= BISPECTRUM_MAX_BINS, "nbins must be between 1 and 32");
+  RF_REQUIRE(ntriples >= 1 && ntriples <= BISPECTRUM_MAX_TRIPLES, "ntriples must be between 1 and 8192");
+  RF_REQUIRE(k_edges[0] >= 0.0, "bad k_edges: the first edge must not be negative");
+  for (int b = 0; b < nbins; ++b) RF_REQUIRE(k_edges[b] < k_edges[b + 1], "bad k_edges: the edges must be strictly increasing");
+  for (int t = 0; t < ntriples; ++t)
+    RF_REQUIRE(0 <= triples[3 * t] && triples[3 * t] <= triples[3 * t + 1] && triples[3 * t + 1] <= triples[3 * t + 2] && triples[3 * t + 2] < nbins,
+               "bad triple: every triple must satisfy 0 <= b1 <= b2 <= b3 < nbins");
+  const double* amp[3] = {amp_x, amp_y, amp_z};
+  const int alen[3] = {p->nx, p->ny, p->nz / 2 + 1};
+  for (int a = 0; a < 3 && !unit; ++a)
+    for (int i = 0; amp[a] && i < alen[a]; ++i)
+      RF_REQUIRE(std::isfinite(amp[a][i]) && amp[a][i] > 0.0, "bad amplitude table: every entry must be finite and positive");
+  RF_REQUIRE(p->have_kgrid, "rf_set_kgrid must be called first");
+  RF_REQUIRE(p->K.ptr && p->has.kspace(), "no k-space data: call rf_generate or rf_upload_k first");
+  const Route r = route(p);
+  RF_REQUIRE(r.kind == Route::Generic || r.kind == Route::Single, "the bispectrum measurement runs on the single-GPU pipelines: not with RF_FLAG_FORCE_SLAB_PATH");
+  RF_HIP(hipSetDevice(p->device));
+  const long long ncells = (long long)p->nx * p->ny * p->nz;
+  const BispectrumLaunch L = bispectrum_launch_shape(p->f64, ncells, nbins, ntriples, p->bs_max_wg);
+  const size_t head_words = bispectrum_head_words(p), part_bytes = (head_words + (size_t)L.rows * ntriples) * 8, field_bytes = (size_t)nbins * p->w_bytes;
+  if (p->bs_mask.bytes < p->k_bytes || p->bs_fields.bytes < field_bytes || p->bs_part.bytes < part_bytes) RF_HIP(hipStreamSynchronize(p->stream));
+  p->bs_nbins = 0;                                  // (no shell fields until the call has run to its end)
+  RF_HIP(p->bs_mask.reserve(p->k_bytes));
+  RF_HIP(p->bs_fields.reserve(field_bytes));
+  RF_HIP(p->bs_part.reserve(part_bytes));
+  double* e2_dev = (double*)p->bs_part.ptr;
+  double* out_dev = e2_dev + (BISPECTRUM_MAX_BINS + 1);
+  unsigned* tri_dev = (unsigned*)(out_dev + BISPECTRUM_MAX_TRIPLES);
+  double* tab_dev = out_dev + BISPECTRUM_MAX_TRIPLES + BISPECTRUM_MAX_TRIPLES / 2;
+  double* part_dev = e2_dev + head_words;
+  std::vector<double> e2((size_t)nbins + 1);
+  for (int b = 0; b <= nbins; ++b) e2[b] = k_edges[b] * k_edges[b];
+  std::vector<unsigned> packed((size_t)ntriples);
+  for (int t = 0; t < ntriples; ++t) packed[t] = bispectrum_pack(triples[3 * t], triples[3 * t + 1], triples[3 * t + 2]);
+  RF_HIP(hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  RF_HIP(hipMemcpyAsync(tri_dev, packed.data(), packed.size() * sizeof(unsigned), hipMemcpyHostToDevice, p->stream));
+  ShellParams g;
+  memset(&g, 0, sizeof(g));
+  g.unit = unit != 0;
+  const double** const amp_dev[3] = {&g.ax, &g.ay, &g.az};
+  for (int a = 0; a < 3; ++a) {
+    if (amp[a] && !unit) {
+      RF_HIP(hipMemcpyAsync(tab_dev, amp[a], (size_t)alen[a] * sizeof(double), hipMemcpyHostToDevice, p->stream));
+      *amp_dev[a] = tab_dev;
+    }
+    tab_dev += alen[a];
+  }
+  g.p.nx = p->nx; g.p.ny = p->ny; g.p.nz = p->nz;
+  g.p.nbins = nbins;
+  g.p.kx2 = p->kx2.get(); g.p.ky2 = p->ky2.get(); g.p.kz2 = p->kz2.get();
+  RF_HIP(p->tl.begin(p->stream, true));
+  for (int b = 0; b < nbins; ++b) {
+    RF_HIP(launch_shell_filter(p->f64, p->K.ptr, p->bs_mask.ptr, g, e2_dev, b, p->bs_max_wg, p->stream));
+    RF_HIP(p->tl.mark(rft::X, p->stream));
+    if (int rc = bispectrum_c2r(p, p->bs_mask.ptr, (char*)p->bs_fields.ptr + (size_t)b * p->w_bytes)) return rc;
+    RF_HIP(p->tl.mark(rft::Y, p->stream));
+  }
+  RF_HIP(launch_bispectrum_sums(p->f64, p->bs_fields.ptr, ncells, nbins, tri_dev, ntriples, p->bs_max_wg, part_dev, out_dev, p->stream));
+  RF_HIP(p->tl.mark(rft::Z, p->stream));
+  RF_HIP(p->tl.end(p->stream));
+  p->has.field_consumed();                          // the field buffer is the transforms' workspace, on every kind of plan
+  RF_HIP(hipMemcpyAsync(sum3, out_dev, (size_t)ntriples * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  p->bs_nbins = nbins;
+  return 0;
+}
+
+int rf_bispectrum_release(rf_plan* p) {
+  if (int rc = bispectrum_check(p)) return rc;
+  RF_HIP(hipSetDevice(p->device));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  p->bs_nbins = 0;
+  RF_HIP(p->bs_mask.release()); RF_HIP(p->bs_fields.release()); RF_HIP(p->bs_part.release());
+  return 0;
+}
+
+int rf_bispectrum_download_shell(rf_plan* p, int b, void* host) {
+  if (int rc = bispectrum_check(p)) return rc;
+  RF_REQUIRE(host, "null argument");
+  RF_REQUIRE(p->bs_nbins > 0 && p->bs_fields.ptr, "no shell fields: call rf_measure_bispectrum first");
+  RF_REQUIRE(b >= 0 && b < p->bs_nbins, "the shell must be one of the last call's bins");
+  RF_HIP(hipSetDevice(p->device));
+  RF_HIP(hipMemcpyAsync(host, (const char*)p->bs_fields.ptr + (size_t)b * p->w_bytes, p->w_bytes, hipMemcpyDeviceToHost, p->stream));
+  RF_HIP(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+int rf_bispectrum_geometry(rf_plan* p, int nbins, int ntriples, int* chunk_cells, int* workgroups, int* partial_rows) {
+  if (int rc = bispectrum_check(p)) return rc;
+  RF_REQUIRE(chunk_cells && workgroups && partial_rows, "null argument");
+  RF_REQUIRE(nbins >= 1 && nbins <= BISPECTRUM_MAX_BINS, "nbins must be between 1 and 32");
+  RF_REQUIRE(ntriples >= 1 && ntriples <= BISPECTRUM_MAX_TRIPLES, "ntriples must be between 1 and 8192");
+  const BispectrumLaunch L = bispectrum_launch_shape(p->f64, (long long)p->nx * p->ny * p->nz, nbins, ntriples, p->bs_max_wg);
+  *chunk_cells = L.chunk; *workgroups = (int)L.gx; *partial_rows = L.rows;
+  return 0;
+}
+
+int rf_bispectrum_set_max_workgroups(rf_plan* p, int n) {
+  if (int rc = bispectrum_check(p)) return rc;
+  RF_REQUIRE(n >= 0 && n <= 65535, "the workgroup cap is 0 (the default) or between 1 and 65535");
+  p->bs_max_wg = n;
+  return 0;
 }
 
 int rf_upload_k(rf_plan* p, const void* host) {

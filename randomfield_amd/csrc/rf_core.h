@@ -607,6 +607,48 @@ RF_HD int bin_cell(const MultipoleParams& g, const double* e2, cplx<T> v, int ix
   return b;
 }
 
+// ------------------------------------------------------- binned bispectrum --
+// The FFT estimator of rf_measure_bispectrum (Scoccimarro 2015; Sefusatti et al. 2016).  Shell b holds the cells power_cell puts into
+// bin b -- the same k^2, the same power_bin on the same squared edges, the DC cell in no shell -- and the shell field D_b is the inverse
+// transform of the half spectrum restricted to it.  The restricted cell:
+//   M = keep ? (T)(amp K) : 0     amp = (ax[ix] ay[iy]) az[iz] in float64 (null table = ones), rounded once to T per component;
+//                                 with all three tables null the kept cell is K itself, bit for bit
+//   M = keep ? 1 : 0              the unit run (delta = 1 inside the shells: the triangle count)
+enum { BISPECTRUM_MAX_BINS = 32, BISPECTRUM_MAX_TRIPLES = 8192 };
+struct ShellParams {
+  PowerParams p;
+  int unit;
+  const double* ax;
+  const double* ay;
+  const double* az;
+};
+template <typename T>
+RF_HD cplx<T> shell_cell(const ShellParams& g, const double* e2, int shell, cplx<T> v, int ix, int iy, int iz) {
+  if (ix == 0 && iy == 0 && iz == 0) return mk<T>((T)0, (T)0);
+  const double k2 = (g.p.kx2[ix] + g.p.ky2[iy]) + g.p.kz2[iz];
+  if (power_bin(e2, g.p.nbins, k2) != shell) return mk<T>((T)0, (T)0);
+  if (g.unit) return mk<T>((T)1, (T)0);
+  if (!(g.ax || g.ay || g.az)) return v;
+  const double amp = ((g.ax ? g.ax[ix] : 1.0) * (g.ay ? g.ay[iy] : 1.0)) * (g.az ? g.az[iz] : 1.0);
+  return mk<T>((T)(amp * (double)v.x), (T)(amp * (double)v.y));
+}
+// One term of s(b1, b2, b3) = sum over x of D_b1 D_b2 D_b3 added to a running sum: the values widened to float64, (a b) c with both
+// products and the sum rounded on their own (never contracted: pragma / volatile as mul_then_add)
+RF_HD double bispectrum_add(double s, double a, double b, double c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const double ab = a * b;
+  const double t = ab * c;
+  return s + t;
+#else
+  volatile double ab = a * b;
+  volatile double t = ab * c;
+  return s + t;
+#endif
+}
+// a triple (b1, b2, b3), 0 <= b < 32, as the reduction's kernels and the emulator carry it: one word
+RF_HD unsigned bispectrum_pack(int b1, int b2, int b3) { return (unsigned)b1 | ((unsigned)b2 << 8) | ((unsigned)b3 << 16); }
+
 // ------------------------------------------- particles: cloud-in-cell paint --
 // One particle of unit mass per lattice cell q = (ix, iy, iz), displaced by s_a(q) (length units); inv_h[a] = 1 / (grid spacing).
 // Per axis, all in float64:

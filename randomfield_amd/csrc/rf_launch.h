@@ -184,6 +184,19 @@ hipError_t launch_bins(int f64, const void* S, const PowerParams& g, const doubl
                        unsigned long long* out, hipStream_t s);
 hipError_t launch_bins(int f64, const void* S, const MultipoleParams& g, const double* e2_dev, unsigned long long* partials, long long plane_words,
                        unsigned long long* out, hipStream_t s);
+// the binned bispectrum (rf_k_bispectrum.hip).  The shell filter M = shell_cell(K) over API-layout half spectra (rf_core.h; K and M must
+// be different arrays; e2_dev: the nbins + 1 squared edges; g.ax / ay / az device tables or null), and the triple-product reduction
+// over the nbins dense shell fields F[nbins][ncells] of the plan's real type: out[t] = sum over cells of D_b1 D_b2 D_b3 for the ntriples
+// packed triples (rf_core.h bispectrum_pack) in device memory, through `partials` (rows x ntriples float64 of bispectrum_launch_shape).
+// max_workgroups: 0 = the default caps (the filter: 4096; the reduction: BISPECTRUM_MAX_WORKGROUPS), else the cap of both grids.
+enum { BISPECTRUM_LDS_BYTES = 40960, BISPECTRUM_MAX_WORKGROUPS = 1024 };
+// chunk: cells per LDS tile; nslots x tpt: the triples a workgroup serves; gx x gy workgroups (chunks in a grid-stride loop x tiles of
+// triples); rows: partial rows = gx x (256 / nslots) cell groups
+struct BispectrumLaunch { int chunk = 64, nslots = 256, tpt = 1, rows = 1; unsigned gx = 1, gy = 1; long long nchunks = 1; size_t lds = 0; };
+BispectrumLaunch bispectrum_launch_shape(int f64, long long ncells, int nbins, int ntriples, int max_workgroups);
+hipError_t launch_shell_filter(int f64, const void* K, void* M, const ShellParams& g, const double* e2_dev, int shell, int max_workgroups, hipStream_t s);
+hipError_t launch_bispectrum_sums(int f64, const void* F, long long ncells, int nbins, const unsigned* triples_dev, int ntriples, int max_workgroups,
+                                  double* partials, double* out, hipStream_t s);
 
 // on-GPU replay of RandomState(seed).normal (rf_k_mt.hip)
 // one stage of the jump tree: states[i + m * dist] = states[i] advanced by m * dist segments, i < nsrc, m = 1 .. nmult

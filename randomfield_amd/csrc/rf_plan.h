@@ -252,6 +252,12 @@ struct rf_plan {
   bool fused_generic = false;          // RF_FLAG_FUSED_GENERIC_GENERATION: realisations generate inside the x pass (no K; has.kspace() untouched)
   rfc::DevBuf<> pw_buf;                 // lazy, rf_measure_power: squared edges, result, per-workgroup partials
   rfc::DevBuf<> mp_buf;                 // lazy, rf_measure_multipoles: squared edges, result, compensation tables, per-workgroup partials (counted by rf_plan_nbytes)
+  // lazy, rf_measure_bispectrum (all counted by rf_plan_nbytes, freed by rf_bispectrum_release or with the plan): bs_mask, one masked half
+  // spectrum (k_bytes); bs_fields, the nbins shell fields (w_bytes each) of the last call; bs_part: [squared edges, 33 slots][result,
+  // 8192 slots][packed triples, 8192 words][amplitude tables: nx, ny, nz/2 + 1 slots][rows x ntriples partials].  bs_nbins: the shell
+  // fields bs_fields holds (0: none); bs_max_wg: rf_bispectrum_set_max_workgroups (0: the launchers' own caps)
+  rfc::DevBuf<> bs_mask, bs_fields, bs_part;
+  int bs_nbins = 0, bs_max_wg = 0;
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations
   rfc::Contents has;                      // what W / W2, stats, K, noise / mt_scratch, L and A hold right now
@@ -285,6 +291,7 @@ struct CallDesc {
   double emit_pscale = 0.0;
   const double* zscale = nullptr;         // the z pass multiplies plane z by zscale[z] (device table: ztab)
   void* pot_target = nullptr;             // the x pass also stores delta(k) / k^2 there (rf_realise_potential)
+  bool intermediate = false;              // the transform's output is an intermediate of the call, not the plan's field: no host sink delivery, no moments (rf_measure_bispectrum)
   // what the call's x pass asks of source(p, ...) (kspace: it transforms that array instead of generating)
   SourceAsk ask(bool kspace) const { return SourceAsk::x_pass(kspace, mode, emit_potential ? SourceAsk::Emitted : pot_target ? SourceAsk::Stored : SourceAsk::Nothing); }
 };

@@ -337,6 +337,58 @@ class Generator(object):
         sums = self._backend.binned_sums(k_edges, source, los, window)
         return powertools.multipole_estimate(*sums, shape=shape, spacing=self.grid_spacing_Mpc_h)
 
+    def measure_bispectrum(self, field=None, *, k_edges=None, nbins=None, triangles="closed", window=None, source="field"):
+        """
+        Binned bispectrum of a field on this grid by the FFT estimator (Scoccimarro 2015; Sefusatti et al. 2016) -- the three-point
+        statistic that tells a second-order (2LPT) mock from a Zel'dovich one of nearly the same P(k).
+
+        ``field`` and ``source`` behave as in :meth:`measure_power_spectrum`: ``source='field'`` transforms the current field first
+        (and, by the same one rule, the spectrum of the last interlaced paint is gone), ``source='kspace'`` reads the spectrum left by
+        ``paint_particles(interlaced=True)`` and leaves it.  ``k_edges`` are ``nbins + 1`` strictly increasing non-negative edges in
+        h/Mpc, at most 32 bins, by default ``powertools.default_bispectrum_edges(shape, spacing, nbins)``: linear up to 2/3 of the
+        Nyquist frequency.  The shells are the bins of :meth:`measure_power_spectrum`.  ``triangles``: ``'closed'``, ``'all'`` or
+        ``'equilateral'`` (``powertools.bispectrum_triples``) or an ``(ntriples, 3)`` array of bins b1 <= b2 <= b3, at most 8192.
+
+        For shell b, D_b(x) is the inverse transform of the spectrum restricted to the shell; a triple sums D_b1 D_b2 D_b3 over the
+        grid, which counts every ordered triangle k1 + k2 + k3 = 0 MODULO THE GRID with k_i in shell b_i.  Triangles that close only
+        through aliasing are part of that sum: none exists while the last edge stays at or below 2/3 of the Nyquist frequency, which
+        is why the default edges end there; with edges beyond it they enter both the data's sum and the triangle count.
+
+        Returns a structured array, one row per triple: ``'bins'`` (three integers), ``'k1'``, ``'k2'``, ``'k3'`` (the mean |k| of
+        each shell's modes), ``'B'`` = (V**2 / N**3) sum_data / sum_unit -- the convention of :meth:`measure_power_spectrum` one order
+        up --, ``'Q'`` = B / (P1 P2 + P2 P3 + P3 P1) with the P(k) of the same spectrum and edges, and ``'ntriangles'`` (float64, the
+        integer number of ordered triangles); rows without a triangle hold NaN in B and Q.  ``window`` (None, ``'ngp'`` / ``'cic'`` /
+        ``'tsc'`` or three per-axis tables as ``powertools.window_compensation`` makes them): delta(k) is multiplied by the square
+        root of the compensation and P is the compensated monopole.
+
+        hip backend: ``rf_measure_bispectrum``, the same bits on every call; the triangle counts are measured once per
+        (edges, triples) and kept, so a second field costs one run.  The device copy of the field is consumed on every grid, and the
+        call keeps one masked spectrum and ``nbins`` fields of device memory until ``plan_c2r.device.bispectrum_release()``.
+        ``distributed=True`` raises ``NotImplementedError``.
+        """
+        if self.distributed:
+            raise NotImplementedError("measure_bispectrum runs on single-GPU plans.")
+        self._check_source(field, source)
+        shape = tuple(self.plan_c2r.shape)
+        if isinstance(window, str):
+            window = powertools.window_compensation(shape, window)
+        elif window is not None:
+            window = powertools._compensation_tables(window, shape)
+        if k_edges is None:
+            k_edges = powertools.default_bispectrum_edges(shape, self.grid_spacing_Mpc_h, nbins)
+        k_edges = np.asarray(k_edges, np.float64).ravel()
+        if not 1 <= len(k_edges) - 1 <= 32:
+            raise ValueError("measure_bispectrum takes between 1 and 32 bins.")
+        if isinstance(triangles, str):
+            triples = powertools.bispectrum_triples(k_edges, triangles)
+        else:
+            triples = np.ascontiguousarray(np.asarray(triangles).reshape(-1, 3), np.intc)
+        if not 1 <= len(triples) <= 8192:
+            raise ValueError("measure_bispectrum takes between 1 and 8192 triples.")
+        shape, k_edges = self._power_inputs(field, k_edges, nbins, source)
+        power, sum3, unit = self._backend.bispectrum_sums(k_edges, triples, source, window)
+        return powertools.bispectrum_estimate(triples, sum3, unit, *power, shape=shape, spacing=self.grid_spacing_Mpc_h)
+
     def _check_source(self, field, source):
         if source not in ("field", "kspace"):
             raise ValueError("Invalid source: {0!r} (expected 'field' or 'kspace').".format(source))

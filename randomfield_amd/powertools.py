@@ -18,7 +18,8 @@ from . import transform
 
 __all__ = ["get_k_bounds", "create_ksq_grids", "ksq_axes", "fill_with_log10k", "validate_power", "filter_power",
            "sigma_table", "tabulate_sigmas", "load_default_power", "make_power", "bin_power", "default_k_edges",
-           "power_estimate", "bin_multipoles", "multipole_estimate", "window_compensation"]
+           "power_estimate", "bin_multipoles", "multipole_estimate", "window_compensation", "bispectrum_triples",
+           "default_bispectrum_edges", "bin_bispectrum", "bispectrum_estimate"]
 
 
 def grid_k_range(shape, spacing):
@@ -265,6 +266,102 @@ def multipole_estimate(count, sum_k, m0, m2, m4, shape, spacing):
     out["P2"] = 2.5 * (3.0 * M2 - M0)
     out["P4"] = 1.125 * (35.0 * M4 - 30.0 * M2 + 3.0 * M0)
     out["nmodes"] = count
+    return out
+
+
+def default_bispectrum_edges(shape, spacing, nbins=None):
+    """``nbins + 1`` linear bin edges in k for :func:`bin_bispectrum`: from the fundamental mode of the longest axis (the first edge of
+    :func:`default_k_edges`) up to 2/3 of the smallest axis' Nyquist frequency.  Below that bound three modes of the grid cannot sum
+    to a non-zero multiple of the grid's period, so no triangle closes through aliasing only.  ``nbins`` defaults to
+    ``min(shape) // 3`` (bins about one fundamental mode of the shortest axis wide), at most 32."""
+    if nbins is None:
+        nbins = max(1, min(min(shape) // 3, 32))
+    nbins = int(nbins)
+    if not 1 <= nbins <= 32:
+        raise ValueError("nbins must be between 1 and 32.")
+    k_nyq = np.pi / spacing
+    first = default_k_edges(shape, spacing, 1)[0]
+    if not first < (2.0 / 3.0) * k_nyq:
+        raise ValueError("the grid has no modes below 2/3 of its Nyquist frequency.")
+    return np.linspace(first, (2.0 / 3.0) * k_nyq, nbins + 1)
+
+
+def bispectrum_triples(edges, which="closed"):
+    """The ``(ntriples, 3)`` integer array of bin triples b1 <= b2 <= b3 of ``nbins + 1`` edges, in lexicographic order.  ``'all'``:
+    every such triple.  ``'closed'``: those whose shells can hold a closed triangle k1 + k2 + k3 = 0 with |k_i| in shell b_i, i.e.
+    ``edges[b3] < edges[b1 + 1] + edges[b2 + 1]`` -- for edges up to 2/3 of the Nyquist frequency the others hold no triangle at
+    all; beyond it triangles that close modulo the grid appear in triples this rule drops.  ``'equilateral'``: b1 = b2 = b3."""
+    edges = np.asarray(edges, np.float64).ravel()
+    nbins = len(edges) - 1
+    if nbins < 1:
+        raise ValueError("edges must hold at least two values.")
+    if which not in ("closed", "all", "equilateral"):
+        raise ValueError("Invalid which: {0!r} (expected 'closed', 'all' or 'equilateral').".format(which))
+    if which == "equilateral":
+        return np.repeat(np.arange(nbins, dtype=np.intc)[:, None], 3, axis=1)
+    out = [(b1, b2, b3) for b1 in range(nbins) for b2 in range(b1, nbins) for b3 in range(b2, nbins)
+           if which == "all" or edges[b3] < edges[b1 + 1] + edges[b2 + 1]]
+    return np.asarray(out, np.intc).reshape(-1, 3)
+
+
+def bin_bispectrum(kdata, spacing, edges, triples, amp=None, unit=False):
+    """The triple sums of the FFT bispectrum estimator -- the numpy statement of the definition the device call
+    ``rf_measure_bispectrum`` implements (csrc/rf_core.h shell_cell, bispectrum_add), in float64 throughout.
+
+    ``kdata``: the ``(nx, ny, nz/2 + 1)`` half spectrum of unnormalised forward-transform values.  Shells are the bins of
+    :func:`bin_power` (``edges`` squared once, the DC cell in none).  ``D_b = irfftn`` (1/N) of the spectrum restricted to shell b,
+    times ``amp = (ax[ix] ay[iy]) az[iz]`` where tables are given; ``unit=True``: 1 inside the shells.  Returns
+    ``sum3[t] = sum_x D_b1 D_b2 D_b3`` per row of ``triples``; N**2 sum3 is the sum of delta(k1) delta(k2) delta(k3) over the ordered
+    triangles k_i in shell b_i that close modulo the grid."""
+    edges = np.asarray(edges, np.float64).ravel()
+    nbins = len(edges) - 1
+    if not 1 <= nbins <= 32 or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+        raise ValueError("edges must be 2 ... 33 strictly increasing non-negative values.")
+    triples = np.asarray(triples).reshape(-1, 3)
+    if not len(triples) or not np.all((0 <= triples[:, 0]) & (triples[:, 0] <= triples[:, 1]) & (triples[:, 1] <= triples[:, 2]) & (triples[:, 2] < nbins)):
+        raise ValueError("every triple must satisfy 0 <= b1 <= b2 <= b3 < nbins.")
+    if kdata.ndim != 3 or kdata.shape[2] < 2:
+        raise ValueError("kdata must be an (nx, ny, nz/2 + 1) half spectrum.")
+    nx, ny, nz = kdata.shape[0], kdata.shape[1], 2 * (kdata.shape[2] - 1)
+    kx2, ky2, kz2 = ksq_axes(nx, ny, nz, spacing)
+    k2 = (kx2[:, None, None] + ky2[None, :, None]) + kz2[None, None, :]
+    b = (np.searchsorted(edges * edges, k2.ravel(), side="right") - 1).reshape(k2.shape)
+    b[0, 0, 0] = -1                          # the DC cell
+    if unit:
+        data = np.ones(k2.shape, np.complex128)
+    else:
+        data = np.asarray(kdata, np.complex128)
+        if amp is not None:
+            ax, ay, az = _compensation_tables(amp, (nx, ny, nz))
+            one = np.ones(1)
+            data = data * (((one if ax is None else ax)[:, None, None] * (one if ay is None else ay)[None, :, None]) * (one if az is None else az)[None, None, :])
+    fields = {}
+    for s in np.unique(triples):
+        fields[int(s)] = np.fft.irfftn(np.where(b == s, data, 0.0), s=(nx, ny, nz), axes=(0, 1, 2))
+    return np.array([np.sum((fields[int(t[0])] * fields[int(t[1])]) * fields[int(t[2])]) for t in triples], np.float64)
+
+
+def bispectrum_estimate(triples, sum3, sum3_unit, count, sum_k, sum_p, shape, spacing):
+    """The structured array ('bins', 'k1', 'k2', 'k3', 'B', 'Q', 'ntriangles') of the sums of :func:`bin_bispectrum` /
+    ``DevicePlan.measure_bispectrum`` (``sum3`` of the data, ``sum3_unit`` of the unit run) and of :func:`bin_power` on the same edges
+    and spectrum (``count, sum_k, sum_p`` -- or a compensated ``m0`` for ``sum_p``).  With N = nx ny nz and V = N spacing**3:
+    ``ntriangles = rint(N**2 sum3_unit)``, ``B = (V**2 / N**3) sum3 / sum3_unit``, ``k_i`` the mean |k| of shell b_i's modes and
+    ``Q = B / (P1 P2 + P2 P3 + P3 P1)`` with ``P = (V / N**2) sum_p / count``; rows without a triangle hold NaN in B and Q."""
+    triples = np.asarray(triples).reshape(-1, 3)
+    n = float(shape[0]) * float(shape[1]) * float(shape[2])
+    P = power_estimate(count, sum_k, sum_p, shape, spacing)
+    out = np.empty(len(triples), [("bins", np.intc, (3,)), ("k1", float), ("k2", float), ("k3", float), ("B", float), ("Q", float),
+                                  ("ntriangles", float)])
+    out["bins"] = triples
+    for i, name in enumerate(("k1", "k2", "k3")):
+        out[name] = P["k"][triples[:, i]]
+    s_unit = np.asarray(sum3_unit, np.float64)
+    out["ntriangles"] = np.rint(n * n * s_unit) + 0.0           # (never -0)
+    p1, p2, p3 = (P["Pk"][triples[:, i]] for i in range(3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        B = np.where(out["ntriangles"] > 0, (spacing ** 6 / n) * np.asarray(sum3, np.float64) / s_unit, np.nan)
+        out["B"] = B
+        out["Q"] = B / (p1 * p2 + p2 * p3 + p3 * p1)
     return out
 
 
