@@ -552,6 +552,13 @@ int g_generic_cap = 0;                  // 0: generic_max_axis(dtype)
 int g_generic_tile = 3;                 // lines per block of the strided passes: 3 = deliberately not dividing the line counts (the walk by
                                         // index); 1 = the kernels' walk, a thread staying on one line (GenericWalk::fixed)
 int g_generic_threads = 1;              // host threads per block (1: the single-thread emulation)
+int g_generic_prefer_split = 1;         // 1: a strided line that fits but prefers the four-step form runs it, as in the library (rf_generic.h
+                                        // generic_axis_form); 0: every line that fits the cap is one line
+// a strided pass stages its stage and position tables behind the line image(s) unless even ONE line leaves no room for them
+// (rf_k_generic.hip strided_shape's last resort: the longest lines that are not smooth)
+inline int generic_tables_fit(const GenericAxis& ax, int elem_bytes) {
+  return (size_t)generic_bufs(ax) * ax.n * elem_bytes + generic_extra_bytes(ax, elem_bytes) <= (size_t)GENERIC_LDS_MAX ? 1 : 0;
+}
 
 // body(tid, sync) on g_generic_threads host threads (thread 0 is the caller); body loops over the blocks of one launch itself and
 // calls sync() after each block, which stands for the workgroup boundary: the LDS image is reused by the next block
@@ -587,11 +594,11 @@ template <typename T> struct EmuGenericOps {
   // one strided pass whose elements come from `from` (rf_generic.h generic_axis_block_from), block after block
   template <class Source>
   int axis_source(Source from, void* dst, const GenericAxis& ax, long long stride, long long inner, long long outer, long long nlines, int which, int sign, double scale) {
-    const int TC = g_generic_tile, nth = nthreads();
+    const int TC = g_generic_tile, nth = nthreads(), tw = generic_tables_fit(ax, (int)sizeof(cplx<T>));
     cplx<T>* lds = lds_image(ax, TC);
     run_generic_threads([&](int tid, auto sync) {
       for (long long b = 0; b * TC < nlines; ++b) {
-        generic_axis_block_from<T>(from, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, 1);
+        generic_axis_block_from<T>(from, (cplx<T>*)dst, ax, stride, inner, outer, nlines, TC, root(which), sign, (T)scale, lds, b, tid, nth, sync, tw);
         sync();
       }
     });
@@ -623,11 +630,11 @@ template <typename T> struct EmuGenericOps {
     return 0;
   }
   int lines(const void* src, void* dst, const GenericLines& L, int which) {
-    const int TC = g_generic_tile, nth = nthreads();
+    const int TC = g_generic_tile, nth = nthreads(), tw = generic_tables_fit(L.ax, (int)sizeof(cplx<T>));
     cplx<T>* lds = lds_image(L.ax, TC);
     run_generic_threads([&](int tid, auto sync) {
       for (long long b = 0; b * TC < L.nlines(); ++b) {
-        generic_lines_block<T>((const cplx<T>*)src, (cplx<T>*)dst, L, TC, root(which), lds, b, tid, nth, sync, 1);
+        generic_lines_block<T>((const cplx<T>*)src, (cplx<T>*)dst, L, TC, root(which), lds, b, tid, nth, sync, tw);
         sync();
       }
     });
@@ -669,17 +676,26 @@ template <typename T> struct EmuGenericOps {
   }
   int copy(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
 };
-// one axis: short (its line fits the cap) or split in two factors that do; false: neither
-inline bool emu_axis(long long n, int cap, GenericAxis& ax, GenericLong& lg) {
-  lg = GenericLong();
-  if (n <= cap) return generic_factor((int)n, ax);
-  return generic_split(n, cap, lg);
-}
+// the form of every axis by the library's rule (rf_generic.h generic_axis_form: x and y are strided, the contiguous axis is not), with the
+// emulator's cap and switch
 template <typename T> bool emu_dims(int nx, int ny, int nz, bool packed, GenericDims& d) {
   const int cap = g_generic_cap > 0 ? g_generic_cap : generic_max_axis(sizeof(T) == 8);
+  const bool prefer = g_generic_prefer_split != 0;
   d.nx = nx; d.ny = ny; d.nz = nz; d.csize = sizeof(cplx<T>);
   if (packed && (nz & 1)) return false;
-  return emu_axis(nx, cap, d.ax, d.lx) && emu_axis(ny, cap, d.ay, d.ly) && emu_axis(packed ? nz / 2 : nz, cap, d.az, d.lz);
+  return generic_axis_form(nx, cap, (int)d.csize, true, d.ax, d.lx, prefer) && generic_axis_form(ny, cap, (int)d.csize, true, d.ay, d.ly, prefer) &&
+         generic_axis_form(packed ? nz / 2 : nz, cap, (int)d.csize, false, d.az, d.lz, prefer);
+}
+// the form of one axis as 32 ints: n1, n2 (0, 0: one line) and, per line (the whole line, or the sub-lines n1 then n2; the second block
+// zero for one line), nf, smooth, whether the stage tables fit behind one line's image(s), and the 12 radices
+inline void emu_form_line(const GenericAxis& ax, int elem_bytes, int* out15) {
+  out15[0] = ax.nf; out15[1] = ax.smooth; out15[2] = generic_tables_fit(ax, elem_bytes);
+  for (int s = 0; s < GENERIC_MAX_FACTORS; ++s) out15[3 + s] = s < ax.nf ? ax.f[s] : 0;
+}
+inline void emu_form_out(const GenericAxis& ax, const GenericLong& lg, int elem_bytes, int* out32) {
+  std::fill(out32, out32 + 32, 0);
+  if (lg.split()) { out32[0] = lg.n1; out32[1] = lg.n2; emu_form_line(lg.a1, elem_bytes, out32 + 2); emu_form_line(lg.a2, elem_bytes, out32 + 17); }
+  else emu_form_line(ax, elem_bytes, out32 + 2);
 }
 
 template <typename T>
@@ -1452,6 +1468,29 @@ int emu_set_rowblock(int rb) { const int old = g_rowblock; g_rowblock = rb; retu
 // the longest line the generic path keeps whole (0 = the library's cap, 8192 complex64 / 4096 complex128): longer axes take the four-step
 // form -- lowered by tests so that small grids exercise it
 int emu_set_generic_cap(int cap) { const int old = g_generic_cap; g_generic_cap = cap; return old; }
+// 1 (default): strided lines that fit the cap but prefer the four-step form run it, as the library decides (rf_generic.h
+// generic_axis_form); 0: every axis that fits is one line.  Returns the old value.
+int emu_set_generic_prefer_split(int on) { const int old = g_generic_prefer_split; g_generic_prefer_split = on ? 1 : 0; return old; }
+// The form an axis of length n runs in (strided: an x or y axis; else the contiguous one) under the emulator's cap and switch -- with
+// their defaults, the library's: out32 as emu_form_out.  Returns 1, or 0 where the axis is not served.
+int emu_generic_axis_form(int f64, long long n, int strided, int* out32) {
+  const int cap = g_generic_cap > 0 ? g_generic_cap : generic_max_axis(f64), es = f64 ? 16 : 8;
+  GenericAxis ax;
+  GenericLong lg;
+  if (!generic_axis_form(n, cap, es, strided != 0, ax, lg, g_generic_prefer_split != 0)) return 0;
+  emu_form_out(ax, lg, es, out32);
+  return 1;
+}
+// ... and of the three axes of a packed (the contiguous axis at nz / 2) or c2c shape: out96 = x, y, z.  0: the emulator refuses the shape
+int emu_generic_shape_form(int f64, int nx, int ny, int nz, int packed, int* out96) {
+  GenericDims d;
+  if (nx < 1 || ny < 1 || nz < 1 || !(f64 ? emu_dims<double>(nx, ny, nz, packed != 0, d) : emu_dims<float>(nx, ny, nz, packed != 0, d))) return 0;
+  const int es = f64 ? 16 : 8;
+  emu_form_out(d.ax, d.lx, es, out96);
+  emu_form_out(d.ay, d.ly, es, out96 + 32);
+  emu_form_out(d.az, d.lz, es, out96 + 64);
+  return 1;
+}
 int emu_set_generic_tile(int tc) { const int old = g_generic_tile; g_generic_tile = tc > 0 ? tc : 3; return old; }
 // host threads per block of the generic path (1, the default: one "thread" with a no-op barrier).  With nth > 1 the block functions
 // run on nth threads with a real barrier; nth a multiple of the tile takes the kernels' own walk (GenericWalk::fixed)

@@ -816,6 +816,18 @@ inline int generic_strided_tile(const GenericAxis& ax, int elem_bytes) {
 // realisation; 2000 points -- 4 lines -- 1.25 against 1.54: stays one pass).  Contiguous axes never: their lines ARE the segments.
 inline bool generic_prefers_split(const GenericAxis& ax, int elem_bytes) { return generic_strided_tile(ax, elem_bytes) < 4; }
 
+// The form ONE axis of length n runs in -- the library's decision (rf_capi.hip generic_dims) and the CPU emulator's (emu/rf_emu.cpp
+// emu_dims): beyond `cap` the four-step form (lg, false if n does not split); else one line of the LDS (ax), unless the line is strided
+// and prefers the four-step form (above) and n splits -- then lg as well, and the sequences run lg.  false: the axis is not served.
+// prefer_split = false (the emulator's switch only) leaves every line that fits as one line.
+inline bool generic_axis_form(long long n, int cap, int elem_bytes, bool strided, GenericAxis& ax, GenericLong& lg, bool prefer_split = true) {
+  lg = GenericLong();
+  if (n > cap) return generic_split(n, cap, lg);
+  if (!generic_factor((int)n, ax)) return false;
+  if (prefer_split && strided && generic_prefers_split(ax, elem_bytes) && !generic_split(n, cap, lg)) lg = GenericLong();
+  return true;
+}
+
 struct GenericDims {
   int nx = 0, ny = 0, nz = 0;
   GenericAxis ax, ay, az;               // az factors nz / 2 (packed plans) or nz (c2c plans); unused where the long form applies

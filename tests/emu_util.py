@@ -308,6 +308,52 @@ def generic_c2c(data, inverse):
     return out
 
 
+def _form(v):
+    """32 ints of emu_form_out -> {"n1", "n2", "lines"}: lines = ({"n", "radices", "smooth", "tables_fit"}, ...), one for an axis that
+    is one line, two (n1 then n2) for the four-step form"""
+    def line(o):
+        radices = tuple(v[o + 3:o + 3 + v[o]])
+        return {"n": int(np.prod(radices, dtype=np.int64)), "radices": radices, "smooth": bool(v[o + 1]), "tables_fit": bool(v[o + 2])}
+    lines = (line(2), line(17)) if v[0] else (line(2),)
+    assert not v[0] or (lines[0]["n"], lines[1]["n"]) == (v[0], v[1])
+    return {"n1": v[0], "n2": v[1], "lines": lines}
+
+
+def generic_axis_form(dtype, n, strided):
+    """The form the library runs an axis of length n in (rf_generic.h generic_axis_form; strided: an x or y axis) under the emulator's
+    cap and prefer-split switch, whose defaults are the library's; None where the axis is not served."""
+    out = (ctypes.c_int * 32)()
+    if not lib().emu_generic_axis_form(int(dtype == np.complex128), ctypes.c_longlong(n), int(bool(strided)), out):
+        return None
+    form = _form(list(out))
+    assert np.prod([l["n"] for l in form["lines"]], dtype=np.int64) == n
+    return form
+
+
+def generic_shape_form(dtype, shape, packed):
+    """generic_axis_form of the three axes of a packed (z at nz / 2) or c2c plan: (x, y, z); None where the shape is refused"""
+    out = (ctypes.c_int * 96)()
+    if not lib().emu_generic_shape_form(int(dtype == np.complex128), *map(int, shape), int(bool(packed)), out):
+        return None
+    return tuple(_form(list(out[32 * i:32 * i + 32])) for i in range(3))
+
+
+class generic_prefer_split:
+    """Context manager: emu_set_generic_prefer_split -- True (the default) is the library's rule, False the one-line form of every axis
+    that fits the cap."""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        self.old = lib().emu_set_generic_prefer_split(int(bool(self.on)))
+        return self
+
+    def __exit__(self, *exc):
+        lib().emu_set_generic_prefer_split(self.old)
+        return False
+
+
 class generic_threads:
     """Context manager: the generic block functions on `nth` host threads with a real barrier (emu_set_generic_threads) and `tile`
     lines per block (emu_set_generic_tile); nth a multiple of the tile is the kernels' own thread walk."""

@@ -246,12 +246,25 @@ GENERIC_SHAPES = [(4, 6, 8), (6, 4, 12), (40, 60, 80), (10, 14, 22), (2, 2, 2), 
                   (4096, 2, 4), (2, 6000, 4), (2, 4, 8192)]          # (axes beyond the tiled kernels: whole lines of up to 8192 complex64)
 
 
+# strided axes the library runs as n1 x n2 by preference (rf_generic.h generic_axis_form: 64 x 64, 80 x 75): the emulator does too, so
+# these run under both settings of its switch -- the four-step form the library launches, and the one line they always covered
+GENERIC_PREFER_SPLIT = [(4096, 2, 4), (2, 6000, 4)]
+
+
 @pytest.mark.parametrize("shape", GENERIC_SHAPES)
 def test_generic_mixed_radix_transforms_against_numpy(shape):
     """The non-power-of-two path (csrc/rf_generic.h): the block functions the generic kernels run, executed by one
     "thread" per block.  c2r = np.fft.irfftn incl. its treatment of non-Hermitian DC / Nyquist bins (the reference's
     backend, transform.py:314), r2c = np.fft.rfftn, c2c = fftn / ifftn; line and row counts that do not divide the
     block sizes are part of the case."""
+    for prefer_split in (True, False) if shape in GENERIC_PREFER_SPLIT else (True,):
+        with emu_util.generic_prefer_split(prefer_split):
+            split = [f["n1"] > 0 for f in emu_util.generic_shape_form(np.complex64, shape, True)]
+            assert any(split) == (prefer_split and shape in GENERIC_PREFER_SPLIT), (shape, split)
+            _generic_mixed_radix_against_numpy(shape)
+
+
+def _generic_mixed_radix_against_numpy(shape):
     rng = np.random.RandomState(5)
     nx, ny, nz = shape
     for tile, (ct, rt, tol) in [(t, c) for t in (3, 1) for c in ((np.complex64, np.float32, 3e-6), (np.complex128, np.float64, 3e-14))]:
