@@ -237,8 +237,8 @@ int queue_x(rf_plan* p, const CallDesc& cd, const GenParams& gp, const void* ksp
   if (fast) RF_HIP(mark(tl, rft::EXTRA, sx, &after_repair));       // in front of the pass; recorded again by the launcher if it splits
   FastGenParams fgp = make_fast(p, cd, gp.seed, gp.seed_dev != nullptr, gp.seed_dev);
   if (src.reads_pairs32()) {
-    fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt_scratch.ptr);      // (a later float64 replay reuses the scratch: the float32 claim goes with it)
-    fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt_rowtab.ptr); fgp.seg_cap = p->seg_cap;
+    fgp.noise32 = reinterpret_cast<const cplx<float>*>(p->mt.scratch.ptr);      // (a later float64 replay reuses the scratch: the float32 claim goes with it)
+    fgp.rowtab = reinterpret_cast<const RowLoc*>(p->mt.rowtab.ptr); fgp.seg_cap = p->mt.seg_cap;
   }
   else if (src.kind == Source::FastDeviates64) fgp.noise = gp.noise;
   if (fast)
@@ -1027,7 +1027,7 @@ int rf_plan_destroy(rf_plan* p) {
 int rf_plan_nbytes(rf_plan* p, size_t* nbytes) {
   RF_REQUIRE(p && nbytes, "null argument");
   *nbytes = p->W.bytes + p->R.bytes + p->W2.bytes + p->R2.bytes + p->X.bytes + p->K.bytes + p->P.bytes + p->L.bytes + p->Q.bytes + p->A.bytes + p->PG.bytes +
-            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt_scratch.bytes + p->mp_buf.bytes + p->KS.bytes +      // (+ resident deviates and the replay's scratch runs)
+            p->G.bytes + p->G2.bytes + p->noise.bytes + p->mt.scratch.bytes + p->mp_buf.bytes + p->KS.bytes +      // (+ resident deviates and the replay's scratch runs)
             p->bs_mask.bytes + p->bs_fields.bytes + p->bs_part.bytes;
   return 0;
 }

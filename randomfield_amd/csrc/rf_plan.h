@@ -21,6 +21,7 @@
 #include "rf_host.h"
 #include "rf_launch.h"
 #include "rf_owned.h"
+#include "rf_replay.h"
 #include "rf_route.h"
 #include "rf_select.h"
 #include "rf_source.h"
@@ -44,6 +45,11 @@ int fail(int code, const std::string& msg);
 #define RF_REQUIRE(cond, msg) \
   do {                        \
     if (!(cond)) return fail(1, msg); \
+  } while (0)
+// ... where a function of the HIP-free headers hands the refusal's text back (nullptr: none)
+#define RF_REFUSE(why)                              \
+  do {                                              \
+    if (const char* w_ = (why)) return fail(1, w_); \
   } while (0)
 
 // RCCL entry points, resolved lazily with dlopen so that single-GPU use never depends on librccl
@@ -111,6 +117,38 @@ inline hipError_t hop(hipEvent_t e, hipStream_t from, hipStream_t to) {
   return hipStreamWaitEvent(to, e, 0);
 }
 
+// The MT19937 replay of a plan (rf_capi_mt.hip; the host arithmetic is rf_replay.h): the uploaded jump table, the device buffers of one
+// replay, the shared replay of a kz-slab job, the block of rf_realise_batch_reference.
+struct MtReplay {
+  JumpTable table;                     // what rf_mt_set_jump keeps on the host
+  DevBuf<uint32_t> pos;                // the table's device rows (rf_replay.h widen_jump_table) ...
+  DevBuf<int> npos_dev;                // ... and their four padded counts per polynomial
+  bool table_uploaded() const { return table.uploaded(pos.get()); }
+  DevBuf<uint32_t> states;
+  DevBuf<unsigned long long> counts, offsets;
+  DevBuf<> scratch;                    // one-pass replay: every segment's accepted pairs, densely from slot seg * (attempts per segment)
+  // float32 deviates (rf_noise_mt19937_ex(single = 1)) stay where the one-pass replay writes them: scratch, every segment's accepted
+  // pairs from slot seg * seg_cap, located through offsets (FastGenParams::seg_*): has.deviates32().  Only one of the two forms
+  // (float64 in cell order in `noise` / float32 in segment order) is valid at a time.
+  unsigned long long seg_cap = 0;
+  int nseg = 0;
+  DevBuf<> rowtab;                     // float32 form: where each row (ix, iy) of the stream starts in the runs (rf_core.h RowLoc, 8 B x nx ny)
+  DevBuf<int> flags;                   // device word: bit 0 = a row spans more than two segments (mt_rowtab_kernel)
+  // distributed replay (rf_mt_share_*): this rank replays segments [sh_first, sh_first + sh_nloc) of the one stream
+  DevBuf<> send, recv;                 // pairs packed by destination rank / stream of this rank as received (float32 mode)
+  DevBuf<long long> sbase;             // device, [nranks]: see mt_share_pack_kernel
+  DevBuf<unsigned long long> first;    // device: first stream cell of every local segment
+  ShareStep step;                      // which of the share calls has run, and the mode of the transport (float32 pairs / float64)
+  int sh_first = 0, sh_nloc = 0;       // rf_mt_share_begin: this rank's first segment and the number of its segments
+  ShareSplit split;                    // rf_mt_share_pack: what this rank sends to and receives from every peer
+  // rf_realise_batch_reference: [start states n x 624][accepted totals n][flags n], kept between calls (allocating and freeing them
+  // cost a device synchronisation per call: one-seed batches are the Generator's call); its events: replay finished / generation pass
+  // has read the runs
+  DevBuf<> br_tmp;
+  int br_cap = 0;
+  Events bev;
+};
+
 }  // namespace rfc
 
 // Everything the plan allocates is a member of an owning type (rf_owned.h): rf_plan_destroy drains the streams and deletes the plan.
@@ -163,7 +201,6 @@ struct rf_plan {
   int sink_layout = 0;
   bool sink_delivered = false;            // the last armed call has delivered
   rfc::Events sink_ev;
-  rfc::Events bev;                        // rf_realise_batch_reference: replay finished / generation pass has read the runs
   int yz_merge = 1;                       // rf_set_merged_yz: 0 never, 1 untimed calls (default), 2 timed calls too (a mark per launch)
   rfc::DevBuf<> P;                        // lazy: saved potential, API layout, at offset 0 of its allocation (ensure_p)
   size_t w_bytes = 0, k_bytes = 0, p_bytes = 0;      // field buffer, k-space side array, potential array (padded rows)
@@ -200,30 +237,8 @@ struct rf_plan {
   std::vector<double> h_kx2, h_ky2, h_kz2;   // host copies (k range of the grid for the fast records)
   rf::SigmaTableHost h_tab;
   rfc::DevBuf<double> noise;              // has.deviates64(): a full set of deviates
-  // float32 deviates (rf_noise_mt19937_ex(single = 1)) stay where the one-pass replay writes them: mt_scratch, every
-  // segment's accepted pairs from slot seg * seg_cap, located through mt_offsets (FastGenParams::seg_*): has.deviates32().  Only one
-  // of the two forms (float64 in cell order / float32 in segment order) is valid at a time.
-  unsigned long long seg_cap = 0;
-  int nseg = 0;
-  rfc::DevBuf<> mt_rowtab;             // float32 form: where each row (ix, iy) of the stream starts in the runs (rf_core.h RowLoc, 8 B x nx ny)
-  rfc::DevBuf<int> mt_flags;           // device word: bit 0 = a row spans more than two segments (mt_rowtab_kernel)
   rfc::DevBuf<> fixbuf;                // nx * ny complex: the repaired kz = 0 slots of the fast generation pass (fix_fill_kernel)
-  // MT19937 replay (rf_noise_mt19937): jump-polynomial bit positions per tree level, scratch
-  rfc::DevBuf<uint32_t> mt_pos;        // set-bit positions of the jump polynomials, widened to 32 bits (scalar loads)
-  std::vector<int> mt_npos;
-  int mt_stride = 0, mt_bps = 0, mt_radix = 2;   // positions per polynomial (padded), blocks of 624 words per segment, tree radix
-  rfc::DevBuf<int> mt_npos_dev;
-  rfc::DevBuf<uint32_t> mt_states;
-  rfc::DevBuf<unsigned long long> mt_counts, mt_offsets;
-  rfc::DevBuf<> mt_scratch;            // one-pass replay: every segment's accepted pairs, densely from slot seg * (attempts per segment)
-  // distributed replay (rf_mt_share_*): this rank replays segments [sh_first, sh_first + sh_nloc) of the one stream
-  rfc::DevBuf<> mt_send, mt_recv;                // pairs packed by destination rank / stream of this rank as received (float32 mode)
-  rfc::DevBuf<long long> mt_sbase;               // device, [nranks]: see mt_share_pack_kernel
-  rfc::DevBuf<unsigned long long> mt_first;      // device: first stream cell of every local segment
-  int sh_state = 0;                              // 0 idle, 1 replayed (begin), 2 packed, 3 exchanged
-  int sh_single = 0, sh_first = 0, sh_nloc = 0;
-  unsigned long long sh_total = 0;
-  std::vector<unsigned long long> sh_sendoff, sh_sendcnt, sh_recvoff, sh_recvcnt;      // pairs, per peer
+  rfc::MtReplay mt;                    // the MT19937 replay (rf_noise_mt19937, rf_mt_share_*, rf_realise_batch_reference): table, buffers, step
   rfc::DevBuf<double> partials;
   long long npartials = 0;
   rfc::DevBuf<double> stats;              // (sum, sumsq) per realisation
@@ -234,8 +249,6 @@ struct rf_plan {
   rfc::Events seeds_ev;
   int seeds_turn = 0;
   rfc::DevBuf<double> coll_scratch;       // 2 doubles on the device for host-side all-reduces (never aliases `stats`)
-  rfc::DevBuf<> br_tmp;                   // rf_realise_batch_reference: [start states n x 624][accepted totals n][flags n], kept between calls
-  int br_cap = 0;                         // (allocating and freeing them cost a device synchronisation per call: one-seed batches are the Generator's call)
   rfc::DevBuf<double> ztab;               // 2 * nz doubles for lognormal / affine tables
   // fused lognormal realisations (rf_realise_lognormal): [growth nz][density nz][A nz][B nz][sigma 8] and the y pass's Parseval partials
   rfc::DevBuf<double> lntab, ypart;
@@ -260,7 +273,7 @@ struct rf_plan {
   int bs_nbins = 0, bs_max_wg = 0;
   struct BatchGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   std::map<int, BatchGraph> graphs;       // captured batch graphs, keyed by the number of realisations
-  rfc::Contents has;                      // what W / W2, stats, K, noise / mt_scratch, L and A hold right now
+  rfc::Contents has;                      // what W / W2, stats, K, noise / mt.scratch, L and A hold right now
 };
 
 namespace rfc {

@@ -7,10 +7,11 @@ Prints one line per result -- `shape dtype call: sha256` -- for fields, k space,
 so that every branch of the tiled launchers is reached (rf_select.h: whole columns and Col2 halves, split and unsplit generation passes,
 tile pairs, the side buffer and the owning lane's repair, the merged y+z launch, 64-bit lane offsets ...), and, first, over every
 exchanging form of a plan's route (rf_route.h: grouped copy or storing y pass, whole or in sub-slabs, single calls and pipelined batches, the
-two stand-ins of a virtual rank).  A call the library refuses
+two stand-ins of a virtual rank), and, last, over the MT19937 replay (replay_lines).  A call the library refuses
 prints the refusal text instead of a digest.  Run it once per build (the default is the library of this tree) and diff the two outputs:
 every line must be equal.  Under `rocprofv3 --kernel-trace -- python tools/launch_parity.py LIB` the ordered list of (kernel, grid,
 workgroup) of two builds can be compared the same way.  Each call takes milliseconds; this is a comparison tool, not a test of values."""
+import ctypes
 import hashlib
 import os
 import sys
@@ -237,6 +238,77 @@ def standin_tails(shape, dtype, power, key):
 ROUTE_SHAPES = [(8, 8, 64), (8, 8, 128), (64, 32, 128), (64, 32, 256)]
 
 
+def replay_lines(power):
+    """The MT19937 replay (rf_capi_mt.hip): the deviates and the accepted count of the whole-stream replay at segment lengths that grow
+    the jump tree by one, two and three stages, the float32 form read by a realisation, the replay shared between two virtual ranks in
+    both modes of its transport, a same-seed batch, and every share call made out of its order, recorded by its refusal"""
+    def deviates(plan, accepted):
+        return plan.download_noise(), np.array([accepted], np.uint64)
+
+    for shape, bps in (((8, 8, 16), 1), ((8, 8, 16), 2), ((16, 16, 32), 1), ((32, 32, 64), 3)):
+        key = "replay %dx%dx%d bps=%d" % (shape + (bps,))
+        plan = tables(_hip.DevicePlan(*shape, np.complex64), power)
+        plan.set_mt_segment_blocks(bps)
+        record(key + " deviates64", lambda: deviates(plan, plan.reference_noise(321)))
+        record(key + " deviates64 second seed", lambda: deviates(plan, plan.reference_noise((2026, 4, 0xFFFFFFFF, 7))))
+        plan.close()
+    key = "replay 32x32x64 default"
+    plan = tables(_hip.DevicePlan(32, 32, 64, np.complex64), power)
+    record(key + " deviates32 accepted", lambda: np.array([plan.reference_noise(321, single=True)], np.uint64))
+    record(key + " deviates32 download", plan.download_noise)
+    record(key + " deviates32 realise", lambda: (plan.realise(noise="resident"),) and field(plan))
+    record(key + " batch reference", lambda: (plan.realise_batch_reference([321, 322]), plan.download_real(), np.array(plan.moments())))
+    record(key + " batch reference realise", lambda: (plan.realise(noise="resident"),) and field(plan))
+    plan.close()
+
+    shape, key = (64, 64, 256), "replay 64x64x256 bps=1 ranks=2"
+    plans = [tables(_hip.DevicePlan(*shape, np.complex64, nranks=2, rank=r), power) for r in range(2)]
+    for p in plans:
+        p.set_mt_segment_blocks(1)
+    for single in (False, True):
+        tag = key + (" float32" if single else " float64")
+        record(tag + " shared", lambda: np.array(_hip.DevicePlan.reference_noise_shared_local(plans, 141, single=single), np.uint64))
+        for p in plans:
+            record(tag + " rank %d deviates" % p.rank, p.download_noise)
+    # the share calls out of order: before any replay, after the replay, after the pack, after the exchange, after the end
+    p, arr = plans[1], (ctypes.c_void_p * 2)(*[q._h.value for q in plans])
+    nseg = p.share_segments()[0]
+    calls = [("gather", p.share_gather), ("pack", lambda: p.share_pack(np.zeros(nseg, np.uint64))), ("exchange", p.share_exchange),
+             ("exchange_local", lambda: _hip.check(_hip.load().rf_mt_share_exchange_local(arr, 2), "rf_mt_share_exchange_local")),
+             ("finish", p.share_finish)]
+
+    def done(tag, call):
+        record("%s %s" % (key, tag), lambda: (call(), np.array([0]))[1:])
+
+    def out_of_order(tag, skip=()):
+        for name, call in calls:
+            if name not in skip:
+                done("out of order %s: %s" % (tag, name), call)
+
+    def begin_and_pack(modes):
+        counts = np.concatenate([q.share_begin(141, single) for q, single in zip(plans, modes)])
+        for q in plans:
+            q.share_pack(counts)
+
+    out_of_order("idle")
+    done("begin", lambda: [q.share_begin(141, True) for q in plans])
+    out_of_order("replayed", skip=("pack",))                 # (gather: refused for the communicator it lacks, not for the step)
+    done("begin and pack", lambda: begin_and_pack((True, True)))
+    out_of_order("packed", skip=("exchange", "exchange_local"))
+    done("rank 0 replayed again", lambda: plans[0].share_begin(141, True))
+    done("out of order rank 0 replayed again: exchange_local", calls[3][1])
+    done("begin and pack in two modes", lambda: begin_and_pack((False, True)))
+    done("out of order packed in two modes: exchange_local", calls[3][1])
+    done("begin and pack again", lambda: begin_and_pack((True, True)))
+    done("exchange_local", calls[3][1])
+    out_of_order("exchanged", skip=("finish",))
+    record(key + " finish", lambda: np.array([q.share_finish() for q in plans], np.uint64))
+    out_of_order("finished")
+    for q in plans:
+        record(key + " after the calls rank %d deviates" % q.rank, q.download_noise)
+        q.close()
+
+
 def main():
     if len(sys.argv) > 1:
         _hip.LIB_PATH = os.path.abspath(sys.argv[1])
@@ -257,6 +329,7 @@ def main():
                 single_plan(shape, dtype, power, key)
                 virtual_ranks(shape, dtype, power, key)
             c2c_plan(shape, dtype, key)
+    replay_lines(power)
     print("# %d lines, sha256 of all: %s" % (len(LINES), hashlib.sha256("\n".join(LINES).encode()).hexdigest()), flush=True)
     return 0
 
